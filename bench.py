@@ -45,6 +45,13 @@ Stalls (N > 1): the conservative schedule (exchange not overlapped) is checked a
   (`config.stalled_schedule`) and leaves with status 3.
 `cpu_baseline` (N = 1): the compiled reference objects (oracle/_ref/ref_run under mpirun) and the
   oracle port (checked / unchecked accessor flavours) on bounded samples, host core counts stated.
+`--dump-outputs DIR`: after the timed regions, the field the last one computed is written to DIR as fp64 .npy files
+  (`config.dumped_outputs` lists them), so that two builds can be compared output for output.  The last region then
+  starts from the device-made hotspot itself, not from wherever the time-bounded clock ramp left the field: the same
+  arguments give the same inputs, and the output is exactly --steps steps of the hotspot.  Up to 6 Mi cells the whole
+  interior is written (`u`, ny x nx); a larger grid gives a fixed seeded sample of 2^21 cells (`u_sample`, with
+  `u_sample_index`: row-major interior indices) and the interior's edge rows and columns (`u_edge_rows`: bottom, top;
+  `u_edge_cols`: left, right).  Either way at most 48 MiB in all.
 """
 from __future__ import annotations
 
@@ -312,6 +319,37 @@ def expected_checksum(nx, ny, bc, dt):
     return None
 
 
+DUMP_FULL_CELLS = 6 << 20    # --dump-outputs: up to 48 MiB of fp64 the whole interior is written
+DUMP_SAMPLE = 1 << 21        # beyond that: this many distinct seeded cells (16 MiB of values + 16 MiB of indices)
+DUMP_SEED = 20261015
+DUMP_EDGE_CELLS = 1 << 19    # the four edges are written while they take at most 4 MiB
+
+
+def dump_plan(nx, ny):
+    """name -> (row-major indices into the ny x nx interior, shape of the array written) for --dump-outputs;
+    a function of the grid alone, so two runs with the same arguments write the same cells"""
+    import numpy as np
+    if nx * ny <= DUMP_FULL_CELLS:
+        return {"u": (np.arange(nx * ny, dtype=np.int64), (ny, nx))}
+    sample = np.sort(np.random.default_rng(DUMP_SEED).choice(nx * ny, size=DUMP_SAMPLE, replace=False)).astype(np.int64)
+    plan = {"u_sample": (sample, sample.shape)}
+    if 2 * (nx + ny) <= DUMP_EDGE_CELLS:
+        x, y = np.arange(nx, dtype=np.int64), np.arange(ny, dtype=np.int64)
+        plan["u_edge_rows"] = (np.concatenate([x, (ny - 1) * nx + x]), (2, nx))
+        plan["u_edge_cols"] = (np.concatenate([y * nx, y * nx + nx - 1]), (2, ny))
+    return plan
+
+
+def tile_values(u, dec, nx, idx):
+    """the entries of `idx` (global row-major interior indices) that lie in this rank's tile `u`: (positions in idx,
+    values)"""
+    import numpy as np
+    gy, gx = np.divmod(idx, nx)
+    ly, lx = gy - dec.y_offset, gx - dec.x_offset
+    mine = (ly >= 0) & (ly < dec.ny_local) & (lx >= 0) & (lx < dec.nx_local)
+    return np.nonzero(mine)[0], u[ly[mine], lx[mine]]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -344,6 +382,8 @@ def main():
                     help="N > 1: -1 pick the fastest exchange schedule on this node; 0, 1, 3, 4, 5 force one")
     ap.add_argument("--lds-bytes", type=int, default=0, help="occupancy limiter experiment (see csim.h)")
     ap.add_argument("--fused-2c", type=int, default=-1, help="0/1: E - 2c as one fma under the overflow guard (bit-identical for every non-NaN cell either way; default: on)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the field the last timed region computed to DIR/<name>.npy (fp64; see the module docstring)")
     ap.add_argument("--tail-split", type=int, default=-1, help="0/1: half-height chunks at the end of a whole-field launch (default: on)")
     ap.add_argument("--fuse", type=int, default=-1,
                     help="time steps per HBM pass: -1 auto (cheapest split of the run into passes of 2..7 steps), 0 off, 2..7")
@@ -669,13 +709,15 @@ def main():
             while time.perf_counter() < box[0]:
                 pass
 
-    def measure(ov, repeats=1):
+    def measure(ov, repeats=1, final=False):
         """`repeats` timed regions of exactly --steps steps under schedule ov, each bracketed by barrier + sync on both
         sides, MAX over ranks; returns the list of region records"""
         set_schedule(ov)
         advance(min(args.steps, 24))          # the schedule's own first launches (code loading) stay outside
         out = []
-        for _ in range(repeats):
+        for i in range(repeats):
+            if final and args.dump_outputs and i == repeats - 1:
+                st.init_gaussian(1.0, 0.05, 0.5, 0.5)   # --dump-outputs: the last region starts from the hotspot
             st.set_option("profile", 8 if multi else 1)
             barrier()
             st.reset_timers()
@@ -755,7 +797,7 @@ def main():
     if len(schedules) == 1:
         wd.arm(args.phase_timeout + expected_seconds(args.repeats), "timed regions")
         S["chosen"] = first
-        S["final"] = measure(first, args.repeats)
+        S["final"] = measure(first, args.repeats, final=True)
         S["measurements"][first] = S["final"]
     else:
         # N > 1 over RCCL: how the exchange is best hidden depends on what the RCCL kernel costs next to the sweep on
@@ -800,7 +842,32 @@ def main():
         set_schedule(best)
         advance(burst)
         S["ramp_steps"] += burst
-        S["final"] = measure(best, args.repeats)
+        S["final"] = measure(best, args.repeats, final=True)
+
+    if args.dump_outputs:
+        wd.arm(args.phase_timeout + 120 * slack, "dumping outputs")
+        u = st.download_interior()
+        files = {}
+        for name, (idx, shape) in dump_plan(args.nx, args.ny).items():
+            parts = [tile_values(u, dec, args.nx, idx)]
+            if world > 1:
+                parts = [None] * world
+                dist.all_gather_object(parts, tile_values(u, dec, args.nx, idx))
+            if rank == 0:
+                a = np.full(len(idx), np.nan)
+                for pos, vals in parts:
+                    a[pos] = vals
+                files[name] = a.reshape(shape)
+                if name == "u_sample":
+                    files["u_sample_index"] = idx.astype(np.float64)
+        del u
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in files.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+            S["dumped"] = dict(dir=args.dump_outputs, files={k: list(a.shape) for k, a in files.items()},
+                               steps=args.steps, start="the device-made gaussian hotspot (the last timed region only)",
+                               sample_seed=DUMP_SEED if "u_sample" in files else None)
 
     wd.arm(args.phase_timeout + 30 * slack, "closing checks")
     S["minmax"] = st.minmax()
@@ -995,6 +1062,8 @@ def build_line(S):
         "roofline": roofline,
         "roofline_valu": roofline_valu,
     }
+    if S.get("dumped"):
+        line["config"]["dumped_outputs"] = S["dumped"]
     if S["cpu"] is not None:
         line["cpu_baseline"] = S["cpu"]
     return line

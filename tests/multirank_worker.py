@@ -148,7 +148,9 @@ def main():
         ok = ok and bool(np.array_equal(glob, z["u_final"]))
         print(f"MULTIRANK engine={args.engine} world={world} case={os.path.basename(args.case)} ok={ok}",
               flush=True)
-    dist.barrier()
+    # not dist.barrier(): that one asks torch for the accelerator, which starts the HIP runtime — on a GPU box every
+    # oracle rank would then hold the GPU open, more processes than a box allows on one GPU
+    dist.monitored_barrier()
     dist.destroy_process_group()
     sys.exit(0 if ok else 1)
 

@@ -78,6 +78,47 @@ def test_preflight_inputs_exist_for_every_world_size_the_driver_runs(bench):
     assert bench.expected_checksum(16384, 16384, "dddd", 0.05) is None and bench.expected_checksum(100, 100, "dddd", 0.1) is None
 
 
+@pytest.mark.parametrize("nx,ny", [(1536, 1024), (3072, 2048), (3072, 2049), (16384, 16384), (32768, 32768),
+                                   (1 << 22, 2)])
+def test_dump_plan_is_fixed_and_within_the_byte_budget(bench, nx, ny):
+    """--dump-outputs writes the same cells on every run with the same grid, fp64, at most 64 MB with the sample index"""
+    import numpy as np
+    plan = bench.dump_plan(nx, ny)
+    again = bench.dump_plan(nx, ny)
+    assert plan.keys() == again.keys() and all(np.array_equal(plan[k][0], again[k][0]) for k in plan)
+    total = sum(len(idx) for idx, _ in plan.values()) + (len(plan["u_sample"][0]) if "u_sample" in plan else 0)
+    assert total * 8 <= 64e6
+    for name, (idx, shape) in plan.items():
+        assert int(np.prod(shape)) == len(idx) and idx.min() >= 0 and idx.max() < nx * ny
+    if nx * ny <= bench.DUMP_FULL_CELLS:
+        assert list(plan) == ["u"] and plan["u"][1] == (ny, nx)
+    else:
+        s = plan["u_sample"][0]
+        assert len(s) == bench.DUMP_SAMPLE and np.all(np.diff(s) > 0)
+        if "u_edge_rows" in plan:
+            rows, cols = plan["u_edge_rows"][0].reshape(2, nx), plan["u_edge_cols"][0].reshape(2, ny)
+            assert np.array_equal(rows // nx, [[0] * nx, [ny - 1] * nx]) and np.array_equal(cols % nx, [[0] * ny, [nx - 1] * ny])
+
+
+def test_dump_reassembles_the_field_from_the_tiles_of_every_rank(bench):
+    """each rank contributes the planned cells of its own tile; together they are the global field's cells"""
+    import numpy as np
+    nx, ny = 3001, 2203
+    field = np.random.default_rng(1).random((ny, nx))
+    xs, ys = [0, 1500, nx], [0, 700, 1400, ny]          # an uneven 2 x 3 decomposition
+    decs = [types.SimpleNamespace(x_offset=xs[i], y_offset=ys[j], nx_local=xs[i + 1] - xs[i], ny_local=ys[j + 1] - ys[j])
+            for i in range(2) for j in range(3)]
+    for name, (idx, shape) in bench.dump_plan(nx, ny).items():
+        got = np.full(len(idx), np.nan)
+        seen = 0
+        for d in decs:
+            tile = field[d.y_offset:d.y_offset + d.ny_local, d.x_offset:d.x_offset + d.nx_local]
+            pos, vals = bench.tile_values(tile, d, nx, idx)
+            got[pos] = vals
+            seen += len(pos)
+        assert seen == len(idx) and np.array_equal(got, field.reshape(-1)[idx]), name
+
+
 WATCHDOG_CHILD = """
 import os, sys, time
 sys.path.insert(0, {root!r})

@@ -135,6 +135,46 @@ def test_bench_checksum_fixture_is_what_the_oracle_computes():
     assert csim.checksum_host(w.gather()) == e["checksum"]
 
 
+def test_bench_dump_outputs_is_the_last_timed_region_bit_for_bit(tmp_path):
+    """--dump-outputs: the field the last timed region computed — exactly --steps steps of the device-made hotspot, so
+    the ORACLE's result for those steps bit for bit — written the same by a second run with the same arguments; above
+    the whole-field size, the seeded sample and the four edges of that field"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    from __graft_entry__ import load_package
+    from oracle import cpu_oracle as ora
+    a, b, c = tmp_path / "a", tmp_path / "b", tmp_path / "c"
+    r = run_bench(["--dump-outputs", str(a)])
+    run_bench(["--dump-outputs", str(b)])
+    assert r["steps"] == 37 and r["config"]["dumped_outputs"]["files"] == {"u": [1024, 1536]}
+    assert sorted(os.listdir(a)) == sorted(os.listdir(b)) == ["u.npy"]
+    ua = np.load(a / "u.npy")
+    assert ua.dtype == np.float64 and np.array_equal(ua, np.load(b / "u.npy"))
+    r = run_bench(["--nx", "4096", "--ny", "2048", "--dump-outputs", str(c)])
+    assert set(r["config"]["dumped_outputs"]["files"]) == {"u_sample", "u_sample_index", "u_edge_rows", "u_edge_cols"}
+    assert sum(f.stat().st_size for f in c.iterdir()) <= 64e6
+
+    csim = load_package()
+    csim.lib()
+    csim.set_device(0)
+    D, vx, vy = 0.05, 0.5, 0.25
+    dt = min(0.1, csim.safe_dt(1.0, 1.0, vx, vy, D))
+    for nx, ny in ((1536, 1024), (4096, 2048)):
+        st = csim.Stepper.single(nx, ny, 1.0, 1.0, csim.bc_codes("dddd"))
+        st.init_gaussian(1.0, 0.05, 0.5, 0.5)
+        want = st.download()
+        st.close()
+        ora.run_single(want, 1.0, 1.0, D, vx, vy, dt, csim.bc_codes("dddd"), 37)
+        want = want[1:-1, 1:-1]
+        if nx == 1536:
+            assert np.array_equal(ua, want)
+            continue
+        idx = np.load(c / "u_sample_index.npy").astype(np.int64)
+        assert np.array_equal(np.load(c / "u_sample.npy"), want.reshape(-1)[idx])
+        assert np.array_equal(np.load(c / "u_edge_rows.npy"), want[[0, -1], :])
+        assert np.array_equal(np.load(c / "u_edge_cols.npy"), want[:, [0, -1]].T)
+
+
 @pytest.mark.parametrize("forced", [True, False])
 def test_bench_two_ranks_host_staged_fallback(forced):
     """two bench ranks sharing this GPU: the fall-back transport bench.py uses when the RCCL communicator cannot be
