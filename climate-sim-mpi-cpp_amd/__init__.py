@@ -151,6 +151,24 @@ def lib() -> C.CDLL:
         "csim_stepper_kernel_time": (i, [vp, i, dp, C.POINTER(C.c_long)]),
         "csim_stepper_comm_time": (i, [vp, dp, C.POINTER(C.c_long)]),
         "csim_stepper_reset_timers": (i, [vp]),
+        "csim_ensemble_create": (i, [i, i, i, i, d, d, ip, d, C.POINTER(vp)]),
+        "csim_ensemble_destroy": (i, [vp]),
+        "csim_ensemble_upload": (i, [vp, i, dp]),
+        "csim_ensemble_download": (i, [vp, i, dp]),
+        "csim_ensemble_upload_all": (i, [vp, dp]),
+        "csim_ensemble_download_all": (i, [vp, dp]),
+        "csim_ensemble_init_gaussian": (i, [vp, i, d, d, d, d]),
+        "csim_ensemble_set_physics": (i, [vp, dp, dp, dp, dp]),
+        "csim_ensemble_run": (i, [vp, i]),
+        "csim_ensemble_sync": (i, [vp]),
+        "csim_ensemble_checksum": (i, [vp, C.POINTER(C.c_ulonglong)]),
+        "csim_ensemble_minmax": (i, [vp, dp]),
+        "csim_ensemble_sum": (i, [vp, dp]),
+        "csim_ensemble_set_option": (i, [vp, C.c_char_p, C.c_long]),
+        "csim_ensemble_get_option": (i, [vp, C.c_char_p, C.POINTER(C.c_long)]),
+        "csim_ensemble_plan": (i, [i, i, i, i, ip]),
+        "csim_ensemble_sign_class": (i, [d, d, d, d, d, d, i, ip]),
+        "csim_ensemble_classes": (i, [i, ip, ip]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -490,3 +508,101 @@ class Stepper:
 
     def reset_timers(self):
         _ck(lib().csim_stepper_reset_timers(self._h))
+
+
+def ensemble_plan(nsteps: int, nx: int, ny: int, fuse: int = -1):
+    """(steps per fused pass, fused passes, single steps) of Ensemble.run(nsteps) — host arithmetic, no GPU"""
+    o = (C.c_int * 3)()
+    _ck(lib().csim_ensemble_plan(nsteps, nx, ny, fuse, o))
+    return o[0], o[1], o[2]
+
+
+def ensemble_sign_class(D, dt, vx, vy, dx=1.0, dy=1.0, fused_2c=1) -> int:
+    """the per-pass launch (upwind-sign class 0..8) a member with these parameters runs in — host only"""
+    c = C.c_int()
+    _ck(lib().csim_ensemble_sign_class(dx, dy, D, dt, vx, vy, fused_2c, C.byref(c)))
+    return c.value
+
+
+def ensemble_launches(classes) -> int:
+    """launches per pass of a batch whose members have these sign classes — host only"""
+    a = (C.c_int * len(classes))(*[int(c) for c in classes])
+    n = C.c_int()
+    _ck(lib().csim_ensemble_classes(len(classes), a, C.byref(n)))
+    return n.value
+
+
+class Ensemble:
+    """B members of one grid shape (own field, own D, dt, vx, vy each) stepped together on one GPU; every member
+    ends bit-identical to a single-rank Stepper run with its own parameters (csim_ensemble_*)."""
+
+    def __init__(self, members, nx, ny, dx=1.0, dy=1.0, bc=(0, 0, 0, 0), bc_value=0.0):
+        self.members, self.nx, self.ny = members, nx, ny
+        h = C.c_void_p()
+        _ck(lib().csim_ensemble_create(members, nx, ny, 1, dx, dy, _i4(bc), bc_value, C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        self.close()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().csim_ensemble_destroy(self._h)
+            self._h = None
+
+    def upload(self, k: int, host: np.ndarray):
+        assert host.shape == (self.ny + 2, self.nx + 2)
+        _ck(lib().csim_ensemble_upload(self._h, k, _dp(np.ascontiguousarray(host, dtype=np.float64))))
+
+    def upload_all(self, host: np.ndarray):
+        assert host.shape == (self.members, self.ny + 2, self.nx + 2)
+        _ck(lib().csim_ensemble_upload_all(self._h, _dp(np.ascontiguousarray(host, dtype=np.float64))))
+
+    def download(self, k: int) -> np.ndarray:
+        out = np.empty((self.ny + 2, self.nx + 2))
+        _ck(lib().csim_ensemble_download(self._h, k, _dp(out)))
+        return out
+
+    def download_all(self) -> np.ndarray:
+        out = np.empty((self.members, self.ny + 2, self.nx + 2))
+        _ck(lib().csim_ensemble_download_all(self._h, _dp(out)))
+        return out
+
+    def init_gaussian(self, k, A=1.0, sigma_frac=0.05, xc_frac=0.5, yc_frac=0.5):
+        _ck(lib().csim_ensemble_init_gaussian(self._h, k, A, sigma_frac, xc_frac, yc_frac))
+
+    def set_physics(self, D, dt, vx, vy):
+        """scalars apply to every member, sequences give one value per member"""
+        arrs = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.members,)))
+                for v in (D, dt, vx, vy)]
+        _ck(lib().csim_ensemble_set_physics(self._h, *[_dp(a) for a in arrs]))
+
+    def run(self, nsteps: int):
+        _ck(lib().csim_ensemble_run(self._h, nsteps))
+
+    def sync(self):
+        _ck(lib().csim_ensemble_sync(self._h))
+
+    def checksums(self):
+        o = (C.c_ulonglong * self.members)()
+        _ck(lib().csim_ensemble_checksum(self._h, o))
+        return [int(v) for v in o]
+
+    def minmax(self) -> np.ndarray:
+        """(members, 2) array: min, max of each member, ghosts included"""
+        o = np.empty((self.members, 2))
+        _ck(lib().csim_ensemble_minmax(self._h, _dp(o)))
+        return o
+
+    def sums(self) -> np.ndarray:
+        o = np.empty(self.members)
+        _ck(lib().csim_ensemble_sum(self._h, _dp(o)))
+        return o
+
+    def set_option(self, key: str, value: int):
+        _ck(lib().csim_ensemble_set_option(self._h, key.encode(), int(value)))
+
+    def get_option(self, key: str) -> int:
+        v = C.c_long()
+        _ck(lib().csim_ensemble_get_option(self._h, key.encode(), C.byref(v)))
+        return v.value

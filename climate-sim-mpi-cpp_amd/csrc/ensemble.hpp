@@ -1,0 +1,63 @@
+// ensemble.hpp — the batched engine behind csim_ensemble_* (include/csim.h): B members of one grid shape, each with
+// its own field and its own (D, dt, vx, vy), stepped together, every kernel launch covering all members (or all
+// members of one upwind-sign class).
+//
+// Device layout: two allocations (ping / pong), each B member slabs of csim_field's padded layout one after the
+// other, slab = (ny + 2 + 2 GHOST_EXTRA) * pitch doubles, so every member starts 128-byte aligned like a csim_field.
+// Member m's row j = 0 is at  alloc + m * slab + GHOST_EXTRA * pitch.
+#pragma once
+
+#include "internal.hpp"
+
+namespace csim {
+
+// The one depth the batched multi-step sweep is instantiated at (profiles/r04_ensemble_depth.jsonl: full ensembles of
+// 256^2 and 512^2 members, T = 4 against T = 6).  -DCSIM_ENS_T=6 builds the other one for that measurement.
+#ifndef CSIM_ENS_T
+#define CSIM_ENS_T 4
+#endif
+constexpr int ENS_DEPTH = CSIM_ENS_T;
+static_assert(ENS_DEPTH >= 2 && ENS_DEPTH <= MAX_FUSE, "ensemble depth out of range");
+
+// upwind-sign flavour of a member (the launch it belongs to): 3 * cx + cy with per axis 0: v < 0, 1: v >= 0,
+// 2: v == 0 on a screened run (fast_thr > 0 and dx, dy without IEEE division) — exactly how the single stepper's
+// launcher picks k_sweepO_dpp<., ., SX, SY>
+constexpr int ENS_CLASSES = 9;
+inline int ens_sign_class(const Phys& p) {
+    const bool screened = p.div_mode <= 1 && p.fast_thr > 0.0;
+    const int cx = screened && p.vx == 0.0 ? 2 : (p.vx >= 0.0 ? 1 : 0);
+    const int cy = screened && p.vy == 0.0 ? 2 : (p.vy >= 0.0 ? 1 : 0);
+    return 3 * cx + cy;
+}
+
+struct EnsGeom {
+    int members;
+    int nx, ny, pitch;
+    long slab;    // doubles from one member's slab to the next
+    long fin_stride;  // doubles of FinLines per member: left, right (ly each), bottom, top (lx each), all 16-B aligned
+    int ly, lx;   // ny, nx rounded up to even
+    int div_mode;
+    int bc[4];
+    double value;
+};
+
+// per-member device table: one opaque entry per member (Phys + FinLines pointers)
+size_t ens_entry_bytes();
+void ens_entry_fill(void* host_entry, const Phys& p, double* const fin_lines[4]);
+
+// T = ENS_DEPTH steps of the members members[0 .. count) (all of one sign class `cls`) in one launch;
+// fin: last pass of a run, the members' FinLines are written (see FinLines in kernels.hip)
+hipError_t ens_launch_sweepO(const EnsGeom& g, const double* in, double* out, const void* table, const int* members,
+                             int count, int cls, bool fin, hipStream_t st);
+// one step of every member
+hipError_t ens_launch_step(const EnsGeom& g, const double* in, double* out, const void* table, hipStream_t st);
+// apply_boundary of every member into a and b; fin: Neumann ghosts from the members' FinLines
+hipError_t ens_launch_ghost_fill(const EnsGeom& g, double* a, double* b, const void* table, bool fin, hipStream_t st);
+// per-member reductions: `rows` partials per member in `partial` (member-major), finished on the host
+constexpr int ENS_REDUCE_ROWS = 64;
+int ens_reduce_rows(int nrows);
+hipError_t ens_launch_checksum(const EnsGeom& g, const double* f, unsigned long long* partial, hipStream_t st);
+hipError_t ens_launch_minmax(const EnsGeom& g, const double* f, double* partial, hipStream_t st);
+hipError_t ens_launch_sum(const EnsGeom& g, const double* f, double* partial, hipStream_t st);
+
+}  // namespace csim

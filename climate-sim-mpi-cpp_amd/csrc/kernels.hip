@@ -815,6 +815,132 @@ __global__ __launch_bounds__(256) void k_sweepO_dpp(const double* __restrict__ i
     }
 }
 
+// -------------------------------------------------------------------------------------------
+// Ghost fill = unpack of the staged neighbour halos (reference src/halo.cpp:28-43) followed by
+// apply_boundary (reference src/boundary.cpp:12-54) in ONE launch, written to the current
+// field and, when `b` is given, identically to the ping-pong partner so that after the sweep
+// and swap the new field carries the same ghost ring the reference gets from its copy
+// (src/main.cpp:104) + ring copy (src/diffusion.cpp:18-25).
+// The reference fills sides sequentially (left, right, bottom, top), which only matters at the
+// four corners; they are evaluated functionally by one thread from values no other thread of
+// this launch writes.
+// -------------------------------------------------------------------------------------------
+struct GhostDev {
+    int bc[4];
+    int phys[4];
+    double value;
+    const double* recv[4];
+    const double* adj[4];  // != nullptr: the adjacent interior line of that side is read from here, not from `a`
+    int ext_depth;  // > 0: also continue physical edges over that many halo cells (see ghost_extend_cell)
+};
+
+__device__ __forceinline__ size_t at(int i, int j, int pitch) {
+    return static_cast<size_t>(j) * pitch + (LPAD - 1) + i;
+}
+
+// One thread's share of a ghost fill (k_ghost_fill, and k_ensemble_ghost in ensemble.hip): t < ny the two ghost
+// columns of row t + 1, t < nx the two ghost rows of column t + 1, t == max(nx, ny) the four corners.
+__device__ __forceinline__ void ghost_fill_cell(double* __restrict__ a, double* __restrict__ b, int nx, int ny,
+                                                int pitch, const GhostDev& g, int t) {
+    auto put = [&](size_t o, double v) {
+        a[o] = v;
+        if (b) b[o] = v;
+    };
+    if (t < ny) {  // ghost columns at row j = t + 1
+        const int j = t + 1;
+        for (int s = CSIM_LEFT; s <= CSIM_RIGHT; ++s) {
+            const int ig = s == CSIM_LEFT ? 0 : nx + 1;
+            const int ia = s == CSIM_LEFT ? 1 : nx;
+            if (g.phys[s]) {
+                if (g.bc[s] == CSIM_BC_DIRICHLET)
+                    put(at(ig, j, pitch), g.value);
+                else if (g.bc[s] == CSIM_BC_NEUMANN)
+                    put(at(ig, j, pitch), g.adj[s] ? g.adj[s][t] : a[at(ia, j, pitch)]);
+            } else if (g.recv[s]) {
+                put(at(ig, j, pitch), g.recv[s][t]);
+            }
+        }
+    }
+    if (t < nx) {  // ghost rows at column i = t + 1
+        const int i = t + 1;
+        for (int s = CSIM_BOTTOM; s <= CSIM_TOP; ++s) {
+            const int jg = s == CSIM_BOTTOM ? 0 : ny + 1;
+            const int ja = s == CSIM_BOTTOM ? 1 : ny;
+            if (g.phys[s]) {
+                if (g.bc[s] == CSIM_BC_DIRICHLET)
+                    put(at(i, jg, pitch), g.value);
+                else if (g.bc[s] == CSIM_BC_NEUMANN)
+                    put(at(i, jg, pitch), g.adj[s] ? g.adj[s][t] : a[at(i, ja, pitch)]);
+            } else if (g.recv[s]) {
+                put(at(i, jg, pitch), g.recv[s][t]);
+            }
+        }
+    }
+    const int tc = nx > ny ? nx : ny;
+    if (t == tc) {  // the four corners
+        for (int cs = CSIM_LEFT; cs <= CSIM_RIGHT; ++cs) {
+            const int ig = cs == CSIM_LEFT ? 0 : nx + 1;
+            const int ia = cs == CSIM_LEFT ? 1 : nx;
+            for (int rs = CSIM_BOTTOM; rs <= CSIM_TOP; ++rs) {
+                const int jg = rs == CSIM_BOTTOM ? 0 : ny + 1;
+                const int ja = rs == CSIM_BOTTOM ? 1 : ny;
+                const bool row_d = g.phys[rs] && g.bc[rs] == CSIM_BC_DIRICHLET;
+                const bool row_n = g.phys[rs] && g.bc[rs] == CSIM_BC_NEUMANN;
+                const bool col_d = g.phys[cs] && g.bc[cs] == CSIM_BC_DIRICHLET;
+                const bool col_n = g.phys[cs] && g.bc[cs] == CSIM_BC_NEUMANN;
+                if (row_d) {
+                    put(at(ig, jg, pitch), g.value);
+                } else if (row_n) {
+                    // row rule copies the already column-filled ghost cell (ig, ja)
+                    double v;
+                    if (col_d)
+                        v = g.value;
+                    else if (col_n)
+                        v = g.adj[cs] ? g.adj[cs][ja - 1] : a[at(ia, ja, pitch)];
+                    else if (!g.phys[cs] && g.recv[cs])
+                        v = g.recv[cs][ja - 1];
+                    else
+                        v = a[at(ig, ja, pitch)];
+                    put(at(ig, jg, pitch), v);
+                } else if (col_d) {
+                    put(at(ig, jg, pitch), g.value);
+                } else if (col_n) {
+                    // column rule copies ghost-row cell (ia, jg): stable (periodic) or just received
+                    double v;
+                    if (!g.phys[rs] && g.recv[rs])
+                        v = g.recv[rs][ia - 1];
+                    else
+                        v = a[at(ia, jg, pitch)];
+                    put(at(ig, jg, pitch), v);
+                }
+            }
+        }
+    }
+}
+
+// ---- wavefront-level reductions --------------------------------------------------------------
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fmin(v, __shfl_xor(v, m, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
+    return v;
+}
+
+// ensemble.hip includes this file for the device code above (the per-cell update, the march and its bodies, the ghost
+// fill rule, the wavefront reductions) and stops
+// here: everything below — launchers, the other kernels, the split-build instantiations — is defined once, in the
+// translation units built from this file itself.
+#ifndef CSIM_SWEEP_CORE_ONLY
+
 // ============================================================================================
 // launcher of the overlapped-strip sweep (templates; see the split-build note below)
 // ============================================================================================
@@ -1151,29 +1277,6 @@ __global__ void k_fill(double* __restrict__ f, int nx, int ny, int pitch, double
     if (i < nx + 2) f[static_cast<size_t>(j) * pitch + (LPAD - 1) + i] = v;
 }
 
-// -------------------------------------------------------------------------------------------
-// Ghost fill = unpack of the staged neighbour halos (reference src/halo.cpp:28-43) followed by
-// apply_boundary (reference src/boundary.cpp:12-54) in ONE launch, written to the current
-// field and, when `b` is given, identically to the ping-pong partner so that after the sweep
-// and swap the new field carries the same ghost ring the reference gets from its copy
-// (src/main.cpp:104) + ring copy (src/diffusion.cpp:18-25).
-// The reference fills sides sequentially (left, right, bottom, top), which only matters at the
-// four corners; they are evaluated functionally by one thread from values no other thread of
-// this launch writes.
-// -------------------------------------------------------------------------------------------
-struct GhostDev {
-    int bc[4];
-    int phys[4];
-    double value;
-    const double* recv[4];
-    const double* adj[4];  // != nullptr: the adjacent interior line of that side is read from here, not from `a`
-    int ext_depth;  // > 0: also continue physical edges over that many halo cells (see ghost_extend_cell)
-};
-
-__device__ __forceinline__ size_t at(int i, int j, int pitch) {
-    return static_cast<size_t>(j) * pitch + (LPAD - 1) + i;
-}
-
 // apply_boundary on the HALO part of a physical side: where a Dirichlet/Neumann edge meets a
 // neighbour side, the ghost line continues over the H halo cells that came from that neighbour
 // (globally, they are the neighbour's own ghost cells of the same physical edge).  t = 8
@@ -1204,85 +1307,13 @@ __global__ __launch_bounds__(256) void k_ghost_fill(double* __restrict__ a, doub
                                                     int nx, int ny, int pitch, GhostDev g) {
     __builtin_amdgcn_s_setprio(3);  // short latency-critical kernel, usually sharing the SIMDs with a bulk sweep
     const int t = blockIdx.x * 256 + threadIdx.x;
-    auto put = [&](size_t o, double v) {
-        a[o] = v;
-        if (b) b[o] = v;
-    };
-    if (t < ny) {  // ghost columns at row j = t + 1
-        const int j = t + 1;
-        for (int s = CSIM_LEFT; s <= CSIM_RIGHT; ++s) {
-            const int ig = s == CSIM_LEFT ? 0 : nx + 1;
-            const int ia = s == CSIM_LEFT ? 1 : nx;
-            if (g.phys[s]) {
-                if (g.bc[s] == CSIM_BC_DIRICHLET)
-                    put(at(ig, j, pitch), g.value);
-                else if (g.bc[s] == CSIM_BC_NEUMANN)
-                    put(at(ig, j, pitch), g.adj[s] ? g.adj[s][t] : a[at(ia, j, pitch)]);
-            } else if (g.recv[s]) {
-                put(at(ig, j, pitch), g.recv[s][t]);
-            }
-        }
-    }
-    if (t < nx) {  // ghost rows at column i = t + 1
-        const int i = t + 1;
-        for (int s = CSIM_BOTTOM; s <= CSIM_TOP; ++s) {
-            const int jg = s == CSIM_BOTTOM ? 0 : ny + 1;
-            const int ja = s == CSIM_BOTTOM ? 1 : ny;
-            if (g.phys[s]) {
-                if (g.bc[s] == CSIM_BC_DIRICHLET)
-                    put(at(i, jg, pitch), g.value);
-                else if (g.bc[s] == CSIM_BC_NEUMANN)
-                    put(at(i, jg, pitch), g.adj[s] ? g.adj[s][t] : a[at(i, ja, pitch)]);
-            } else if (g.recv[s]) {
-                put(at(i, jg, pitch), g.recv[s][t]);
-            }
-        }
-    }
     const int tc = nx > ny ? nx : ny;
     if (g.ext_depth > 0 && t > tc && t <= tc + 8 * g.ext_depth) {
         // (same values as the corner thread wherever the two overlap, so the order is immaterial)
         ghost_extend_cell(a, nx, ny, pitch, g.ext_depth, g.bc, g.phys, g.value, t - tc - 1);
         return;
     }
-    if (t == tc) {  // the four corners
-        for (int cs = CSIM_LEFT; cs <= CSIM_RIGHT; ++cs) {
-            const int ig = cs == CSIM_LEFT ? 0 : nx + 1;
-            const int ia = cs == CSIM_LEFT ? 1 : nx;
-            for (int rs = CSIM_BOTTOM; rs <= CSIM_TOP; ++rs) {
-                const int jg = rs == CSIM_BOTTOM ? 0 : ny + 1;
-                const int ja = rs == CSIM_BOTTOM ? 1 : ny;
-                const bool row_d = g.phys[rs] && g.bc[rs] == CSIM_BC_DIRICHLET;
-                const bool row_n = g.phys[rs] && g.bc[rs] == CSIM_BC_NEUMANN;
-                const bool col_d = g.phys[cs] && g.bc[cs] == CSIM_BC_DIRICHLET;
-                const bool col_n = g.phys[cs] && g.bc[cs] == CSIM_BC_NEUMANN;
-                if (row_d) {
-                    put(at(ig, jg, pitch), g.value);
-                } else if (row_n) {
-                    // row rule copies the already column-filled ghost cell (ig, ja)
-                    double v;
-                    if (col_d)
-                        v = g.value;
-                    else if (col_n)
-                        v = g.adj[cs] ? g.adj[cs][ja - 1] : a[at(ia, ja, pitch)];
-                    else if (!g.phys[cs] && g.recv[cs])
-                        v = g.recv[cs][ja - 1];
-                    else
-                        v = a[at(ig, ja, pitch)];
-                    put(at(ig, jg, pitch), v);
-                } else if (col_d) {
-                    put(at(ig, jg, pitch), g.value);
-                } else if (col_n) {
-                    // column rule copies ghost-row cell (ia, jg): stable (periodic) or just received
-                    double v;
-                    if (!g.phys[rs] && g.recv[rs])
-                        v = g.recv[rs][ia - 1];
-                    else
-                        v = a[at(ia, jg, pitch)];
-                    put(at(ig, jg, pitch), v);
-                }
-            }
-        }
-    }
+    ghost_fill_cell(a, b, nx, ny, pitch, g, t);
 }
 
 // The four edge lines of the NEXT field, computed from the current one and written directly
@@ -1402,23 +1433,7 @@ __global__ __launch_bounds__(256) void k_gaussian(double* __restrict__ f, int nx
     f[at(i + 1, j + 1, pitch)] = A * exp(-r2 / (2.0 * sig * sig));
 }
 
-// ---- wavefront-level reductions --------------------------------------------------------------
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmin(v, __shfl_xor(v, m, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
-}
-
+// ---- reductions (wave_min / wave_max / wave_sum: above, shared with ensemble.hip) ------------
 // KIND 0: min/max over i0..i1, j0..j1 ; KIND 1: sum ; KIND 2: max |a-b|
 template <int KIND>
 __global__ __launch_bounds__(256) void k_reduce(const double* __restrict__ a,
@@ -1691,5 +1706,6 @@ hipError_t launch_checksum(const double* f, int nx, int ny, int pitch, long x_of
 }
 
 #endif  // !CSIM_INST_T
+#endif  // !CSIM_SWEEP_CORE_ONLY
 
 }  // namespace csim

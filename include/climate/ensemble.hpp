@@ -1,0 +1,87 @@
+// include/climate/ensemble.hpp — RAII handle of the batched stepper (csim_ensemble_* in include/csim.h): B members of
+// one grid shape, each with its own field and (D, dt, vx, vy), advanced together on one GPU.  Every member ends bit
+// for bit where a single-rank climate::Stepper run with its own parameters would.  Calls only the C ABI.
+#pragma once
+#include <cstddef>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "csim.h"
+
+namespace climate {
+
+class Ensemble {
+public:
+    Ensemble(int members, int nx, int ny, double dx, double dy, const int bc[4], double bc_value = 0.0)
+        : members_(members), nx_(nx), ny_(ny) {
+        check(csim_ensemble_create(members, nx, ny, 1, dx, dy, bc, bc_value, &h_));
+    }
+    ~Ensemble() { csim_ensemble_destroy(h_); }
+    Ensemble(const Ensemble&) = delete;
+    Ensemble& operator=(const Ensemble&) = delete;
+
+    int members() const { return members_; }
+    std::size_t member_size() const { return static_cast<std::size_t>(nx_ + 2) * static_cast<std::size_t>(ny_ + 2); }
+
+    // reference layout with the ghost ring, (ny+2) x (nx+2) per member; the _all forms: members x that, contiguous
+    void upload(int member, const std::vector<double>& a) { check(csim_ensemble_upload(h_, member, sized(a, 1))); }
+    void upload_all(const std::vector<double>& a) { check(csim_ensemble_upload_all(h_, sized(a, members_))); }
+    std::vector<double> download(int member) {
+        std::vector<double> a(member_size());
+        check(csim_ensemble_download(h_, member, a.data()));
+        return a;
+    }
+    std::vector<double> download_all() {
+        std::vector<double> a(member_size() * members_);
+        check(csim_ensemble_download_all(h_, a.data()));
+        return a;
+    }
+    void init_gaussian(int member, double A, double sigma_frac, double xc_frac, double yc_frac) {
+        check(csim_ensemble_init_gaussian(h_, member, A, sigma_frac, xc_frac, yc_frac));
+    }
+    // one value per member each (dt as given: clamp with csim_safe_dt)
+    void set_physics(const std::vector<double>& D, const std::vector<double>& dt, const std::vector<double>& vx,
+                     const std::vector<double>& vy) {
+        const std::size_t n = static_cast<std::size_t>(members_);
+        if (D.size() != n || dt.size() != n || vx.size() != n || vy.size() != n)
+            throw std::invalid_argument("set_physics: one value per member");
+        check(csim_ensemble_set_physics(h_, D.data(), dt.data(), vx.data(), vy.data()));
+    }
+    void run(int nsteps) { check(csim_ensemble_run(h_, nsteps)); }
+    void sync() { check(csim_ensemble_sync(h_)); }
+    std::vector<unsigned long long> checksums() {
+        std::vector<unsigned long long> c(static_cast<std::size_t>(members_));
+        check(csim_ensemble_checksum(h_, c.data()));
+        return c;
+    }
+    std::vector<double> minmax() {  // min, max per member (ghosts included)
+        std::vector<double> m(2 * static_cast<std::size_t>(members_));
+        check(csim_ensemble_minmax(h_, m.data()));
+        return m;
+    }
+    std::vector<double> sums() {
+        std::vector<double> s(static_cast<std::size_t>(members_));
+        check(csim_ensemble_sum(h_, s.data()));
+        return s;
+    }
+    void set_option(const char* key, long value) { check(csim_ensemble_set_option(h_, key, value)); }
+    long get_option(const char* key) const {
+        long v = 0;
+        check(csim_ensemble_get_option(h_, key, &v));
+        return v;
+    }
+
+private:
+    static void check(int rc) {
+        if (rc != CSIM_OK) throw std::runtime_error(std::string("csim: ") + csim_last_error());
+    }
+    const double* sized(const std::vector<double>& a, int n) const {
+        if (a.size() != member_size() * static_cast<std::size_t>(n)) throw std::invalid_argument("ensemble: array size");
+        return a.data();
+    }
+    csim_ensemble* h_ = nullptr;
+    int members_, nx_, ny_;
+};
+
+}  // namespace climate

@@ -271,6 +271,51 @@ int csim_stepper_kernel_time(csim_stepper* s, int steps_per_launch, double* tota
 int csim_stepper_comm_time(csim_stepper* s, double* total_ms, long* passes);
 int csim_stepper_reset_timers(csim_stepper* s);
 
+/* ---- ensemble: many small fields on one GPU ------------------------------------------------ */
+/* B members share grid shape, spacing, boundary types and boundary value; each has its own field and its own
+ * (D, dt, vx, vy).  A run advances every member exactly as csim_stepper_run advances a single-rank stepper holding
+ * that member's field with its parameters (bit for bit, ghost ring included), with a few launches per pass for the
+ * whole batch.  Host arrays use the reference layout per member; the _all variants take members x (ny+2) x (nx+2)
+ * contiguous doubles.  One handle per GPU, not thread-safe.  Multi-rank members, per-member boundary types and the
+ * "contract" mode are not supported. */
+typedef struct csim_ensemble csim_ensemble;
+int csim_ensemble_create(int members, int nx, int ny, int halo, double dx, double dy, const int bc[4],
+                         double bc_value, csim_ensemble** out); /* zero-filled fields */
+int csim_ensemble_destroy(csim_ensemble* e);
+int csim_ensemble_upload(csim_ensemble* e, int member, const double* host_with_ghosts);
+int csim_ensemble_download(csim_ensemble* e, int member, double* host_with_ghosts);
+int csim_ensemble_upload_all(csim_ensemble* e, const double* host);
+int csim_ensemble_download_all(csim_ensemble* e, double* host);
+/* gaussian hotspot of one member, on the device, as csim_stepper_init_gaussian on one rank: the member's whole array,
+ * ghost ring included, is zeroed first, in both ping-pong buffers */
+int csim_ensemble_init_gaussian(csim_ensemble* e, int member, double A, double sigma_frac, double xc_frac,
+                                double yc_frac);
+/* one value per member each; dt is used as given (clamp with csim_safe_dt), it must be finite */
+int csim_ensemble_set_physics(csim_ensemble* e, const double* D, const double* dt, const double* vx, const double* vy);
+/* nsteps reference steps of every member, enqueued without host syncs: csim_ensemble_plan's passes */
+int csim_ensemble_run(csim_ensemble* e, int nsteps);
+int csim_ensemble_sync(csim_ensemble* e);
+/* per member, each in one launch for the whole batch: csim_stepper_checksum's value of a one-rank stepper holding the
+ * member's field (out[B]); min and max over the whole array, ghosts included (out[2B]: min, max of member 0, ...); the
+ * sum over the interior (out[B]: per-block partial sums added in a fixed order, so the same field gives the same bits
+ * every time; it may differ from another summation order in the last bits) */
+int csim_ensemble_checksum(csim_ensemble* e, unsigned long long* out);
+int csim_ensemble_minmax(csim_ensemble* e, double* out);
+int csim_ensemble_sum(csim_ensemble* e, double* out);
+/* options (unknown keys: CSIM_ERR_ARG; "contract": CSIM_ERR_UNSUPPORTED), results never depend on them:
+ *   "fuse"        -1 (default) passes of the ensemble depth where the grid allows; 0 / 1 single steps only
+ *   "fused_2c"    0/1 (default 1), as for csim_stepper_set_option
+ *   "depth_used"  read-only: time steps per pass of the last run (1 = single steps only) */
+int csim_ensemble_set_option(csim_ensemble* e, const char* key, long value);
+int csim_ensemble_get_option(const csim_ensemble* e, const char* key, long* value);
+/* host-only pass planner of csim_ensemble_run: out[0] = steps per fused pass (1: none; members with nx or ny below
+ * the depth step singly), out[1] = fused passes, out[2] = single steps after them (nsteps = out[1] out[0] + out[2]) */
+int csim_ensemble_plan(int nsteps, int nx, int ny, int fuse, int out[3]);
+/* host-only: the launch (upwind-sign class 0..8) a member with these parameters belongs to, and the number of
+ * launches per pass of a batch with the given classes */
+int csim_ensemble_sign_class(double dx, double dy, double D, double dt, double vx, double vy, int fused_2c, int* cls);
+int csim_ensemble_classes(int members, const int* cls, int* nlaunches);
+
 #ifdef __cplusplus
 }
 #endif
