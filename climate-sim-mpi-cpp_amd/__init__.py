@@ -13,6 +13,7 @@ calls raise.  (The directory name contains '-', so import it through
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -164,6 +165,9 @@ def lib() -> C.CDLL:
         "csim_ensemble_checksum": (i, [vp, C.POINTER(C.c_ulonglong)]),
         "csim_ensemble_minmax": (i, [vp, dp]),
         "csim_ensemble_sum": (i, [vp, dp]),
+        "csim_ensemble_stats": (i, [vp, i, dp, dp, dp, dp]),
+        "csim_ensemble_stats_begin": (i, [vp, i]),
+        "csim_ensemble_stats_wait": (i, [vp, C.POINTER(dp), C.POINTER(dp), C.POINTER(dp), C.POINTER(dp)]),
         "csim_ensemble_set_option": (i, [vp, C.c_char_p, C.c_long]),
         "csim_ensemble_get_option": (i, [vp, C.c_char_p, C.POINTER(C.c_long)]),
         "csim_ensemble_plan": (i, [i, i, i, i, ip]),
@@ -532,6 +536,10 @@ def ensemble_launches(classes) -> int:
     return n.value
 
 
+EnsembleStats = collections.namedtuple("EnsembleStats", "mean var min max")
+EnsembleStats.__doc__ = """per-cell statistics over an ensemble's members, (ny+2, nx+2) each, ghost ring included"""
+
+
 class Ensemble:
     """B members of one grid shape (own field, own D, dt, vx, vy each) stepped together on one GPU; every member
     ends bit-identical to a single-rank Stepper run with its own parameters (csim_ensemble_*)."""
@@ -598,6 +606,24 @@ class Ensemble:
         o = np.empty(self.members)
         _ck(lib().csim_ensemble_sum(self._h, _dp(o)))
         return o
+
+    def stats(self, ddof=1) -> EnsembleStats:
+        """per-cell mean, variance (divided by members - ddof), min and max over the members: numpy's mean, var,
+        fmin.reduce and fmax.reduce over the member axis, bit for bit (csim_ensemble_stats)"""
+        out = EnsembleStats(*[np.empty((self.ny + 2, self.nx + 2)) for _ in range(4)])
+        _ck(lib().csim_ensemble_stats(self._h, int(ddof), *[_dp(a) for a in out]))
+        return out
+
+    def stats_begin(self, ddof=1):
+        """start stats() of the current state without waiting; run() may follow before stats_wait()"""
+        _ck(lib().csim_ensemble_stats_begin(self._h, int(ddof)))
+
+    def stats_wait(self) -> EnsembleStats:
+        """the statistics stats_begin() captured (copies)"""
+        ptrs = [C.POINTER(C.c_double)() for _ in range(4)]
+        _ck(lib().csim_ensemble_stats_wait(self._h, *[C.byref(p) for p in ptrs]))
+        shape = (self.ny + 2, self.nx + 2)
+        return EnsembleStats(*[np.ctypeslib.as_array(p, shape=shape).copy() for p in ptrs])
 
     def set_option(self, key: str, value: int):
         _ck(lib().csim_ensemble_set_option(self._h, key.encode(), int(value)))

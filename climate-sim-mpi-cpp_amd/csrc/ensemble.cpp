@@ -28,6 +28,13 @@ struct csim_ensemble {
     int class_off[ENS_CLASSES + 1] = {};
     bool ring_ok = false;             // ghost rings filled and static (no Neumann side)
     int fuse = -1, fused_2c = 1, depth_used = 0;
+    // per-cell statistics (csim_ensemble_stats*), created on first use: the kernel's output (mean, var, min, max),
+    // its pinned host copy, and the stream that copies it while the ensemble steps on
+    double* stats_d = nullptr;
+    double* stats_h = nullptr;
+    hipStream_t s_io = nullptr;
+    hipEvent_t ev_stats = nullptr;
+    bool stats_pending = false;
 
     double* view(int buf, int m) const {
         return alloc[buf] + static_cast<size_t>(m) * g.slab + static_cast<size_t>(GHOST_EXTRA) * g.pitch;
@@ -67,6 +74,25 @@ int ensure_tables(csim_ensemble* e) {
     CSIM_HIP(hipMemcpyAsync(e->order, order.data(), sizeof(int) * B, hipMemcpyHostToDevice, e->st));
     CSIM_HIP(hipStreamSynchronize(e->st));  // the host vectors go out of scope
     e->dirty = false;
+    return CSIM_OK;
+}
+
+size_t stats_cells(const csim_ensemble* e) { return static_cast<size_t>(e->g.nx + 2) * (e->g.ny + 2); }
+
+// checks ddof, makes the statistics' resources, lets an in-flight copy finish (it reads stats_d), and enqueues the
+// kernel on the ensemble's stream after everything enqueued so far
+int stats_launch(csim_ensemble* e, int ddof) {
+    CSIM_REQUIRE(ddof == 0 || ddof == 1, "ddof must be 0 or 1");
+    CSIM_REQUIRE(e->g.members - ddof >= 1, "members - ddof must be >= 1");
+    CSIM_REQUIRE(stats_cells(e) <= 0x7fffff00u, "grid too large for the statistics");
+    const size_t bytes = 4 * sizeof(double) * stats_cells(e);
+    // each piece is created once; a failed allocation is reported and retried by the next call
+    if (!e->s_io) CSIM_HIP(hipStreamCreateWithFlags(&e->s_io, hipStreamNonBlocking));
+    if (!e->ev_stats) CSIM_HIP(hipEventCreateWithFlags(&e->ev_stats, hipEventDisableTiming));
+    if (!e->stats_d) CSIM_HIP(hipMalloc(reinterpret_cast<void**>(&e->stats_d), bytes));
+    if (!e->stats_h) CSIM_HIP(hipHostMalloc(reinterpret_cast<void**>(&e->stats_h), bytes, hipHostMallocDefault));
+    if (e->stats_pending) CSIM_HIP(hipStreamSynchronize(e->s_io));
+    CSIM_HIP(ens_launch_stats(e->g, e->base(e->cur), ddof, e->stats_d, e->st));
     return CSIM_OK;
 }
 
@@ -157,6 +183,11 @@ int csim_ensemble_create(int members, int nx, int ny, int halo, double dx, doubl
 int csim_ensemble_destroy(csim_ensemble* e) {
     if (!e) return CSIM_OK;
     if (e->st) (void)hipStreamSynchronize(e->st);
+    if (e->s_io) (void)hipStreamSynchronize(e->s_io);
+    if (e->stats_d) (void)hipFree(e->stats_d);
+    if (e->stats_h) (void)hipHostFree(e->stats_h);
+    if (e->ev_stats) (void)hipEventDestroy(e->ev_stats);
+    if (e->s_io) (void)hipStreamDestroy(e->s_io);
     for (double* a : e->alloc)
         if (a) (void)hipFree(a);
     if (e->fin) (void)hipFree(e->fin);
@@ -338,6 +369,46 @@ int csim_ensemble_sum(csim_ensemble* e, double* out) {
         for (int k = 1; k < R; ++k) acc += h[static_cast<size_t>(m) * R + k];
         out[m] = acc;
     }
+    return CSIM_OK;
+}
+
+int csim_ensemble_stats(csim_ensemble* e, int ddof, double* mean, double* var, double* min, double* max) {
+    CSIM_REQUIRE(e, "null ensemble");
+    int rc = stats_launch(e, ddof);
+    if (rc) return rc;
+    const size_t n = stats_cells(e);
+    double* const outs[4] = {mean, var, min, max};
+    for (int k = 0; k < 4; ++k)
+        if (outs[k])
+            CSIM_HIP(hipMemcpyAsync(outs[k], e->stats_d + k * n, sizeof(double) * n, hipMemcpyDeviceToHost, e->st));
+    CSIM_HIP(hipStreamSynchronize(e->st));
+    return CSIM_OK;
+}
+
+// As csim_stepper_snapshot_begin: the kernel runs in stream order on the ensemble's stream (the sweeps after it write
+// the other buffer first, and never stats_d), and only the copy to the pinned buffer goes to s_io, so the next run
+// does not wait for it.
+int csim_ensemble_stats_begin(csim_ensemble* e, int ddof) {
+    CSIM_REQUIRE(e, "null ensemble");
+    int rc = stats_launch(e, ddof);
+    if (rc) return rc;
+    CSIM_HIP(hipEventRecord(e->ev_stats, e->st));
+    CSIM_HIP(hipStreamWaitEvent(e->s_io, e->ev_stats, 0));
+    CSIM_HIP(hipMemcpyAsync(e->stats_h, e->stats_d, 4 * sizeof(double) * stats_cells(e), hipMemcpyDeviceToHost,
+                            e->s_io));
+    e->stats_pending = true;
+    return CSIM_OK;
+}
+
+int csim_ensemble_stats_wait(csim_ensemble* e, const double** mean, const double** var, const double** min,
+                             const double** max) {
+    CSIM_REQUIRE(e, "null ensemble");
+    if (!e->stats_pending) return fail(CSIM_ERR_STATE, "no statistics in flight: csim_ensemble_stats_begin first");
+    CSIM_HIP(hipStreamSynchronize(e->s_io));
+    e->stats_pending = false;
+    const double** const outs[4] = {mean, var, min, max};
+    for (int k = 0; k < 4; ++k)
+        if (outs[k]) *outs[k] = e->stats_h + k * stats_cells(e);
     return CSIM_OK;
 }
 

@@ -60,4 +60,9 @@ hipError_t ens_launch_checksum(const EnsGeom& g, const double* f, unsigned long 
 hipError_t ens_launch_minmax(const EnsGeom& g, const double* f, double* partial, hipStream_t st);
 hipError_t ens_launch_sum(const EnsGeom& g, const double* f, double* partial, hipStream_t st);
 
+// per-cell statistics over all members (ensemble_stats.hip), one launch: out = mean, var (divided by members - ddof),
+// min, max, each dense (ny+2) x (nx+2); members beyond STATS_LDS_MEMBERS are read twice
+constexpr int STATS_LDS_MEMBERS = 320;  // 320 x 64 cells x 8 B = 160 KiB of LDS
+hipError_t ens_launch_stats(const EnsGeom& g, const double* f, int ddof, double* out, hipStream_t st);
+
 }  // namespace csim

@@ -11,6 +11,11 @@
 
 namespace climate {
 
+// per-cell statistics over the members, each member_size() values in the reference layout (see csim_ensemble_stats)
+struct EnsembleStats {
+    std::vector<double> mean, var, min, max;
+};
+
 class Ensemble {
 public:
     Ensemble(int members, int nx, int ny, double dx, double dy, const int bc[4], double bc_value = 0.0)
@@ -64,6 +69,23 @@ public:
         std::vector<double> s(static_cast<std::size_t>(members_));
         check(csim_ensemble_sum(h_, s.data()));
         return s;
+    }
+    EnsembleStats stats(int ddof = 1) {
+        EnsembleStats r;
+        for (std::vector<double>* v : {&r.mean, &r.var, &r.min, &r.max}) v->resize(member_size());
+        check(csim_ensemble_stats(h_, ddof, r.mean.data(), r.var.data(), r.min.data(), r.max.data()));
+        return r;
+    }
+    // captured after everything enqueued so far; run() may be called before stats_wait()
+    void stats_begin(int ddof = 1) { check(csim_ensemble_stats_begin(h_, ddof)); }
+    // host pointers of member_size() values each, valid until the next stats_begin() or destruction
+    struct StatsView {
+        const double *mean, *var, *min, *max;
+    };
+    StatsView stats_wait() {
+        StatsView v{};
+        check(csim_ensemble_stats_wait(h_, &v.mean, &v.var, &v.min, &v.max));
+        return v;
     }
     void set_option(const char* key, long value) { check(csim_ensemble_set_option(h_, key, value)); }
     long get_option(const char* key) const {

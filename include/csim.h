@@ -302,6 +302,19 @@ int csim_ensemble_sync(csim_ensemble* e);
 int csim_ensemble_checksum(csim_ensemble* e, unsigned long long* out);
 int csim_ensemble_minmax(csim_ensemble* e, double* out);
 int csim_ensemble_sum(csim_ensemble* e, double* out);
+/* per-cell statistics over the members, one launch for the whole batch: mean, variance (divided by members - ddof,
+ * ddof 0 or 1, members - ddof >= 1), min and max, each in the reference layout (ny+2) x (nx+2), ghost ring included.
+ * Bit for bit: s = +0, s += x_k in member order, mean = s / B; q = +0, q += (x_k - mean)^2 in member order,
+ * var = q / (B - ddof); fmin / fmax in member order (NaN members skipped unless all are NaN) -- numpy's mean, var,
+ * fmin.reduce and fmax.reduce over axis 0.  Any output may be NULL (not copied); synchronous.  No set_physics needed. */
+int csim_ensemble_stats(csim_ensemble* e, int ddof, double* mean, double* var, double* min, double* max);
+/* the same, captured without stalling: computed on the ensemble's stream after everything enqueued so far, copied to
+ * pinned host buffers on a second stream; csim_ensemble_run may be called meanwhile.  A _begin while one is in flight
+ * first waits for it. */
+int csim_ensemble_stats_begin(csim_ensemble* e, int ddof);
+/* pointers stay valid until the next _begin or destroy (any may be NULL); CSIM_ERR_STATE when nothing is in flight */
+int csim_ensemble_stats_wait(csim_ensemble* e, const double** mean, const double** var, const double** min,
+                             const double** max);
 /* options (unknown keys: CSIM_ERR_ARG; "contract": CSIM_ERR_UNSUPPORTED), results never depend on them:
  *   "fuse"        -1 (default) passes of the ensemble depth where the grid allows; 0 / 1 single steps only
  *   "fused_2c"    0/1 (default 1), as for csim_stepper_set_option
