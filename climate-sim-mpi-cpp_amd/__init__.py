@@ -168,6 +168,10 @@ def lib() -> C.CDLL:
         "csim_ensemble_stats": (i, [vp, i, dp, dp, dp, dp]),
         "csim_ensemble_stats_begin": (i, [vp, i]),
         "csim_ensemble_stats_wait": (i, [vp, C.POINTER(dp), C.POINTER(dp), C.POINTER(dp), C.POINTER(dp)]),
+        "csim_ensemble_quantiles": (i, [vp, i, dp, i, dp, dp, dp]),
+        "csim_ensemble_quantiles_begin": (i, [vp, i, dp, i, dp]),
+        "csim_ensemble_quantiles_wait": (i, [vp, C.POINTER(dp), C.POINTER(dp)]),
+        "csim_ensemble_quantile_plan": (i, [i, i, dp, ip, ip, dp]),
         "csim_ensemble_set_option": (i, [vp, C.c_char_p, C.c_long]),
         "csim_ensemble_get_option": (i, [vp, C.c_char_p, C.POINTER(C.c_long)]),
         "csim_ensemble_plan": (i, [i, i, i, i, ip]),
@@ -536,8 +540,26 @@ def ensemble_launches(classes) -> int:
     return n.value
 
 
+def ensemble_quantile_plan(members: int, q):
+    """numpy's "linear" (lo, hi, gamma) of each level q for this many members, as lists — host only"""
+    qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+    n = len(qs)
+    lo, hi, g = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), np.empty(max(n, 1))
+    _ck(lib().csim_ensemble_quantile_plan(int(members), n, _dp(qs), lo, hi, _dp(g)))
+    return list(lo[:n]), list(hi[:n]), [float(v) for v in g[:n]]
+
+
 EnsembleStats = collections.namedtuple("EnsembleStats", "mean var min max")
 EnsembleStats.__doc__ = """per-cell statistics over an ensemble's members, (ny+2, nx+2) each, ghost ring included"""
+
+
+EnsembleQuantiles = collections.namedtuple("EnsembleQuantiles", "q exceed")
+EnsembleQuantiles.__doc__ = """per-cell quantiles (nq, ny+2, nx+2) and exceedance probabilities (nt, ny+2, nx+2) over an
+ensemble's members, ghost ring included"""
+
+
+def _levels(v):
+    return np.ascontiguousarray(np.atleast_1d(np.asarray(v, dtype=np.float64)))
 
 
 class Ensemble:
@@ -546,6 +568,7 @@ class Ensemble:
 
     def __init__(self, members, nx, ny, dx=1.0, dy=1.0, bc=(0, 0, 0, 0), bc_value=0.0):
         self.members, self.nx, self.ny = members, nx, ny
+        self._q_counts = (0, 0)  # levels and thresholds of the last quantiles_begin()
         h = C.c_void_p()
         _ck(lib().csim_ensemble_create(members, nx, ny, 1, dx, dy, _i4(bc), bc_value, C.byref(h)))
         self._h = h
@@ -624,6 +647,29 @@ class Ensemble:
         _ck(lib().csim_ensemble_stats_wait(self._h, *[C.byref(p) for p in ptrs]))
         shape = (self.ny + 2, self.nx + 2)
         return EnsembleStats(*[np.ctypeslib.as_array(p, shape=shape).copy() for p in ptrs])
+
+    def quantiles(self, q, thresholds=()) -> EnsembleQuantiles:
+        """per-cell np.quantile(members, q, axis=0) (method "linear"; NaN where a member is NaN) and
+        np.mean(members > t, axis=0) for each threshold t (csim_ensemble_quantiles)"""
+        qs, ts = _levels(q), _levels(thresholds)
+        shape = (self.ny + 2, self.nx + 2)
+        out = EnsembleQuantiles(np.empty((len(qs),) + shape), np.empty((len(ts),) + shape))
+        _ck(lib().csim_ensemble_quantiles(self._h, len(qs), _dp(qs), len(ts), _dp(ts), _dp(out.q), _dp(out.exceed)))
+        return out
+
+    def quantiles_begin(self, q, thresholds=()):
+        """start quantiles() of the current state without waiting; run() may follow before quantiles_wait()"""
+        qs, ts = _levels(q), _levels(thresholds)
+        _ck(lib().csim_ensemble_quantiles_begin(self._h, len(qs), _dp(qs), len(ts), _dp(ts)))
+        self._q_counts = (len(qs), len(ts))
+
+    def quantiles_wait(self) -> EnsembleQuantiles:
+        """the quantiles quantiles_begin() captured (copies)"""
+        pq, pp = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
+        _ck(lib().csim_ensemble_quantiles_wait(self._h, C.byref(pq), C.byref(pp)))
+        shape = (self.ny + 2, self.nx + 2)
+        return EnsembleQuantiles(*[np.ctypeslib.as_array(p, shape=(n,) + shape).copy() if n else np.empty((0,) + shape)
+                                   for p, n in zip((pq, pp), self._q_counts)])
 
     def set_option(self, key: str, value: int):
         _ck(lib().csim_ensemble_set_option(self._h, key.encode(), int(value)))

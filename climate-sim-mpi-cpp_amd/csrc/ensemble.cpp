@@ -35,6 +35,15 @@ struct csim_ensemble {
     hipStream_t s_io = nullptr;
     hipEvent_t ev_stats = nullptr;
     bool stats_pending = false;
+    // per-cell quantiles (csim_ensemble_quantiles*), the same pieces with a copy stream of their own, so that neither
+    // kind of capture waits for the other's copy; the buffers grow when a call needs more fields
+    double* q_d = nullptr;
+    double* q_h = nullptr;
+    int q_dcap = 0, q_hcap = 0;  // fields each buffer holds
+    int q_nq = 0;                // levels of the capture in flight (its exceedance fields follow them in q_h)
+    hipStream_t s_qio = nullptr;
+    hipEvent_t ev_q = nullptr;
+    bool q_pending = false;
 
     double* view(int buf, int m) const {
         return alloc[buf] + static_cast<size_t>(m) * g.slab + static_cast<size_t>(GHOST_EXTRA) * g.pitch;
@@ -93,6 +102,73 @@ int stats_launch(csim_ensemble* e, int ddof) {
     if (!e->stats_h) CSIM_HIP(hipHostMalloc(reinterpret_cast<void**>(&e->stats_h), bytes, hipHostMallocDefault));
     if (e->stats_pending) CSIM_HIP(hipStreamSynchronize(e->s_io));
     CSIM_HIP(ens_launch_stats(e->g, e->base(e->cur), ddof, e->stats_d, e->st));
+    return CSIM_OK;
+}
+
+// numpy's "linear" plan of level q for n values (np.quantile; numpy/lib/_function_base_impl.py, _QuantileMethods
+// ['linear'], _get_indexes, _get_gamma): v = (n - 1) q; at or past the last index both neighbours are the last one and
+// gamma = v + 1 (numpy's index -1); q is in [0, 1], so v is never below 0
+void quantile_plan(int n, double q, int* lo, int* hi, double* gamma) {
+    const double v = static_cast<double>(n - 1) * q;
+    if (v >= static_cast<double>(n - 1)) {
+        *lo = *hi = n - 1;
+        *gamma = v - (-1.0);
+    } else {
+        const double f = std::floor(v);
+        *lo = static_cast<int>(f);
+        *hi = *lo + 1;
+        *gamma = v - f;
+    }
+}
+
+int check_levels(int nq, const double* q) {
+    CSIM_REQUIRE(nq >= 0 && nq <= QUANT_MAX_LEVELS, "nq must be 0 .. 16");
+    CSIM_REQUIRE(nq == 0 || q, "null levels");
+    for (int k = 0; k < nq; ++k) CSIM_REQUIRE(q[k] >= 0.0 && q[k] <= 1.0, "quantile levels must be in [0, 1]");  // NaN too
+    return CSIM_OK;
+}
+
+// checks the arguments, makes the quantiles' resources, lets an in-flight copy finish (it reads q_d), and enqueues the
+// kernel on the ensemble's stream after everything enqueued so far
+int quantiles_launch(csim_ensemble* e, int nq, const double* q, int nt, const double* thr, bool pinned) {
+    int rc = check_levels(nq, q);
+    if (rc) return rc;
+    CSIM_REQUIRE(nt >= 0 && nt <= QUANT_MAX_LEVELS, "nt must be 0 .. 16");
+    CSIM_REQUIRE(nt == 0 || thr, "null thresholds");
+    CSIM_REQUIRE(nq + nt >= 1, "nothing to compute: nq + nt must be >= 1");
+    if (e->g.members > QUANT_MAX_MEMBERS)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_quantiles: at most 4096 members (the largest sorting network)");
+    CSIM_REQUIRE(stats_cells(e) * QUANT_MAX_LEVELS * 2 <= 0x7fffff00u, "grid too large for the quantiles");
+    QuantArgs qa{};
+    qa.nq = nq;
+    qa.nt = nt;
+    for (int k = 0; k < nq; ++k) quantile_plan(e->g.members, q[k], &qa.lo[k], &qa.hi[k], &qa.g[k]);
+    for (int k = 0; k < nt; ++k) qa.thr[k] = thr[k];
+
+    if (!e->s_qio) CSIM_HIP(hipStreamCreateWithFlags(&e->s_qio, hipStreamNonBlocking));
+    if (!e->ev_q) CSIM_HIP(hipEventCreateWithFlags(&e->ev_q, hipEventDisableTiming));
+    if (e->q_pending) CSIM_HIP(hipStreamSynchronize(e->s_qio));
+    // grow a buffer that is too small for this call: nothing reads q_d or q_h once the copy above and the kernels
+    // enqueued so far are done; a failed allocation leaves the buffer absent, and the next call tries again
+    const int fields = nq + nt;
+    const size_t bytes = sizeof(double) * fields * stats_cells(e);
+    if (fields > e->q_dcap) {
+        CSIM_HIP(hipStreamSynchronize(e->st));
+        if (e->q_d) (void)hipFree(e->q_d);
+        e->q_d = nullptr;
+        e->q_dcap = 0;
+        CSIM_HIP(hipMalloc(reinterpret_cast<void**>(&e->q_d), bytes));
+        e->q_dcap = fields;
+    }
+    if (pinned && fields > e->q_hcap) {
+        if (e->q_h) (void)hipHostFree(e->q_h);
+        e->q_h = nullptr;
+        e->q_hcap = 0;
+        e->q_pending = false;
+        CSIM_HIP(hipHostMalloc(reinterpret_cast<void**>(&e->q_h), bytes, hipHostMallocDefault));
+        e->q_hcap = fields;
+    }
+    CSIM_HIP(ens_launch_quantiles(e->g, e->base(e->cur), qa, e->q_d, e->st));
     return CSIM_OK;
 }
 
@@ -188,6 +264,11 @@ int csim_ensemble_destroy(csim_ensemble* e) {
     if (e->stats_h) (void)hipHostFree(e->stats_h);
     if (e->ev_stats) (void)hipEventDestroy(e->ev_stats);
     if (e->s_io) (void)hipStreamDestroy(e->s_io);
+    if (e->s_qio) (void)hipStreamSynchronize(e->s_qio);
+    if (e->q_d) (void)hipFree(e->q_d);
+    if (e->q_h) (void)hipHostFree(e->q_h);
+    if (e->ev_q) (void)hipEventDestroy(e->ev_q);
+    if (e->s_qio) (void)hipStreamDestroy(e->s_qio);
     for (double* a : e->alloc)
         if (a) (void)hipFree(a);
     if (e->fin) (void)hipFree(e->fin);
@@ -409,6 +490,53 @@ int csim_ensemble_stats_wait(csim_ensemble* e, const double** mean, const double
     const double** const outs[4] = {mean, var, min, max};
     for (int k = 0; k < 4; ++k)
         if (outs[k]) *outs[k] = e->stats_h + k * stats_cells(e);
+    return CSIM_OK;
+}
+
+int csim_ensemble_quantiles(csim_ensemble* e, int nq, const double* q, int nt, const double* thr, double* out_q,
+                            double* out_p) {
+    CSIM_REQUIRE(e, "null ensemble");
+    int rc = quantiles_launch(e, nq, q, nt, thr, false);
+    if (rc) return rc;
+    const size_t n = stats_cells(e);
+    if (out_q && nq)
+        CSIM_HIP(hipMemcpyAsync(out_q, e->q_d, sizeof(double) * nq * n, hipMemcpyDeviceToHost, e->st));
+    if (out_p && nt)
+        CSIM_HIP(hipMemcpyAsync(out_p, e->q_d + nq * n, sizeof(double) * nt * n, hipMemcpyDeviceToHost, e->st));
+    CSIM_HIP(hipStreamSynchronize(e->st));
+    return CSIM_OK;
+}
+
+// As csim_ensemble_stats_begin, with the copy on s_qio
+int csim_ensemble_quantiles_begin(csim_ensemble* e, int nq, const double* q, int nt, const double* thr) {
+    CSIM_REQUIRE(e, "null ensemble");
+    int rc = quantiles_launch(e, nq, q, nt, thr, true);
+    if (rc) return rc;
+    CSIM_HIP(hipEventRecord(e->ev_q, e->st));
+    CSIM_HIP(hipStreamWaitEvent(e->s_qio, e->ev_q, 0));
+    CSIM_HIP(hipMemcpyAsync(e->q_h, e->q_d, sizeof(double) * (nq + nt) * stats_cells(e), hipMemcpyDeviceToHost,
+                            e->s_qio));
+    e->q_nq = nq;
+    e->q_pending = true;
+    return CSIM_OK;
+}
+
+int csim_ensemble_quantiles_wait(csim_ensemble* e, const double** out_q, const double** out_p) {
+    CSIM_REQUIRE(e, "null ensemble");
+    if (!e->q_pending) return fail(CSIM_ERR_STATE, "no quantiles in flight: csim_ensemble_quantiles_begin first");
+    CSIM_HIP(hipStreamSynchronize(e->s_qio));
+    e->q_pending = false;
+    if (out_q) *out_q = e->q_h;
+    if (out_p) *out_p = e->q_h + e->q_nq * stats_cells(e);
+    return CSIM_OK;
+}
+
+int csim_ensemble_quantile_plan(int members, int nq, const double* q, int* lo, int* hi, double* gamma) {
+    CSIM_REQUIRE(members >= 1, "members must be >= 1");
+    int rc = check_levels(nq, q);
+    if (rc) return rc;
+    CSIM_REQUIRE(nq == 0 || (lo && hi && gamma), "null output");
+    for (int k = 0; k < nq; ++k) quantile_plan(members, q[k], &lo[k], &hi[k], &gamma[k]);
     return CSIM_OK;
 }
 

@@ -65,4 +65,17 @@ hipError_t ens_launch_sum(const EnsGeom& g, const double* f, double* partial, hi
 constexpr int STATS_LDS_MEMBERS = 320;  // 320 x 64 cells x 8 B = 160 KiB of LDS
 hipError_t ens_launch_stats(const EnsGeom& g, const double* f, int ddof, double* out, hipStream_t st);
 
+// per-cell quantiles and exceedance probabilities over all members (ensemble_quantiles.hip), one launch: out = nq
+// quantile fields, then nt exceedance fields, each dense (ny+2) x (nx+2).  (lo[k], hi[k], g[k]): numpy's "linear" plan
+// of level k for this many members (csim_ensemble_quantile_plan)
+constexpr int QUANT_MAX_LEVELS = 16;       // levels and thresholds per call, each
+constexpr int QUANT_MAX_MEMBERS = 4096;    // the largest sorting network instantiated (64 values per lane of a wave)
+struct QuantArgs {
+    int nq, nt;
+    int lo[QUANT_MAX_LEVELS], hi[QUANT_MAX_LEVELS];
+    double g[QUANT_MAX_LEVELS];
+    double thr[QUANT_MAX_LEVELS];
+};
+hipError_t ens_launch_quantiles(const EnsGeom& g, const double* f, const QuantArgs& qa, double* out, hipStream_t st);
+
 }  // namespace csim

@@ -16,6 +16,12 @@ struct EnsembleStats {
     std::vector<double> mean, var, min, max;
 };
 
+// per-cell quantiles and exceedance probabilities over the members (see csim_ensemble_quantiles): q holds one field of
+// member_size() values per level, exceed one per threshold, one after the other
+struct EnsembleQuantiles {
+    std::vector<double> q, exceed;
+};
+
 class Ensemble {
 public:
     Ensemble(int members, int nx, int ny, double dx, double dy, const int bc[4], double bc_value = 0.0)
@@ -87,6 +93,31 @@ public:
         check(csim_ensemble_stats_wait(h_, &v.mean, &v.var, &v.min, &v.max));
         return v;
     }
+    EnsembleQuantiles quantiles(const std::vector<double>& q, const std::vector<double>& thresholds = {}) {
+        EnsembleQuantiles r;
+        r.q.resize(q.size() * member_size());
+        r.exceed.resize(thresholds.size() * member_size());
+        check(csim_ensemble_quantiles(h_, static_cast<int>(q.size()), q.data(), static_cast<int>(thresholds.size()),
+                                      thresholds.data(), r.q.data(), r.exceed.data()));
+        return r;
+    }
+    // captured after everything enqueued so far; run() may be called before quantiles_wait()
+    void quantiles_begin(const std::vector<double>& q, const std::vector<double>& thresholds = {}) {
+        check(csim_ensemble_quantiles_begin(h_, static_cast<int>(q.size()), q.data(),
+                                            static_cast<int>(thresholds.size()), thresholds.data()));
+        q_levels_ = q.size();
+        q_thresholds_ = thresholds.size();
+    }
+    // host pointers of levels (thresholds) x member_size() values, valid until the next quantiles_begin() or destruction
+    struct QuantilesView {
+        const double *q, *exceed;
+        std::size_t levels, thresholds;
+    };
+    QuantilesView quantiles_wait() {
+        QuantilesView v{nullptr, nullptr, q_levels_, q_thresholds_};
+        check(csim_ensemble_quantiles_wait(h_, &v.q, &v.exceed));
+        return v;
+    }
     void set_option(const char* key, long value) { check(csim_ensemble_set_option(h_, key, value)); }
     long get_option(const char* key) const {
         long v = 0;
@@ -104,6 +135,7 @@ private:
     }
     csim_ensemble* h_ = nullptr;
     int members_, nx_, ny_;
+    std::size_t q_levels_ = 0, q_thresholds_ = 0;  // of the last quantiles_begin()
 };
 
 }  // namespace climate

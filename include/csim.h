@@ -315,6 +315,26 @@ int csim_ensemble_stats_begin(csim_ensemble* e, int ddof);
 /* pointers stay valid until the next _begin or destroy (any may be NULL); CSIM_ERR_STATE when nothing is in flight */
 int csim_ensemble_stats_wait(csim_ensemble* e, const double** mean, const double** var, const double** min,
                              const double** max);
+/* per-cell quantiles and exceedance probabilities over the members, one launch for the whole batch, each output field
+ * in the reference layout (ny+2) x (nx+2), ghost ring included.  q[0..nq): levels in [0, 1] (numpy "linear");
+ * thr[0..nt): out_p = (members with x > thr) / members.  out_q: nq fields, out_p: nt fields, one after the other;
+ * either may be NULL (not copied).  0 <= nq, nt <= 16, nq + nt >= 1.  Synchronous.  No set_physics needed.
+ * Bit for bit, per cell with s the members in ascending order and (lo, hi, g) = csim_ensemble_quantile_plan:
+ * d = s[hi] - s[lo], g >= 0.5 ? s[hi] - d * (1 - g) : s[lo] + d * g, NaN if any member is NaN -- np.quantile(x, q,
+ * axis=0) but for the sign of a zero result; out_p is np.mean(x > thr, axis=0).
+ * At most 4096 members (csim_ensemble_create allows 65535): more give CSIM_ERR_UNSUPPORTED. */
+int csim_ensemble_quantiles(csim_ensemble* e, int nq, const double* q, int nt, const double* thr,
+                            double* out_q, double* out_p);
+/* the same, captured as csim_ensemble_stats_begin captures (the kernel in stream order, the copy to pinned host
+ * buffers on a stream of its own); a _begin while one is in flight first waits for it.  Statistics and quantiles may
+ * be in flight together, and neither waits for the other's copy. */
+int csim_ensemble_quantiles_begin(csim_ensemble* e, int nq, const double* q, int nt, const double* thr);
+/* nq and nt fields of the capture; pointers stay valid until the next _begin or destroy (either may be NULL);
+ * CSIM_ERR_STATE when nothing is in flight */
+int csim_ensemble_quantiles_wait(csim_ensemble* e, const double** out_q, const double** out_p);
+/* host-only: numpy's (lo, hi, gamma) of each level for this many members (v = (members - 1) * q; past the last index
+ * lo = hi = members - 1 and gamma = v + 1, numpy's index -1) */
+int csim_ensemble_quantile_plan(int members, int nq, const double* q, int* lo, int* hi, double* gamma);
 /* options (unknown keys: CSIM_ERR_ARG; "contract": CSIM_ERR_UNSUPPORTED), results never depend on them:
  *   "fuse"        -1 (default) passes of the ensemble depth where the grid allows; 0 / 1 single steps only
  *   "fused_2c"    0/1 (default 1), as for csim_stepper_set_option
