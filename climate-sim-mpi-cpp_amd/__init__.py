@@ -65,6 +65,15 @@ class Msg(C.Structure):
     _fields_ = [("peer", C.c_int), ("dir", C.c_int), ("count", C.c_long)]
 
 
+VERIFY_MAX_THRESHOLDS = 16
+
+
+class CsimVerifyScores(C.Structure):
+    """csim_verify_scores of include/csim.h"""
+    _fields_ = [("cells", C.c_longlong), ("nan_cells", C.c_longlong), ("crps", C.c_double), ("rmse", C.c_double),
+                ("spread", C.c_double), ("brier", C.c_double * VERIFY_MAX_THRESHOLDS)]
+
+
 def build(force: bool = False) -> str:
     """Compile csrc/ for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force or not os.path.exists(LIB_PATH):
@@ -172,6 +181,12 @@ def lib() -> C.CDLL:
         "csim_ensemble_quantiles_begin": (i, [vp, i, dp, i, dp]),
         "csim_ensemble_quantiles_wait": (i, [vp, C.POINTER(dp), C.POINTER(dp)]),
         "csim_ensemble_quantile_plan": (i, [i, i, dp, ip, ip, dp]),
+        "csim_ensemble_verify": (i, [vp, dp, i, i, i, dp, dp, dp, C.POINTER(C.c_ulonglong),
+                                     C.POINTER(CsimVerifyScores)]),
+        "csim_ensemble_verify_begin": (i, [vp, dp, i, i, i, dp]),
+        "csim_ensemble_verify_wait": (i, [vp, C.POINTER(dp), C.POINTER(dp), C.POINTER(C.POINTER(C.c_ulonglong)),
+                                          C.POINTER(CsimVerifyScores)]),
+        "csim_ensemble_rank_slot": (i, [C.c_longlong, i, ip]),
         "csim_ensemble_set_option": (i, [vp, C.c_char_p, C.c_long]),
         "csim_ensemble_get_option": (i, [vp, C.c_char_p, C.POINTER(C.c_long)]),
         "csim_ensemble_plan": (i, [i, i, i, i, ip]),
@@ -558,6 +573,26 @@ EnsembleQuantiles.__doc__ = """per-cell quantiles (nq, ny+2, nx+2) and exceedanc
 ensemble's members, ghost ring included"""
 
 
+EnsembleVerification = collections.namedtuple("EnsembleVerification", "crps brier rank_hist scores")
+EnsembleVerification.__doc__ = """verification of an ensemble against a truth: per-cell CRPS (ny+2, nx+2) and Brier scores
+(nt, ny+2, nx+2), ghost ring included, the interior's rank histogram (M+1,) uint64, and VerifyScores"""
+
+VerifyScores = collections.namedtuple("VerifyScores", "cells nan_cells crps rmse spread brier")
+VerifyScores.__doc__ = """domain scores over the non-NaN interior cells: their count, the NaN interior cells, mean CRPS,
+RMSE of the ensemble mean, spread (root mean variance) and the mean Brier score per threshold (nt,)"""
+
+
+def ensemble_rank_slot(g: int, ties: int) -> int:
+    """the rank histogram's tie-break: splitmix64(g) mod (ties + 1) — host only"""
+    v = C.c_int()
+    _ck(lib().csim_ensemble_rank_slot(int(g), int(ties), C.byref(v)))
+    return v.value
+
+
+def _scores(sc: CsimVerifyScores, nt: int) -> VerifyScores:
+    return VerifyScores(sc.cells, sc.nan_cells, sc.crps, sc.rmse, sc.spread, np.array(sc.brier[:nt], dtype=np.float64))
+
+
 def _levels(v):
     return np.ascontiguousarray(np.atleast_1d(np.asarray(v, dtype=np.float64)))
 
@@ -569,6 +604,7 @@ class Ensemble:
     def __init__(self, members, nx, ny, dx=1.0, dy=1.0, bc=(0, 0, 0, 0), bc_value=0.0):
         self.members, self.nx, self.ny = members, nx, ny
         self._q_counts = (0, 0)  # levels and thresholds of the last quantiles_begin()
+        self._v_counts = (0, 0)  # forecast members and thresholds of the last verify_begin()
         h = C.c_void_p()
         _ck(lib().csim_ensemble_create(members, nx, ny, 1, dx, dy, _i4(bc), bc_value, C.byref(h)))
         self._h = h
@@ -670,6 +706,45 @@ class Ensemble:
         shape = (self.ny + 2, self.nx + 2)
         return EnsembleQuantiles(*[np.ctypeslib.as_array(p, shape=(n,) + shape).copy() if n else np.empty((0,) + shape)
                                    for p, n in zip((pq, pp), self._q_counts)])
+
+    def _truth_args(self, truth, truth_member):
+        if truth is not None:
+            truth = np.ascontiguousarray(truth, dtype=np.float64)
+            if truth.shape != (self.ny + 2, self.nx + 2):
+                raise ValueError(f"truth must have shape {(self.ny + 2, self.nx + 2)}")
+        forecast = self.members - (truth_member is not None)
+        return truth, (None if truth is None else _dp(truth)), -1 if truth_member is None else int(truth_member), forecast
+
+    def verify(self, truth=None, *, truth_member=None, thresholds=(), fair=False) -> EnsembleVerification:
+        """CRPS, Brier scores, rank histogram and domain scores of the members against a truth: a host field
+        (ny+2, nx+2), or member truth_member against the other members (csim_ensemble_verify)"""
+        truth, tp, tm, M = self._truth_args(truth, truth_member)
+        ts = _levels(thresholds)
+        shape = (self.ny + 2, self.nx + 2)
+        crps, brier = np.empty(shape), np.empty((len(ts),) + shape)
+        hist, sc = np.zeros(max(M, 0) + 1, dtype=np.uint64), CsimVerifyScores()
+        _ck(lib().csim_ensemble_verify(self._h, tp, tm, int(bool(fair)), len(ts), _dp(ts), _dp(crps), _dp(brier),
+                                       hist.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(sc)))
+        return EnsembleVerification(crps, brier, hist, _scores(sc, len(ts)))
+
+    def verify_begin(self, truth=None, *, truth_member=None, thresholds=(), fair=False):
+        """start verify() of the current state without waiting; run() may follow before verify_wait()"""
+        truth, tp, tm, M = self._truth_args(truth, truth_member)
+        ts = _levels(thresholds)
+        _ck(lib().csim_ensemble_verify_begin(self._h, tp, tm, int(bool(fair)), len(ts), _dp(ts)))
+        self._v_counts = (M, len(ts))
+
+    def verify_wait(self) -> EnsembleVerification:
+        """the verification verify_begin() captured (copies)"""
+        pc, pb = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
+        ph, sc = C.POINTER(C.c_ulonglong)(), CsimVerifyScores()
+        _ck(lib().csim_ensemble_verify_wait(self._h, C.byref(pc), C.byref(pb), C.byref(ph), C.byref(sc)))
+        M, nt = self._v_counts
+        shape = (self.ny + 2, self.nx + 2)
+        crps = np.ctypeslib.as_array(pc, shape=shape).copy()
+        brier = np.ctypeslib.as_array(pb, shape=(nt,) + shape).copy() if nt else np.empty((0,) + shape)
+        hist = np.ctypeslib.as_array(ph, shape=(M + 1,)).copy()
+        return EnsembleVerification(crps, brier, hist, _scores(sc, nt))
 
     def set_option(self, key: str, value: int):
         _ck(lib().csim_ensemble_set_option(self._h, key.encode(), int(value)))

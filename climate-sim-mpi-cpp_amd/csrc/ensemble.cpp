@@ -44,6 +44,20 @@ struct csim_ensemble {
     hipStream_t s_qio = nullptr;
     hipEvent_t ev_q = nullptr;
     bool q_pending = false;
+    // verification (csim_ensemble_verify*), the same pieces again: one device buffer (histogram, per-workgroup counts
+    // and sums, CRPS, Brier fields; grown to the largest call), its pinned copy, a copy stream, and a device copy of
+    // a host truth with its pinned staging buffer (ev_vtruth: the staging buffer's copy has run)
+    double* v_d = nullptr;
+    double* v_h = nullptr;
+    size_t v_dcap = 0, v_hcap = 0;  // doubles each buffer holds
+    double* vtruth_d = nullptr;
+    double* vtruth_h = nullptr;
+    hipEvent_t ev_vtruth = nullptr;
+    bool vtruth_used = false;
+    hipStream_t s_vio = nullptr;
+    hipEvent_t ev_v = nullptr;
+    bool v_pending = false;
+    int v_forecast = 0, v_nt = 0, v_blocks = 0;  // of the capture in flight
 
     double* view(int buf, int m) const {
         return alloc[buf] + static_cast<size_t>(m) * g.slab + static_cast<size_t>(GHOST_EXTRA) * g.pitch;
@@ -172,6 +186,117 @@ int quantiles_launch(csim_ensemble* e, int nq, const double* q, int nt, const do
     return CSIM_OK;
 }
 
+// the verification buffer, in doubles: rank histogram (M + 1), counts (2 per workgroup), sums (VERIFY_SUMS per
+// workgroup), CRPS, nt Brier fields
+struct VerifyLayout {
+    size_t hist, counts, sums, crps, brier, total;
+};
+VerifyLayout verify_layout(int forecast, int blocks, int nt, size_t cells) {
+    VerifyLayout l{};
+    l.hist = 0;
+    l.counts = l.hist + forecast + 1;
+    l.sums = l.counts + 2 * static_cast<size_t>(blocks);
+    l.crps = l.sums + static_cast<size_t>(VERIFY_SUMS) * blocks;
+    l.brier = l.crps + cells;
+    l.total = l.brier + static_cast<size_t>(nt) * cells;
+    return l;
+}
+
+// the domain scores from the per-workgroup records, added in workgroup order
+void verify_finish(const unsigned long long* counts, const double* sums, int blocks, int nt, csim_verify_scores* s) {
+    long long n = 0, nan = 0;
+    for (int b = 0; b < blocks; ++b) {
+        n += static_cast<long long>(counts[2 * b]);
+        nan += static_cast<long long>(counts[2 * b + 1]);
+    }
+    double tot[VERIFY_SUMS] = {};
+    for (int q = 0; q < 3 + nt; ++q) {
+        double acc = sums[q];
+        for (int b = 1; b < blocks; ++b) acc += sums[static_cast<size_t>(b) * VERIFY_SUMS + q];
+        tot[q] = acc;
+    }
+    const double cells = static_cast<double>(n), nanv = std::nan("");
+    std::memset(s, 0, sizeof(*s));
+    s->cells = n;
+    s->nan_cells = nan;
+    s->crps = n ? tot[0] / cells : nanv;
+    s->rmse = n ? std::sqrt(tot[1] / cells) : nanv;
+    s->spread = n ? std::sqrt(tot[2] / cells) : nanv;
+    for (int k = 0; k < nt; ++k) s->brier[k] = n ? tot[3 + k] / cells : nanv;
+}
+
+// checks the arguments, makes the verification's resources, lets an in-flight copy finish (it reads v_d), stages a
+// host truth, and enqueues the histogram's zeroing and the kernel on the ensemble's stream after everything enqueued
+// so far.  *forecast, *blocks: of this call
+int verify_launch(csim_ensemble* e, const double* truth, int truth_member, int fair, int nt, const double* thr,
+                  bool pinned, int* forecast, int* blocks) {
+    const int B = e->g.members;
+    CSIM_REQUIRE((truth != nullptr) != (truth_member >= 0), "give exactly one truth: a host field or a member");
+    CSIM_REQUIRE(truth_member >= -1 && truth_member < B, "truth_member out of range");
+    CSIM_REQUIRE(nt >= 0 && nt <= VERIFY_MAX_THRESHOLDS, "nt must be 0 .. 16");
+    CSIM_REQUIRE(nt == 0 || thr, "null thresholds");
+    CSIM_REQUIRE(fair == 0 || fair == 1, "fair must be 0 or 1");
+    const int M = truth ? B : B - 1;
+    CSIM_REQUIRE(M >= 1, "no forecast members: a truth member needs at least two members");
+    CSIM_REQUIRE(!fair || M >= 2, "the fair CRPS needs at least two forecast members");
+    if (M > VERIFY_MAX_MEMBERS)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_verify: at most 4096 forecast members (the largest sorting network)");
+    CSIM_REQUIRE(stats_cells(e) * (VERIFY_MAX_THRESHOLDS + 1) <= 0x7fffff00u, "grid too large for the verification");
+    const size_t cells = stats_cells(e);
+    const int nb = ens_verify_blocks(e->g, M);
+    const VerifyLayout l = verify_layout(M, nb, nt, cells);
+
+    if (!e->s_vio) CSIM_HIP(hipStreamCreateWithFlags(&e->s_vio, hipStreamNonBlocking));
+    if (!e->ev_v) CSIM_HIP(hipEventCreateWithFlags(&e->ev_v, hipEventDisableTiming));
+    if (!e->ev_vtruth) CSIM_HIP(hipEventCreateWithFlags(&e->ev_vtruth, hipEventDisableTiming));
+    if (e->v_pending) CSIM_HIP(hipStreamSynchronize(e->s_vio));
+    // grow a buffer that is too small for this call (as quantiles_launch does)
+    if (l.total > e->v_dcap) {
+        CSIM_HIP(hipStreamSynchronize(e->st));
+        if (e->v_d) (void)hipFree(e->v_d);
+        e->v_d = nullptr;
+        e->v_dcap = 0;
+        CSIM_HIP(hipMalloc(reinterpret_cast<void**>(&e->v_d), sizeof(double) * l.total));
+        e->v_dcap = l.total;
+    }
+    if (pinned && l.total > e->v_hcap) {
+        if (e->v_h) (void)hipHostFree(e->v_h);
+        e->v_h = nullptr;
+        e->v_hcap = 0;
+        e->v_pending = false;
+        CSIM_HIP(hipHostMalloc(reinterpret_cast<void**>(&e->v_h), sizeof(double) * l.total, hipHostMallocDefault));
+        e->v_hcap = l.total;
+    }
+    VerifyArgs va{};
+    va.forecast = M;
+    va.truth_member = truth ? B : truth_member;
+    va.nt = nt;
+    va.fair = fair;
+    for (int k = 0; k < nt; ++k) va.thr[k] = thr[k];
+    if (truth) {  // copied before the call returns: host -> pinned staging -> device, in stream order
+        if (!e->vtruth_d) CSIM_HIP(hipMalloc(reinterpret_cast<void**>(&e->vtruth_d), sizeof(double) * cells));
+        if (!e->vtruth_h)
+            CSIM_HIP(hipHostMalloc(reinterpret_cast<void**>(&e->vtruth_h), sizeof(double) * cells, hipHostMallocDefault));
+        if (e->vtruth_used) CSIM_HIP(hipEventSynchronize(e->ev_vtruth));  // the staging buffer's last copy is done
+        std::memcpy(e->vtruth_h, truth, sizeof(double) * cells);
+        CSIM_HIP(hipMemcpyAsync(e->vtruth_d, e->vtruth_h, sizeof(double) * cells, hipMemcpyHostToDevice, e->st));
+        CSIM_HIP(hipEventRecord(e->ev_vtruth, e->st));
+        e->vtruth_used = true;
+        va.truth = e->vtruth_d;
+    }
+    VerifyOut o{};
+    o.hist = reinterpret_cast<unsigned long long*>(e->v_d + l.hist);
+    o.counts = reinterpret_cast<unsigned long long*>(e->v_d + l.counts);
+    o.sums = e->v_d + l.sums;
+    o.crps = e->v_d + l.crps;
+    o.brier = e->v_d + l.brier;
+    CSIM_HIP(hipMemsetAsync(o.hist, 0, sizeof(unsigned long long) * (M + 1), e->st));
+    CSIM_HIP(ens_launch_verify(e->g, e->base(e->cur), va, o, e->st));
+    *forecast = M;
+    *blocks = nb;
+    return CSIM_OK;
+}
+
 int ghost_fill(csim_ensemble* e, bool fin) {
     CSIM_HIP(ens_launch_ghost_fill(e->g, e->base(e->cur), e->base(1 - e->cur), e->table, fin, e->st));
     return CSIM_OK;
@@ -269,6 +394,14 @@ int csim_ensemble_destroy(csim_ensemble* e) {
     if (e->q_h) (void)hipHostFree(e->q_h);
     if (e->ev_q) (void)hipEventDestroy(e->ev_q);
     if (e->s_qio) (void)hipStreamDestroy(e->s_qio);
+    if (e->s_vio) (void)hipStreamSynchronize(e->s_vio);
+    if (e->v_d) (void)hipFree(e->v_d);
+    if (e->v_h) (void)hipHostFree(e->v_h);
+    if (e->vtruth_d) (void)hipFree(e->vtruth_d);
+    if (e->vtruth_h) (void)hipHostFree(e->vtruth_h);
+    if (e->ev_vtruth) (void)hipEventDestroy(e->ev_vtruth);
+    if (e->ev_v) (void)hipEventDestroy(e->ev_v);
+    if (e->s_vio) (void)hipStreamDestroy(e->s_vio);
     for (double* a : e->alloc)
         if (a) (void)hipFree(a);
     if (e->fin) (void)hipFree(e->fin);
@@ -537,6 +670,74 @@ int csim_ensemble_quantile_plan(int members, int nq, const double* q, int* lo, i
     if (rc) return rc;
     CSIM_REQUIRE(nq == 0 || (lo && hi && gamma), "null output");
     for (int k = 0; k < nq; ++k) quantile_plan(members, q[k], &lo[k], &hi[k], &gamma[k]);
+    return CSIM_OK;
+}
+
+int csim_ensemble_verify(csim_ensemble* e, const double* truth, int truth_member, int fair, int nt, const double* thr,
+                         double* out_crps, double* out_brier, unsigned long long* rank_hist,
+                         csim_verify_scores* scores) {
+    CSIM_REQUIRE(e, "null ensemble");
+    int M = 0, nb = 0;
+    int rc = verify_launch(e, truth, truth_member, fair, nt, thr, false, &M, &nb);
+    if (rc) return rc;
+    const size_t cells = stats_cells(e);
+    const VerifyLayout l = verify_layout(M, nb, nt, cells);
+    std::vector<double> rec;
+    if (out_crps)
+        CSIM_HIP(hipMemcpyAsync(out_crps, e->v_d + l.crps, sizeof(double) * cells, hipMemcpyDeviceToHost, e->st));
+    if (out_brier && nt)
+        CSIM_HIP(hipMemcpyAsync(out_brier, e->v_d + l.brier, sizeof(double) * nt * cells, hipMemcpyDeviceToHost, e->st));
+    if (rank_hist)
+        CSIM_HIP(hipMemcpyAsync(rank_hist, e->v_d + l.hist, sizeof(unsigned long long) * (M + 1), hipMemcpyDeviceToHost,
+                                e->st));
+    if (scores) {
+        rec.resize(l.crps - l.counts);
+        CSIM_HIP(hipMemcpyAsync(rec.data(), e->v_d + l.counts, sizeof(double) * rec.size(), hipMemcpyDeviceToHost, e->st));
+    }
+    CSIM_HIP(hipStreamSynchronize(e->st));
+    if (scores)
+        verify_finish(reinterpret_cast<const unsigned long long*>(rec.data()), rec.data() + (l.sums - l.counts), nb, nt,
+                      scores);
+    return CSIM_OK;
+}
+
+// As csim_ensemble_quantiles_begin, with the copy on s_vio; the scores are finished in _wait
+int csim_ensemble_verify_begin(csim_ensemble* e, const double* truth, int truth_member, int fair, int nt,
+                               const double* thr) {
+    CSIM_REQUIRE(e, "null ensemble");
+    int M = 0, nb = 0;
+    int rc = verify_launch(e, truth, truth_member, fair, nt, thr, true, &M, &nb);
+    if (rc) return rc;
+    const VerifyLayout l = verify_layout(M, nb, nt, stats_cells(e));
+    CSIM_HIP(hipEventRecord(e->ev_v, e->st));
+    CSIM_HIP(hipStreamWaitEvent(e->s_vio, e->ev_v, 0));
+    CSIM_HIP(hipMemcpyAsync(e->v_h, e->v_d, sizeof(double) * l.total, hipMemcpyDeviceToHost, e->s_vio));
+    e->v_forecast = M;
+    e->v_nt = nt;
+    e->v_blocks = nb;
+    e->v_pending = true;
+    return CSIM_OK;
+}
+
+int csim_ensemble_verify_wait(csim_ensemble* e, const double** out_crps, const double** out_brier,
+                              const unsigned long long** rank_hist, csim_verify_scores* scores) {
+    CSIM_REQUIRE(e, "null ensemble");
+    if (!e->v_pending) return fail(CSIM_ERR_STATE, "no verification in flight: csim_ensemble_verify_begin first");
+    CSIM_HIP(hipStreamSynchronize(e->s_vio));
+    e->v_pending = false;
+    const VerifyLayout l = verify_layout(e->v_forecast, e->v_blocks, e->v_nt, stats_cells(e));
+    if (out_crps) *out_crps = e->v_h + l.crps;
+    if (out_brier) *out_brier = e->v_h + l.brier;
+    if (rank_hist) *rank_hist = reinterpret_cast<const unsigned long long*>(e->v_h + l.hist);
+    if (scores)
+        verify_finish(reinterpret_cast<const unsigned long long*>(e->v_h + l.counts), e->v_h + l.sums, e->v_blocks,
+                      e->v_nt, scores);
+    return CSIM_OK;
+}
+
+int csim_ensemble_rank_slot(long long g, int ties, int* slot) {
+    CSIM_REQUIRE(slot && g >= 0 && ties >= 0, "bad argument");
+    *slot = static_cast<int>(verify_mix(static_cast<unsigned long long>(g)) % (static_cast<unsigned long long>(ties) + 1));
     return CSIM_OK;
 }
 

@@ -78,4 +78,40 @@ struct QuantArgs {
 };
 hipError_t ens_launch_quantiles(const EnsGeom& g, const double* f, const QuantArgs& qa, double* out, hipStream_t st);
 
+// ensemble verification against one truth per cell (ensemble_verify.hip), one launch: the per-cell CRPS and Brier
+// scores (dense (ny+2) x (nx+2) each), the rank histogram of the interior (M + 1 bins, one integer atomic per bin and
+// workgroup into `hist`, which the caller zeroes), and per-workgroup partial sums of the domain scores, which the host
+// adds in workgroup order.  M forecast members: all B with a truth field, or the B - 1 others with truth member t.
+constexpr int VERIFY_MAX_THRESHOLDS = 16;
+constexpr int VERIFY_MAX_MEMBERS = QUANT_MAX_MEMBERS;  // forecast members, the largest sorting network
+constexpr int VERIFY_SUMS = 3 + VERIFY_MAX_THRESHOLDS;  // partials per workgroup: CRPS, (m - y)^2, var, Brier[16]
+constexpr int VERIFY_GRID_MAX = 1024;                   // workgroups per launch, at most (each loops over its tiles)
+struct VerifyArgs {
+    int forecast;          // M
+    int truth_member;      // t, or B with `truth` (then no member is skipped)
+    int nt;
+    int fair;
+    const double* truth;   // device, dense (ny+2) x (nx+2); null with a truth member
+    double thr[VERIFY_MAX_THRESHOLDS];
+};
+struct VerifyOut {
+    double* crps;               // one field
+    double* brier;              // nt fields
+    unsigned long long* hist;   // M + 1 bins, zeroed by the caller
+    unsigned long long* counts; // per workgroup: non-NaN interior cells, NaN interior cells
+    double* sums;               // per workgroup: VERIFY_SUMS partial sums over the non-NaN interior cells
+};
+int ens_verify_blocks(const EnsGeom& g, int forecast);  // workgroups of the launch: records in counts / sums
+hipError_t ens_launch_verify(const EnsGeom& g, const double* f, const VerifyArgs& va, const VerifyOut& o,
+                             hipStream_t st);
+
+// the rank histogram's tie-break: splitmix64's finaliser of the interior index g; a cell with `eq` members equal to the
+// truth goes to bin lt + mix(g) mod (eq + 1)
+__host__ __device__ inline unsigned long long verify_mix(unsigned long long z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 }  // namespace csim

@@ -22,7 +22,9 @@
 // wave's reads down one cell's members are free of bank conflicts.  A wave then holds its cell as E = P/64 values per
 // lane (element e*64 + lane), runs the strides >= 64 inside each lane and the others across lanes (ds_bpermute), writes
 // the sorted column back in place, and one lane per level reads s[lo], s[hi] from there (instantiated per E = 2 .. 64).
+// The networks' pieces are in ensemble_sort.hpp, shared with ensemble_verify.hip.
 #include "ensemble.hpp"
+#include "ensemble_sort.hpp"
 
 #pragma clang fp contract(off)
 
@@ -32,30 +34,6 @@ namespace {
 
 constexpr int QUANT_LDS_BUDGET = 64 * 1024;  // form 2 tile target: two workgroups (eight waves) per CU
 constexpr int QUANT_TILE_MAX = 16;           // form 2 cells per tile, at most
-
-__device__ __forceinline__ void cmpx(double& a, double& b) {  // a <- min, b <- max
-    const double lo = fmin(a, b), hi = fmax(a, b);
-    a = lo;
-    b = hi;
-}
-
-// s[k] for a wave-uniform k (kernel argument) without dynamic register indexing.  Masks rather than selects: a chain
-// of `k == i ? s[i] : r` is folded into a load through a selected pointer, which sends s to scratch.
-template <int P>
-__device__ __forceinline__ double pick(const double (&s)[P], int k) {
-    unsigned long long r = 0;
-#pragma unroll
-    for (int i = 0; i < P; ++i) r |= __builtin_bit_cast(unsigned long long, s[i]) & (0ull - (k == i));
-    return __builtin_bit_cast(double, r);
-}
-
-// lane src/4's x (two ds_bpermute_b32; __shfl_xor's double form goes through memory)
-__device__ __forceinline__ double bpermute(double x, int src) {
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, x);
-    const unsigned lo = __builtin_amdgcn_ds_bpermute(src, static_cast<int>(b));
-    const unsigned hi = __builtin_amdgcn_ds_bpermute(src, static_cast<int>(b >> 32));
-    return __builtin_bit_cast(double, (static_cast<unsigned long long>(hi) << 32) | lo);
-}
 
 __device__ __forceinline__ double lerp_numpy(double a, double b, double g, bool nan) {
     const double d = b - a;
@@ -95,21 +73,7 @@ __global__ __launch_bounds__(64) void k_quantiles_lane(const double* __restrict_
         }
     }
 
-    // bitonic network, ascending, static indices throughout
-#pragma unroll
-    for (int k = 2; k <= P; k <<= 1) {
-#pragma unroll
-        for (int h = k >> 1; h > 0; h >>= 1) {
-#pragma unroll
-            for (int e = 0; e < P; ++e) {
-                const int o = e ^ h;
-                if (o > e) {
-                    if ((e & k) == 0) cmpx(s[e], s[o]);
-                    else cmpx(s[o], s[e]);
-                }
-            }
-        }
-    }
+    CSIM_SORT_LANE(s, P);  // bitonic network, ascending, static indices throughout
 
 #pragma unroll
     for (int q = 0; q < QUANT_MAX_LEVELS; ++q) {
@@ -117,43 +81,6 @@ __global__ __launch_bounds__(64) void k_quantiles_lane(const double* __restrict_
             const double r = lerp_numpy(pick(s, qa.lo[q]), pick(s, qa.hi[q]), qa.g[q], nan);
             if (valid) out[static_cast<size_t>(q) * ncells + c] = r;
         }
-    }
-}
-
-// Form 2's network, element e*64 + lane in v[e] of that lane.  Strides below 64 go across lanes; the merge size k
-// and the stride are runtime values there (the register index is static either way).
-template <int E>
-__device__ __forceinline__ void cross_stages(double (&v)[E], int lane, int k, int h0) {
-    for (int h = h0; h > 0; h >>= 1) {
-        const bool lower = (lane & h) == 0;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const double y = bpermute(v[e], (lane ^ h) << 2);
-            const bool up = (((e << 6) | lane) & k) == 0;
-            v[e] = lower == up ? fmin(v[e], y) : fmax(v[e], y);
-        }
-    }
-}
-
-// merges of K * 64 .. P elements: strides K/2 .. 1 (x 64) inside each lane with static indices and directions,
-// then strides 32 .. 1 across lanes.  Runtime strides inside a lane would need a choice among register pairs, which
-// the compiler turns into pointers and scratch.
-template <int E, int K>
-__device__ __forceinline__ void merges_from(double (&v)[E], int lane) {
-    if constexpr (K <= E) {
-#pragma unroll
-        for (int H = K / 2; H > 0; H >>= 1) {
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const int o = e ^ H;
-                if (o > e) {
-                    if ((e & K) == 0) cmpx(v[e], v[o]);
-                    else cmpx(v[o], v[e]);
-                }
-            }
-        }
-        cross_stages(v, lane, K * 64, 32);
-        merges_from<E, 2 * K>(v, lane);
     }
 }
 

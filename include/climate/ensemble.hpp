@@ -22,6 +22,14 @@ struct EnsembleQuantiles {
     std::vector<double> q, exceed;
 };
 
+// verification against a truth (see csim_ensemble_verify): crps one field of member_size() values, brier one per
+// threshold, rank_hist M + 1 bins (M forecast members), scores over the non-NaN interior cells
+struct EnsembleVerification {
+    std::vector<double> crps, brier;
+    std::vector<unsigned long long> rank_hist;
+    csim_verify_scores scores;
+};
+
 class Ensemble {
 public:
     Ensemble(int members, int nx, int ny, double dx, double dy, const int bc[4], double bc_value = 0.0)
@@ -118,6 +126,42 @@ public:
         check(csim_ensemble_quantiles_wait(h_, &v.q, &v.exceed));
         return v;
     }
+    // the members against a host truth field (member_size() values)
+    EnsembleVerification verify(const std::vector<double>& truth, const std::vector<double>& thresholds = {},
+                                bool fair = false) {
+        return verify_any(sized(truth, 1), -1, members_, thresholds, fair);
+    }
+    // member t against the other members, in their order
+    EnsembleVerification verify_member(int t, const std::vector<double>& thresholds = {}, bool fair = false) {
+        return verify_any(nullptr, t, members_ - 1, thresholds, fair);
+    }
+    // captured after everything enqueued so far (a host truth is copied before the call returns); run() may be called
+    // before verify_wait()
+    void verify_begin(const std::vector<double>& truth, const std::vector<double>& thresholds = {}, bool fair = false) {
+        check(csim_ensemble_verify_begin(h_, sized(truth, 1), -1, fair ? 1 : 0, static_cast<int>(thresholds.size()),
+                                         thresholds.data()));
+        v_forecast_ = static_cast<std::size_t>(members_);
+        v_thresholds_ = thresholds.size();
+    }
+    void verify_member_begin(int t, const std::vector<double>& thresholds = {}, bool fair = false) {
+        check(csim_ensemble_verify_begin(h_, nullptr, t, fair ? 1 : 0, static_cast<int>(thresholds.size()),
+                                         thresholds.data()));
+        v_forecast_ = static_cast<std::size_t>(members_ - 1);
+        v_thresholds_ = thresholds.size();
+    }
+    // host pointers (crps: member_size(), brier: thresholds x member_size(), rank_hist: bins values), valid until the
+    // next verify_begin() or destruction, and the finished scores
+    struct VerifyView {
+        const double *crps, *brier;
+        const unsigned long long* rank_hist;
+        std::size_t thresholds, bins;
+        csim_verify_scores scores;
+    };
+    VerifyView verify_wait() {
+        VerifyView v{nullptr, nullptr, nullptr, v_thresholds_, v_forecast_ + 1, {}};
+        check(csim_ensemble_verify_wait(h_, &v.crps, &v.brier, &v.rank_hist, &v.scores));
+        return v;
+    }
     void set_option(const char* key, long value) { check(csim_ensemble_set_option(h_, key, value)); }
     long get_option(const char* key) const {
         long v = 0;
@@ -133,9 +177,20 @@ private:
         if (a.size() != member_size() * static_cast<std::size_t>(n)) throw std::invalid_argument("ensemble: array size");
         return a.data();
     }
+    EnsembleVerification verify_any(const double* truth, int t, int forecast, const std::vector<double>& thresholds,
+                                    bool fair) {
+        EnsembleVerification r{};
+        r.crps.resize(member_size());
+        r.brier.resize(thresholds.size() * member_size());
+        r.rank_hist.resize(static_cast<std::size_t>(forecast > 0 ? forecast : 0) + 1);
+        check(csim_ensemble_verify(h_, truth, t, fair ? 1 : 0, static_cast<int>(thresholds.size()), thresholds.data(),
+                                   r.crps.data(), r.brier.data(), r.rank_hist.data(), &r.scores));
+        return r;
+    }
     csim_ensemble* h_ = nullptr;
     int members_, nx_, ny_;
     std::size_t q_levels_ = 0, q_thresholds_ = 0;  // of the last quantiles_begin()
+    std::size_t v_forecast_ = 0, v_thresholds_ = 0;  // of the last verify_begin()
 };
 
 }  // namespace climate

@@ -335,6 +335,46 @@ int csim_ensemble_quantiles_wait(csim_ensemble* e, const double** out_q, const d
 /* host-only: numpy's (lo, hi, gamma) of each level for this many members (v = (members - 1) * q; past the last index
  * lo = hi = members - 1 and gamma = v + 1, numpy's index -1) */
 int csim_ensemble_quantile_plan(int members, int nq, const double* q, int* lo, int* hi, double* gamma);
+/* verification of the members against one truth per cell, one launch for the whole batch.  The truth is either a
+ * host field (truth, reference layout, copied before the call returns; truth_member = -1) and the M = B members are the
+ * forecast, or member t = truth_member (truth = NULL) and the M = B - 1 others, in their order, are the forecast.
+ * A cell is NaN when the truth or any forecast member is.  Per cell, without FMA contraction, every sum from +0:
+ *   a = sum |x_k - y|;  lt = #(x_k < y), eq = #(x_k == y);  m = sum x_k / M;  v = sum (x_k - m)(x_k - m) / (M - 1)
+ *   c = sum_{i=1}^{M-1} w_i (s_i - s_{i-1}), s the members ascending, w_i = (double)(i (M - i));
+ *   CRPS = a / M - c / W, W = M M (fair = 0) or M (M - 1) (fair = 1, M >= 2);  NaN on a NaN cell
+ *   Brier_k = (p - o)(p - o), p = #(x > thr_k) / M (as csim_ensemble_quantiles), o = y > thr_k ? 1 : 0;  NaN on a NaN
+ *   cell.  out_crps: one field, out_brier: nt fields (0 <= nt <= CSIM_VERIFY_MAX_THRESHOLDS), ghost ring included.
+ * Order of the sums a, sum x_k, sum (x_k - m)^2 (member order k) and c (sorted order i):
+ *   M <= 64: one running sum in that order.
+ *   M > 64: term k goes to lane k % 64; lane l sums its terms in increasing k from +0 (a lane without terms holds +0);
+ *   the 64 lane sums are combined as l[j] = l[j] + l[j ^ h] for h = 32, 16, 8, 4, 2, 1, all j at once; the sum is l[0].
+ * rank_hist (M + 1 bins) counts the non-NaN interior cells (i = 1..nx, j = 1..ny) at rank lt + mix(g) mod (eq + 1),
+ * g = (j - 1) nx + (i - 1), mix the splitmix64 finaliser (csim_ensemble_rank_slot).  scores: over the n non-NaN
+ * interior cells, the means of CRPS and of each Brier score, rmse = sqrt(sum (m - y)^2 / n), spread = sqrt(sum v / n)
+ * (NaN when n = 0), from per-workgroup partial sums added in a fixed order: the same state gives the same bits.
+ * Any output may be NULL (not computed on the host / not copied).  Synchronous.  No set_physics needed; the members'
+ * fields are not modified.  Errors: CSIM_ERR_ARG unless exactly one truth is given, for truth_member outside -1 .. B-1,
+ * nt outside 0 .. 16, fair not 0 / 1, fair with M < 2, no forecast member; CSIM_ERR_UNSUPPORTED for M > 4096. */
+#define CSIM_VERIFY_MAX_THRESHOLDS 16
+typedef struct csim_verify_scores {
+    long long cells, nan_cells;
+    double crps, rmse, spread;
+    double brier[CSIM_VERIFY_MAX_THRESHOLDS]; /* first nt used, the rest 0 */
+} csim_verify_scores;
+int csim_ensemble_verify(csim_ensemble* e, const double* truth, int truth_member, int fair, int nt, const double* thr,
+                         double* out_crps, double* out_brier, unsigned long long* rank_hist,
+                         csim_verify_scores* scores);
+/* the same, captured as csim_ensemble_quantiles_begin captures (kernel in stream order, the copy to pinned host buffers
+ * on a stream of its own; a host truth is copied before the call returns).  A _begin while one is in flight first
+ * waits for it.  Statistics, quantiles and verification may be in flight together. */
+int csim_ensemble_verify_begin(csim_ensemble* e, const double* truth, int truth_member, int fair, int nt,
+                               const double* thr);
+/* the capture's fields and histogram (pointers valid until the next _begin or destroy; any may be NULL) and its scores,
+ * finished here; CSIM_ERR_STATE when nothing is in flight */
+int csim_ensemble_verify_wait(csim_ensemble* e, const double** out_crps, const double** out_brier,
+                              const unsigned long long** rank_hist, csim_verify_scores* scores);
+/* host-only: the rank histogram's tie-break, mix(g) mod (ties + 1) for g >= 0, ties >= 0 */
+int csim_ensemble_rank_slot(long long g, int ties, int* slot);
 /* options (unknown keys: CSIM_ERR_ARG; "contract": CSIM_ERR_UNSUPPORTED), results never depend on them:
  *   "fuse"        -1 (default) passes of the ensemble depth where the grid allows; 0 / 1 single steps only
  *   "fused_2c"    0/1 (default 1), as for csim_stepper_set_option
