@@ -47,7 +47,9 @@ def lib() -> C.CDLL:
         L.ora_diffusion_step.argtypes = [dp, dp, C.c_int, C.c_int] + [C.c_double] * 4
         L.ora_advection_step.argtypes = [dp, dp, C.c_int, C.c_int] + [C.c_double] * 5
         L.ora_step_tile.argtypes = [dp, dp, C.c_int, C.c_int] + [C.c_double] * 6 + [ip, ip]
+        L.ora_step_tile_value.argtypes = [dp, dp, C.c_int, C.c_int] + [C.c_double] * 6 + [ip, ip, C.c_double]
         L.ora_run_single.argtypes = [dp, C.c_int, C.c_int] + [C.c_double] * 6 + [ip, C.c_int]
+        L.ora_run_single_value.argtypes = [dp, C.c_int, C.c_int] + [C.c_double] * 6 + [ip, C.c_int, C.c_double]
         L.ora_dims_create.argtypes = [C.c_int, ip]
         L.ora_decomp.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, ip]
         L.ora_gaussian.argtypes = [dp] + [C.c_int] * 6 + [C.c_double] * 6
@@ -102,16 +104,20 @@ def advection_step(u, out, dx, dy, vx, vy, dt) -> None:
     lib().ora_advection_step(_dp(u), _dp(out), nx, ny, dx, dy, vx, vy, dt)
 
 
-def step_tile(u, tmp, dx, dy, D, vx, vy, dt, bc, phys) -> None:
-    """boundary (physical sides only) -> copy -> diffusion -> advection; result in tmp."""
+def step_tile(u, tmp, dx, dy, D, vx, vy, dt, bc, phys, value=0.0) -> None:
+    """boundary (physical sides only; Dirichlet sides take `value`) -> copy -> diffusion -> advection; result in tmp."""
     ny, nx = u.shape[0] - 2, u.shape[1] - 2
-    lib().ora_step_tile(_dp(u), _dp(tmp), nx, ny, dx, dy, D, vx, vy, dt, _i4(bc), _i4(phys))
+    lib().ora_step_tile_value(_dp(u), _dp(tmp), nx, ny, dx, dy, D, vx, vy, dt, _i4(bc), _i4(phys), value)
 
 
-def run_single(u, dx, dy, D, vx, vy, dt, bc, steps) -> None:
-    """`steps` full reference steps in place on one tile with four physical sides."""
+def run_single(u, dx, dy, D, vx, vy, dt, bc, steps, value=0.0) -> None:
+    """`steps` full reference steps in place on one tile with four physical sides; Dirichlet sides take `value`
+    (the reference driver's 0.0 unless given; -0.0 is a value of its own)."""
     ny, nx = u.shape[0] - 2, u.shape[1] - 2
-    lib().ora_run_single(_dp(u), nx, ny, dx, dy, D, vx, vy, dt, _i4(bc), steps)
+    if value == 0.0 and not np.signbit(value):
+        lib().ora_run_single(_dp(u), nx, ny, dx, dy, D, vx, vy, dt, _i4(bc), steps)
+    else:
+        lib().ora_run_single_value(_dp(u), nx, ny, dx, dy, D, vx, vy, dt, _i4(bc), steps, value)
 
 
 def dims_create(size):

@@ -179,25 +179,33 @@ void ora_advection_step_checked(const double* u, double* out, int nx, int ny, do
 
 /* One reference time step on ONE tile whose ghosts already hold neighbour data on the
  * non-physical sides: boundary -> copy -> diffusion -> advection (src/main.cpp:102-107).
- * The caller swaps u and tmp afterwards (src/main.cpp:109). */
-void ora_step_tile(double* u, double* tmp, int nx, int ny, double dx, double dy, double D,
-                   double vx, double vy, double dt, const int bc[4], const int phys[4]) {
-    ora_apply_boundary(u, nx, ny, bc, phys, 0.0);
+ * The caller swaps u and tmp afterwards (src/main.cpp:109).  `value`: the Dirichlet value
+ * handed to apply_boundary (the reference driver passes 0.0). */
+void ora_step_tile_value(double* u, double* tmp, int nx, int ny, double dx, double dy, double D,
+                         double vx, double vy, double dt, const int bc[4], const int phys[4],
+                         double value) {
+    ora_apply_boundary(u, nx, ny, bc, phys, value);
     memcpy(tmp, u, sizeof(double) * (size_t)(nx + 2) * (size_t)(ny + 2));
     ora_diffusion_step(u, tmp, nx, ny, dx, dy, D, dt);
     ora_advection_step(u, tmp, nx, ny, dx, dy, vx, vy, dt);
 }
 
-/* Single-tile convenience: `steps` full steps in place (result in u). */
-void ora_run_single(double* u, int nx, int ny, double dx, double dy, double D, double vx,
-                    double vy, double dt, const int bc[4], int steps) {
+void ora_step_tile(double* u, double* tmp, int nx, int ny, double dx, double dy, double D,
+                   double vx, double vy, double dt, const int bc[4], const int phys[4]) {
+    ora_step_tile_value(u, tmp, nx, ny, dx, dy, D, vx, vy, dt, bc, phys, 0.0);
+}
+
+/* Single-tile convenience: `steps` full steps in place (result in u), Dirichlet sides held at
+ * `value`. */
+void ora_run_single_value(double* u, int nx, int ny, double dx, double dy, double D, double vx,
+                          double vy, double dt, const int bc[4], int steps, double value) {
     const size_t n = (size_t)(nx + 2) * (size_t)(ny + 2);
     double* a = u;
     double* b = (double*)malloc(n * sizeof(double));
     const int phys[4] = {1, 1, 1, 1};
     memcpy(b, u, n * sizeof(double));
     for (int s = 0; s < steps; ++s) {
-        ora_step_tile(a, b, nx, ny, dx, dy, D, vx, vy, dt, bc, phys);
+        ora_step_tile_value(a, b, nx, ny, dx, dy, D, vx, vy, dt, bc, phys, value);
         double* t = a;
         a = b;
         b = t;
@@ -208,6 +216,12 @@ void ora_run_single(double* u, int nx, int ny, double dx, double dy, double D, d
     } else {
         free(b);
     }
+}
+
+/* the reference driver's loop: Dirichlet value 0.0 (src/main.cpp:103) */
+void ora_run_single(double* u, int nx, int ny, double dx, double dy, double D, double vx,
+                    double vy, double dt, const int bc[4], int steps) {
+    ora_run_single_value(u, nx, ny, dx, dy, D, vx, vy, dt, bc, steps, 0.0);
 }
 
 /* ---- decomposition (reference src/decomp.cpp:5-34) -----------------------------------

@@ -8,12 +8,13 @@
 // The loop in mode "run" replays the call order of the reference driver
 // (reference src/main.cpp:62-109): Decomp2D::init -> Field u,tmp(h=1) -> IC ->
 // per step { exchange_halos; apply_boundary(.,.,bc,0.0); copy u->tmp;
-// diffusion_step; advection_step; swap }.  NetCDF/YAML are not involved (PnetCDF and
-// yaml-cpp are absent from the image, so src/io.cpp, src/init.cpp and src/main.cpp
+// diffusion_step; advection_step; swap }, with --bc_value (default 0.0) in place of the
+// driver's 0.0.  NetCDF/YAML are not involved (PnetCDF and yaml-cpp are absent from the image, so src/io.cpp, src/init.cpp and src/main.cpp
 // are not buildable here; the gaussian IC below restates src/init.cpp:12-33).
 //
 // Modes (first argument):
-//   run        full multi-rank time loop; dumps per-rank local fields (ghosts included)
+//   run        full multi-rank time loop; dumps per-rank local fields (ghosts included); --bc_value is
+//              the Dirichlet value handed to apply_boundary each step
 //   unit       one diffusion_step and/or advection_step on rank 0 (ring-copy/accumulate)
 //   boundary   apply_boundary alone on rank 0 with a caller-chosen fill value
 //   decomp     prints Decomp2D of every rank as one text line each
@@ -148,6 +149,7 @@ int mode_run(const Args& a, int rank, int size) {
     const BCConfig bc = bc_from_code(a.str("bc", "dddd"));
     const std::string out = a.str("out", "");
     const bool clamp = a.integer("clamp", 1) != 0;
+    const double bc_value = a.num("bc_value", 0.0);  // the reference's driver always passes 0.0
 
     if (clamp) {  // reference src/main.cpp:42-49
         const double lim = safe_dt(dx, dy, vx, vy, D);
@@ -182,7 +184,7 @@ int mode_run(const Args& a, int rank, int size) {
     for (int n = 0; n < steps; ++n) {
         const double ts = MPI_Wtime();
         exchange_halos(u, dec, MPI_COMM_WORLD);
-        apply_boundary(u, dec, bc, 0.0);
+        apply_boundary(u, dec, bc, bc_value);
         std::copy(u.data.begin(), u.data.end(), tmp.data.begin());
         diffusion_step(u, tmp, D, dt);
         advection_step(u, tmp, vx, vy, dt);

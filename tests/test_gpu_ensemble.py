@@ -36,21 +36,21 @@ def random_fields(B, nx, ny, seed):
     return rng.standard_normal((B, ny + 2, nx + 2))
 
 
-def oracle_runs(u0s, phys, bc, steps, dx=1.0, dy=1.0):
+def oracle_runs(u0s, phys, bc, steps, dx=1.0, dy=1.0, value=0.0):
     ora.lib()  # loaded (built if need be) once, before the threads use it
 
     def one(k):
         u = u0s[k].copy()
         D, dt, vx, vy = phys[k]
-        ora.run_single(u, dx, dy, D, vx, vy, dt, bc, steps)
+        ora.run_single(u, dx, dy, D, vx, vy, dt, bc, steps, value=value)
         return u
     with ThreadPoolExecutor(8) as ex:  # the oracle's C loop releases the GIL
         return list(ex.map(one, range(len(u0s))))
 
 
-def run_ensemble(csim, u0s, phys, bc, steps, dx=1.0, dy=1.0, fuse=None, calls=None):
+def run_ensemble(csim, u0s, phys, bc, steps, dx=1.0, dy=1.0, fuse=None, calls=None, bc_value=0.0):
     B, ny2, nx2 = u0s.shape
-    e = csim.Ensemble(B, nx2 - 2, ny2 - 2, dx, dy, bc)
+    e = csim.Ensemble(B, nx2 - 2, ny2 - 2, dx, dy, bc, bc_value)
     if fuse is not None:
         e.set_option("fuse", fuse)
     e.upload_all(u0s)

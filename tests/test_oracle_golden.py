@@ -140,3 +140,60 @@ def test_periodic_is_noop_equals_dirichlet_zero():
     ora.run_single(a, 1.0, 1.0, 0.1, 0.3, -0.2, 0.1, ora.bc_codes("pppp"), 6)
     ora.run_single(b, 1.0, 1.0, 0.1, 0.3, -0.2, 0.1, ora.bc_codes("dddd"), 6)
     assert np.array_equal(a, b)
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.int64)
+
+
+def test_dirichlet_value_fixture_holds_the_values():
+    """the harness's --bc_value reached apply_boundary: every Dirichlet ghost line of the 1-rank result holds the case's
+    value to the bit (-0.0 included), and every value differs from the driver's +0.0"""
+    z, cases = _load(os.path.join(GOLDEN, "dirichlet_value.npz"))
+    assert any(c["ranks"] == [1, 4, 8] for c in cases)
+    for c in cases:
+        k, v = c["idx"], c["bc_value"]
+        assert v != 0.0 or np.signbit(v), c
+        got = z[f"c{k}_local_np1_rank0"]
+        lines = {0: got[1:-1, 0], 1: got[1:-1, -1], 2: got[0, 1:-1], 3: got[-1, 1:-1]}
+        sides = [s for s, code in enumerate(ora.bc_codes(c["bc"])) if code == ora.DIRICHLET]
+        assert sides, c
+        for s in sides:
+            assert (bits(lines[s]) == bits(np.float64(v))).all(), (c["name"], s)
+
+
+def test_dirichlet_value_single_tile_bit_exact():
+    z, cases = _load(os.path.join(GOLDEN, "dirichlet_value.npz"))
+    for c in cases:
+        k = c["idx"]
+        dt = float(z[f"c{k}_dt_effective"])
+        assert dt == min(c["dt"], ora.safe_dt(c["dx"], c["dy"], c["vx"], c["vy"], c["D"]))
+        u = with_ghosts(z[f"c{k}_u0"])
+        ora.run_single(u, c["dx"], c["dy"], c["D"], c["vx"], c["vy"], dt, ora.bc_codes(c["bc"]), c["steps"],
+                       value=c["bc_value"])
+        assert np.array_equal(bits(u[1:-1, 1:-1]), bits(z[f"c{k}_u_final"])), c["name"]
+        assert np.array_equal(bits(u), bits(z[f"c{k}_local_np1_rank0"])), c["name"]
+        # the value matters: the driver's 0.0 gives another field
+        u0 = with_ghosts(z[f"c{k}_u0"])
+        ora.run_single(u0, c["dx"], c["dy"], c["D"], c["vx"], c["vy"], dt, ora.bc_codes(c["bc"]), c["steps"])
+        assert not np.array_equal(bits(u0), bits(u)), c["name"]
+        for p in c["ranks"]:  # decomposition-invariant: the ranks' interiors reassemble to the same field
+            g = np.zeros_like(z[f"c{k}_u_final"])
+            for r, row in enumerate(z[f"c{k}_decomp_np{p}"]):
+                lnx, lny, xo, yo = row[8:12]
+                g[yo:yo + lny, xo:xo + lnx] = z[f"c{k}_local_np{p}_rank{r}"][1:-1, 1:-1]
+            assert np.array_equal(bits(g), bits(z[f"c{k}_u_final"])), (c["name"], p)
+
+
+@pytest.mark.parametrize("bcs", ["dnpd", "nnnn", "pppp", "dddd"])
+def test_run_single_value_zero_is_run_single(bcs):
+    """ora_run_single_value with +0.0 is the reference driver's loop (ora_run_single), bit for bit"""
+    rng = np.random.default_rng(len(bcs) + ord(bcs[0]))
+    u0 = rng.standard_normal((23, 31))
+    a, b = u0.copy(), u0.copy()
+    ora.run_single(a, 0.5, 2.0, 0.02, -0.3, 0.2, 0.05, ora.bc_codes(bcs), 9)
+    ora.lib().ora_run_single_value(ora._dp(b), 29, 21, 0.5, 2.0, 0.02, -0.3, 0.2, 0.05, ora._i4(ora.bc_codes(bcs)), 9, 0.0)
+    assert np.array_equal(bits(a), bits(b))
+    c = u0.copy()
+    ora.run_single(c, 0.5, 2.0, 0.02, -0.3, 0.2, 0.05, ora.bc_codes(bcs), 9, value=0.0)
+    assert np.array_equal(bits(a), bits(c))
