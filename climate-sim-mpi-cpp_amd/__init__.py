@@ -187,6 +187,9 @@ def lib() -> C.CDLL:
         "csim_ensemble_verify_wait": (i, [vp, C.POINTER(dp), C.POINTER(dp), C.POINTER(C.POINTER(C.c_ulonglong)),
                                           C.POINTER(CsimVerifyScores)]),
         "csim_ensemble_rank_slot": (i, [C.c_longlong, i, ip]),
+        "csim_ensemble_assimilate": (i, [vp, i, ip, ip, dp, dp, d, d, i, i, dp, dp, dp, dp, ip]),
+        "csim_ensemble_gc_table": (i, [d, d, d, i, i, ip, ip, dp]),
+        "csim_ensemble_assim_plan": (i, [i, ip, ip, i, i, i, ip, ip]),
         "csim_ensemble_set_option": (i, [vp, C.c_char_p, C.c_long]),
         "csim_ensemble_get_option": (i, [vp, C.c_char_p, C.POINTER(C.c_long)]),
         "csim_ensemble_plan": (i, [i, i, i, i, ip]),
@@ -589,6 +592,53 @@ def ensemble_rank_slot(g: int, ties: int) -> int:
     return v.value
 
 
+EnsembleAnalysis = collections.namedtuple("EnsembleAnalysis", "nlevels prior_mean prior_var post_mean post_var")
+EnsembleAnalysis.__doc__ = """an analysis (Ensemble.assimilate): the plan's level count and, per observation in input
+order, the forecast mean and variance at its cell when its turn came and the analysis mean and variance there after
+all observations"""
+
+
+def _ints(v, n=None):
+    """int32 copy of integral values (integer dtype, or floats with no fraction) within the int32 range"""
+    v = np.atleast_1d(np.asarray(v))
+    if v.ndim != 1:
+        raise ValueError("expected a one-dimensional sequence of indices")
+    if v.size and not np.issubdtype(v.dtype, np.integer):
+        if not np.issubdtype(v.dtype, np.floating) or not np.all(np.isfinite(v)) or np.any(v != np.trunc(v)):
+            raise ValueError("indices must be integral")
+    if v.size and (v.min() < np.iinfo(np.int32).min or v.max() > np.iinfo(np.int32).max):
+        raise ValueError("indices out of the int32 range")
+    a = np.ascontiguousarray(v, dtype=np.int32)
+    if n is not None and a.shape != (n,):
+        raise ValueError(f"expected {n} values")
+    return a
+
+
+def _ip(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def ensemble_gc_table(dx, dy, loc, nx, ny) -> np.ndarray:
+    """the Gaspari-Cohn localisation table of csim_ensemble_gc_table, shape (2 ly + 1, 2 lx + 1) — host only"""
+    lx, ly = C.c_int(), C.c_int()
+    _ck(lib().csim_ensemble_gc_table(float(dx), float(dy), float(loc), int(nx), int(ny), C.byref(lx), C.byref(ly),
+                                     None))
+    t = np.empty((2 * ly.value + 1, 2 * lx.value + 1))
+    _ck(lib().csim_ensemble_gc_table(float(dx), float(dy), float(loc), int(nx), int(ny), C.byref(lx), C.byref(ly),
+                                     _dp(t)))
+    return t
+
+
+def ensemble_assim_plan(i, j, lx, ly, ordered=False) -> np.ndarray:
+    """the level of each observation (int32) in csim_ensemble_assimilate's plan — host only"""
+    ii = _ints(i)
+    jj = _ints(j, len(ii))
+    lev, nl = np.zeros(len(ii), dtype=np.int32), C.c_int()
+    _ck(lib().csim_ensemble_assim_plan(len(ii), _ip(ii), _ip(jj), int(lx), int(ly), int(bool(ordered)), _ip(lev),
+                                       C.byref(nl)))
+    return lev
+
+
 def _scores(sc: CsimVerifyScores, nt: int) -> VerifyScores:
     return VerifyScores(sc.cells, sc.nan_cells, sc.crps, sc.rmse, sc.spread, np.array(sc.brier[:nt], dtype=np.float64))
 
@@ -745,6 +795,25 @@ class Ensemble:
         brier = np.ctypeslib.as_array(pb, shape=(nt,) + shape).copy() if nt else np.empty((0,) + shape)
         hist = np.ctypeslib.as_array(ph, shape=(M + 1,)).copy()
         return EnsembleVerification(crps, brier, hist, _scores(sc, nt))
+
+    def assimilate(self, i, j, y, r, loc, inflation=1.0, truth_member=None, ordered=False, diagnostics=True):
+        """serial EnSRF analysis of the forecast members with point observations at interior cells (i, j), values y
+        and error variances r (a scalar broadcasts), Gaspari-Cohn length loc (csim_ensemble_assimilate).  With
+        diagnostics: an EnsembleAnalysis (synchronous); without: the level count, and the work is only enqueued"""
+        ii = _ints(i)
+        n = len(ii)
+        jj = _ints(j, n)
+        yy = np.ascontiguousarray(np.broadcast_to(np.asarray(y, dtype=np.float64), (n,)))
+        rr = np.ascontiguousarray(np.broadcast_to(np.asarray(r, dtype=np.float64), (n,)))
+        tm = -1 if truth_member is None else int(truth_member)
+        nl = C.c_int()
+        outs = [np.empty(n) for _ in range(4)] if diagnostics else [None] * 4
+        ptr = [_dp(o) if o is not None else None for o in outs]
+        _ck(lib().csim_ensemble_assimilate(self._h, n, _ip(ii), _ip(jj), _dp(yy), _dp(rr), float(loc),
+                                           float(inflation), tm, int(bool(ordered)), *ptr, C.byref(nl)))
+        if not diagnostics:
+            return nl.value
+        return EnsembleAnalysis(nl.value, *outs)
 
     def set_option(self, key: str, value: int):
         _ck(lib().csim_ensemble_set_option(self._h, key.encode(), int(value)))

@@ -2,9 +2,11 @@
 // ensemble.hip, device layout in ensemble.hpp).  Each member is advanced exactly as csim_stepper_run advances a
 // single-rank stepper holding the same field with the same parameters, ghost ring included.
 #include <algorithm>
+#include <cstdlib>
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "ensemble.hpp"
@@ -58,6 +60,14 @@ struct csim_ensemble {
     hipEvent_t ev_v = nullptr;
     bool v_pending = false;
     int v_forecast = 0, v_nt = 0, v_blocks = 0;  // of the capture in flight
+    // analysis (csim_ensemble_assimilate): one device buffer (the call's inputs in plan order and its localisation
+    // table, then per-observation scalars, diagnostics and one batch's h'_k), the pinned staging buffer the inputs go
+    // through, and the event after the staging buffer's last copy (ev_a).  Both buffers grow to the largest call.
+    char* a_d = nullptr;
+    char* a_h = nullptr;
+    size_t a_dcap = 0, a_hcap = 0;  // bytes
+    hipEvent_t ev_a = nullptr;
+    bool a_used = false;
 
     double* view(int buf, int m) const {
         return alloc[buf] + static_cast<size_t>(m) * g.slab + static_cast<size_t>(GHOST_EXTRA) * g.pitch;
@@ -297,6 +307,114 @@ int verify_launch(csim_ensemble* e, const double* truth, int truth_member, int f
     return CSIM_OK;
 }
 
+// the localisation half-width along one axis: the largest a >= 0 with a * h < 2 loc, at most n - 1
+int gc_half(double h, double loc, int n) {
+    const double s = 2.0 * loc;
+    if (static_cast<double>(n - 1) * h < s) return n - 1;
+    int a = static_cast<int>(std::min(std::floor(s / h), static_cast<double>(n - 1)));
+    while (a > 0 && static_cast<double>(a) * h >= s) --a;
+    while (a + 1 < n && static_cast<double>(a + 1) * h < s) ++a;
+    return a;
+}
+
+// Gaspari-Cohn in the Horner forms of csim.h, clamped at +0
+double gc_value(double z) {
+    double v = 0.0;
+    if (z <= 1.0)
+        v = ((((-0.25 * z + 0.5) * z + 0.625) * z - 5.0 / 3.0) * z) * z + 1.0;
+    else if (z < 2.0)
+        v = ((((z / 12.0 - 0.5) * z + 0.625) * z + 5.0 / 3.0) * z - 5.0) * z + 4.0 - 2.0 / (3.0 * z);
+    return v > 0.0 ? v : 0.0;
+}
+
+void gc_fill(double dx, double dy, double loc, int lx, int ly, double* table) {
+    const int tw = 2 * lx + 1;
+    for (int b = -ly; b <= ly; ++b)
+        for (int a = -lx; a <= lx; ++a) {
+            const double ax = static_cast<double>(a) * dx, by = static_cast<double>(b) * dy;
+            table[static_cast<size_t>(b + ly) * tw + (a + lx)] = gc_value(std::sqrt(ax * ax + by * by) / loc);
+        }
+}
+
+// the levels of csim_ensemble_assim_plan.  Spatial buckets of (2 lx + 1) x (2 ly + 1) cells: observations that
+// conflict lie in the same bucket or in one of its eight neighbours.  First fit keeps one bucket map per level,
+// ordered mode one for all earlier observations.
+int assim_levels(int n, const int* oi, const int* oj, int lx, int ly, bool ordered, int* level) {
+    const long long wx = 2LL * lx, wy = 2LL * ly;
+    auto bucket = [&](long long v, long long w) { return v >= 0 ? v / (w + 1) : -((-v + w) / (w + 1)); };
+    auto key = [](long long bi, long long bj) { return static_cast<unsigned long long>(bi) * 0x9E3779B97F4A7C15ull ^
+                                                       static_cast<unsigned long long>(bj); };
+    using Map = std::unordered_map<unsigned long long, std::vector<int>>;
+    // calls f(p) for every observation p of map m in the 3 x 3 buckets around o that conflicts with o; stops when f
+    // returns true
+    auto scan = [&](const Map& m, int o, auto&& f) {
+        const long long bi = bucket(oi[o], wx), bj = bucket(oj[o], wy);
+        for (long long u = bi - 1; u <= bi + 1; ++u)
+            for (long long v = bj - 1; v <= bj + 1; ++v) {
+                auto it = m.find(key(u, v));
+                if (it == m.end()) continue;
+                for (int p : it->second)
+                    if (std::llabs(static_cast<long long>(oi[p]) - oi[o]) <= wx &&
+                        std::llabs(static_cast<long long>(oj[p]) - oj[o]) <= wy && f(p))
+                        return;
+            }
+    };
+    int nl = 0;
+    if (ordered) {
+        Map all;
+        for (int o = 0; o < n; ++o) {
+            int lv = 0;
+            scan(all, o, [&](int p) {
+                lv = std::max(lv, level[p] + 1);
+                return false;
+            });
+            level[o] = lv;
+            nl = std::max(nl, lv + 1);
+            all[key(bucket(oi[o], wx), bucket(oj[o], wy))].push_back(o);
+        }
+        return nl;
+    }
+    std::vector<Map> per;
+    for (int o = 0; o < n; ++o) {
+        int lv = 0;
+        for (;; ++lv) {
+            if (lv == static_cast<int>(per.size())) break;
+            bool hit = false;
+            scan(per[lv], o, [&](int) { return hit = true; });
+            if (!hit) break;
+        }
+        if (lv == static_cast<int>(per.size())) per.emplace_back();
+        per[lv][key(bucket(oi[o], wx), bucket(oj[o], wy))].push_back(o);
+        level[o] = lv;
+    }
+    return static_cast<int>(per.size());
+}
+
+// byte layout of the analysis buffer: the staged inputs (y, r, table, i, j, input index), then the device-only
+// scalars (3 per observation), prior and posterior diagnostics (2 each per observation) and one batch's h'_k
+struct AssimLayout {
+    size_t y, r, rho, i, j, idx, staged, scal, prior, post, hp, total;
+};
+AssimLayout assim_layout(size_t n, size_t tcells, size_t hp) {
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    AssimLayout l{};
+    l.y = 0;
+    l.r = up(l.y + 8 * n);
+    l.rho = up(l.r + 8 * n);
+    l.i = up(l.rho + 8 * tcells);
+    l.j = up(l.i + 4 * n);
+    l.idx = up(l.j + 4 * n);
+    l.staged = up(l.idx + 4 * n);
+    l.scal = l.staged;
+    l.prior = up(l.scal + 24 * n);
+    l.post = up(l.prior + 16 * n);
+    l.hp = up(l.post + 16 * n);
+    l.total = up(l.hp + 8 * hp);
+    return l;
+}
+
+constexpr size_t ASSIM_HP_DOUBLES = size_t(1) << 23;  // h'_k of one batch: 64 MiB, at least 8192 observations
+
 int ghost_fill(csim_ensemble* e, bool fin) {
     CSIM_HIP(ens_launch_ghost_fill(e->g, e->base(e->cur), e->base(1 - e->cur), e->table, fin, e->st));
     return CSIM_OK;
@@ -402,6 +520,9 @@ int csim_ensemble_destroy(csim_ensemble* e) {
     if (e->ev_vtruth) (void)hipEventDestroy(e->ev_vtruth);
     if (e->ev_v) (void)hipEventDestroy(e->ev_v);
     if (e->s_vio) (void)hipStreamDestroy(e->s_vio);
+    if (e->a_d) (void)hipFree(e->a_d);
+    if (e->a_h) (void)hipHostFree(e->a_h);
+    if (e->ev_a) (void)hipEventDestroy(e->ev_a);
     for (double* a : e->alloc)
         if (a) (void)hipFree(a);
     if (e->fin) (void)hipFree(e->fin);
@@ -738,6 +859,153 @@ int csim_ensemble_verify_wait(csim_ensemble* e, const double** out_crps, const d
 int csim_ensemble_rank_slot(long long g, int ties, int* slot) {
     CSIM_REQUIRE(slot && g >= 0 && ties >= 0, "bad argument");
     *slot = static_cast<int>(verify_mix(static_cast<unsigned long long>(g)) % (static_cast<unsigned long long>(ties) + 1));
+    return CSIM_OK;
+}
+
+int csim_ensemble_gc_table(double dx, double dy, double loc, int nx, int ny, int* lx, int* ly, double* table) {
+    CSIM_REQUIRE(lx && ly, "null argument");
+    CSIM_REQUIRE(std::isfinite(dx) && dx > 0 && std::isfinite(dy) && dy > 0, "dx/dy must be finite and > 0");
+    CSIM_REQUIRE(std::isfinite(loc) && loc > 0, "loc must be finite and > 0");
+    CSIM_REQUIRE(nx >= 1 && ny >= 1, "empty grid");
+    *lx = gc_half(dx, loc, nx);
+    *ly = gc_half(dy, loc, ny);
+    if (table) gc_fill(dx, dy, loc, *lx, *ly, table);
+    return CSIM_OK;
+}
+
+int csim_ensemble_assim_plan(int nobs, const int* i, const int* j, int lx, int ly, int ordered, int* level,
+                             int* nlevels) {
+    CSIM_REQUIRE(nlevels, "null nlevels");
+    CSIM_REQUIRE(nobs >= 0, "nobs must be >= 0");
+    CSIM_REQUIRE(nobs == 0 || (i && j && level), "null array");
+    CSIM_REQUIRE(lx >= 0 && ly >= 0, "lx and ly must be >= 0");
+    CSIM_REQUIRE(ordered == 0 || ordered == 1, "ordered must be 0 or 1");
+    if (nobs > ASSIM_MAX_OBS) return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assim_plan: at most 2^20 observations");
+    *nlevels = assim_levels(nobs, i, j, lx, ly, ordered == 1, level);
+    return CSIM_OK;
+}
+
+int csim_ensemble_assimilate(csim_ensemble* e, int nobs, const int* i, const int* j, const double* y, const double* r,
+                             double loc, double inflation, int truth_member, int ordered, double* prior_mean,
+                             double* prior_var, double* post_mean, double* post_var, int* nlevels) {
+    CSIM_REQUIRE(e, "null ensemble");
+    const EnsGeom& g = e->g;
+    const int B = g.members;
+    CSIM_REQUIRE(nobs >= 0, "nobs must be >= 0");
+    CSIM_REQUIRE(nobs == 0 || (i && j && y && r), "null observation array");
+    CSIM_REQUIRE(std::isfinite(loc) && loc > 0, "loc must be finite and > 0");
+    CSIM_REQUIRE(std::isfinite(inflation) && inflation >= 1.0, "inflation must be finite and >= 1");
+    CSIM_REQUIRE(truth_member >= -1 && truth_member < B, "truth_member out of range");
+    CSIM_REQUIRE(ordered == 0 || ordered == 1, "ordered must be 0 or 1");
+    const int M = truth_member >= 0 ? B - 1 : B;
+    CSIM_REQUIRE(M >= 2, "the analysis needs at least two forecast members");
+    if (M > ASSIM_MAX_MEMBERS)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate: at most 1024 forecast members");
+    if (nobs > ASSIM_MAX_OBS) return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate: at most 2^20 observations");
+    for (int o = 0; o < nobs; ++o) {
+        CSIM_REQUIRE(i[o] >= 1 && i[o] <= g.nx && j[o] >= 1 && j[o] <= g.ny, "observation outside the interior");
+        CSIM_REQUIRE(std::isfinite(y[o]), "observation value must be finite");
+        CSIM_REQUIRE(std::isfinite(r[o]) && r[o] > 0, "observation error variance must be finite and > 0");
+    }
+    int lx = 0, ly = 0;
+    int rc = csim_ensemble_gc_table(e->dx, e->dy, loc, g.nx, g.ny, &lx, &ly, nullptr);
+    if (rc) return rc;
+    std::vector<int> level(nobs);
+    int nl = nobs ? assim_levels(nobs, i, j, lx, ly, ordered == 1, level.data()) : 0;
+    if (nlevels) *nlevels = nl;
+    const bool diag = prior_mean || prior_var || post_mean || post_var;
+    if (nobs == 0 && inflation == 1.0) return diag ? csim_ensemble_sync(e) : CSIM_OK;
+
+    // plan order: by level, then input index (a counting sort)
+    std::vector<int> off(nl + 1, 0), ord(nobs);
+    for (int o = 0; o < nobs; ++o) ++off[level[o] + 1];
+    for (int L = 0; L < nl; ++L) off[L + 1] += off[L];
+    {
+        std::vector<int> fill(off.begin(), off.end() - 1);
+        for (int o = 0; o < nobs; ++o) ord[fill[level[o]]++] = o;
+    }
+    const size_t tcells = static_cast<size_t>(2 * lx + 1) * (2 * ly + 1);
+    const int batch = static_cast<int>(std::min<size_t>(ASSIM_HP_DOUBLES / M, ASSIM_MAX_OBS));
+    const size_t hp = static_cast<size_t>(std::min(nobs, batch)) * M;
+    const AssimLayout l = assim_layout(nobs, tcells, hp);
+
+    // resources: the device buffer grows after the work already enqueued is done with it, the staging buffer after
+    // its last copy has run
+    if (!e->ev_a) CSIM_HIP(hipEventCreateWithFlags(&e->ev_a, hipEventDisableTiming));
+    if (l.total > e->a_dcap) {
+        CSIM_HIP(hipStreamSynchronize(e->st));
+        if (e->a_d) (void)hipFree(e->a_d);
+        e->a_d = nullptr;
+        e->a_dcap = 0;
+        CSIM_HIP(hipMalloc(reinterpret_cast<void**>(&e->a_d), l.total));
+        e->a_dcap = l.total;
+    }
+    if (e->a_used) CSIM_HIP(hipEventSynchronize(e->ev_a));
+    e->a_used = false;
+    if (l.staged > e->a_hcap) {
+        if (e->a_h) (void)hipHostFree(e->a_h);
+        e->a_h = nullptr;
+        e->a_hcap = 0;
+        CSIM_HIP(hipHostMalloc(reinterpret_cast<void**>(&e->a_h), l.staged, hipHostMallocDefault));
+        e->a_hcap = l.staged;
+    }
+    char* h = e->a_h;
+    auto* hy = reinterpret_cast<double*>(h + l.y);
+    auto* hr = reinterpret_cast<double*>(h + l.r);
+    auto* hi = reinterpret_cast<int*>(h + l.i);
+    auto* hj = reinterpret_cast<int*>(h + l.j);
+    auto* hx = reinterpret_cast<int*>(h + l.idx);
+    for (int q = 0; q < nobs; ++q) {
+        const int o = ord[q];
+        hy[q] = y[o], hr[q] = r[o], hi[q] = i[o], hj[q] = j[o], hx[q] = o;
+    }
+    gc_fill(e->dx, e->dy, loc, lx, ly, reinterpret_cast<double*>(h + l.rho));
+    CSIM_HIP(hipMemcpyAsync(e->a_d, h, l.staged, hipMemcpyHostToDevice, e->st));
+    CSIM_HIP(hipEventRecord(e->ev_a, e->st));
+    e->a_used = true;
+
+    AssimArgs a{};
+    a.forecast = M;
+    a.truth_member = truth_member >= 0 ? truth_member : B;
+    a.lx = lx, a.ly = ly;
+    a.rho = reinterpret_cast<const double*>(e->a_d + l.rho);
+    a.obs.i = reinterpret_cast<const int*>(e->a_d + l.i);
+    a.obs.j = reinterpret_cast<const int*>(e->a_d + l.j);
+    a.obs.idx = reinterpret_cast<const int*>(e->a_d + l.idx);
+    a.obs.y = reinterpret_cast<const double*>(e->a_d + l.y);
+    a.obs.r = reinterpret_cast<const double*>(e->a_d + l.r);
+    a.scal = reinterpret_cast<double*>(e->a_d + l.scal);
+    a.hp = reinterpret_cast<double*>(e->a_d + l.hp);
+    a.prior = prior_mean || prior_var ? reinterpret_cast<double*>(e->a_d + l.prior) : nullptr;
+    double* f = e->base(e->cur);
+    if (inflation != 1.0) CSIM_HIP(ens_launch_assim_inflate(g, f, M, a.truth_member, inflation - 1.0, e->st));
+    for (int L = 0; L < nl; ++L)
+        for (int q0 = off[L]; q0 < off[L + 1]; q0 += batch) {
+            const int n = std::min(batch, off[L + 1] - q0);
+            long wcells = 0;
+            for (int q = q0; q < q0 + n; ++q) {
+                const long w = std::min(g.nx, hi[q] + lx) - std::max(1, hi[q] - lx) + 1;
+                const long hgt = std::min(g.ny, hj[q] + ly) - std::max(1, hj[q] - ly) + 1;
+                wcells = std::max(wcells, w * hgt);
+            }
+            CSIM_HIP(ens_launch_assim_prior(g, f, a, q0, n, e->st));
+            CSIM_HIP(ens_launch_assim_update(g, f, a, q0, n, wcells, e->st));
+        }
+    if (!diag) return CSIM_OK;
+    auto* post = reinterpret_cast<double*>(e->a_d + l.post);
+    if (post_mean || post_var) CSIM_HIP(ens_launch_assim_post(g, f, a, nobs, post, e->st));
+    std::vector<double> pr(2 * static_cast<size_t>(nobs)), po(2 * static_cast<size_t>(nobs));
+    if (a.prior && nobs)
+        CSIM_HIP(hipMemcpyAsync(pr.data(), a.prior, sizeof(double) * pr.size(), hipMemcpyDeviceToHost, e->st));
+    if ((post_mean || post_var) && nobs)
+        CSIM_HIP(hipMemcpyAsync(po.data(), post, sizeof(double) * po.size(), hipMemcpyDeviceToHost, e->st));
+    CSIM_HIP(hipStreamSynchronize(e->st));
+    for (int o = 0; o < nobs; ++o) {
+        if (prior_mean) prior_mean[o] = pr[2 * static_cast<size_t>(o)];
+        if (prior_var) prior_var[o] = pr[2 * static_cast<size_t>(o) + 1];
+        if (post_mean) post_mean[o] = po[2 * static_cast<size_t>(o)];
+        if (post_var) post_var[o] = po[2 * static_cast<size_t>(o) + 1];
+    }
     return CSIM_OK;
 }
 

@@ -105,6 +105,41 @@ int ens_verify_blocks(const EnsGeom& g, int forecast);  // workgroups of the lau
 hipError_t ens_launch_verify(const EnsGeom& g, const double* f, const VerifyArgs& va, const VerifyOut& o,
                              hipStream_t st);
 
+// the analysis (ensemble_assim.hip): the serial EnSRF of csim.h, one level of mutually non-conflicting observations
+// after the other, two launches per batch of a level: assim_prior (one wave per observation: h'_k and its scalars)
+// and assim_update (one wave per 64 cells of one observation's window).  Observations are in plan order; `first` is
+// the batch's first plan position, `count` its observations.
+constexpr int ASSIM_MAX_MEMBERS = 1024;
+constexpr int ASSIM_MAX_OBS = 1 << 20;
+struct AssimObs {                 // device arrays, plan order
+    const int* i;
+    const int* j;
+    const int* idx;               // input index (the diagnostics are in input order)
+    const double* y;
+    const double* r;
+};
+struct AssimArgs {
+    int forecast;                 // M
+    int truth_member;             // t, or B (no member skipped)
+    int lx, ly;
+    const double* rho;            // (2 ly + 1) x (2 lx + 1)
+    AssimObs obs;
+    double* scal;                 // 3 per plan position: d, alpha, delta
+    double* hp;                   // M per observation of the batch: h'_k
+    double* prior;                // 2 per input index: hbar, p (null: not wanted)
+};
+// the batch's h'_k and scalars, then its window updates; wcells: the largest clipped window of the batch in cells
+hipError_t ens_launch_assim_prior(const EnsGeom& g, const double* f, const AssimArgs& a, int first, int count,
+                                  hipStream_t st);
+hipError_t ens_launch_assim_update(const EnsGeom& g, double* f, const AssimArgs& a, int first, int count,
+                                   long wcells, hipStream_t st);
+// x_k <- x_k + lm1 (x_k - xbar) on every interior cell of the forecast members
+hipError_t ens_launch_assim_inflate(const EnsGeom& g, double* f, int forecast, int truth_member, double lm1,
+                                    hipStream_t st);
+// the posterior mean and variance at each observation's cell, 2 per input index
+hipError_t ens_launch_assim_post(const EnsGeom& g, const double* f, const AssimArgs& a, int nobs, double* post,
+                                 hipStream_t st);
+
 // the rank histogram's tie-break: splitmix64's finaliser of the interior index g; a cell with `eq` members equal to the
 // truth goes to bin lt + mix(g) mod (eq + 1)
 __host__ __device__ inline unsigned long long verify_mix(unsigned long long z) {

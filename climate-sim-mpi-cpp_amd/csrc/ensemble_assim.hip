@@ -1,0 +1,233 @@
+// ensemble_assim.hip — the analysis of csim_ensemble_assimilate (host side in ensemble.cpp): the serial ensemble
+// square-root filter of csim.h, localised with the host's Gaspari-Cohn table.  Needs only the slab layout of
+// ensemble.hpp.
+//
+// The host sorts the observations into levels (csim_ensemble_assim_plan); observations of one level have disjoint
+// windows and none lies in another's window, so each level is one batch of independent rank-1 updates, two launches:
+//   assim_prior   one wave per observation: h_k of the M forecast members, hbar, h'_k (to `hp`), p, d, alpha, delta.
+//                 It runs apart from the update so that no workgroup of an observation can overwrite the observed cell
+//                 while another workgroup of that observation still reads it.
+//   assim_update  one wave per 64 cells of one observation's window (blockIdx.y: the observation, blockIdx.x: which
+//                 64 cells of its window clipped to the interior, row-major), so h'_k and the scalars are the same in
+//                 every lane of a wave, and lanes that follow i within a window row load each member coalesced.
+//                 M <= 64: each lane reads its cell of every member once into registers and writes it once.  M > 64:
+//                 three passes over the members (mean, covariance, update); a window's members stay in L2 between them.
+// Forecast member k is member k + (k >= t) of the ensemble (t = B: none skipped).  Every sum is a running sum from +0
+// in member order, without FMA contraction; / and sqrt are IEEE fp64 (no fast-math), so the numpy restatement of the
+// csim.h block gives the same bits.  Only interior cells of the forecast members are written; ghost rings, member t
+// and the other ping-pong buffer are never touched.
+#include <algorithm>
+
+#include "ensemble.hpp"
+
+#pragma clang fp contract(off)
+
+namespace csim {
+
+namespace {
+
+constexpr int ASSIM_GRID_Y = 65535;  // observations per launch row (larger batches loop)
+
+__device__ __forceinline__ double* cell(double* f, int i, int j, int pitch) {
+    return f + static_cast<ptrdiff_t>(j) * pitch + (LPAD - 1) + i;
+}
+
+__global__ __launch_bounds__(64) void k_assim_prior(const double* __restrict__ f, int pitch, long slab, AssimArgs a,
+                                                    int first) {
+    extern __shared__ double sh[];  // M values (dynamic: a small ensemble does not pay for 1024)
+    const int lane = threadIdx.x;
+    const int M = a.forecast, t = a.truth_member;
+    const int q = first + blockIdx.x;
+    const double* p = f + static_cast<ptrdiff_t>(a.obs.j[q]) * pitch + (LPAD - 1) + a.obs.i[q];
+    for (int k = lane; k < M; k += 64) sh[k] = p[static_cast<ptrdiff_t>(k + (k >= t)) * slab];
+    __syncthreads();
+    double s = 0.0;
+    for (int k = 0; k < M; ++k) s = s + sh[k];
+    const double hbar = s / static_cast<double>(M);
+    __syncthreads();
+    double* __restrict__ hp = a.hp + static_cast<size_t>(blockIdx.x) * M;
+    for (int k = lane; k < M; k += 64) {
+        const double v = sh[k] - hbar;
+        sh[k] = v;
+        hp[k] = v;
+    }
+    __syncthreads();
+    double ss = 0.0;
+    for (int k = 0; k < M; ++k) ss = ss + sh[k] * sh[k];
+    const double pv = ss / static_cast<double>(M - 1);
+    const double r = a.obs.r[q];
+    const double d = pv + r;
+    if (lane == 0) {
+        a.scal[3 * static_cast<size_t>(q)] = d;
+        a.scal[3 * static_cast<size_t>(q) + 1] = 1.0 / (1.0 + sqrt(r / d));
+        a.scal[3 * static_cast<size_t>(q) + 2] = a.obs.y[q] - hbar;
+        if (a.prior) {
+            const size_t o = 2 * static_cast<size_t>(a.obs.idx[q]);
+            a.prior[o] = hbar;
+            a.prior[o + 1] = pv;
+        }
+    }
+}
+
+// P > 0: the members in registers (P >= M); P = 0: re-read.  h'_k is staged in LDS (M values, dynamic) and read again
+// after a barrier for the update, so that the compiler does not keep all M of them live next to the members.  With
+// h'_k held in registers instead, P = 64 took 256 VGPRs plus AGPRs (one wave per SIMD); this form compiles to 177
+// VGPRs and no AGPRs (two waves per SIMD), DESIGN §7f.  P steps 4, 8, 16, 32, 48, 64: lanes load P values, those
+// past M being member M - 1 again
+template <int P>
+__global__ __launch_bounds__(64) void k_assim_update(double* __restrict__ f, int nx, int ny, int pitch, long slab,
+                                                     AssimArgs a, int first, int count) {
+    extern __shared__ double sh[];  // M values
+    const int lane = threadIdx.x;
+    const int M = a.forecast, t = a.truth_member, lx = a.lx, ly = a.ly, tw = 2 * lx + 1;
+    const double den = static_cast<double>(M), cden = static_cast<double>(M - 1);
+    for (int o = blockIdx.y; o < count; o += gridDim.y) {
+        const int q = first + o;
+        const int io = a.obs.i[q], jo = a.obs.j[q];
+        const int i0 = max(1, io - lx), i1 = min(nx, io + lx), j0 = max(1, jo - ly), j1 = min(ny, jo + ly);
+        const long W = i1 - i0 + 1, cells = W * (j1 - j0 + 1);
+        if (static_cast<long>(blockIdx.x) * 64 >= cells) continue;  // the same in every lane
+        const double d = a.scal[3 * static_cast<size_t>(q)], alpha = a.scal[3 * static_cast<size_t>(q) + 1];
+        const double delta = a.scal[3 * static_cast<size_t>(q) + 2];
+        __syncthreads();  // the last observation's readers of sh are done
+        for (int k = lane; k < M; k += 64) sh[k] = a.hp[static_cast<size_t>(o) * M + k];
+        __syncthreads();
+        for (long e0 = static_cast<long>(blockIdx.x) * 64; e0 < cells; e0 += static_cast<long>(gridDim.x) * 64) {
+            const long e = std::min(e0 + lane, cells - 1);  // lanes past the end redo the last cell and store nothing
+            const int row = static_cast<int>(e / W);
+            const int ci = i0 + static_cast<int>(e - row * W), cj = j0 + row;
+            const double rho = a.rho[static_cast<size_t>(cj - jo + ly) * tw + (ci - io + lx)];
+            const bool act = e0 + lane < cells && rho > 0.0;
+            double* p = cell(f, ci, cj, pitch);
+            if constexpr (P > 0) {
+                // member base pointers are wave-uniform, the cell's offset in a member is one 32-bit lane value
+                const unsigned off = static_cast<unsigned>(cj * pitch + (LPAD - 1) + ci);
+                // k >= M (P > M) loads member M - 1 again: no branch per member; the sums skip those
+                double x[P];
+#pragma unroll
+                for (int k = 0; k < P; ++k) {
+                    const int kk = min(k, M - 1);
+                    x[k] = f[static_cast<size_t>(kk + (kk >= t)) * slab + off];
+                }
+                double s = 0.0;
+#pragma unroll
+                for (int k = 0; k < P; ++k)
+                    if (k < M) s = s + x[k];
+                const double xbar = s / den;
+                double c = 0.0;
+#pragma unroll
+                for (int k = 0; k < P; ++k)
+                    if (k < M) c = c + (x[k] - xbar) * sh[k];
+                const double g = (rho * (c / cden)) / d;
+                const double beta = alpha * g;
+                __syncthreads();
+#pragma unroll
+                for (int k = 0; k < P; ++k)
+                    if (act && k < M) f[static_cast<size_t>(k + (k >= t)) * slab + off] = x[k] + (g * delta - beta * sh[k]);
+            } else {
+                double s = 0.0;
+                for (int k = 0; k < M; ++k) s = s + p[static_cast<ptrdiff_t>(k + (k >= t)) * slab];
+                const double xbar = s / den;
+                double c = 0.0;
+                for (int k = 0; k < M; ++k) c = c + (p[static_cast<ptrdiff_t>(k + (k >= t)) * slab] - xbar) * sh[k];
+                const double g = (rho * (c / cden)) / d;
+                const double beta = alpha * g;
+                if (act)
+                    for (int k = 0; k < M; ++k) {
+                        double* pk = p + static_cast<ptrdiff_t>(k + (k >= t)) * slab;
+                        *pk = *pk + (g * delta - beta * sh[k]);
+                    }
+            }
+        }
+    }
+}
+
+// one thread per interior cell (lanes along i), two passes over the members
+__global__ __launch_bounds__(256) void k_assim_inflate(double* __restrict__ f, int nx, int ny, int pitch, long slab,
+                                                       int M, int t, double lm1) {
+    const long cells = static_cast<long>(nx) * ny;
+    const double den = static_cast<double>(M);
+    for (long e = static_cast<long>(blockIdx.x) * 256 + threadIdx.x; e < cells;
+         e += static_cast<long>(gridDim.x) * 256) {
+        const int j = static_cast<int>(e / nx);
+        double* p = cell(f, static_cast<int>(e - static_cast<long>(j) * nx) + 1, j + 1, pitch);
+        double s = 0.0;
+        for (int k = 0; k < M; ++k) s = s + p[static_cast<ptrdiff_t>(k + (k >= t)) * slab];
+        const double xbar = s / den;
+        for (int k = 0; k < M; ++k) {
+            double* pk = p + static_cast<ptrdiff_t>(k + (k >= t)) * slab;
+            const double x = *pk;
+            *pk = x + lm1 * (x - xbar);
+        }
+    }
+}
+
+// one thread per observation
+__global__ __launch_bounds__(256) void k_assim_post(const double* __restrict__ f, int pitch, long slab, AssimArgs a,
+                                                    int nobs, double* __restrict__ post) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= nobs) return;
+    const int M = a.forecast, t = a.truth_member;
+    const double* p = f + static_cast<ptrdiff_t>(a.obs.j[q]) * pitch + (LPAD - 1) + a.obs.i[q];
+    double s = 0.0;
+    for (int k = 0; k < M; ++k) s = s + p[static_cast<ptrdiff_t>(k + (k >= t)) * slab];
+    const double m = s / static_cast<double>(M);
+    double v = 0.0;
+    for (int k = 0; k < M; ++k) {
+        const double dx = p[static_cast<ptrdiff_t>(k + (k >= t)) * slab] - m;
+        v = v + dx * dx;
+    }
+    const size_t o = 2 * static_cast<size_t>(a.obs.idx[q]);
+    post[o] = m;
+    post[o + 1] = v / static_cast<double>(M - 1);
+}
+
+template <int P>
+hipError_t launch_update(const EnsGeom& g, double* f, const AssimArgs& a, int first, int count, long wcells,
+                         hipStream_t st) {
+    const dim3 grid(static_cast<unsigned>((wcells + 63) / 64), static_cast<unsigned>(std::min(count, ASSIM_GRID_Y)));
+    hipLaunchKernelGGL(k_assim_update<P>, grid, dim3(64), sizeof(double) * a.forecast, st, f, g.nx, g.ny, g.pitch, g.slab, a, first, count);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t ens_launch_assim_prior(const EnsGeom& g, const double* f, const AssimArgs& a, int first, int count,
+                                  hipStream_t st) {
+    if (count <= 0) return hipSuccess;
+    if (a.forecast < 2 || a.forecast > ASSIM_MAX_MEMBERS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_assim_prior, dim3(count), dim3(64), sizeof(double) * a.forecast, st, f, g.pitch, g.slab, a, first);
+    return hipGetLastError();
+}
+
+hipError_t ens_launch_assim_update(const EnsGeom& g, double* f, const AssimArgs& a, int first, int count,
+                                   long wcells, hipStream_t st) {
+    if (count <= 0 || wcells <= 0) return hipSuccess;
+    const int M = a.forecast;
+    if (M < 2 || M > ASSIM_MAX_MEMBERS || wcells > 64L * 0x7fffffffL) return hipErrorInvalidValue;
+    if (M <= 4) return launch_update<4>(g, f, a, first, count, wcells, st);
+    if (M <= 8) return launch_update<8>(g, f, a, first, count, wcells, st);
+    if (M <= 16) return launch_update<16>(g, f, a, first, count, wcells, st);
+    if (M <= 32) return launch_update<32>(g, f, a, first, count, wcells, st);
+    if (M <= 48) return launch_update<48>(g, f, a, first, count, wcells, st);
+    if (M <= 64) return launch_update<64>(g, f, a, first, count, wcells, st);
+    return launch_update<0>(g, f, a, first, count, wcells, st);
+}
+
+hipError_t ens_launch_assim_inflate(const EnsGeom& g, double* f, int forecast, int truth_member, double lm1,
+                                    hipStream_t st) {
+    const long cells = static_cast<long>(g.nx) * g.ny;
+    const unsigned blocks = static_cast<unsigned>(std::min<long>((cells + 255) / 256, 65536L));
+    hipLaunchKernelGGL(k_assim_inflate, dim3(blocks), dim3(256), 0, st, f, g.nx, g.ny, g.pitch, g.slab, forecast,
+                       truth_member, lm1);
+    return hipGetLastError();
+}
+
+hipError_t ens_launch_assim_post(const EnsGeom& g, const double* f, const AssimArgs& a, int nobs, double* post,
+                                 hipStream_t st) {
+    if (nobs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_assim_post, dim3((nobs + 255) / 256), dim3(256), 0, st, f, g.pitch, g.slab, a, nobs, post);
+    return hipGetLastError();
+}
+
+}  // namespace csim

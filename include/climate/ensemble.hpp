@@ -30,6 +30,13 @@ struct EnsembleVerification {
     csim_verify_scores scores;
 };
 
+// an analysis (see csim_ensemble_assimilate): the plan's level count and, per observation in input order, the forecast
+// mean and variance at its cell at its turn and the analysis mean and variance there after all observations
+struct EnsembleAnalysis {
+    int nlevels = 0;
+    std::vector<double> prior_mean, prior_var, post_mean, post_var;
+};
+
 class Ensemble {
 public:
     Ensemble(int members, int nx, int ny, double dx, double dy, const int bc[4], double bc_value = 0.0)
@@ -162,6 +169,30 @@ public:
         check(csim_ensemble_verify_wait(h_, &v.crps, &v.brier, &v.rank_hist, &v.scores));
         return v;
     }
+    // serial EnSRF analysis with point observations (i[o], j[o], y[o], r[o]), Gaspari-Cohn length loc; t = -1: all
+    // members are the forecast, else member t is left alone.  Synchronous, with the diagnostics
+    EnsembleAnalysis assimilate(const std::vector<int>& i, const std::vector<int>& j, const std::vector<double>& y,
+                                const std::vector<double>& r, double loc, double inflation = 1.0, int t = -1,
+                                bool ordered = false) {
+        const std::size_t n = obs_size(i, j, y, r);
+        EnsembleAnalysis a;
+        a.prior_mean.resize(n), a.prior_var.resize(n), a.post_mean.resize(n), a.post_var.resize(n);
+        check(csim_ensemble_assimilate(h_, static_cast<int>(n), i.data(), j.data(), y.data(), r.data(), loc, inflation,
+                                       t, ordered ? 1 : 0, a.prior_mean.data(), a.prior_var.data(), a.post_mean.data(),
+                                       a.post_var.data(), &a.nlevels));
+        return a;
+    }
+    // the same without diagnostics: enqueued on the ensemble's stream (the observations are copied before it returns),
+    // so that run() follows without a host wait; returns the level count
+    int assimilate_enqueue(const std::vector<int>& i, const std::vector<int>& j, const std::vector<double>& y,
+                           const std::vector<double>& r, double loc, double inflation = 1.0, int t = -1,
+                           bool ordered = false) {
+        int nl = 0;
+        check(csim_ensemble_assimilate(h_, static_cast<int>(obs_size(i, j, y, r)), i.data(), j.data(), y.data(),
+                                       r.data(), loc, inflation, t, ordered ? 1 : 0, nullptr, nullptr, nullptr,
+                                       nullptr, &nl));
+        return nl;
+    }
     void set_option(const char* key, long value) { check(csim_ensemble_set_option(h_, key, value)); }
     long get_option(const char* key) const {
         long v = 0;
@@ -186,6 +217,12 @@ private:
         check(csim_ensemble_verify(h_, truth, t, fair ? 1 : 0, static_cast<int>(thresholds.size()), thresholds.data(),
                                    r.crps.data(), r.brier.data(), r.rank_hist.data(), &r.scores));
         return r;
+    }
+    static std::size_t obs_size(const std::vector<int>& i, const std::vector<int>& j, const std::vector<double>& y,
+                                const std::vector<double>& r) {
+        if (j.size() != i.size() || y.size() != i.size() || r.size() != i.size())
+            throw std::invalid_argument("ensemble: observation arrays of different sizes");
+        return i.size();
     }
     csim_ensemble* h_ = nullptr;
     int members_, nx_, ny_;

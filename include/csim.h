@@ -375,6 +375,65 @@ int csim_ensemble_verify_wait(csim_ensemble* e, const double** out_crps, const d
                               const unsigned long long** rank_hist, csim_verify_scores* scores);
 /* host-only: the rank histogram's tie-break, mix(g) mod (ties + 1) for g >= 0, ties >= 0 */
 int csim_ensemble_rank_slot(long long g, int ties, int* slot);
+/* analysis: pulls the forecast members towards point observations with the serial ensemble square-root filter
+ * (Whitaker & Hamill 2002), localised with Gaspari & Cohn (1999).  Deterministic: no perturbed observations, no
+ * random numbers, no matrix solves (every observation is a rank-1 update).
+ * Observation o (0 <= o < nobs) is the interior cell (i[o], j[o]) of the reference layout (1 <= i <= nx,
+ * 1 <= j <= ny, field [j, i]) with value y[o] and error variance r[o] > 0; the observation operator picks that cell.
+ * The forecast members x_k, k = 0 .. M-1, are all B members (truth_member = -1), or the B - 1 others, in their order,
+ * with truth_member = t (as csim_ensemble_verify); member t is not modified.  2 <= M <= CSIM_ASSIM_MAX_MEMBERS.
+ * Localisation: rho = the table of csim_ensemble_gc_table(dx, dy, loc, nx, ny), with its half-widths lx, ly.
+ * Inflation lambda >= 1: when lambda != 1, before the first observation every interior cell of every forecast member
+ * becomes  x_k + (lambda - 1) (x_k - xbar),  xbar = sum x_k / M  (lambda - 1 formed on the host); lambda == 1 changes
+ * nothing.  The observations are then taken one at a time, sorted by (level, input index), level from
+ * csim_ensemble_assim_plan(nobs, i, j, lx, ly, ordered).  Per observation, without FMA contraction, every sum a
+ * running sum from +0 in member order k = 0 .. M-1:
+ *
+ *     h_k = x_k(i_o, j_o);  hbar = sum h_k / M;  h'_k = h_k - hbar
+ *     p = sum h'_k h'_k / (M-1);  d = p + r_o;  alpha = 1 / (1 + sqrt(r_o / d));  delta = y_o - hbar
+ *     for every interior cell c = (i_o+a, j_o+b), |a| <= lx, |b| <= ly, with rho = rho[b+ly][a+lx] > 0:
+ *         xbar = sum x_k(c) / M;  x'_k = x_k(c) - xbar
+ *         cov  = sum x'_k h'_k / (M-1)
+ *         g    = (rho cov) / d;  beta = alpha g
+ *         x_k(c) <- x_k(c) + (g delta - beta h'_k)
+ *
+ * The division and the square root are IEEE fp64, correctly rounded.  Observations of one level are in disjoint
+ * windows, so they commute exactly: the result is the serial filter in that order, whatever the launches.  The ghost
+ * ring of every member (both ping-pong buffers), every cell outside all windows, and member t are left as they were.
+ * Diagnostics, nobs values each in input order, any may be NULL: prior_mean, prior_var = hbar and p of each
+ * observation at its turn; post_mean, post_var = sum x_k / M and sum (x_k - m)(x_k - m) / (M-1) at each observation's
+ * cell after all observations.  *nlevels (may be NULL): the plan's level count.
+ * With all four diagnostics NULL the call only enqueues its work on the ensemble's stream (the observations are copied
+ * before it returns) and returns without waiting; otherwise it synchronises.  Statistics, quantile and verification
+ * captures begun before the call see the state before the analysis.  No set_physics needed.  nobs = 0 with
+ * lambda = 1 changes nothing.
+ * Errors: CSIM_ERR_ARG for an observation outside the interior, r <= 0 or non-finite, y non-finite, loc <= 0 or
+ * non-finite, lambda < 1 or non-finite, truth_member outside -1 .. B-1, M < 2, ordered not 0 / 1, nobs < 0, a null
+ * i / j / y / r with nobs > 0; CSIM_ERR_UNSUPPORTED for M > CSIM_ASSIM_MAX_MEMBERS or nobs > CSIM_ASSIM_MAX_OBS. */
+#define CSIM_ASSIM_MAX_MEMBERS 1024
+#define CSIM_ASSIM_MAX_OBS (1 << 20)
+int csim_ensemble_assimilate(csim_ensemble* e, int nobs, const int* i, const int* j, const double* y, const double* r,
+                             double loc, double inflation, int truth_member, int ordered, double* prior_mean,
+                             double* prior_var, double* post_mean, double* post_var, int* nlevels);
+/* host-only: the Gaspari-Cohn localisation table.  loc = c > 0 in the units of dx and dy (support 2c).
+ * lx = min(largest a >= 0 with (double)a * dx < 2 c, nx - 1), ly the same with dy and ny.  table (may be NULL: only
+ * the sizes) gets (2 ly + 1) x (2 lx + 1) values, row b + ly, column a + lx:  GC(z), z = sqrt((a dx)^2 + (b dy)^2) / c,
+ * each product and sum rounded in that order, and in Horner form
+ *   z <= 1:     ((((-0.25 z + 0.5) z + 0.625) z - 5/3) z) z + 1
+ *   1 < z < 2:  ((((z/12 - 0.5) z + 0.625) z + 5/3) z - 5) z + 4 - 2/(3 z)
+ *   z >= 2:     0
+ * (5/3 the rounded quotient, z/12 = z / 12, 2/(3 z) = 2 / (3 z), left to right: (... + 4) - 2/(3 z)), then
+ * max(., +0).  The device only reads this table.  Errors: CSIM_ERR_ARG for dx, dy, loc
+ * not finite and > 0, nx or ny < 1, null lx / ly. */
+int csim_ensemble_gc_table(double dx, double dy, double loc, int nx, int ny, int* lx, int* ly, double* table);
+/* host-only: the levels of csim_ensemble_assimilate.  Observations o and p conflict when |i_o - i_p| <= 2 lx and
+ * |j_o - j_p| <= 2 ly (their windows may overlap).  ordered = 0 (first fit): in input order, each observation goes to
+ * the lowest level holding no observation it conflicts with.  ordered = 1 (the caller's order kept): level(o) = 1 + the
+ * highest level of an earlier observation conflicting with o, 0 when there is none.  level: nobs values;
+ * *nlevels = 1 + the highest level (0 for nobs = 0).  Errors: CSIM_ERR_ARG for nobs < 0, lx or ly < 0, ordered not
+ * 0 / 1, null arrays with nobs > 0, null nlevels; CSIM_ERR_UNSUPPORTED for nobs > CSIM_ASSIM_MAX_OBS. */
+int csim_ensemble_assim_plan(int nobs, const int* i, const int* j, int lx, int ly, int ordered, int* level,
+                             int* nlevels);
 /* options (unknown keys: CSIM_ERR_ARG; "contract": CSIM_ERR_UNSUPPORTED), results never depend on them:
  *   "fuse"        -1 (default) passes of the ensemble depth where the grid allows; 0 / 1 single steps only
  *   "fused_2c"    0/1 (default 1), as for csim_stepper_set_option
