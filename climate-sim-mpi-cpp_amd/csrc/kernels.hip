@@ -383,6 +383,8 @@ struct SweepArgs {
     FrameSync fs;
 };
 constexpr int SWEEP_ARGS_KERNARG_OFFSET = 16;  // two pointers precede it; alignof(SweepArgs) == 8
+static_assert(alignof(SweepArgs) <= 8 && 2 * sizeof(void*) == SWEEP_ARGS_KERNARG_OFFSET,
+              "LateArgs reads SweepArgs from the kernel-argument segment right behind the two field pointers");
 
 struct LateArgs {
     typedef const SweepArgs __attribute__((address_space(4))) * Ptr;

@@ -5,20 +5,36 @@
 
 namespace csim {
 
+// Fold the recorded event pairs into prof_ms / prof_launches and empty the pool.  The pairs were recorded on whichever
+// streams the schedule of their pass used — the compute stream, the comm stream, or the relay pair of the bulk-first
+// passes (prof_begin(s, T, X), prof_start(.., Y, ..), prof_end(s, F)) — and hipEventElapsedTime refuses a pair whose
+// events have not completed (hipErrorNotReady), so the fold waits for ALL of the stepper's streams first, on the path
+// csim_stepper_sync takes (wait_streams: a dead peer ends in CSIM_ERR_RCCL, a bounded wait in CSIM_ERR_TIMEOUT, and
+// then the pool is left as it is: the pairs are folded by the next call that finds the streams drained).  It is a host
+// wait only: nothing is enqueued and `tail` stays where it is, so a fold in the middle of a run (prof_begin, pool
+// full) does not touch the relay hand-over.  A pair that cannot be read even then is dropped with the rest of the
+// pool, nothing of this fold is added to the totals, and the error is returned once: later timer calls start clean.
 int prof_fold(csim_stepper* s) {
     if (s->ev_used == 0) return CSIM_OK;
     int rc0 = prof_close(s);
     if (rc0) return rc0;
-    CSIM_HIP(hipStreamSynchronize(s->s_comp));
-    CSIM_HIP(hipStreamSynchronize(s->s_comm));
-    for (size_t k = 0; k + 1 < s->ev_used; k += 2) {
+    rc0 = wait_streams(s);
+    if (rc0) return rc0;
+    double ms_sum[csim::MAX_FUSE + 2]{};
+    long launches[csim::MAX_FUSE + 2]{};
+    const size_t used = s->ev_used;
+    s->ev_used = 0;
+    for (size_t k = 0; k + 1 < used; k += 2) {
         float ms = 0.f;
         CSIM_HIP(hipEventElapsedTime(&ms, s->ev_pool[k], s->ev_pool[k + 1]));
         const int t = s->ev_steps[k / 2];
-        s->prof_ms[t] += ms;
-        s->prof_launches[t] += s->ev_count[k / 2];
+        ms_sum[t] += ms;
+        launches[t] += s->ev_count[k / 2];
     }
-    s->ev_used = 0;
+    for (int t = 0; t <= csim_stepper::PROF_COMM; ++t) {
+        s->prof_ms[t] += ms_sum[t];
+        s->prof_launches[t] += launches[t];
+    }
     return CSIM_OK;
 }
 // one start/stop event pair of the current (sampled) pass: start recorded now on `st`; kind = time

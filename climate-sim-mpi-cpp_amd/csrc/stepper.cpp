@@ -34,9 +34,7 @@ int fused_depth(const csim_stepper* s) {
     return depth >= 2 && dpp_family ? depth : 1;
 }
 
-}  // namespace csim
-
-// Wait for both streams.  With an RCCL communicator the wait polls instead of blocking, so that an asynchronous
+// Wait for the stepper's streams.  With an RCCL communicator the wait polls instead of blocking, so that an asynchronous
 // communicator error (a peer that died, a failed transport: ncclCommGetAsyncError) ends it with CSIM_ERR_RCCL
 // instead of a silent hang on a stream nobody will ever complete — the reference's MPI_Waitall
 // (src/halo.cpp:46) would abort the job through the MPI error handler.  Option "sync_timeout_ms" > 0 bounds the
@@ -62,12 +60,28 @@ static int wait_stream(csim_stepper* s, hipStream_t st, const std::chrono::stead
             if (s->sync_timeout_ms > 0) {
                 const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
                 if (ms > static_cast<double>(s->sync_timeout_ms))
-                    return fail(CSIM_ERR_TIMEOUT, "csim_stepper_sync: streams still busy after " +
+                    return fail(CSIM_ERR_TIMEOUT, "streams still busy after " +
                                                       std::to_string(s->sync_timeout_ms) + " ms (option sync_timeout_ms)");
             }
         }
     }
 }
+
+// every stream a pass may have used: the compute stream, the relay pair, the comm stream (csim_stepper_sync, and
+// prof_fold before it reads its events)
+int wait_streams(csim_stepper* s) {
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = wait_stream(s, s->s_comp, t0);
+    if (rc) return rc;
+    for (hipStream_t r : s->s_relay)
+        if (r) {
+            rc = wait_stream(s, r, t0);
+            if (rc) return rc;
+        }
+    return wait_stream(s, s->s_comm, t0);
+}
+
+}  // namespace csim
 
 extern "C" {
 
@@ -461,15 +475,7 @@ int csim_stepper_exchange_halos(csim_stepper* s) {
 
 int csim_stepper_sync(csim_stepper* s) {
     CSIM_REQUIRE(s, "null stepper");
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = wait_stream(s, s->s_comp, t0);
-    if (rc) return rc;
-    for (hipStream_t r : s->s_relay)
-        if (r) {
-            rc = wait_stream(s, r, t0);
-            if (rc) return rc;
-        }
-    return wait_stream(s, s->s_comm, t0);
+    return wait_streams(s);
 }
 
 // Position-weighted 64-bit checksum of the local interior (k_checksum): the per-rank values of a decomposition

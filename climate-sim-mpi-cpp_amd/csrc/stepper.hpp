@@ -151,6 +151,7 @@ bool valid_bc(const int bc[4]);
 
 // stepper.cpp
 int settle(csim_stepper* s);  // the field state back onto the compute stream (see csim_stepper::tail)
+int wait_streams(csim_stepper* s);  // host wait for s_comp, s_relay[], s_comm: polls the communicator, honours sync_timeout_ms
 bool depth_ok(const csim_stepper* s, int depth);
 int fused_depth(const csim_stepper* s);
 

@@ -259,9 +259,12 @@ int csim_stepper_sum(csim_stepper* s, double* out);
  *                    height the most recent fused launch actually used */
 int csim_stepper_set_option(csim_stepper* s, const char* key, long value);
 int csim_stepper_get_option(const csim_stepper* s, const char* key, long* value);
-/* with option "profile"=1: HIP-event time (on the compute stream) and count of the sweep
- * launches since the last reset, per kernel kind: steps_per_launch = 1 selects the single-step
- * kernel, 2..7 the kernels that advance that many time steps per HBM pass */
+/* with option "profile"=1: HIP-event time and count of the sweep launches since the last reset, per kernel
+ * kind: steps_per_launch = 1 selects the single-step kernel, 2..7 the kernels that advance that many time steps
+ * per HBM pass (a multi-rank pass is one bracket around its frame and bulk launches; a single-rank run of equal
+ * launches is one bracket, counted per launch).  The timer calls may follow csim_stepper_run directly: they wait
+ * for every stream of the stepper the way csim_stepper_sync does (CSIM_ERR_RCCL / CSIM_ERR_TIMEOUT included,
+ * after which the recorded events are kept for the next call) before they read the events */
 int csim_stepper_kernel_time(csim_stepper* s, int steps_per_launch, double* total_ms,
                              long* launches);
 /* same sampling, multi-rank runs over RCCL with "overlap" = 1: HIP-event time of the comm-stream chain

@@ -101,7 +101,8 @@ def test_torus_at_tile_scale_every_schedule_equals_the_oracle(csim):
     for opts in [dict(overlap=0, fuse=0), dict(overlap=1, fuse=-1), dict(overlap=0, fuse=-1), dict(overlap=1, fuse=6), dict(overlap=3, fuse=6),
                  dict(overlap=1, fuse=4, rows_per_chunk=64), dict(overlap=1, fuse=3), dict(overlap=1, fuse=5),
                  dict(overlap=3, fuse=-1), dict(overlap=3, fuse=5, rows_per_chunk=40), dict(overlap=3, fuse=2),
-                 dict(overlap=4, fuse=-1), dict(overlap=4, fuse=7), dict(overlap=5, fuse=-1), dict(overlap=4, fuse=3)]:
+                 dict(overlap=4, fuse=-1), dict(overlap=4, fuse=7), dict(overlap=5, fuse=-1), dict(overlap=4, fuse=3),
+                 dict(overlap=5, fuse=-1, relay=0)]:
         st = csim.Stepper(d, 1.0, 1.0, csim.bc_codes("dddd"))
         st.comm_init(csim.comm_unique_id())
         for k, v in opts.items():
@@ -145,7 +146,7 @@ def test_torus_mixed_physical_and_linked_sides_depth6(csim, sides, bc, overlap):
 
 @pytest.mark.parametrize("sides,bc", [((1, 1, 0, 0), "ddnp"), ((0, 0, 1, 1), "pndd"), ((1, 1, 0, 0), "ddnn"), ((0, 0, 1, 1), "nndd"),
                                       ((1, 1, 1, 1), "dddd")])
-@pytest.mark.parametrize("overlap", [3, 4, 1])
+@pytest.mark.parametrize("overlap", [3, 4, 1, 5])
 def test_mixed_sides_depths_7_6_5_on_one_stepper(csim, sides, bc, overlap):
     """the comm-stream chain (faces -> halo cells, ghost ring, extension of the physical edges over the halo,
     corners) with linked sides next to physical Neumann / Periodic / Dirichlet sides, passes of depth 7, 6 and 5 on
@@ -215,7 +216,7 @@ def test_torus_on_an_8192_square_tile_bulk_with_tail_region(csim):
     ref = None
     for opts in [dict(overlap=0, fuse=0), dict(overlap=3, fuse=6), dict(overlap=4, fuse=7), dict(overlap=5, fuse=-1),
                  dict(overlap=3, fuse=6, tail_split=0), dict(overlap=1, fuse=5, rows_per_chunk=50),
-                 dict(overlap=3, fuse=6, direct_faces=0)]:
+                 dict(overlap=3, fuse=6, direct_faces=0), dict(overlap=5, fuse=-1, relay=0)]:
         st = csim.Stepper(d, 1.0, 1.0, csim.bc_codes("dddd"))
         st.comm_init(csim.comm_unique_id())
         for k, v in opts.items():
@@ -270,7 +271,7 @@ def test_fuzz_random_torus_cases_vs_oracle(csim):
                                                        float(np.abs(got - want)[mask].max()))
 
 
-@pytest.mark.parametrize("overlap", [3, 4, 1])
+@pytest.mark.parametrize("overlap", [3, 4, 1, 5])
 def test_keep_warm_leaves_the_run_untouched(csim, overlap):
     """csim_stepper_keep_warm (bench.py's wait between the cross-rank barrier and the timed region): whole-tile
     launches into the scratch buffer between run() calls — also between a run that left faces pre-unpacked for
@@ -449,7 +450,7 @@ def test_physical_bottom_and_top_next_to_linked_sides_every_depth_and_schedule(c
     mask = CORNERLESS(ny, nx)
     for steps, fuse in ((7, 7), (5, 5), (6, 6), (4, 4), (20, -1)):
         want = torus_oracle(u0, 1.0, 1.0, D, vx, vy, dt, steps, sides, codes)
-        for overlap in (4, 3, 1):
+        for overlap in (4, 3, 1, 5):
             st = csim.Stepper(self_neighbor_decomp(csim, nx, ny, sides), 1.0, 1.0, codes)
             st.comm_init(csim.comm_unique_id())
             st.set_option("overlap", overlap)

@@ -19,17 +19,32 @@ WORKER = os.path.join(HERE, "multirank_worker.py")
 from ports import rendezvous_port as free_port  # noqa: E402  (below the ephemeral range: see tests/ports.py)
 
 
+VERDICT = "MULTIRANK engine="   # the line a worker run ends with: ... ok=True / ok=False
+
+
+def repeat_worth(rc, out):
+    """whether a finished worker run may be started once more: only when it ended WITHOUT a verdict and its output
+    shows the one failure the repeat was written for — the rendezvous store could not listen on its port
+    (DistNetworkError / EADDRINUSE, profiles/r03_multirank_rendezvous_race.txt).  A run that printed its verdict is
+    never repeated; any other run without one (a rank that hung until the workers' faulthandler dumped the stacks,
+    a crash) is a failure of the test."""
+    if rc == 0 or VERDICT in out:
+        return False
+    return "DistNetworkError" in out or "EADDRINUSE" in out
+
+
 def launch(world, engine, case, timeout=300):
     """start `world` worker processes directly (env rendezvous on 127.0.0.1, no launcher process:
-    a GPU box allows few processes on its card).  A run that ends WITHOUT a verdict line — a rank stuck in the
-    rendezvous or elsewhere: the workers dump their stacks and leave after 150 s — is started once more on a fresh
-    port, and the first attempt's output is raised as a warning so that it stays visible; a run that printed its
-    verdict (ok=True / ok=False) is never repeated."""
+    a GPU box allows few processes on its card).  A run that lost the race for its rendezvous port (repeat_worth) is
+    started once more on a fresh port, and the first attempt's output is raised as a warning so that it stays visible;
+    every other run without a verdict line fails the test with what the workers dumped."""
     rc, out = _launch_once(world, engine, case, timeout)
-    if rc != 0 and "MULTIRANK engine=" not in out:
+    if repeat_worth(rc, out):
         import warnings
-        warnings.warn(f"multi-rank worker run without a verdict (rc {rc}), repeated once; first attempt said:\n{out[-4000:]}")
+        warnings.warn(f"multi-rank worker run lost its rendezvous port (rc {rc}), repeated once; first attempt said:\n{out[-4000:]}")
         rc, out = _launch_once(world, engine, case, timeout)
+    elif rc != 0 and VERDICT not in out:
+        pytest.fail(f"multi-rank worker run without a verdict (rc {rc}), not repeated:\n{out[-6000:]}")
     return rc, out
 
 
@@ -85,3 +100,32 @@ def test_world6_and_8_gloo_oracle(world):
     for case in cases:
         rc, out = launch(world, "oracle", case)
         assert rc == 0 and "ok=True" in out, out[-2000:]
+
+
+# three output shapes of a worker run, as the repeat decision sees them: the rendezvous failure as recorded in
+# profiles/r03_multirank_rendezvous_race.txt (shortened), a stack dump of the workers' faulthandler without a verdict,
+# and a verdict line
+OUT_RENDEZVOUS = """  File "/usr/local/lib/python3.10/dist-packages/torch/distributed/rendezvous.py", line 200, in _create_c10d_store
+    return TCPStore(
+torch.distributed.DistNetworkError: The server socket has failed to listen on any local network address. port: 34723, useIpv6: false, code: -98, name: EADDRINUSE, message: address already in use
+Timeout (0:02:30)!
+Thread 0x00007698fc01e740 (most recent call first):
+  File "/usr/local/lib/python3.10/dist-packages/torch/distributed/rendezvous.py", line 200 in _create_c10d_store
+"""
+OUT_HUNG = """Timeout (0:02:30)!
+Thread 0x00007f3a5c1fe740 (most recent call first):
+  File "climate_sim_mpi_cpp_amd/__init__.py", line 490 in sync
+  File "tests/multirank_worker.py", line 121 in main
+  File "tests/multirank_worker.py", line 157 in <module>
+"""
+OUT_WRONG = "MULTIRANK engine=hip world=4 case=run_a ok=False linf=3.1e-05\n"
+
+
+def test_repeat_only_for_the_rendezvous_failure():
+    assert repeat_worth(1, OUT_RENDEZVOUS)
+    assert not repeat_worth(1, OUT_HUNG)          # a hung rank: fails the test, is not run again
+    assert not repeat_worth(124, "")              # killed at the time limit without a word
+    assert not repeat_worth(-11, OUT_HUNG)
+    assert not repeat_worth(1, OUT_WRONG)         # a verdict, even a bad one, stands
+    assert not repeat_worth(1, OUT_RENDEZVOUS + OUT_WRONG)
+    assert not repeat_worth(0, "MULTIRANK engine=oracle world=2 case=run_a ok=True\n")
