@@ -190,6 +190,10 @@ def lib() -> C.CDLL:
         "csim_ensemble_assimilate": (i, [vp, i, ip, ip, dp, dp, d, d, i, i, dp, dp, dp, dp, ip]),
         "csim_ensemble_gc_table": (i, [d, d, d, i, i, ip, ip, dp]),
         "csim_ensemble_assim_plan": (i, [i, ip, ip, i, i, i, ip, ip]),
+        "csim_ensemble_perturb": (i, [vp, C.c_ulonglong, C.c_uint, d, d, i, i]),
+        "csim_philox4x32": (i, [C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+        "csim_normal_from_bits": (i, [C.c_ulonglong, dp]),
+        "csim_ensemble_perturb_taps": (i, [d, d, i, i, ip, dp]),
         "csim_ensemble_set_option": (i, [vp, C.c_char_p, C.c_long]),
         "csim_ensemble_get_option": (i, [vp, C.c_char_p, C.POINTER(C.c_long)]),
         "csim_ensemble_plan": (i, [i, i, i, i, ip]),
@@ -639,6 +643,38 @@ def ensemble_assim_plan(i, j, lx, ly, ordered=False) -> np.ndarray:
     return lev
 
 
+PERTURB_MAX_RADIUS = 32
+
+
+def philox4x32(ctr, key):
+    """Philox4x32-10 of a counter (4 x uint32) under a key (2 x uint32): 4 x uint32 (csim_philox4x32) — host only"""
+    c, k, o = (C.c_uint * 4)(*[int(v) for v in ctr]), (C.c_uint * 2)(*[int(v) for v in key]), (C.c_uint * 4)()
+    _ck(lib().csim_philox4x32(c, k, o))
+    return np.array(o[:], dtype=np.uint32)
+
+
+def normal_from_bits(bits):
+    """the normal deviate csim_ensemble_perturb makes of 64 random bits (csim_normal_from_bits); a scalar or an array
+    of uint64 — host only"""
+    b = np.asarray(bits, dtype=np.uint64)
+    out = np.empty(b.shape)
+    z, fn = C.c_double(), lib().csim_normal_from_bits
+    flat = out.reshape(-1)
+    for n, v in enumerate(b.reshape(-1).tolist()):
+        _ck(fn(v, C.byref(z)))
+        flat[n] = z.value
+    return out if out.ndim else float(out)
+
+
+def ensemble_perturb_taps(d, corr_len, n, periodic=False) -> np.ndarray:
+    """the 2 R + 1 smoothing taps of csim_ensemble_perturb along an axis of n cells of spacing d — host only"""
+    R = C.c_int()
+    _ck(lib().csim_ensemble_perturb_taps(float(d), float(corr_len), int(n), int(bool(periodic)), C.byref(R), None))
+    t = np.empty(2 * R.value + 1)
+    _ck(lib().csim_ensemble_perturb_taps(float(d), float(corr_len), int(n), int(bool(periodic)), C.byref(R), _dp(t)))
+    return t
+
+
 def _scores(sc: CsimVerifyScores, nt: int) -> VerifyScores:
     return VerifyScores(sc.cells, sc.nan_cells, sc.crps, sc.rmse, sc.spread, np.array(sc.brier[:nt], dtype=np.float64))
 
@@ -814,6 +850,17 @@ class Ensemble:
         if not diagnostics:
             return nl.value
         return EnsembleAnalysis(nl.value, *outs)
+
+    def perturb(self, sigma, corr_len, seed, draw=0, centered=False, truth_member=None):
+        """adds sigma times a seeded Gaussian random field of correlation length corr_len to the interior of every
+        forecast member; a pure function of (seed, draw, member, cell), enqueued without waiting
+        (csim_ensemble_perturb)"""
+        seed, draw = int(seed), int(draw)
+        if not (0 <= seed < 1 << 64 and 0 <= draw < 1 << 32):
+            raise ValueError("seed must fit 64 bits and draw 32 bits, unsigned")
+        tm = -1 if truth_member is None else int(truth_member)
+        _ck(lib().csim_ensemble_perturb(self._h, seed, draw, float(sigma), float(corr_len),
+                                        centered if isinstance(centered, int) else int(bool(centered)), tm))
 
     def set_option(self, key: str, value: int):
         _ck(lib().csim_ensemble_set_option(self._h, key.encode(), int(value)))

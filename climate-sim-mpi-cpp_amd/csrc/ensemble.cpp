@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "ensemble.hpp"
+#include "ensemble_noise.hpp"
 #include "stepper.hpp"
 
 using namespace csim;
@@ -334,6 +335,24 @@ void gc_fill(double dx, double dy, double loc, int lx, int ly, double* table) {
             const double ax = static_cast<double>(a) * dx, by = static_cast<double>(b) * dy;
             table[static_cast<size_t>(b + ly) * tw + (a + lx)] = gc_value(std::sqrt(ax * ax + by * by) / loc);
         }
+}
+
+// the smoothing taps of csim_ensemble_perturb along one axis (csim_ensemble_perturb_taps): the radius, and with `taps`
+// the 2 R + 1 Gaspari-Cohn weights scaled to unit sum of squares
+int perturb_radius(double d, double c, int n, bool periodic) {
+    return c == 0.0 ? 0 : gc_half(d, c, periodic ? (n - 1) / 2 + 1 : n);
+}
+
+void perturb_fill(double d, double c, int R, double* taps) {
+    if (c == 0.0) {
+        taps[0] = 1.0;
+        return;
+    }
+    for (int o = -R; o <= R; ++o) taps[o + R] = gc_value(static_cast<double>(std::abs(o)) * d / c);
+    double S = 0.0;
+    for (int o = 0; o <= 2 * R; ++o) S = S + taps[o] * taps[o];
+    const double norm = std::sqrt(S);
+    for (int o = 0; o <= 2 * R; ++o) taps[o] = taps[o] / norm;
 }
 
 // the levels of csim_ensemble_assim_plan.  Spatial buckets of (2 lx + 1) x (2 ly + 1) cells: observations that
@@ -1006,6 +1025,60 @@ int csim_ensemble_assimilate(csim_ensemble* e, int nobs, const int* i, const int
         if (post_mean) post_mean[o] = po[2 * static_cast<size_t>(o)];
         if (post_var) post_var[o] = po[2 * static_cast<size_t>(o) + 1];
     }
+    return CSIM_OK;
+}
+
+int csim_philox4x32(const unsigned ctr[4], const unsigned key[2], unsigned out[4]) {
+    CSIM_REQUIRE(ctr && key && out, "null argument");
+    unsigned c[4] = {ctr[0], ctr[1], ctr[2], ctr[3]};
+    philox4x32(c, key[0], key[1]);
+    for (int k = 0; k < 4; ++k) out[k] = c[k];
+    return CSIM_OK;
+}
+
+int csim_normal_from_bits(unsigned long long bits, double* z) {
+    CSIM_REQUIRE(z, "null argument");
+    *z = normal_from_bits(bits);
+    return CSIM_OK;
+}
+
+int csim_ensemble_perturb_taps(double d, double corr_len, int n, int periodic, int* R, double* taps) {
+    CSIM_REQUIRE(R, "null argument");
+    CSIM_REQUIRE(std::isfinite(d) && d > 0, "the spacing must be finite and > 0");
+    CSIM_REQUIRE(std::isfinite(corr_len) && corr_len >= 0, "corr_len must be finite and >= 0");
+    CSIM_REQUIRE(n >= 1, "empty axis");
+    CSIM_REQUIRE(periodic == 0 || periodic == 1, "periodic must be 0 or 1");
+    *R = perturb_radius(d, corr_len, n, periodic == 1);
+    if (*R > PERTURB_MAX_RADIUS)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_perturb_taps: the radius exceeds CSIM_PERTURB_MAX_RADIUS");
+    if (taps) perturb_fill(d, corr_len, *R, taps);
+    return CSIM_OK;
+}
+
+int csim_ensemble_perturb(csim_ensemble* e, unsigned long long seed, unsigned draw, double sigma, double corr_len,
+                          int centered, int truth_member) {
+    CSIM_REQUIRE(e, "null ensemble");
+    const EnsGeom& g = e->g;
+    const int B = g.members;
+    CSIM_REQUIRE(std::isfinite(sigma), "sigma must be finite");
+    CSIM_REQUIRE(std::isfinite(corr_len) && corr_len >= 0, "corr_len must be finite and >= 0");
+    CSIM_REQUIRE(centered == 0 || centered == 1, "centered must be 0 or 1");
+    CSIM_REQUIRE(truth_member >= -1 && truth_member < B, "truth_member out of range");
+    const int M = truth_member >= 0 ? B - 1 : B;
+    CSIM_REQUIRE(M >= 1, "no forecast member");
+    CSIM_REQUIRE(!centered || M >= 2, "centering needs at least two forecast members");
+    PerturbArgs a{};
+    a.perx = g.bc[CSIM_LEFT] == CSIM_BC_PERIODIC && g.bc[CSIM_RIGHT] == CSIM_BC_PERIODIC;
+    a.pery = g.bc[CSIM_BOTTOM] == CSIM_BC_PERIODIC && g.bc[CSIM_TOP] == CSIM_BC_PERIODIC;
+    int rc = csim_ensemble_perturb_taps(e->dx, corr_len, g.nx, a.perx, &a.rx, a.tx);
+    if (!rc) rc = csim_ensemble_perturb_taps(e->dy, corr_len, g.ny, a.pery, &a.ry, a.ty);
+    if (rc) return rc;
+    if (sigma == 0.0) return CSIM_OK;
+    a.seed_lo = static_cast<unsigned>(seed), a.seed_hi = static_cast<unsigned>(seed >> 32), a.draw = draw;
+    a.forecast = M;
+    a.truth_member = truth_member >= 0 ? truth_member : B;
+    a.sigma = sigma;
+    CSIM_HIP(ens_launch_perturb(g, e->base(e->cur), a, centered == 1, e->st));
     return CSIM_OK;
 }
 

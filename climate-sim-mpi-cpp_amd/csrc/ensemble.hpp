@@ -140,6 +140,21 @@ hipError_t ens_launch_assim_inflate(const EnsGeom& g, double* f, int forecast, i
 hipError_t ens_launch_assim_post(const EnsGeom& g, const double* f, const AssimArgs& a, int nobs, double* post,
                                  hipStream_t st);
 
+// the perturbation of csim_ensemble_perturb (ensemble_perturb.hip), one launch: x_k += sigma p_k on every interior
+// cell of the forecast members, p_k the white noise of ensemble_noise.hpp smoothed with the host's taps along x, then
+// along y (csim_ensemble_perturb_taps; tx[o + rx], ty[o + ry]), less its mean over the members when centered
+constexpr int PERTURB_TAPS = 2 * 32 + 1;  // 2 CSIM_PERTURB_MAX_RADIUS + 1
+struct PerturbArgs {
+    unsigned seed_lo, seed_hi, draw;
+    int forecast;                 // M
+    int truth_member;             // t, or B (no member skipped)
+    int rx, ry;                   // tap radii
+    int perx, pery;               // axis periodic
+    double sigma;
+    double tx[PERTURB_TAPS], ty[PERTURB_TAPS];
+};
+hipError_t ens_launch_perturb(const EnsGeom& g, double* f, const PerturbArgs& a, bool centered, hipStream_t st);
+
 // the rank histogram's tie-break: splitmix64's finaliser of the interior index g; a cell with `eq` members equal to the
 // truth goes to bin lt + mix(g) mod (eq + 1)
 __host__ __device__ inline unsigned long long verify_mix(unsigned long long z) {

@@ -193,6 +193,13 @@ public:
                                        nullptr, &nl));
         return nl;
     }
+    // adds sigma times a seeded Gaussian random field of correlation length corr_len to the interior of every forecast
+    // member (t = -1: all members, else member t is left alone); enqueued on the ensemble's stream, so that run() follows
+    // without a host wait (see csim_ensemble_perturb)
+    void perturb(double sigma, double corr_len, unsigned long long seed, unsigned draw = 0, bool centered = false,
+                 int t = -1) {
+        check(csim_ensemble_perturb(h_, seed, draw, sigma, corr_len, centered ? 1 : 0, t));
+    }
     void set_option(const char* key, long value) { check(csim_ensemble_set_option(h_, key, value)); }
     long get_option(const char* key) const {
         long v = 0;

@@ -437,6 +437,60 @@ int csim_ensemble_gc_table(double dx, double dy, double loc, int nx, int ny, int
  * 0 / 1, null arrays with nobs > 0, null nlevels; CSIM_ERR_UNSUPPORTED for nobs > CSIM_ASSIM_MAX_OBS. */
 int csim_ensemble_assim_plan(int nobs, const int* i, const int* j, int lx, int ly, int ordered, int* level,
                              int* nlevels);
+/* perturbation: adds sigma p_k to every interior cell of every forecast member k, p_k a unit-variance Gaussian random
+ * field with the compact Gaspari-Cohn-shaped correlation of length corr_len, a pure function of (seed, draw, member
+ * index, cell): additive inflation / model-error noise between analysis and forecast, or the spread of a fresh
+ * ensemble, without a host round trip.  All fp64 arithmetic IEEE, without FMA contraction, every sum a running sum
+ * from +0 in the stated order; integer arithmetic modulo 2^32 / 2^64.
+ *
+ * 1. Generator: Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9,
+ *    0xBB67AE85, ten rounds), csim_philox4x32(ctr, key, out).
+ * 2. Normal deviate from 64 bits, csim_normal_from_bits(bits, &z):  k = bits >> 12;  u = ((double)k + 0.5) 2^-52
+ *    (exact, in (0, 1));  q = u - 0.5 (exact);  z = PPND16(u), Wichura's AS241 with its published coefficients, every
+ *    polynomial of degree 7 in Horner form from the highest coefficient:
+ *      |q| <= 0.425:  r = 0.180625 - q q;  z = (q A(r)) / B(r)
+ *      otherwise:     t = q < 0 ? u : 1 - u;  r = sqrt(-ln t);  r <= 5: C(r - 1.6) / D(r - 1.6), else
+ *                     E(r - 5) / F(r - 5);  negated for q < 0
+ *    with the library's own ln:  (m, e) = frexp(t);  if m < the double nearest sqrt(1/2): m <- 2 m, e <- e - 1;
+ *    s = (m - 1) / (m + 1);  w = s s;  p = 1/23;  for n = 21, 19, .., 1: p = p w + 1/n (1/n the rounded quotient);
+ *    ln t = (double)e LN2 + 2 (s p),  LN2 = 0x3FE62E42FEFA39EF.  |z| <= 8.21.
+ * 3. Taps along one axis, csim_ensemble_perturb_taps(d, corr_len, n, periodic, &R, taps), c = corr_len >= 0 in the
+ *    units of dx, dy.  c == 0: R = 0, taps = {1}.  Otherwise R = min(largest a >= 0 with (double)a d < 2 c,
+ *    periodic ? (n - 1) / 2 : n - 1);  g[o] = GC(((double)|o| d) / c), o = -R .. R, GC the Horner forms of
+ *    csim_ensemble_gc_table, then max(., +0);  S = sum g[o] g[o] in increasing o;  taps[o + R] = g[o] / sqrt(S).
+ *    The device only reads the two tables tx (dx, nx) and ty (dy, ny), of radii Rx and Ry.
+ * 4. Lattice.  Axis x is periodic iff bc[LEFT] == bc[RIGHT] == PERIODIC, y likewise with BOTTOM / TOP.  The noise
+ *    lives on Px x Py lattice points, Px = nx on a periodic axis, else nx + 2 Rx.  Interior column i = 1 .. nx with
+ *    offset o reads lattice column a(i, o) = (i - 1 + o) mod nx (periodic) or i - 1 + o + Rx; rows b(j, o) the same.
+ *    L = b Px + a as a 64-bit integer.  A periodic field gets seamless noise, a bounded one unit variance up to its
+ *    edge.
+ * 5. White noise.  w_k(L) = normal_from_bits(out[2 s] | out[2 s + 1] << 32), s = L & 1,
+ *    out = philox(ctr = (lo32(L >> 1), hi32(L >> 1), k, draw), key = (lo32(seed), hi32(seed))).  k is the member's
+ *    index in the ensemble (not its position among the forecast members): member k's field depends neither on B nor
+ *    on truth_member.
+ * 6. Smoothing, x first:  hx_k(b, i) = sum_{o = -Rx .. Rx} tx[o] w_k(b Px + a(i, o)), then
+ *    p_k(i, j) = sum_{o = -Ry .. Ry} ty[o] hx_k(b(j, o), i),  each product rounded, sums in increasing o.
+ * 7. Centring and update.  The forecast members are all B (truth_member = -1) or the B - 1 others (member t is not
+ *    modified), as in csim_ensemble_verify; M of them.  centered = 1: pbar(i, j) = (sum_k p_k) / M in member order,
+ *    p_k <- p_k - pbar, so that the ensemble mean moves by rounding only; the fields are NOT rescaled by
+ *    sqrt(M / (M - 1)), their variance is (M - 1) / M.  Then x_k <- x_k + sigma p_k on every interior cell.
+ * The ghost ring of every member (both ping-pong buffers), the buffer that is not current and member t are left as
+ * they were.  sigma == 0 changes nothing and launches nothing.  The call enqueues on the ensemble's stream and returns
+ * without waiting, so run -> perturb -> run and assimilate -> perturb -> run need no host round trip; statistics,
+ * quantile and verification captures begun before the call see the state before it.  No set_physics needed.
+ * Errors: CSIM_ERR_ARG for sigma or corr_len not finite, corr_len < 0, centered not 0 / 1, truth_member outside
+ * -1 .. B-1, no forecast member, centered with M < 2; CSIM_ERR_UNSUPPORTED for Rx or Ry > CSIM_PERTURB_MAX_RADIUS. */
+#define CSIM_PERTURB_MAX_RADIUS 32
+int csim_ensemble_perturb(csim_ensemble* e, unsigned long long seed, unsigned draw, double sigma, double corr_len,
+                          int centered, int truth_member);
+/* host-only: item 1.  Known answers: ctr 0 0 0 0, key 0 0 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8 */
+int csim_philox4x32(const unsigned ctr[4], const unsigned key[2], unsigned out[4]);
+/* host-only: item 2 */
+int csim_normal_from_bits(unsigned long long bits, double* z);
+/* host-only: item 3; taps (may be NULL: only *R) gets 2 R + 1 values.  Errors: CSIM_ERR_ARG for d not finite and > 0,
+ * corr_len not finite and >= 0, n < 1, periodic not 0 / 1, null R; CSIM_ERR_UNSUPPORTED for
+ * R > CSIM_PERTURB_MAX_RADIUS */
+int csim_ensemble_perturb_taps(double d, double corr_len, int n, int periodic, int* R, double* taps);
 /* options (unknown keys: CSIM_ERR_ARG; "contract": CSIM_ERR_UNSUPPORTED), results never depend on them:
  *   "fuse"        -1 (default) passes of the ensemble depth where the grid allows; 0 / 1 single steps only
  *   "fused_2c"    0/1 (default 1), as for csim_stepper_set_option
