@@ -194,6 +194,8 @@ def lib() -> C.CDLL:
         "csim_philox4x32": (i, [C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
         "csim_normal_from_bits": (i, [C.c_ulonglong, dp]),
         "csim_ensemble_perturb_taps": (i, [d, d, i, i, ip, dp]),
+        "csim_ensemble_prior_capture": (i, [vp, i, i]),
+        "csim_ensemble_relax": (i, [vp, i, d, i, dp]),
         "csim_ensemble_set_option": (i, [vp, C.c_char_p, C.c_long]),
         "csim_ensemble_get_option": (i, [vp, C.c_char_p, C.POINTER(C.c_long)]),
         "csim_ensemble_plan": (i, [i, i, i, i, ip]),
@@ -675,6 +677,19 @@ def ensemble_perturb_taps(d, corr_len, n, periodic=False) -> np.ndarray:
     return t
 
 
+RELAX_SPREAD, RELAX_PERT = 1, 2  # CSIM_RELAX_SPREAD (RTPS), CSIM_RELAX_PERT (RTPP)
+_RELAX_MODES = {"spread": RELAX_SPREAD, "rtps": RELAX_SPREAD, "pert": RELAX_PERT, "rtpp": RELAX_PERT}
+
+
+def _relax_mode(mode) -> int:
+    """"spread" / "rtps", "pert" / "rtpp", or the integer code as it is (the library checks it)"""
+    if isinstance(mode, str):
+        if mode.lower() not in _RELAX_MODES:
+            raise ValueError(f"unknown relaxation mode {mode!r}")
+        return _RELAX_MODES[mode.lower()]
+    return int(mode)
+
+
 def _scores(sc: CsimVerifyScores, nt: int) -> VerifyScores:
     return VerifyScores(sc.cells, sc.nan_cells, sc.crps, sc.rmse, sc.spread, np.array(sc.brier[:nt], dtype=np.float64))
 
@@ -835,7 +850,9 @@ class Ensemble:
     def assimilate(self, i, j, y, r, loc, inflation=1.0, truth_member=None, ordered=False, diagnostics=True):
         """serial EnSRF analysis of the forecast members with point observations at interior cells (i, j), values y
         and error variances r (a scalar broadcasts), Gaspari-Cohn length loc (csim_ensemble_assimilate).  With
-        diagnostics: an EnsembleAnalysis (synchronous); without: the level count, and the work is only enqueued"""
+        diagnostics: an EnsembleAnalysis (synchronous); without: the level count, and the work is only enqueued.
+        inflation= is one factor for the whole field, applied before the analysis; prior_capture() before and relax()
+        after the analysis is the spatially selective alternative"""
         ii = _ints(i)
         n = len(ii)
         jj = _ints(j, n)
@@ -861,6 +878,23 @@ class Ensemble:
         tm = -1 if truth_member is None else int(truth_member)
         _ck(lib().csim_ensemble_perturb(self._h, seed, draw, float(sigma), float(corr_len),
                                         centered if isinstance(centered, int) else int(bool(centered)), tm))
+
+    def prior_capture(self, mode="spread", truth_member=None):
+        """keeps what relax() of the same mode and truth member needs of the current (forecast) state: the per-cell
+        spread ("spread", RTPS) or the members themselves ("pert", RTPP); valid until the next run of at least one
+        step or the next capture, enqueued without waiting (csim_ensemble_prior_capture)"""
+        mode, tm = _relax_mode(mode), -1 if truth_member is None else int(truth_member)
+        _ck(lib().csim_ensemble_prior_capture(self._h, mode, tm))
+
+    def relax(self, alpha, mode="spread", truth_member=None, factor=False):
+        """relaxation inflation after an analysis, cell by cell: towards the captured spread (x_k += f (x_k - mean),
+        f = alpha (sb - sa) / sa; cells with f == 0 are not written) or the captured perturbations.  Enqueued without
+        waiting; with factor=True ("spread" only) synchronous, returning f as a (ny+2, nx+2) array
+        (csim_ensemble_relax)"""
+        mode, tm = _relax_mode(mode), -1 if truth_member is None else int(truth_member)
+        out = np.empty((self.ny + 2, self.nx + 2)) if factor else None
+        _ck(lib().csim_ensemble_relax(self._h, mode, float(alpha), tm, None if out is None else _dp(out)))
+        return out
 
     def set_option(self, key: str, value: int):
         _ck(lib().csim_ensemble_set_option(self._h, key.encode(), int(value)))

@@ -69,6 +69,14 @@ struct csim_ensemble {
     size_t a_dcap = 0, a_hcap = 0;  // bytes
     hipEvent_t ev_a = nullptr;
     bool a_used = false;
+    // relaxation (csim_ensemble_prior_capture / csim_ensemble_relax).  A capture lives in the handle's own storage, so
+    // that no call that writes the ping-pong buffers touches it: sqrt(v_b) per interior cell (RTPS), a copy of the
+    // current buffer (RTPP, allocated at the first such capture), and the factor field of a call that asks for it
+    double* rx_sb = nullptr;
+    double* rx_prior = nullptr;
+    double* rx_factor = nullptr;
+    int rx_mode = 0;    // mode of the valid capture; 0: none (cleared by a run of nsteps > 0)
+    int rx_truth = -1;  // its truth_member
 
     double* view(int buf, int m) const {
         return alloc[buf] + static_cast<size_t>(m) * g.slab + static_cast<size_t>(GHOST_EXTRA) * g.pitch;
@@ -434,6 +442,19 @@ AssimLayout assim_layout(size_t n, size_t tcells, size_t hp) {
 
 constexpr size_t ASSIM_HP_DOUBLES = size_t(1) << 23;  // h'_k of one batch: 64 MiB, at least 8192 observations
 
+// the checks csim_ensemble_prior_capture and csim_ensemble_relax share; *forecast = M
+int relax_check(const csim_ensemble* e, int mode, int truth_member, int* forecast) {
+    const int B = e->g.members;
+    CSIM_REQUIRE(mode == CSIM_RELAX_SPREAD || mode == CSIM_RELAX_PERT, "mode must be CSIM_RELAX_SPREAD or CSIM_RELAX_PERT");
+    CSIM_REQUIRE(truth_member >= -1 && truth_member < B, "truth_member out of range");
+    const int M = truth_member >= 0 ? B - 1 : B;
+    CSIM_REQUIRE(M >= 2, "the relaxation needs at least two forecast members");
+    if (M > ASSIM_MAX_MEMBERS) return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_relax: at most 1024 forecast members");
+    CSIM_REQUIRE(e->g.slab <= 0x7fffffffL, "grid too large for the relaxation");
+    *forecast = M;
+    return CSIM_OK;
+}
+
 int ghost_fill(csim_ensemble* e, bool fin) {
     CSIM_HIP(ens_launch_ghost_fill(e->g, e->base(e->cur), e->base(1 - e->cur), e->table, fin, e->st));
     return CSIM_OK;
@@ -542,6 +563,9 @@ int csim_ensemble_destroy(csim_ensemble* e) {
     if (e->a_d) (void)hipFree(e->a_d);
     if (e->a_h) (void)hipHostFree(e->a_h);
     if (e->ev_a) (void)hipEventDestroy(e->ev_a);
+    if (e->rx_sb) (void)hipFree(e->rx_sb);
+    if (e->rx_prior) (void)hipFree(e->rx_prior);
+    if (e->rx_factor) (void)hipFree(e->rx_factor);
     for (double* a : e->alloc)
         if (a) (void)hipFree(a);
     if (e->fin) (void)hipFree(e->fin);
@@ -634,6 +658,7 @@ int csim_ensemble_run(csim_ensemble* e, int nsteps) {
     if (rc) return rc;
     const int q = plan[1], r = plan[2];
     const bool stat = e->static_ring();
+    if (nsteps > 0) e->rx_mode = 0;  // the forecast a relaxation capture was taken of is gone
     // q passes of ENS_DEPTH steps, one launch per sign class present; the last one of the run leaves the FinLines
     // (unless the ring is static) from which the closing ghost fill makes the reference's ring
     for (int k = 0; k < q; ++k) {
@@ -1079,6 +1104,67 @@ int csim_ensemble_perturb(csim_ensemble* e, unsigned long long seed, unsigned dr
     a.truth_member = truth_member >= 0 ? truth_member : B;
     a.sigma = sigma;
     CSIM_HIP(ens_launch_perturb(g, e->base(e->cur), a, centered == 1, e->st));
+    return CSIM_OK;
+}
+
+int csim_ensemble_prior_capture(csim_ensemble* e, int mode, int truth_member) {
+    CSIM_REQUIRE(e, "null ensemble");
+    const EnsGeom& g = e->g;
+    int M = 0;
+    int rc = relax_check(e, mode, truth_member, &M);
+    if (rc) return rc;
+    // each buffer is created once; a failed allocation is reported and retried by the next call
+    if (mode == CSIM_RELAX_SPREAD && !e->rx_sb)
+        CSIM_HIP(hipMalloc(reinterpret_cast<void**>(&e->rx_sb), sizeof(double) * static_cast<size_t>(g.nx) * g.ny));
+    const size_t bytes = sizeof(double) * static_cast<size_t>(g.slab) * g.members;
+    if (mode == CSIM_RELAX_PERT && !e->rx_prior) CSIM_HIP(hipMalloc(reinterpret_cast<void**>(&e->rx_prior), bytes));
+    e->rx_mode = 0;  // from here on the last capture is being overwritten (in stream order, after its readers)
+    if (mode == CSIM_RELAX_SPREAD)
+        CSIM_HIP(ens_launch_relax_capture(g, e->base(e->cur), M, truth_member >= 0 ? truth_member : g.members, e->rx_sb,
+                                          e->st));
+    else
+        CSIM_HIP(hipMemcpyAsync(e->rx_prior, e->alloc[e->cur], bytes, hipMemcpyDeviceToDevice, e->st));
+    e->rx_mode = mode;
+    e->rx_truth = truth_member;
+    return CSIM_OK;
+}
+
+int csim_ensemble_relax(csim_ensemble* e, int mode, double alpha, int truth_member, double* out_factor) {
+    CSIM_REQUIRE(e, "null ensemble");
+    const EnsGeom& g = e->g;
+    int M = 0;
+    int rc = relax_check(e, mode, truth_member, &M);
+    if (rc) return rc;
+    CSIM_REQUIRE(std::isfinite(alpha) && alpha >= 0.0 && alpha <= 1.0, "alpha must be in [0, 1]");
+    CSIM_REQUIRE(!(out_factor && mode == CSIM_RELAX_PERT), "out_factor is for CSIM_RELAX_SPREAD only");
+    if (e->rx_mode != mode || e->rx_truth != truth_member)
+        return fail(CSIM_ERR_STATE, "csim_ensemble_relax: no valid capture of this mode and truth member "
+                                    "(csim_ensemble_prior_capture after the last run)");
+    const size_t cells = stats_cells(e);
+    if (alpha == 0.0) {
+        if (!out_factor) return CSIM_OK;
+        std::fill(out_factor, out_factor + cells, 0.0);
+        return csim_ensemble_sync(e);
+    }
+    if (out_factor && !e->rx_factor)
+        CSIM_HIP(hipMalloc(reinterpret_cast<void**>(&e->rx_factor), sizeof(double) * cells));
+    // Only interior cells of the forecast members in the current buffer are written, as in csim_ensemble_assimilate:
+    // ring_ok is only ever true for rings without a Neumann side, whose ghosts do not depend on the interior, Neumann
+    // rings are rebuilt from the interior before every pass, and the FinLines were consumed by the ghost fill that ended
+    // the run that wrote them, so nothing cached goes stale.
+    const int t = truth_member >= 0 ? truth_member : g.members;
+    if (mode == CSIM_RELAX_PERT) {
+        CSIM_HIP(ens_launch_relax_pert(g, e->base(e->cur), e->rx_prior + static_cast<size_t>(GHOST_EXTRA) * g.pitch, M, t,
+                                       alpha, e->st));
+        return CSIM_OK;
+    }
+    if (out_factor) CSIM_HIP(hipMemsetAsync(e->rx_factor, 0, sizeof(double) * cells, e->st));  // the ghost ring: +0
+    CSIM_HIP(ens_launch_relax_spread(g, e->base(e->cur), M, t, alpha, e->rx_sb, out_factor ? e->rx_factor : nullptr,
+                                     e->st));
+    if (!out_factor) return CSIM_OK;
+    // as csim_ensemble_stats: copied in stream order, and the call waits for it
+    CSIM_HIP(hipMemcpyAsync(out_factor, e->rx_factor, sizeof(double) * cells, hipMemcpyDeviceToHost, e->st));
+    CSIM_HIP(hipStreamSynchronize(e->st));
     return CSIM_OK;
 }
 

@@ -155,6 +155,20 @@ struct PerturbArgs {
 };
 hipError_t ens_launch_perturb(const EnsGeom& g, double* f, const PerturbArgs& a, bool centered, hipStream_t st);
 
+// the relaxation of csim_ensemble_prior_capture / csim_ensemble_relax (ensemble_relax.hip), one launch each; forecast
+// member k is member k + (k >= truth_member) (truth_member = B: none skipped), 2 <= forecast <= ASSIM_MAX_MEMBERS.
+// sb: nx * ny values, interior cell (i, j) at (j - 1) nx + (i - 1).
+// sb = sqrt(v) of mv(x) on every interior cell
+hipError_t ens_launch_relax_capture(const EnsGeom& g, const double* f, int forecast, int truth_member, double* sb,
+                                    hipStream_t st);
+// RTPS: x_k <- x_k + fac (x_k - m) where fac != 0; factor (null: not wanted): dense (ny+2) x (nx+2), gets fac on
+// the interior
+hipError_t ens_launch_relax_spread(const EnsGeom& g, double* f, int forecast, int truth_member, double alpha,
+                                   const double* sb, double* factor, hipStream_t st);
+// RTPP: x_k <- x_k + alpha ((xb_k - m_b) - (x_k - m)); fb: the captured copy of a whole ping-pong buffer, addressed as f
+hipError_t ens_launch_relax_pert(const EnsGeom& g, double* f, const double* fb, int forecast, int truth_member,
+                                 double alpha, hipStream_t st);
+
 // the rank histogram's tie-break: splitmix64's finaliser of the interior index g; a cell with `eq` members equal to the
 // truth goes to bin lt + mix(g) mod (eq + 1)
 __host__ __device__ inline unsigned long long verify_mix(unsigned long long z) {

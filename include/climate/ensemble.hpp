@@ -200,6 +200,18 @@ public:
                  int t = -1) {
         check(csim_ensemble_perturb(h_, seed, draw, sigma, corr_len, centered ? 1 : 0, t));
     }
+    // relaxation inflation (see csim_ensemble_relax), mode CSIM_RELAX_SPREAD (RTPS) or CSIM_RELAX_PERT (RTPP); t as in
+    // assimilate.  prior_capture() keeps what relax() needs of the forecast, before the analysis; relax() after the
+    // analysis pulls its perturbations back towards the forecast ones.  Both are enqueued on the ensemble's stream, so
+    // that prior_capture(); assimilate_enqueue(); relax(); run() needs no host wait
+    void prior_capture(int mode, int t = -1) { check(csim_ensemble_prior_capture(h_, mode, t)); }
+    void relax(int mode, double alpha, int t = -1) { check(csim_ensemble_relax(h_, mode, alpha, t, nullptr)); }
+    // RTPS, synchronous: the factor f of every cell (member_size() values, +0 on the ghost ring)
+    std::vector<double> relax_factor(double alpha, int t = -1) {
+        std::vector<double> f(member_size());
+        check(csim_ensemble_relax(h_, CSIM_RELAX_SPREAD, alpha, t, f.data()));
+        return f;
+    }
     void set_option(const char* key, long value) { check(csim_ensemble_set_option(h_, key, value)); }
     long get_option(const char* key) const {
         long v = 0;

@@ -491,6 +491,49 @@ int csim_normal_from_bits(unsigned long long bits, double* z);
  * corr_len not finite and >= 0, n < 1, periodic not 0 / 1, null R; CSIM_ERR_UNSUPPORTED for
  * R > CSIM_PERTURB_MAX_RADIUS */
 int csim_ensemble_perturb_taps(double d, double corr_len, int n, int periodic, int* R, double* taps);
+/* relaxation inflation: after an analysis, pulls the analysis perturbations of every interior cell back towards the
+ * forecast ones, cell by cell: relaxation to prior spread (RTPS, Whitaker & Hamill 2012) or to prior perturbations
+ * (RTPP, Zhang et al. 2004).  Unlike the multiplicative inflation of csim_ensemble_assimilate and the additive noise
+ * of csim_ensemble_perturb it is selective in space: where no observation acted nothing changes, where the analysis
+ * removed spread part of it is given back.  The cycle is  run -> prior_capture -> assimilate -> relax -> run.
+ * The forecast members x_k, k = 0 .. M-1, are all B members (truth_member = -1) or the B - 1 others in their order
+ * (member t is never read or written), as in csim_ensemble_assimilate; 2 <= M <= CSIM_ASSIM_MAX_MEMBERS.  Interior
+ * cells only (i = 1 .. nx, j = 1 .. ny).  All fp64 arithmetic IEEE, without FMA contraction, / and sqrt correctly
+ * rounded, every sum a running sum from +0 in member order k = 0 .. M-1.  Per cell:
+ *
+ *     mv(x):  s = sum x_k;  m = s / M;  q = sum (x_k - m)(x_k - m);  v = q / (M-1)
+ *
+ * capture, CSIM_RELAX_SPREAD:  (m_b, v_b) = mv(x);  sb = sqrt(v_b) is kept in a device field of the handle.
+ * capture, CSIM_RELAX_PERT:    every member is kept as it is, xb_k, in a device copy of the handle (the size of one
+ *     ping-pong buffer, allocated at the first such capture and kept until destroy).
+ * relax, CSIM_RELAX_SPREAD:    (m, v) = mv(x);  sa = sqrt(v);  f = sa > 0 ? alpha ((sb - sa) / sa) : +0.
+ *     Where f == 0 the cell is NOT written; elsewhere  x_k <- x_k + f (x_k - m)  for every forecast member.  (f < 0,
+ *     where the analysis spread exceeds the prior's, deflates; a NaN sa gives f = +0, a NaN sb with sa > 0 gives NaN.)
+ *     Outside every observation window an analysis leaves the members' bits alone, so sa is computed from the same
+ *     bits in the same order as sb, sb - sa is exactly +0 and the cell keeps its bits, a -0 included.
+ * relax, CSIM_RELAX_PERT:      m = mv(x).m;  m_b = mv(xb).m;  x_k <- x_k + alpha ((xb_k - m_b) - (x_k - m))  for every
+ *     forecast member, every cell.
+ *
+ * alpha is finite, 0 <= alpha <= 1; alpha == 0 changes nothing and launches nothing (out_factor then gets +0
+ * everywhere).  out_factor (RTPS only, may be NULL; must be NULL for RTPP): a host field in the reference layout,
+ * (ny+2) x (nx+2), that gets f on the interior and +0 on the ghost ring.  With out_factor == NULL the call only enqueues
+ * on the ensemble's stream and returns without waiting, so capture -> assimilate -> relax -> perturb -> run needs no
+ * host round trip; with it the call synchronises.  Both calls are ordered on the ensemble's stream: statistics,
+ * quantile and verification captures begun before relax see the state before it.  The ghost ring of every member
+ * (both ping-pong buffers), the buffer that is not current and member t are left as they were.  No set_physics needed.
+ * Validity: a capture is valid for relax with the same mode and the same truth_member until the next
+ * csim_ensemble_run with nsteps > 0 (a guard against relaxing towards a stale forecast) or the next capture of either
+ * mode.  relax consumes nothing: a second call relaxes the relaxed state against the same prior.  Assimilation,
+ * perturbation, statistics, quantiles, verification, a run of 0 steps, uploads and init_gaussian do not invalidate a
+ * capture (its storage is the handle's own, not a ping-pong buffer).
+ * Errors: CSIM_ERR_ARG for mode not 1 / 2, truth_member outside -1 .. B-1, M < 2, alpha not finite or outside [0, 1],
+ * out_factor with RTPP; CSIM_ERR_UNSUPPORTED for M > CSIM_ASSIM_MAX_MEMBERS; CSIM_ERR_STATE for relax without a valid
+ * capture of that mode and truth member.  Errors are reported before anything is enqueued and leave the members and a
+ * valid capture as they were. */
+#define CSIM_RELAX_SPREAD 1 /* RTPS */
+#define CSIM_RELAX_PERT 2   /* RTPP */
+int csim_ensemble_prior_capture(csim_ensemble* e, int mode, int truth_member);
+int csim_ensemble_relax(csim_ensemble* e, int mode, double alpha, int truth_member, double* out_factor);
 /* options (unknown keys: CSIM_ERR_ARG; "contract": CSIM_ERR_UNSUPPORTED), results never depend on them:
  *   "fuse"        -1 (default) passes of the ensemble depth where the grid allows; 0 / 1 single steps only
  *   "fused_2c"    0/1 (default 1), as for csim_stepper_set_option
