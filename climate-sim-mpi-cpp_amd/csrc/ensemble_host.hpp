@@ -1,0 +1,216 @@
+// ensemble_host.hpp — what the host translation units behind csim_ensemble_* share: the ensemble handle and the small
+// owning helpers its features are built from.  Host only: the device translation units compile ensemble.hpp and never
+// see this file.  The layout of the ensemble's host side is the table at the top of ensemble.cpp.
+#pragma once
+#include <vector>
+
+#include "ensemble.hpp"
+#include "stepper.hpp"
+
+// returns the status of a call that failed (it has set the error text)
+#define CSIM_TRY(expr)           \
+    do {                         \
+        int rc_ = (expr);        \
+        if (rc_) return rc_;     \
+    } while (0)
+
+namespace csim {
+
+// A device buffer, made on first use and grown to the largest request.  reserve: a buffer that is large enough is
+// untouched; one that is too small is replaced, after `idle` (if given) has drained, since work enqueued there may
+// still use the old one.  A failed allocation leaves the buffer absent (cap 0), and the next call tries again.
+struct DeviceBuf {
+    void* p = nullptr;
+    size_t cap = 0;  // bytes
+    template <class T = double> T* as() const { return static_cast<T*>(p); }
+    int reserve(size_t bytes, hipStream_t idle = nullptr) {
+        if (bytes <= cap) return CSIM_OK;
+        if (idle) CSIM_HIP(hipStreamSynchronize(idle));
+        release();
+        CSIM_HIP(hipMalloc(&p, bytes));
+        cap = bytes;
+        return CSIM_OK;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr, cap = 0;
+    }
+};
+
+// The same in pinned host memory; the owner sees to it that no copy still uses a buffer that is replaced.
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t cap = 0;  // bytes
+    template <class T = double> T* as() const { return static_cast<T*>(p); }
+    int reserve(size_t bytes) {
+        if (bytes <= cap) return CSIM_OK;
+        release();
+        CSIM_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+        cap = bytes;
+        return CSIM_OK;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr, cap = 0;
+    }
+};
+
+// The result of a diagnostic kernel and its way to the host (the _begin / _wait pairs).  As csim_stepper_snapshot_begin:
+// the kernel runs in stream order on the ensemble's stream (the sweeps after it write the other ping-pong buffer first,
+// and never `dev`), and only the copy to the pinned buffer goes to `io`, so the next run does not wait for it.  Every
+// kind of capture has a Capture, and so a copy stream, of its own: none waits for another kind's copy.
+struct Capture {
+    DeviceBuf dev;
+    PinnedBuf host;
+    hipStream_t io = nullptr;   // non-blocking, carries the copies to `host`
+    hipEvent_t done = nullptr;  // the kernel that wrote `dev` has run
+    bool pending = false;       // a copy to `host` is in flight or waits to be fetched
+    // Before the kernel is enqueued: lets a copy in flight finish (it reads `dev`) and makes room for `bytes`, in
+    // `host` too when the call is a _begin.  `idle` as in DeviceBuf::reserve.  A replaced pinned buffer has nothing
+    // to fetch any more.
+    int prepare(size_t bytes, bool pinned, hipStream_t idle) {
+        if (!io) CSIM_HIP(hipStreamCreateWithFlags(&io, hipStreamNonBlocking));
+        if (!done) CSIM_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        if (pending) CSIM_HIP(hipStreamSynchronize(io));
+        CSIM_TRY(dev.reserve(bytes, idle));
+        if (!pinned || bytes <= host.cap) return CSIM_OK;
+        pending = false;
+        return host.reserve(bytes);
+    }
+    // after the kernel: `bytes` of `dev` to `host` on `io`, once everything enqueued on `st` so far is done
+    int begin(size_t bytes, hipStream_t st) {
+        CSIM_HIP(hipEventRecord(done, st));
+        CSIM_HIP(hipStreamWaitEvent(io, done, 0));
+        CSIM_HIP(hipMemcpyAsync(host.p, dev.p, bytes, hipMemcpyDeviceToHost, io));
+        pending = true;
+        return CSIM_OK;
+    }
+    int wait(const char* none_in_flight) {
+        if (!pending) return fail(CSIM_ERR_STATE, none_in_flight);
+        CSIM_HIP(hipStreamSynchronize(io));
+        pending = false;
+        return CSIM_OK;
+    }
+    void release() {
+        if (io) (void)hipStreamSynchronize(io);
+        dev.release();
+        host.release();
+        if (done) (void)hipEventDestroy(done);
+        if (io) (void)hipStreamDestroy(io);
+        done = nullptr, io = nullptr, pending = false;
+    }
+};
+
+// A host input on its way to the device, copied before the call returns: host -> pinned staging -> device, in stream
+// order.
+struct Staging {
+    PinnedBuf host;
+    hipEvent_t copied = nullptr;  // the last copy out of `host` has run
+    bool used = false;
+    // *h: room for `bytes`, to be filled by the caller, once the last copy out of the buffer has run (the event is
+    // made here, at the first input that is staged)
+    int acquire(size_t bytes, void** h) {
+        if (!copied) CSIM_HIP(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
+        if (used) CSIM_HIP(hipEventSynchronize(copied));
+        used = false;
+        CSIM_TRY(host.reserve(bytes));
+        *h = host.p;
+        return CSIM_OK;
+    }
+    int send(void* dst, size_t bytes, hipStream_t st) {
+        CSIM_HIP(hipMemcpyAsync(dst, host.p, bytes, hipMemcpyHostToDevice, st));
+        CSIM_HIP(hipEventRecord(copied, st));
+        used = true;
+        return CSIM_OK;
+    }
+    void release() {
+        host.release();
+        if (copied) (void)hipEventDestroy(copied);
+        copied = nullptr, used = false;
+    }
+};
+
+// Of B members, *M are forecast members and member *t is the truth that is left out (*t = B: none): forecast member k
+// is member k + (k >= *t).  With min_msg, *M >= min_m is required; with max_msg, more than max_m are unsupported.
+// The verification and the analysis pass neither and make those two checks themselves, because they have other
+// argument checks that fire between the range check and the bounds, and the order in which checks fire is kept.
+inline int forecast_split(int B, int truth_member, int* M, int* t, int min_m = 0, const char* min_msg = nullptr,
+                          int max_m = 0, const char* max_msg = nullptr) {
+    CSIM_REQUIRE(truth_member >= -1 && truth_member < B, "truth_member out of range");
+    *M = truth_member >= 0 ? B - 1 : B;
+    *t = truth_member >= 0 ? truth_member : B;
+    if (min_msg) CSIM_REQUIRE(*M >= min_m, min_msg);
+    if (max_msg && *M > max_m) return fail(CSIM_ERR_UNSUPPORTED, max_msg);
+    return CSIM_OK;
+}
+
+}  // namespace csim
+
+struct csim_ensemble {
+    csim::EnsGeom g{};
+    double dx = 1.0, dy = 1.0;
+    double* alloc[2] = {nullptr, nullptr};
+    int cur = 0;                      // alloc[cur] holds the current fields
+    double* fin = nullptr;            // FinLines of every member
+    void* table = nullptr;            // device: per-member entry (ens_entry_bytes() each)
+    int* order = nullptr;             // device: member indices grouped by sign class
+    double* scratch = nullptr;        // reduction partials
+    hipStream_t st = nullptr;
+    std::vector<double> D, dt, vx, vy;
+    bool physics = false;             // set_physics has been called
+    bool dirty = true;                // table / order need an upload
+    int class_off[csim::ENS_CLASSES + 1] = {};
+    bool ring_ok = false;             // ghost rings filled and static (no Neumann side)
+    int fuse = -1, fused_2c = 1, depth_used = 0;
+
+    // What each feature owns, created on its first use and given back by its release().
+    // per-cell statistics (csim_ensemble_stats*): mean, var, min, max
+    struct Stats {
+        csim::Capture cap;
+        void release() { cap.release(); }
+    } stats;
+    // per-cell quantiles (csim_ensemble_quantiles*): nq quantile fields, then the exceedance fields
+    struct Quant {
+        csim::Capture cap;
+        int nq = 0;  // levels of the capture in flight
+        void release() { cap.release(); }
+    } quant;
+    // verification (csim_ensemble_verify*): one buffer (VerifyLayout), and the device copy of a host truth
+    struct Verify {
+        csim::Capture cap;
+        csim::DeviceBuf truth;
+        csim::Staging stage;
+        int forecast = 0, nt = 0, blocks = 0;  // of the capture in flight
+        void release() { cap.release(), truth.release(), stage.release(); }
+    } verify;
+    // analysis (csim_ensemble_assimilate): one device buffer (AssimLayout) and the staging of its inputs
+    struct Assim {
+        csim::DeviceBuf dev;
+        csim::Staging stage;
+        void release() { dev.release(), stage.release(); }
+    } assim;
+    // relaxation (csim_ensemble_prior_capture / csim_ensemble_relax).  A capture lives in the handle's own storage, so
+    // that no call that writes the ping-pong buffers touches it: sqrt(v_b) per interior cell (RTPS), a copy of the
+    // current buffer (RTPP, allocated at the first such capture), and the factor field of a call that asks for it
+    struct Relax {
+        csim::DeviceBuf sb, prior, factor;
+        int mode = 0;    // mode of the valid capture; 0: none (cleared by a run of nsteps > 0)
+        int truth = -1;  // its truth_member
+        void release() { sb.release(), prior.release(), factor.release(); }
+    } relax;
+
+    double* view(int buf, int m) const {
+        return alloc[buf] + static_cast<size_t>(m) * g.slab + static_cast<size_t>(csim::GHOST_EXTRA) * g.pitch;
+    }
+    double* base(int buf) const { return alloc[buf] + static_cast<size_t>(csim::GHOST_EXTRA) * g.pitch; }
+    bool static_ring() const {
+        for (int k = 0; k < 4; ++k)
+            if (g.bc[k] == CSIM_BC_NEUMANN) return false;
+        return true;
+    }
+};
+
+namespace csim {
+// cells of a dense per-cell field, ghost ring included
+inline size_t stats_cells(const csim_ensemble* e) { return static_cast<size_t>(e->g.nx + 2) * (e->g.ny + 2); }
+}  // namespace csim
