@@ -17,6 +17,7 @@ import collections
 import ctypes as C
 import os
 import subprocess
+import weakref
 
 import numpy as np
 
@@ -66,6 +67,12 @@ class Msg(C.Structure):
 
 
 VERIFY_MAX_THRESHOLDS = 16
+
+
+class CsimObsCycle(C.Structure):
+    """csim_obs_cycle of include/csim.h: one recorded analysis of an observation network"""
+    _fields_ = [(k, C.c_double) for k in ("n", "has_truth", "sum_ob", "sum_ob2", "sum_oa", "sum_oa2", "sum_oa_ob",
+                                          "sum_ab_ob", "sum_vb", "sum_va", "sum_r", "sum_eb2", "sum_ea2")]
 
 
 class CsimVerifyScores(C.Structure):
@@ -196,6 +203,16 @@ def lib() -> C.CDLL:
         "csim_ensemble_perturb_taps": (i, [d, d, i, i, ip, dp]),
         "csim_ensemble_prior_capture": (i, [vp, i, i]),
         "csim_ensemble_relax": (i, [vp, i, d, i, dp]),
+        "csim_obs_network_create": (i, [vp, i, ip, ip, dp, d, i, i, C.POINTER(vp)]),
+        "csim_obs_network_destroy": (i, [vp]),
+        "csim_obs_network_info": (i, [vp, ip, ip, ip, ip]),
+        "csim_obs_network_set_values": (i, [vp, dp]),
+        "csim_obs_network_observe": (i, [vp, i, C.c_ulonglong, C.c_uint, i]),
+        "csim_obs_noise": (i, [C.c_ulonglong, C.c_uint, C.c_uint, dp]),
+        "csim_ensemble_assimilate_network": (i, [vp, vp, d, i, i]),
+        "csim_obs_network_fetch": (i, [vp, dp, dp, dp, dp, dp, dp]),
+        "csim_obs_network_log": (i, [vp, i, C.POINTER(CsimObsCycle), ip]),
+        "csim_obs_network_log_reset": (i, [vp]),
         "csim_ensemble_set_option": (i, [vp, C.c_char_p, C.c_long]),
         "csim_ensemble_get_option": (i, [vp, C.c_char_p, C.POINTER(C.c_long)]),
         "csim_ensemble_plan": (i, [i, i, i, i, ip]),
@@ -690,6 +707,110 @@ def _relax_mode(mode) -> int:
     return int(mode)
 
 
+def obs_noise(seed, draw, o):
+    """the deviate z_o that ObsNetwork.observe adds (times sqrt(r_o)) to observation o under (seed, draw); o a scalar or
+    an array of input indices (csim_obs_noise) — host only"""
+    seed, draw = int(seed), int(draw)
+    if not (0 <= seed < 1 << 64 and 0 <= draw < 1 << 32):
+        raise ValueError("seed must fit 64 bits and draw 32 bits, unsigned")
+    idx = np.asarray(o, dtype=np.uint32)
+    out = np.empty(idx.shape)
+    z, fn = C.c_double(), lib().csim_obs_noise
+    flat = out.reshape(-1)
+    for n, v in enumerate(idx.reshape(-1).tolist()):
+        _ck(fn(seed, draw, v, C.byref(z)))
+        flat[n] = z.value
+    return out if out.ndim else float(out)
+
+
+ObsNetworkInfo = collections.namedtuple("ObsNetworkInfo", "nobs nlevels lx ly")
+ObsValues = collections.namedtuple("ObsValues", "y truth bg_mean bg_var post_mean post_var")
+ObsValues.__doc__ = """what ObsNetwork.fetch() returns, each per observation in input order or None where the network
+does not hold it: the values, the source member's own values (after observe), and the forecast members' mean and
+variance at the cell before and after the last recorded analysis"""
+OBS_CYCLE_FIELDS = tuple(k for k, _ in CsimObsCycle._fields_)
+
+
+class ObsNetwork:
+    """point observations that live on the device (csim_obs_network_*): planned once, their values drawn on the GPU
+    from a member or set from the host, read by Ensemble.assimilate_network without staging.  Made by
+    Ensemble.obs_network(); closing the ensemble closes its networks."""
+
+    def __init__(self, ens, i, j, r, loc, ordered=False, log_cycles=0):
+        ii = _ints(i)
+        n = len(ii)
+        jj = _ints(j, n)
+        rr = np.ascontiguousarray(np.broadcast_to(np.asarray(r, dtype=np.float64), (n,)))
+        h = C.c_void_p()
+        _ck(lib().csim_obs_network_create(ens._h, n, _ip(ii), _ip(jj), _dp(rr), float(loc), int(bool(ordered)),
+                                          int(log_cycles), C.byref(h)))
+        self._h, self._ens, self.nobs = h, ens, n
+        ens._nets.add(self)
+
+    def __del__(self):
+        self.close()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().csim_obs_network_destroy(self._h)
+            self._h = None
+            self._ens._nets.discard(self)
+
+    @property
+    def info(self) -> ObsNetworkInfo:
+        v = [C.c_int() for _ in range(4)]
+        _ck(lib().csim_obs_network_info(self._h, *[C.byref(x) for x in v]))
+        return ObsNetworkInfo(*[x.value for x in v])
+
+    def set_values(self, y):
+        """the values, one per observation in input order; copied before the call returns, enqueued without waiting"""
+        yy = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+        if yy.shape != (self.nobs,):
+            raise ValueError(f"expected {self.nobs} values")
+        _ck(lib().csim_obs_network_set_values(self._h, _dp(yy)))
+
+    def observe(self, source_member, seed, draw=0, noise=True):
+        """the values from member source_member at the observed cells, with noise plus sqrt(r) times the seeded
+        deviates obs_noise(seed, draw, o); enqueued without waiting (csim_obs_network_observe)"""
+        seed, draw = int(seed), int(draw)
+        if not (0 <= seed < 1 << 64 and 0 <= draw < 1 << 32):
+            raise ValueError("seed must fit 64 bits and draw 32 bits, unsigned")
+        _ck(lib().csim_obs_network_observe(self._h, int(source_member), seed, draw,
+                                           noise if isinstance(noise, int) else int(bool(noise))))
+
+    def fetch(self) -> ObsValues:
+        """waits for the ensemble's stream; whatever the network holds of ObsValues (csim_obs_network_fetch)"""
+        fn, n = lib().csim_obs_network_fetch, self.nobs
+        got = []
+        for group in ((0,), (1,), (2, 3, 4, 5)):
+            outs = [np.empty(n) for _ in group]
+            args = [None] * 6
+            for k, a in zip(group, outs):
+                args[k] = _dp(a)
+            rc = fn(self._h, *args)
+            if rc == 4:  # CSIM_ERR_STATE: not held
+                outs = [None for _ in group]
+            else:
+                _ck(rc)
+            got += outs
+        return ObsValues(*got)
+
+    def log(self) -> np.ndarray:
+        """waits for the ensemble's stream; the recorded analyses, oldest first, as a structured array with the fields
+        of csim_obs_cycle (csim_obs_network_log)"""
+        k = C.c_int()
+        _ck(lib().csim_obs_network_log(self._h, 0, None, C.byref(k)))
+        rec = (CsimObsCycle * max(k.value, 1))()
+        _ck(lib().csim_obs_network_log(self._h, k.value, rec, C.byref(k)))
+        out = np.zeros(k.value, dtype=[(f, np.float64) for f in OBS_CYCLE_FIELDS])
+        for c in range(k.value):
+            out[c] = tuple(getattr(rec[c], f) for f in OBS_CYCLE_FIELDS)
+        return out
+
+    def log_reset(self):
+        _ck(lib().csim_obs_network_log_reset(self._h))
+
+
 def _scores(sc: CsimVerifyScores, nt: int) -> VerifyScores:
     return VerifyScores(sc.cells, sc.nan_cells, sc.crps, sc.rmse, sc.spread, np.array(sc.brier[:nt], dtype=np.float64))
 
@@ -706,6 +827,9 @@ class Ensemble:
         self.members, self.nx, self.ny = members, nx, ny
         self._q_counts = (0, 0)  # levels and thresholds of the last quantiles_begin()
         self._v_counts = (0, 0)  # forecast members and thresholds of the last verify_begin()
+        # observation networks that are alive (the library destroys them with the ensemble); weak, so that a network,
+        # which keeps its ensemble alive, makes no reference cycle with it
+        self._nets = weakref.WeakSet()
         h = C.c_void_p()
         _ck(lib().csim_ensemble_create(members, nx, ny, 1, dx, dy, _i4(bc), bc_value, C.byref(h)))
         self._h = h
@@ -715,6 +839,9 @@ class Ensemble:
 
     def close(self):
         if getattr(self, "_h", None):
+            for net in list(self._nets):
+                net._h = None
+            self._nets.clear()
             lib().csim_ensemble_destroy(self._h)
             self._h = None
 
@@ -867,6 +994,20 @@ class Ensemble:
         if not diagnostics:
             return nl.value
         return EnsembleAnalysis(nl.value, *outs)
+
+    def obs_network(self, i, j, r, loc, ordered=False, log_cycles=0) -> ObsNetwork:
+        """an observation network on the device: cells (i, j), error variances r (a scalar broadcasts), Gaspari-Cohn
+        length loc and the plan of assimilate(), made once; log_cycles: room for that many recorded analyses
+        (csim_obs_network_create)"""
+        return ObsNetwork(self, i, j, r, loc, ordered, log_cycles)
+
+    def assimilate_network(self, net: ObsNetwork, inflation=1.0, truth_member=None, record=False):
+        """the analysis of assimilate() with the network's observations, always enqueued without waiting; record=True
+        also appends the cycle's innovation statistics to the network's log on the device
+        (csim_ensemble_assimilate_network)"""
+        tm = -1 if truth_member is None else int(truth_member)
+        _ck(lib().csim_ensemble_assimilate_network(self._h, net._h, float(inflation), tm,
+                                                   record if isinstance(record, int) else int(bool(record))))
 
     def perturb(self, sigma, corr_len, seed, draw=0, centered=False, truth_member=None):
         """adds sigma times a seeded Gaussian random field of correlation length corr_len to the interior of every

@@ -8,6 +8,8 @@
 //                      plan), verification (and its rank slot)
 //   ensemble_da.cpp    data assimilation: the Gaspari-Cohn table, the analysis and its plan, Philox / normal numbers,
 //                      perturbations and their taps, relaxation (prior capture, relax)
+//   ensemble_obs.cpp   observation networks: create / destroy, values from the host or from a member, the analysis that
+//                      reads a network, its diagnostics and log
 #include <cmath>
 #include <string>
 #include <vector>
@@ -133,6 +135,7 @@ int csim_ensemble_create(int members, int nx, int ny, int halo, double dx, doubl
 int csim_ensemble_destroy(csim_ensemble* e) {
     if (!e) return CSIM_OK;
     if (e->st) (void)hipStreamSynchronize(e->st);
+    e->obs.release();
     e->stats.release();
     e->quant.release();
     e->verify.release();

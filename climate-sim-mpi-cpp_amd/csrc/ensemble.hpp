@@ -169,6 +169,31 @@ hipError_t ens_launch_relax_spread(const EnsGeom& g, double* f, int forecast, in
 hipError_t ens_launch_relax_pert(const EnsGeom& g, double* f, const double* fb, int forecast, int truth_member,
                                  double alpha, hipStream_t st);
 
+// the observation network of csim_obs_network_* (ensemble_obs.hip).  Device arrays in plan order but for `pos`, `bg`
+// and `post`, which go by input index; the analysis reads i, j, idx, y and r through an AssimArgs.
+constexpr int OBS_CHUNK = 256;       // input indices per chunk of the log's sums
+constexpr int OBS_CYCLE_FIELDS = 13; // doubles of a csim_obs_cycle: n, has_truth and the 11 sums
+constexpr int OBS_SUMS = 11;
+struct ObsArgs {
+    int nobs;
+    const int* i;
+    const int* j;
+    const int* idx;               // input index of a plan position
+    const int* pos;               // plan position of an input index
+    const double* r;
+    const double* sr;             // sqrt(r)
+    double* y;
+    double* xt;
+    const double* bg;             // 2 per input index: hb, vb
+    const double* post;           // 2 per input index: ha, va
+    double* part;                 // OBS_SUMS per chunk: T_c
+};
+// y and xt of every observation from member `member`; noise: y = xt + sr z, z the deviate of (seed, draw, input index)
+hipError_t ens_launch_obs_observe(const EnsGeom& g, const double* f, const ObsArgs& a, int member, unsigned seed_lo,
+                                  unsigned seed_hi, unsigned draw, bool noise, hipStream_t st);
+// the chunk sums T_c, then their fold in chunk order into the record `slot` (OBS_CYCLE_FIELDS doubles)
+hipError_t ens_launch_obs_cycle(const ObsArgs& a, bool has_truth, double* slot, hipStream_t st);
+
 // the rank histogram's tie-break: splitmix64's finaliser of the interior index g; a cell with `eq` members equal to the
 // truth goes to bin lt + mix(g) mod (eq + 1)
 __host__ __device__ inline unsigned long long verify_mix(unsigned long long z) {

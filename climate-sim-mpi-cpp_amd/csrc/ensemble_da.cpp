@@ -138,8 +138,6 @@ AssimLayout assim_layout(size_t n, size_t tcells, size_t hp) {
     return l;
 }
 
-constexpr size_t ASSIM_HP_DOUBLES = size_t(1) << 23;  // h'_k of one batch: 64 MiB, at least 8192 observations
-
 // the checks csim_ensemble_prior_capture and csim_ensemble_relax share
 int relax_check(const csim_ensemble* e, int mode, int truth_member, int* M, int* t) {
     CSIM_REQUIRE(mode == CSIM_RELAX_SPREAD || mode == CSIM_RELAX_PERT, "mode must be CSIM_RELAX_SPREAD or CSIM_RELAX_PERT");
@@ -150,6 +148,38 @@ int relax_check(const csim_ensemble* e, int mode, int truth_member, int* M, int*
 }
 
 }  // namespace
+
+namespace csim {
+
+void assim_batches(const EnsGeom& g, int nlevels, const int* off, const int* pi, const int* pj, int lx, int ly,
+                   int batch, std::vector<AssimBatch>* out) {
+    out->clear();
+    for (int L = 0; L < nlevels; ++L)
+        for (int q0 = off[L]; q0 < off[L + 1]; q0 += batch) {
+            const int n = std::min(batch, off[L + 1] - q0);
+            long wcells = 0;
+            for (int q = q0; q < q0 + n; ++q) {
+                const long w = std::min(g.nx, pi[q] + lx) - std::max(1, pi[q] - lx) + 1;
+                const long hgt = std::min(g.ny, pj[q] + ly) - std::max(1, pj[q] - ly) + 1;
+                wcells = std::max(wcells, w * hgt);
+            }
+            out->push_back({q0, n, wcells});
+        }
+}
+
+int assim_enqueue(csim_ensemble* e, const AssimArgs& a, double inflation, const std::vector<AssimBatch>& batches) {
+    const EnsGeom& g = e->g;
+    double* f = e->base(e->cur);
+    if (inflation != 1.0)
+        CSIM_HIP(ens_launch_assim_inflate(g, f, a.forecast, a.truth_member, inflation - 1.0, e->st));
+    for (const AssimBatch& b : batches) {
+        CSIM_HIP(ens_launch_assim_prior(g, f, a, b.first, b.count, e->st));
+        CSIM_HIP(ens_launch_assim_update(g, f, a, b.first, b.count, b.wcells, e->st));
+    }
+    return CSIM_OK;
+}
+
+}  // namespace csim
 
 extern "C" {
 
@@ -215,7 +245,7 @@ int csim_ensemble_assimilate(csim_ensemble* e, int nobs, const int* i, const int
         for (int o = 0; o < nobs; ++o) ord[fill[level[o]]++] = o;
     }
     const size_t tcells = static_cast<size_t>(2 * lx + 1) * (2 * ly + 1);
-    const int batch = static_cast<int>(std::min<size_t>(ASSIM_HP_DOUBLES / M, ASSIM_MAX_OBS));
+    const int batch = assim_batch_size(M);
     const size_t hp = static_cast<size_t>(std::min(nobs, batch)) * M;
     const AssimLayout l = assim_layout(nobs, tcells, hp);
 
@@ -251,20 +281,10 @@ int csim_ensemble_assimilate(csim_ensemble* e, int nobs, const int* i, const int
     a.scal = reinterpret_cast<double*>(d + l.scal);
     a.hp = reinterpret_cast<double*>(d + l.hp);
     a.prior = prior_mean || prior_var ? reinterpret_cast<double*>(d + l.prior) : nullptr;
+    std::vector<AssimBatch> batches;
+    assim_batches(g, nl, off.data(), hi, hj, lx, ly, batch, &batches);
+    CSIM_TRY(assim_enqueue(e, a, inflation, batches));
     double* f = e->base(e->cur);
-    if (inflation != 1.0) CSIM_HIP(ens_launch_assim_inflate(g, f, M, a.truth_member, inflation - 1.0, e->st));
-    for (int L = 0; L < nl; ++L)
-        for (int q0 = off[L]; q0 < off[L + 1]; q0 += batch) {
-            const int n = std::min(batch, off[L + 1] - q0);
-            long wcells = 0;
-            for (int q = q0; q < q0 + n; ++q) {
-                const long w = std::min(g.nx, hi[q] + lx) - std::max(1, hi[q] - lx) + 1;
-                const long hgt = std::min(g.ny, hj[q] + ly) - std::max(1, hj[q] - ly) + 1;
-                wcells = std::max(wcells, w * hgt);
-            }
-            CSIM_HIP(ens_launch_assim_prior(g, f, a, q0, n, e->st));
-            CSIM_HIP(ens_launch_assim_update(g, f, a, q0, n, wcells, e->st));
-        }
     if (!diag) return CSIM_OK;
     auto* post = reinterpret_cast<double*>(d + l.post);
     if (post_mean || post_var) CSIM_HIP(ens_launch_assim_post(g, f, a, nobs, post, e->st));

@@ -2,6 +2,7 @@
 // owning helpers its features are built from.  Host only: the device translation units compile ensemble.hpp and never
 // see this file.  The layout of the ensemble's host side is the table at the top of ensemble.cpp.
 #pragma once
+#include <algorithm>
 #include <vector>
 
 #include "ensemble.hpp"
@@ -198,6 +199,11 @@ struct csim_ensemble {
         int truth = -1;  // its truth_member
         void release() { sb.release(), prior.release(), factor.release(); }
     } relax;
+    // observation networks (csim_obs_network_*, ensemble_obs.cpp): the ones that are alive; each owns its device buffer
+    struct Obs {
+        std::vector<csim_obs_network*> nets;
+        void release();  // destroys them
+    } obs;
 
     double* view(int buf, int m) const {
         return alloc[buf] + static_cast<size_t>(m) * g.slab + static_cast<size_t>(csim::GHOST_EXTRA) * g.pitch;
@@ -213,4 +219,18 @@ struct csim_ensemble {
 namespace csim {
 // cells of a dense per-cell field, ghost ring included
 inline size_t stats_cells(const csim_ensemble* e) { return static_cast<size_t>(e->g.nx + 2) * (e->g.ny + 2); }
+
+// The launches of an analysis (ensemble_da.cpp), shared by csim_ensemble_assimilate and
+// csim_ensemble_assimilate_network.  h'_k of one batch: 64 MiB, at least 8192 observations
+constexpr size_t ASSIM_HP_DOUBLES = size_t(1) << 23;
+inline int assim_batch_size(int M) { return static_cast<int>(std::min<size_t>(ASSIM_HP_DOUBLES / M, ASSIM_MAX_OBS)); }
+struct AssimBatch {
+    int first, count;  // plan positions
+    long wcells;       // the largest clipped window of the batch in cells
+};
+// the batches of a plan: level L holds the plan positions off[L] .. off[L + 1), (pi, pj) the cells in plan order
+void assim_batches(const EnsGeom& g, int nlevels, const int* off, const int* pi, const int* pj, int lx, int ly,
+                   int batch, std::vector<AssimBatch>* out);
+// the inflation (when != 1), then assim_prior and assim_update of every batch in turn, on the ensemble's stream
+int assim_enqueue(csim_ensemble* e, const AssimArgs& a, double inflation, const std::vector<AssimBatch>& batches);
 }  // namespace csim

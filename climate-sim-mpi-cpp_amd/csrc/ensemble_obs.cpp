@@ -1,0 +1,326 @@
+// ensemble_obs.cpp — the observation network (csim_obs_network_* and csim_ensemble_assimilate_network of include/csim.h;
+// kernels in ensemble_obs.hip): observations that are planned once and live on the device.  create does what
+// csim_ensemble_assimilate does per call (checks, Gaspari-Cohn table, levels, plan order, upload); the analysis then
+// only points an AssimArgs into the network's buffer and enqueues the launches of ensemble_da.cpp's assim_enqueue.
+#include <cmath>
+#include <memory>
+#include <new>
+#include <vector>
+
+#include "ensemble_host.hpp"
+#include "ensemble_noise.hpp"
+
+using namespace csim;
+
+namespace {
+
+// byte layout of a network's device buffer.  Written once at create: i, j, idx, r, sr (plan order), pos (by input
+// index) and the table.  Then y and xt (plan order), the analysis's scalars and one batch's h'_k, the background and
+// posterior diagnostics (2 per input index each), the chunk sums of the last record and the log.
+struct ObsLayout {
+    size_t i, j, idx, pos, r, sr, rho, fixed, y, xt, scal, bg, post, part, hp, log, total;
+};
+ObsLayout obs_layout(size_t n, size_t tcells, size_t hp, size_t log_cycles) {
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t chunks = (n + OBS_CHUNK - 1) / OBS_CHUNK;
+    ObsLayout l{};
+    l.i = 0;
+    l.j = up(l.i + 4 * n);
+    l.idx = up(l.j + 4 * n);
+    l.pos = up(l.idx + 4 * n);
+    l.r = up(l.pos + 4 * n);
+    l.sr = up(l.r + 8 * n);
+    l.rho = up(l.sr + 8 * n);
+    l.fixed = up(l.rho + 8 * tcells);
+    l.y = l.fixed;
+    l.xt = up(l.y + 8 * n);
+    l.scal = up(l.xt + 8 * n);
+    l.bg = up(l.scal + 24 * n);
+    l.post = up(l.bg + 16 * n);
+    l.part = up(l.post + 16 * n);
+    l.hp = up(l.part + 8 * OBS_SUMS * chunks);
+    l.log = up(l.hp + 8 * hp);
+    l.total = up(l.log + 8 * OBS_CYCLE_FIELDS * log_cycles);
+    return l;
+}
+
+static_assert(sizeof(csim_obs_cycle) == sizeof(double) * OBS_CYCLE_FIELDS, "csim_obs_cycle is 13 doubles");
+
+}  // namespace
+
+struct csim_obs_network {
+    csim_ensemble* e = nullptr;
+    int nobs = 0, nlevels = 0, lx = 0, ly = 0, log_cycles = 0;
+    std::vector<int> off, pi, pj, idx;  // the plan: level offsets; cells and input index of every plan position
+    std::vector<AssimBatch> batches;    // its launches for batches_m forecast members (made at the first analysis)
+    int batches_m = 0;
+    ObsLayout l{};
+    DeviceBuf dev;
+    Staging stage;                      // of set_values
+    bool has_values = false, has_truth = false, has_diag = false;
+    int cycles = 0;                     // records in the log
+    template <class T> T* at(size_t byte) const { return reinterpret_cast<T*>(dev.as<char>() + byte); }
+    ObsArgs args() const {
+        ObsArgs a{};
+        a.nobs = nobs;
+        a.i = at<int>(l.i), a.j = at<int>(l.j), a.idx = at<int>(l.idx), a.pos = at<int>(l.pos);
+        a.r = at<double>(l.r), a.sr = at<double>(l.sr);
+        a.y = at<double>(l.y), a.xt = at<double>(l.xt);
+        a.bg = at<double>(l.bg), a.post = at<double>(l.post), a.part = at<double>(l.part);
+        return a;
+    }
+    void release() { dev.release(), stage.release(); }
+};
+
+void csim_ensemble::Obs::release() {
+    for (csim_obs_network* n : nets) {
+        n->release();
+        delete n;
+    }
+    nets.clear();
+}
+
+namespace {
+
+// nobs values in plan order on the device -> input order on the host; the stream must be idle afterwards
+int fetch_plan_order(const csim_obs_network* n, size_t byte, double* out) {
+    std::vector<double> buf(n->nobs);
+    CSIM_HIP(hipMemcpyAsync(buf.data(), n->at<char>(byte), sizeof(double) * buf.size(), hipMemcpyDeviceToHost, n->e->st));
+    CSIM_HIP(hipStreamSynchronize(n->e->st));
+    for (int q = 0; q < n->nobs; ++q) out[n->idx[q]] = buf[q];
+    return CSIM_OK;
+}
+
+// (mean, variance) pairs by input index on the device -> two host arrays, either may be null
+int fetch_pairs(const csim_obs_network* n, size_t byte, double* mean, double* var) {
+    if (!mean && !var) return CSIM_OK;
+    std::vector<double> buf(2 * static_cast<size_t>(n->nobs));
+    CSIM_HIP(hipMemcpyAsync(buf.data(), n->at<char>(byte), sizeof(double) * buf.size(), hipMemcpyDeviceToHost, n->e->st));
+    CSIM_HIP(hipStreamSynchronize(n->e->st));
+    for (int o = 0; o < n->nobs; ++o) {
+        if (mean) mean[o] = buf[2 * static_cast<size_t>(o)];
+        if (var) var[o] = buf[2 * static_cast<size_t>(o) + 1];
+    }
+    return CSIM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int csim_obs_network_create(csim_ensemble* e, int nobs, const int* i, const int* j, const double* r, double loc,
+                            int ordered, int log_cycles, csim_obs_network** out) {
+    CSIM_REQUIRE(out, "out is null");
+    *out = nullptr;
+    CSIM_REQUIRE(e, "null ensemble");
+    const EnsGeom& g = e->g;
+    CSIM_REQUIRE(nobs >= 1, "nobs must be >= 1");
+    CSIM_REQUIRE(i && j && r, "null observation array");
+    CSIM_REQUIRE(std::isfinite(loc) && loc > 0, "loc must be finite and > 0");
+    CSIM_REQUIRE(ordered == 0 || ordered == 1, "ordered must be 0 or 1");
+    CSIM_REQUIRE(log_cycles >= 0 && log_cycles <= 65536, "log_cycles must be in 0 .. 65536");
+    if (nobs > ASSIM_MAX_OBS) return fail(CSIM_ERR_UNSUPPORTED, "csim_obs_network_create: at most 2^20 observations");
+    for (int o = 0; o < nobs; ++o) {
+        CSIM_REQUIRE(i[o] >= 1 && i[o] <= g.nx && j[o] >= 1 && j[o] <= g.ny, "observation outside the interior");
+        CSIM_REQUIRE(std::isfinite(r[o]) && r[o] > 0, "observation error variance must be finite and > 0");
+    }
+    // the network is the caller's only once everything has worked; no exception crosses the C ABI
+    struct Drop {
+        void operator()(csim_obs_network* p) const {
+            p->release();
+            delete p;
+        }
+    };
+    try {
+        int lx = 0, ly = 0, nl = 0;
+        CSIM_TRY(csim_ensemble_gc_table(e->dx, e->dy, loc, g.nx, g.ny, &lx, &ly, nullptr));
+        std::vector<int> level(nobs);
+        CSIM_TRY(csim_ensemble_assim_plan(nobs, i, j, lx, ly, ordered, level.data(), &nl));
+
+        std::unique_ptr<csim_obs_network, Drop> n(new csim_obs_network);
+        n->e = e, n->nobs = nobs, n->nlevels = nl, n->lx = lx, n->ly = ly, n->log_cycles = log_cycles;
+        // plan order: by level, then input index (a counting sort), as csim_ensemble_assimilate
+        n->off.assign(nl + 1, 0);
+        for (int o = 0; o < nobs; ++o) ++n->off[level[o] + 1];
+        for (int L = 0; L < nl; ++L) n->off[L + 1] += n->off[L];
+        n->pi.resize(nobs), n->pj.resize(nobs), n->idx.resize(nobs);
+        {
+            std::vector<int> fill(n->off.begin(), n->off.end() - 1);
+            for (int o = 0; o < nobs; ++o) n->idx[fill[level[o]]++] = o;
+        }
+        // h'_k of the largest batch of either number of forecast members
+        size_t hp = 0;
+        for (int M = g.members - 1; M <= g.members; ++M)
+            if (M >= 2 && M <= ASSIM_MAX_MEMBERS)
+                hp = std::max(hp, static_cast<size_t>(std::min(nobs, assim_batch_size(M))) * M);
+        const size_t tcells = static_cast<size_t>(2 * lx + 1) * (2 * ly + 1);
+        n->l = obs_layout(nobs, tcells, hp, log_cycles);
+        const ObsLayout& l = n->l;
+        std::vector<char> h(l.fixed, 0);
+        auto* hi = reinterpret_cast<int*>(h.data() + l.i);
+        auto* hj = reinterpret_cast<int*>(h.data() + l.j);
+        auto* hx = reinterpret_cast<int*>(h.data() + l.idx);
+        auto* hpos = reinterpret_cast<int*>(h.data() + l.pos);
+        auto* hr = reinterpret_cast<double*>(h.data() + l.r);
+        auto* hs = reinterpret_cast<double*>(h.data() + l.sr);
+        for (int q = 0; q < nobs; ++q) {
+            const int o = n->idx[q];
+            n->pi[q] = hi[q] = i[o], n->pj[q] = hj[q] = j[o], hx[q] = o, hpos[o] = q;
+            hr[q] = r[o], hs[q] = std::sqrt(r[o]);
+        }
+        int rc = csim_ensemble_gc_table(e->dx, e->dy, loc, g.nx, g.ny, &lx, &ly, reinterpret_cast<double*>(h.data() + l.rho));
+        if (rc == CSIM_OK) rc = n->dev.reserve(l.total);
+        hipError_t err = hipSuccess;
+        if (rc == CSIM_OK) {
+            err = hipMemsetAsync(n->dev.p, 0, l.total, e->st);
+            if (err == hipSuccess) err = hipMemcpyAsync(n->dev.p, h.data(), l.fixed, hipMemcpyHostToDevice, e->st);
+            if (err == hipSuccess) err = hipStreamSynchronize(e->st);  // h goes away
+        }
+        if (rc != CSIM_OK) return rc;
+        if (err != hipSuccess) return fail(CSIM_ERR_HIP, std::string("csim_obs_network_create: ") + hipGetErrorString(err));
+        e->obs.nets.push_back(n.get());
+        *out = n.release();
+        return CSIM_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(CSIM_ERR_STATE, "csim_obs_network_create: out of host memory");
+    }
+}
+
+int csim_obs_network_destroy(csim_obs_network* n) {
+    if (!n) return CSIM_OK;
+    csim_ensemble* e = n->e;
+    if (e->st) (void)hipStreamSynchronize(e->st);  // work enqueued there may still use the buffer
+    e->obs.nets.erase(std::remove(e->obs.nets.begin(), e->obs.nets.end(), n), e->obs.nets.end());
+    n->release();
+    delete n;
+    return CSIM_OK;
+}
+
+int csim_obs_network_info(const csim_obs_network* n, int* nobs, int* nlevels, int* lx, int* ly) {
+    CSIM_REQUIRE(n, "null network");
+    if (nobs) *nobs = n->nobs;
+    if (nlevels) *nlevels = n->nlevels;
+    if (lx) *lx = n->lx;
+    if (ly) *ly = n->ly;
+    return CSIM_OK;
+}
+
+int csim_obs_network_set_values(csim_obs_network* n, const double* y) {
+    CSIM_REQUIRE(n, "null network");
+    CSIM_REQUIRE(y, "null values");
+    for (int o = 0; o < n->nobs; ++o) CSIM_REQUIRE(std::isfinite(y[o]), "observation value must be finite");
+    void* staged = nullptr;
+    CSIM_TRY(n->stage.acquire(sizeof(double) * n->nobs, &staged));
+    auto* hy = static_cast<double*>(staged);
+    for (int q = 0; q < n->nobs; ++q) hy[q] = y[n->idx[q]];
+    CSIM_TRY(n->stage.send(n->at<char>(n->l.y), sizeof(double) * n->nobs, n->e->st));
+    n->has_values = true;
+    n->has_truth = false;
+    return CSIM_OK;
+}
+
+int csim_obs_network_observe(csim_obs_network* n, int source_member, unsigned long long seed, unsigned draw,
+                             int noise) {
+    CSIM_REQUIRE(n, "null network");
+    csim_ensemble* e = n->e;
+    CSIM_REQUIRE(source_member >= 0 && source_member < e->g.members, "source_member out of range");
+    CSIM_REQUIRE(noise == 0 || noise == 1, "noise must be 0 or 1");
+    CSIM_HIP(ens_launch_obs_observe(e->g, e->base(e->cur), n->args(), source_member, static_cast<unsigned>(seed),
+                                    static_cast<unsigned>(seed >> 32), draw, noise == 1, e->st));
+    n->has_values = true;
+    n->has_truth = true;
+    return CSIM_OK;
+}
+
+int csim_obs_noise(unsigned long long seed, unsigned draw, unsigned o, double* z) {
+    CSIM_REQUIRE(z, "null argument");
+    unsigned c[4] = {o, 0u, 0xFFFFFFFFu, draw};
+    philox4x32(c, static_cast<unsigned>(seed), static_cast<unsigned>(seed >> 32));
+    *z = normal_from_bits(static_cast<unsigned long long>(c[0]) | (static_cast<unsigned long long>(c[1]) << 32));
+    return CSIM_OK;
+}
+
+int csim_ensemble_assimilate_network(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
+                                     int record) {
+    CSIM_REQUIRE(e, "null ensemble");
+    CSIM_REQUIRE(n, "null network");
+    CSIM_REQUIRE(n->e == e, "the network belongs to another ensemble");
+    const EnsGeom& g = e->g;
+    CSIM_REQUIRE(std::isfinite(inflation) && inflation >= 1.0, "inflation must be finite and >= 1");
+    int M = 0, t = 0;
+    CSIM_TRY(forecast_split(g.members, truth_member, &M, &t));
+    CSIM_REQUIRE(M >= 2, "the analysis needs at least two forecast members");
+    if (M > ASSIM_MAX_MEMBERS)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_network: at most 1024 forecast members");
+    CSIM_REQUIRE(record == 0 || record == 1, "record must be 0 or 1");
+    if (!n->has_values)
+        return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_network: the network has no values yet "
+                                    "(csim_obs_network_set_values or csim_obs_network_observe)");
+    if (record && n->cycles >= n->log_cycles)
+        return fail(CSIM_ERR_STATE, n->log_cycles ? "csim_ensemble_assimilate_network: the log is full"
+                                                  : "csim_ensemble_assimilate_network: the network has no log");
+    if (n->batches_m != M) {
+        assim_batches(g, n->nlevels, n->off.data(), n->pi.data(), n->pj.data(), n->lx, n->ly, assim_batch_size(M),
+                      &n->batches);
+        n->batches_m = M;
+    }
+    const ObsArgs oa = n->args();
+    AssimArgs a{};
+    a.forecast = M;
+    a.truth_member = t;
+    a.lx = n->lx, a.ly = n->ly;
+    a.rho = n->at<double>(n->l.rho);
+    a.obs.i = oa.i, a.obs.j = oa.j, a.obs.idx = oa.idx, a.obs.y = oa.y, a.obs.r = oa.r;
+    a.scal = n->at<double>(n->l.scal);
+    a.hp = n->at<double>(n->l.hp);
+    a.prior = nullptr;
+    const double* f = e->base(e->cur);
+    if (record) CSIM_HIP(ens_launch_assim_post(g, f, a, n->nobs, n->at<double>(n->l.bg), e->st));
+    CSIM_TRY(assim_enqueue(e, a, inflation, n->batches));
+    if (!record) return CSIM_OK;
+    CSIM_HIP(ens_launch_assim_post(g, f, a, n->nobs, n->at<double>(n->l.post), e->st));
+    CSIM_HIP(ens_launch_obs_cycle(oa, n->has_truth,
+                                  n->at<double>(n->l.log) + static_cast<size_t>(OBS_CYCLE_FIELDS) * n->cycles, e->st));
+    ++n->cycles;
+    n->has_diag = true;
+    return CSIM_OK;
+}
+
+int csim_obs_network_fetch(csim_obs_network* n, double* y, double* truth, double* bg_mean, double* bg_var,
+                           double* post_mean, double* post_var) {
+    CSIM_REQUIRE(n, "null network");
+    if (y && !n->has_values) return fail(CSIM_ERR_STATE, "csim_obs_network_fetch: the network has no values yet");
+    if (truth && !n->has_truth)
+        return fail(CSIM_ERR_STATE, "csim_obs_network_fetch: the values were not observed from a member");
+    if ((bg_mean || bg_var || post_mean || post_var) && !n->has_diag)
+        return fail(CSIM_ERR_STATE, "csim_obs_network_fetch: no analysis has been recorded");
+    CSIM_HIP(hipStreamSynchronize(n->e->st));
+    if (y) CSIM_TRY(fetch_plan_order(n, n->l.y, y));
+    if (truth) CSIM_TRY(fetch_plan_order(n, n->l.xt, truth));
+    CSIM_TRY(fetch_pairs(n, n->l.bg, bg_mean, bg_var));
+    CSIM_TRY(fetch_pairs(n, n->l.post, post_mean, post_var));
+    return CSIM_OK;
+}
+
+int csim_obs_network_log(csim_obs_network* n, int max, csim_obs_cycle* out, int* ncycles) {
+    CSIM_REQUIRE(n, "null network");
+    CSIM_REQUIRE(max >= 0 && (max == 0 || out), "max must be >= 0, with room for that many records");
+    CSIM_HIP(hipStreamSynchronize(n->e->st));
+    const int k = std::min(max, n->cycles);
+    if (k > 0) {
+        CSIM_HIP(hipMemcpyAsync(out, n->at<char>(n->l.log), sizeof(csim_obs_cycle) * k, hipMemcpyDeviceToHost, n->e->st));
+        CSIM_HIP(hipStreamSynchronize(n->e->st));
+    }
+    if (ncycles) *ncycles = n->cycles;
+    return CSIM_OK;
+}
+
+int csim_obs_network_log_reset(csim_obs_network* n) {
+    CSIM_REQUIRE(n, "null network");
+    if (n->log_cycles)
+        CSIM_HIP(hipMemsetAsync(n->at<char>(n->l.log), 0, sizeof(csim_obs_cycle) * n->log_cycles, n->e->st));
+    n->cycles = 0;
+    return CSIM_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,107 @@
+// ensemble_obs.hip — the kernels of the observation network (csim_obs_network_* in include/csim.h, host side in
+// ensemble_obs.cpp).  Needs only the slab layout of ensemble.hpp and the random numbers of ensemble_noise.hpp.
+//
+//   k_obs_observe  one lane per observation (plan position q): the gather of x_s(i, j) from the source member, and
+//                  with noise one Philox call on the counter (input index, 0, 0xFFFFFFFF, draw) and the normal
+//                  quantile of its first 64 bits; stores y and xt in plan order.  The deviate depends on the input
+//                  index alone, so neither the plan nor the launch geometry shows in the result.
+//   k_obs_chunks   one lane per chunk of OBS_CHUNK consecutive input indices: T_c of the eleven sums of a
+//                  csim_obs_cycle, each a running sum from +0 in input order.
+//   k_obs_cycle    one wave: lane f folds T_c of sum f in chunk order from +0 into the log's record.
+// The background and posterior diagnostics that k_obs_chunks reads are written by the analysis's own k_assim_post
+// (ens_launch_assim_post), before and after the analysis.  Every product is rounded, no FMA contraction.
+#include "ensemble.hpp"
+#include "ensemble_noise.hpp"
+
+#pragma clang fp contract(off)
+
+namespace csim {
+
+namespace {
+
+__global__ __launch_bounds__(256) void k_obs_observe(const double* __restrict__ f, int pitch, long slab, ObsArgs a,
+                                                     int member, unsigned seed_lo, unsigned seed_hi, unsigned draw,
+                                                     int noise) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= a.nobs) return;
+    const double xt = f[static_cast<ptrdiff_t>(member) * slab + static_cast<ptrdiff_t>(a.j[q]) * pitch + (LPAD - 1) +
+                        a.i[q]];
+    double y = xt;
+    if (noise) {
+        unsigned c[4] = {static_cast<unsigned>(a.idx[q]), 0u, 0xFFFFFFFFu, draw};
+        philox4x32(c, seed_lo, seed_hi);
+        const double z = normal_from_bits(static_cast<unsigned long long>(c[0]) |
+                                          (static_cast<unsigned long long>(c[1]) << 32));
+        y = xt + a.sr[q] * z;
+    }
+    a.y[q] = y;
+    a.xt[q] = xt;
+}
+
+__global__ __launch_bounds__(64) void k_obs_chunks(ObsArgs a, int nchunks, int has_truth) {
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= nchunks) return;
+    double s[OBS_SUMS];
+#pragma unroll
+    for (int k = 0; k < OBS_SUMS; ++k) s[k] = 0.0;
+    const int o1 = min(a.nobs, (c + 1) * OBS_CHUNK);
+    for (int o = c * OBS_CHUNK; o < o1; ++o) {
+        const int q = a.pos[o];
+        const double y = a.y[q];
+        const double hb = a.bg[2 * static_cast<size_t>(o)], vb = a.bg[2 * static_cast<size_t>(o) + 1];
+        const double ha = a.post[2 * static_cast<size_t>(o)], va = a.post[2 * static_cast<size_t>(o) + 1];
+        const double ob = y - hb, oa = y - ha, ab = ha - hb;
+        s[0] = s[0] + ob;
+        s[1] = s[1] + ob * ob;
+        s[2] = s[2] + oa;
+        s[3] = s[3] + oa * oa;
+        s[4] = s[4] + oa * ob;
+        s[5] = s[5] + ab * ob;
+        s[6] = s[6] + vb;
+        s[7] = s[7] + va;
+        s[8] = s[8] + a.r[q];
+        if (has_truth) {
+            const double xt = a.xt[q];
+            const double eb = hb - xt, ea = ha - xt;
+            s[9] = s[9] + eb * eb;
+            s[10] = s[10] + ea * ea;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < OBS_SUMS; ++k) a.part[static_cast<size_t>(c) * OBS_SUMS + k] = s[k];
+}
+
+__global__ __launch_bounds__(64) void k_obs_cycle(const double* __restrict__ part, int nchunks, int nobs, int has_truth,
+                                                  double* __restrict__ slot) {
+    const int k = threadIdx.x;
+    if (k == 0) {
+        slot[0] = static_cast<double>(nobs);
+        slot[1] = has_truth ? 1.0 : 0.0;
+    }
+    if (k >= OBS_SUMS) return;
+    double s = 0.0;
+    for (int c = 0; c < nchunks; ++c) s = s + part[static_cast<size_t>(c) * OBS_SUMS + k];
+    slot[2 + k] = s;
+}
+
+}  // namespace
+
+hipError_t ens_launch_obs_observe(const EnsGeom& g, const double* f, const ObsArgs& a, int member, unsigned seed_lo,
+                                  unsigned seed_hi, unsigned draw, bool noise, hipStream_t st) {
+    if (a.nobs <= 0 || member < 0 || member >= g.members) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_obs_observe, dim3((a.nobs + 255) / 256), dim3(256), 0, st, f, g.pitch, g.slab, a, member,
+                       seed_lo, seed_hi, draw, noise ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t ens_launch_obs_cycle(const ObsArgs& a, bool has_truth, double* slot, hipStream_t st) {
+    if (a.nobs <= 0) return hipErrorInvalidValue;
+    const int nchunks = (a.nobs + OBS_CHUNK - 1) / OBS_CHUNK;
+    hipLaunchKernelGGL(k_obs_chunks, dim3((nchunks + 63) / 64), dim3(64), 0, st, a, nchunks, has_truth ? 1 : 0);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL(k_obs_cycle, dim3(1), dim3(64), 0, st, a.part, nchunks, a.nobs, has_truth ? 1 : 0, slot);
+    return hipGetLastError();
+}
+
+}  // namespace csim

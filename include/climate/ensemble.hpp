@@ -2,7 +2,9 @@
 // one grid shape, each with its own field and (D, dt, vx, vy), advanced together on one GPU.  Every member ends bit
 // for bit where a single-rank climate::Stepper run with its own parameters would.  Calls only the C ABI.
 #pragma once
+#include <algorithm>
 #include <cstddef>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -37,13 +39,101 @@ struct EnsembleAnalysis {
     std::vector<double> prior_mean, prior_var, post_mean, post_var;
 };
 
+// what an observation network holds per observation, in input order (see csim_obs_network_fetch); truth is empty
+// unless the values were observed from a member, the diagnostics are empty before the first recorded analysis
+struct ObsValues {
+    std::vector<double> y, truth, bg_mean, bg_var, post_mean, post_var;
+};
+
+class Ensemble;
+
+// point observations that live on the device (csim_obs_network_*): planned once, their values drawn on the GPU from a
+// member or set from the host, read by Ensemble::assimilate(ObsNetwork&, ...) without staging.  Move-only; made by
+// Ensemble::obs_network().  The library destroys the networks of an ensemble with it; the ensemble then empties the
+// handle this class shares with it, so a network that outlives its ensemble is safe to destroy or move, and every
+// other call on it throws.
+class ObsNetwork {
+public:
+    ~ObsNetwork() { close(); }
+    ObsNetwork(ObsNetwork&&) noexcept = default;
+    ObsNetwork& operator=(ObsNetwork&& o) noexcept {
+        if (this != &o) {
+            close();
+            slot_ = std::move(o.slot_), nobs_ = o.nobs_;
+        }
+        return *this;
+    }
+    ObsNetwork(const ObsNetwork&) = delete;
+    ObsNetwork& operator=(const ObsNetwork&) = delete;
+
+    std::size_t size() const { return nobs_; }
+    int levels() const {
+        int nl = 0;
+        check(csim_obs_network_info(handle(), nullptr, &nl, nullptr, nullptr));
+        return nl;
+    }
+    // one finite value per observation, copied before the call returns; enqueued
+    void set_values(const std::vector<double>& y) {
+        if (y.size() != nobs_) throw std::invalid_argument("obs network: one value per observation");
+        check(csim_obs_network_set_values(handle(), y.data()));
+    }
+    // the values from member source_member, with noise plus sqrt(r) times the deviates of (seed, draw); enqueued
+    void observe(int source_member, unsigned long long seed, unsigned draw = 0, bool noise = true) {
+        check(csim_obs_network_observe(handle(), source_member, seed, draw, noise ? 1 : 0));
+    }
+    // waits for the ensemble's stream
+    ObsValues fetch(bool truth = false, bool diagnostics = false) {
+        ObsValues v;
+        v.y.resize(nobs_);
+        if (truth) v.truth.resize(nobs_);
+        if (diagnostics)
+            for (std::vector<double>* a : {&v.bg_mean, &v.bg_var, &v.post_mean, &v.post_var}) a->resize(nobs_);
+        check(csim_obs_network_fetch(handle(), v.y.data(), truth ? v.truth.data() : nullptr,
+                                     diagnostics ? v.bg_mean.data() : nullptr, diagnostics ? v.bg_var.data() : nullptr,
+                                     diagnostics ? v.post_mean.data() : nullptr,
+                                     diagnostics ? v.post_var.data() : nullptr));
+        return v;
+    }
+    // waits for the ensemble's stream: the recorded analyses, oldest first
+    std::vector<csim_obs_cycle> log() {
+        int k = 0;
+        check(csim_obs_network_log(handle(), 0, nullptr, &k));
+        std::vector<csim_obs_cycle> out(static_cast<std::size_t>(k));
+        check(csim_obs_network_log(handle(), k, out.data(), &k));
+        return out;
+    }
+    void log_reset() { check(csim_obs_network_log_reset(handle())); }
+
+private:
+    friend class Ensemble;
+    // the handle, shared with the ensemble that made it: null once either side has destroyed the network
+    struct Slot {
+        csim_obs_network* h = nullptr;
+    };
+    ObsNetwork(std::shared_ptr<Slot> slot, std::size_t nobs) : slot_(std::move(slot)), nobs_(nobs) {}
+    csim_obs_network* handle() const { return slot_ ? slot_->h : nullptr; }  // null: the library refuses the call
+    void close() {
+        if (slot_ && slot_->h) csim_obs_network_destroy(slot_->h);
+        if (slot_) slot_->h = nullptr;
+        slot_.reset();
+    }
+    static void check(int rc) {
+        if (rc != CSIM_OK) throw std::runtime_error(std::string("csim: ") + csim_last_error());
+    }
+    std::shared_ptr<Slot> slot_;
+    std::size_t nobs_ = 0;
+};
+
 class Ensemble {
 public:
     Ensemble(int members, int nx, int ny, double dx, double dy, const int bc[4], double bc_value = 0.0)
         : members_(members), nx_(nx), ny_(ny) {
         check(csim_ensemble_create(members, nx, ny, 1, dx, dy, bc, bc_value, &h_));
     }
-    ~Ensemble() { csim_ensemble_destroy(h_); }
+    ~Ensemble() {
+        for (auto& slot : nets_) slot->h = nullptr;  // csim_ensemble_destroy destroys the networks that are alive
+        csim_ensemble_destroy(h_);
+    }
     Ensemble(const Ensemble&) = delete;
     Ensemble& operator=(const Ensemble&) = delete;
 
@@ -193,6 +283,24 @@ public:
                                        nullptr, &nl));
         return nl;
     }
+    // an observation network on the device: cells, error variances, localisation and plan made once; log_cycles: room
+    // for that many recorded analyses (see csim_obs_network_create)
+    ObsNetwork obs_network(const std::vector<int>& i, const std::vector<int>& j, const std::vector<double>& r,
+                           double loc, bool ordered = false, int log_cycles = 0) {
+        if (j.size() != i.size() || r.size() != i.size())
+            throw std::invalid_argument("ensemble: observation arrays of different sizes");
+        nets_.erase(std::remove_if(nets_.begin(), nets_.end(), [](const auto& slot) { return !slot->h; }), nets_.end());
+        auto slot = std::make_shared<ObsNetwork::Slot>();
+        check(csim_obs_network_create(h_, static_cast<int>(i.size()), i.data(), j.data(), r.data(), loc,
+                                      ordered ? 1 : 0, log_cycles, &slot->h));
+        nets_.push_back(slot);
+        return ObsNetwork(std::move(slot), i.size());
+    }
+    // the analysis with the network's observations, always enqueued; record: also append the cycle's innovation
+    // statistics to the network's log on the device (see csim_ensemble_assimilate_network)
+    void assimilate(ObsNetwork& net, double inflation = 1.0, int t = -1, bool record = false) {
+        check(csim_ensemble_assimilate_network(h_, net.handle(), inflation, t, record ? 1 : 0));
+    }
     // adds sigma times a seeded Gaussian random field of correlation length corr_len to the interior of every forecast
     // member (t = -1: all members, else member t is left alone); enqueued on the ensemble's stream, so that run() follows
     // without a host wait (see csim_ensemble_perturb)
@@ -244,6 +352,7 @@ private:
         return i.size();
     }
     csim_ensemble* h_ = nullptr;
+    std::vector<std::shared_ptr<ObsNetwork::Slot>> nets_;  // the handles of the networks made here that are alive
     int members_, nx_, ny_;
     std::size_t q_levels_ = 0, q_thresholds_ = 0;  // of the last quantiles_begin()
     std::size_t v_forecast_ = 0, v_thresholds_ = 0;  // of the last verify_begin()

@@ -534,6 +534,71 @@ int csim_ensemble_perturb_taps(double d, double corr_len, int n, int periodic, i
 #define CSIM_RELAX_PERT 2   /* RTPP */
 int csim_ensemble_prior_capture(csim_ensemble* e, int mode, int truth_member);
 int csim_ensemble_relax(csim_ensemble* e, int mode, double alpha, int truth_member, double* out_factor);
+/* observation network: the observations of an analysis as an object that lives on the device.  It is planned once
+ * (cells, error variances, localisation, levels); its values are drawn on the GPU from a member, with seeded noise, or
+ * set from the host; the analysis reads it without staging and logs innovation statistics on the device, to be fetched
+ * once.  A K-cycle observing-system simulation experiment,
+ *     run -> observe -> prior_capture -> assimilate_network(record) -> relax -> perturb,   K times, then one log,
+ * is K enqueue-only cycles and one fetch.  All fp64 arithmetic IEEE, without FMA contraction, every product rounded.
+ *
+ * create: observation o (0 <= o < nobs, nobs >= 1) is the interior cell (i[o], j[o]) with error variance r[o], loc and
+ *   ordered as in csim_ensemble_assimilate, and validated as there (CSIM_ERR_ARG: a cell outside the interior, r not
+ *   finite and > 0, loc not finite and > 0, ordered not 0 / 1, nobs < 1, log_cycles outside 0 .. 65536, a null array;
+ *   CSIM_ERR_UNSUPPORTED: nobs > CSIM_ASSIM_MAX_OBS).  The table and lx, ly are those of csim_ensemble_gc_table, the
+ *   levels those of csim_ensemble_assim_plan, the order (level, input index).  Everything the kernels read is put on
+ *   the device once, sqrt(r_o) (correctly rounded) included, with room for the values, the log of log_cycles records
+ *   and the diagnostics.  The network is bound to the ensemble's geometry and stream; csim_ensemble_destroy destroys
+ *   the networks that are still alive, and their handles are invalid from then on.
+ * info: any pointer may be NULL.
+ * set_values: y[o], nobs finite values in input order (a non-finite one: CSIM_ERR_ARG, before anything is enqueued),
+ *   copied before the call returns; the call only enqueues.  Clears has_truth.
+ * observe: for every o, xt_o = x_s(i_o, j_o), s = source_member, in the current buffer after everything enqueued so
+ *   far.  noise = 1:  y_o = xt_o + sqrt(r_o) z_o  (the product rounded, then the sum);  noise = 0:  y_o = xt_o, its
+ *   bits (a -0 stays).  z_o = the value of csim_obs_noise for (seed, draw, o):
+ *   csim_normal_from_bits of  out[0] | out[1] << 32,  out = csim_philox4x32 with ctr = (o, 0, 0xFFFFFFFF, draw),
+ *   key = (lo32(seed), hi32(seed)).  Counter word 2 is no member index, so the stream is disjoint from every field of
+ *   csim_ensemble_perturb under the same seed and draw; z_o depends on the input index o alone.  xt is kept and
+ *   has_truth set.  Only enqueues.  CSIM_ERR_ARG: source_member outside 0 .. B-1, noise not 0 / 1.
+ * assimilate_network: the analysis of csim_ensemble_assimilate with (i, j, y, r, loc, ordered) of the network and the
+ *   inflation and truth_member given, bit for bit, and always only enqueued: no host planning, no staging copy.
+ *   record = 1 also computes, per observation at its cell, with mv of csim_ensemble_relax over the forecast members:
+ *   (hb_o, vb_o) = mv(x) before the inflation and the first observation, (ha_o, va_o) = mv(x) after the last (the
+ *   post_mean and post_var of csim_ensemble_assimilate), and appends one csim_obs_cycle to the log on the device.
+ *   Every sum_ field: for each chunk c of 256 consecutive input indices T_c = the running sum of the terms from +0 in
+ *   input order; the field = the running sum of T_c from +0 in chunk order.  Terms:
+ *     n = (double)nobs;  has_truth = 0 or 1
+ *     ob: y - hb;  ob2: (y - hb)(y - hb);  oa: y - ha;  oa2: (y - ha)(y - ha);  oa_ob: (y - ha)(y - hb)
+ *     ab_ob: (ha - hb)(y - hb);  vb: vb;  va: va;  r: r
+ *     eb2: (hb - xt)(hb - xt);  ea2: (ha - xt)(ha - xt);  both sums +0 when has_truth is 0
+ *   (sum_oa_ob / sum_r is the ratio of Desroziers et al. 2005, 1 for consistent error statistics.)
+ *   Errors, all before anything is enqueued: those of csim_ensemble_assimilate for inflation, truth_member and M;
+ *   CSIM_ERR_ARG for a network of another ensemble and record not 0 / 1; CSIM_ERR_STATE when the network has no values
+ *   yet, and with record = 1 when the log is full or log_cycles is 0.  Values stay valid until they are replaced.
+ * fetch: synchronises the ensemble's stream; y, truth (= xt; CSIM_ERR_STATE when has_truth is 0) and bg_mean, bg_var,
+ *   post_mean, post_var (hb, vb, ha, va of the last recorded analysis; CSIM_ERR_STATE when there is none), nobs values
+ *   each in input order.  Any pointer may be NULL.
+ * log: synchronises; out gets min(max, cycles) records, oldest first; *ncycles (may be NULL) the number recorded since
+ *   create or the last reset.  log_reset is enqueued. */
+typedef struct csim_obs_network csim_obs_network;
+int csim_obs_network_create(csim_ensemble* e, int nobs, const int* i, const int* j, const double* r, double loc,
+                            int ordered, int log_cycles, csim_obs_network** out);
+int csim_obs_network_destroy(csim_obs_network* n);
+int csim_obs_network_info(const csim_obs_network* n, int* nobs, int* nlevels, int* lx, int* ly);
+int csim_obs_network_set_values(csim_obs_network* n, const double* y);
+int csim_obs_network_observe(csim_obs_network* n, int source_member, unsigned long long seed, unsigned draw,
+                             int noise);
+/* host-only: z_o of observe */
+int csim_obs_noise(unsigned long long seed, unsigned draw, unsigned o, double* z);
+int csim_ensemble_assimilate_network(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
+                                     int record);
+int csim_obs_network_fetch(csim_obs_network* n, double* y, double* truth, double* bg_mean, double* bg_var,
+                           double* post_mean, double* post_var);
+typedef struct csim_obs_cycle {
+    double n, has_truth, sum_ob, sum_ob2, sum_oa, sum_oa2, sum_oa_ob, sum_ab_ob, sum_vb, sum_va, sum_r, sum_eb2,
+        sum_ea2;
+} csim_obs_cycle;
+int csim_obs_network_log(csim_obs_network* n, int max, csim_obs_cycle* out, int* ncycles);
+int csim_obs_network_log_reset(csim_obs_network* n);
 /* options (unknown keys: CSIM_ERR_ARG; "contract": CSIM_ERR_UNSUPPORTED), results never depend on them:
  *   "fuse"        -1 (default) passes of the ensemble depth where the grid allows; 0 / 1 single steps only
  *   "fused_2c"    0/1 (default 1), as for csim_stepper_set_option
