@@ -1,6 +1,6 @@
 // api.cpp — the C ABI of include/csim.h, part 1: library / device, host-side scalars, MPI-free decomposition,
 // the exchange plan, the device Field mirror and the reference-granularity operators.  (The time-loop stepper:
-// stepper.cpp, passes.cpp, planner.cpp, profile.cpp; kernels: kernels.hip.)  Compiled with hipcc; host code only.
+// stepper.cpp, passes.cpp, planner.cpp, profile.cpp; kernels: kernels.hip, sweepO.hpp, sweep_core.hpp.)  Compiled with hipcc; host code only.
 #include "stepper.hpp"
 
 namespace csim {

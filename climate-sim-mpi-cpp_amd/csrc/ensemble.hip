@@ -1,12 +1,12 @@
-// ensemble.hip — gfx950 kernels of the batched stepper (csim_ensemble_*, host side in ensemble.cpp).
+// ensemble.hip — gfx950 kernels of the batched stepper (csim_ensemble_*; host side: ensemble.cpp and the units behind
+// ensemble_host.hpp).
 //
 // Many small members fill the GPU together: every launch below covers all members (the multi-step sweep: all
 // members of one upwind-sign class), so a pass costs the same few launches whatever B is.  The multi-step sweep
-// shares the single stepper's march (sweepO_march and its edge bodies, kernels.hip) — this file includes the device
-// part of kernels.hip and only adds the member indexing around it.  Every member is a single-rank field with four
+// shares the single stepper's march (sweepO_march and its edge bodies: sweep_core.hpp, the only part of the sweep
+// this file includes) and adds the member indexing around it.  Every member is a single-rank field with four
 // physical sides: the edge bodies do the boundary work inside the pass, nothing is exchanged.
-#define CSIM_SWEEP_CORE_ONLY
-#include "kernels.hip"
+#include "sweep_core.hpp"
 
 #include "ensemble.hpp"
 
@@ -237,7 +237,7 @@ hipError_t ens_sweepO_div(const EnsGeom& g, const double* in, double* out, const
     int ry = 64;
     while (ry > 6 && static_cast<long>(count) * a.nstrips * cdivl(g.ny, ry) < 8192) ry >>= 1;
     if (ry < 6) ry = 6;
-    ry += (6 - (ry + 2 * (T - 1)) % 6) % 6;  // whole groups of six march iterations
+    ry = whole_groups<T>(ry);  // whole groups of six march iterations
     if (ry > g.ny) ry = g.ny;
     a.ry = ry;
     a.nchunks = cdivl(g.ny, ry);

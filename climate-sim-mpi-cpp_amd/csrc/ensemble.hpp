@@ -46,7 +46,7 @@ size_t ens_entry_bytes();
 void ens_entry_fill(void* host_entry, const Phys& p, double* const fin_lines[4]);
 
 // T = ENS_DEPTH steps of the members members[0 .. count) (all of one sign class `cls`) in one launch;
-// fin: last pass of a run, the members' FinLines are written (see FinLines in kernels.hip)
+// fin: last pass of a run, the members' FinLines are written (see FinLines in sweep_core.hpp)
 hipError_t ens_launch_sweepO(const EnsGeom& g, const double* in, double* out, const void* table, const int* members,
                              int count, int cls, bool fin, hipStream_t st);
 // one step of every member

@@ -1,4 +1,4 @@
-// ensemble_assim.hip — the analysis of csim_ensemble_assimilate (host side in ensemble.cpp): the serial ensemble
+// ensemble_assim.hip — the analysis of csim_ensemble_assimilate (host side in ensemble_da.cpp): the serial ensemble
 // square-root filter of csim.h, localised with the host's Gaspari-Cohn table.  Needs only the slab layout of
 // ensemble.hpp.
 //

@@ -1,4 +1,4 @@
-// ensemble_perturb.hip — the kernel of csim_ensemble_perturb (host side in ensemble.cpp): x_k += sigma p_k on every
+// ensemble_perturb.hip — the kernel of csim_ensemble_perturb (host side in ensemble_da.cpp): x_k += sigma p_k on every
 // interior cell of the forecast members, p_k a smoothed white-noise field that is a pure function of (seed, draw,
 // member, cell), as include/csim.h defines it.  Needs only the slab layout of ensemble.hpp and ensemble_noise.hpp.
 //

@@ -1,6 +1,6 @@
 // ensemble_quantiles.hip — per-cell quantiles and exceedance probabilities over the members of an ensemble
-// (csim_ensemble_quantiles*, host side in ensemble.cpp).  Needs only the slab layout of ensemble.hpp, not the sweep core
-// of kernels.hip.
+// (csim_ensemble_quantiles*, host side in ensemble_diag.cpp).  Needs only the slab layout of ensemble.hpp, not the sweep core
+// (sweep_core.hpp).
 //
 // For every cell of the reference layout (ny+2) x (nx+2), ghost ring included, with s the members' values in ascending
 // order and (lo, hi, g) numpy's "linear" plan of a level (csim_ensemble_quantile_plan, made on the host):

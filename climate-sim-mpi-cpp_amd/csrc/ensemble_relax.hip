@@ -1,5 +1,5 @@
 // ensemble_relax.hip — the relaxation inflation of csim_ensemble_prior_capture / csim_ensemble_relax (host side in
-// ensemble.cpp): relaxation to prior spread (RTPS) and to prior perturbations (RTPP), the block in csim.h.  Needs
+// ensemble_da.cpp): relaxation to prior spread (RTPS) and to prior perturbations (RTPP), the block in csim.h.  Needs
 // only the slab layout of ensemble.hpp.
 //
 // Every kernel: one lane per interior cell, numbered row by row, lanes along i, so each member's load coalesces.

@@ -1,5 +1,5 @@
 // ensemble_stats.hip — per-cell statistics over the members of an ensemble (csim_ensemble_stats*, host side in
-// ensemble.cpp).  Needs only the slab layout of ensemble.hpp, not the sweep core of kernels.hip.
+// ensemble_diag.cpp).  Needs only the slab layout of ensemble.hpp, not the sweep core (sweep_core.hpp).
 //
 // For every cell of the reference layout (ny+2) x (nx+2), ghost ring included, with x_k member k's value:
 //   s = +0; s = s + x_k (k = 0 .. B-1);  mean = s / B                  (IEEE division)

@@ -1,5 +1,5 @@
 // ensemble_verify.hip — verification of an ensemble against one truth per cell (csim_ensemble_verify*, host side in
-// ensemble.cpp): per-cell CRPS and Brier scores, the rank histogram and the domain scores, from one read of the
+// ensemble_diag.cpp): per-cell CRPS and Brier scores, the rank histogram and the domain scores, from one read of the
 // members.  Needs only the slab layout of ensemble.hpp and the sorting networks of ensemble_sort.hpp.
 //
 // M forecast members x_k and the truth y per cell (csim.h has the whole definition).  Forecast member k is member

@@ -75,14 +75,14 @@ struct SweepCfg {
     int* rows_used = nullptr;  // out: chunk height of the last whole-field / bulk launch (option "last_rows")
 };
 
-// ---- kernel launchers (kernels.hip) --------------------------------------------------------
+// ---- kernel launchers (kernels.hip; launch_sweepO's templates: sweepO.hpp) -----------------
 // All pointers are device pointers in the padded layout above.
 hipError_t launch_sweep(const double* in, double* out, int nx, int ny, int pitch, const Phys& p,
                         const SweepCfg& cfg, hipStream_t st);
 // T = 2..7 fused time steps per pass (overlapped strips).  kind[s] = CSIM_BC_* on physical sides, 3 on
 // neighbour sides; part: 0 = every tile, 1 = frame tiles only, 2 = all but the frame tiles.
 // fin_lines (last pass of a run, all four or nullptr): per side the level T-1 line the final ghost
-// fill needs — see FinLines in kernels.hip
+// fill needs — see FinLines in sweep_core.hpp
 // part 3 = frame and bulk in ONE grid (frame tiles dispatched first); with `sync` the frame wavefronts
 // count themselves on sync->counter and the last one stores sync->pass into sync->flag (signal memory a
 // stream can wait on with hipStreamWaitValue64), see k_sweepO_dpp

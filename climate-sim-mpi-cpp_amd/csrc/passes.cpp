@@ -393,7 +393,7 @@ int tune_rows(csim_stepper* s, const Phys& p, int T, bool preferred_depth) {
 }  // namespace csim
 
 // Which arithmetic flavour of the multi-step sweep these parameters select (read-only options "fused_2c_active",
-// "diffusion_only_active").  v == 0: the screened interior body drops the advection term (kernels.hip, cell) — another
+// "diffusion_only_active").  v == 0: the screened interior body drops the advection term (sweep_core.hpp, cell) — another
 // balance of arithmetic against HBM traffic, so the chunk heights found for the other flavour are not carried over.
 static void note_flavour(csim_stepper* s, const Phys& p) {
     s->fused_2c_active = p.fast_thr > 0.0 && p.div_mode != 3;

@@ -1,5 +1,5 @@
 // stepper.hpp — what the translation units behind include/csim.h share: the stepper handle and the helpers
-// that cross file boundaries.  Layout of the host side of the engine (kernels live in kernels.hip):
+// that cross file boundaries.  Layout of the host side of the engine (kernels live in kernels.hip and sweepO.hpp, over sweep_core.hpp):
 //   api.cpp      library / device, safe_dt, decomposition, exchange plan, Field mirror, reference-granularity operators
 //   stepper.cpp  the stepper handle: create / destroy, communicator, upload / download / snapshots, external halo
 //                transport, reductions, options, timers

@@ -1,0 +1,383 @@
+// sweepO.hpp — k_sweepO_dpp (2-7 steps/pass, overlapped strips, the DEFAULT sweep) around the march of
+// sweep_core.hpp, and its launcher templates sweepO_div / sweepO_T.  sweepO_inst.hip instantiates one depth per
+// translation unit; kernels.hip only declares sweepO_T.  In file order: what the kernel alone needs (face stores,
+// the CSIM_TRACE hook of tools/wavetrace.hip), the kernel, the launcher.
+#pragma once
+#include "sweep_core.hpp"
+
+#pragma clang fp contract(off)
+
+namespace csim {
+
+// Direct faces (merged launch): one cell (column i in 0..nx+1, row j in 0..ny+1; 0 and n+1 = ghost lines) of the
+// field a frame tile has just written goes into every face of the NEXT pass it belongs to.  Indexing is
+// k_halo2_pack's for depth H: column faces [c][j] over rows 0..ny+1, row faces [r][i] over columns 0..nx+1 (the
+// ghost entries travel along: Periodic ghosts are never rewritten), corner blocks [r][c] of interior cells.
+__device__ __forceinline__ void face_store_cell(const FrameSync& fs, int i, int j, double v, int nx, int ny) {
+    const int H = fs.face_depth;
+    const unsigned long long bits = static_cast<unsigned long long>(__double_as_longlong(v));
+    auto put = [&](double* face, int idx) {  // write-through, like the tile's own result stores
+        __hip_atomic_store(reinterpret_cast<unsigned long long*>(face + idx), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    const bool in_i = i >= 1 && i <= nx, in_j = j >= 1 && j <= ny;
+    const bool l = in_i && i <= H, r = in_i && i >= nx - H + 1, b = in_j && j <= H, t = in_j && j >= ny - H + 1;
+    const int cl = i - 1, cr = i - (nx - H + 1), rb = j - 1, rt = j - (ny - H + 1);
+    if (l && fs.face[0]) put(fs.face[0], cl * (ny + 2) + j);
+    if (r && fs.face[1]) put(fs.face[1], cr * (ny + 2) + j);
+    if (b && fs.face[2]) put(fs.face[2], rb * (nx + 2) + i);
+    if (t && fs.face[3]) put(fs.face[3], rt * (nx + 2) + i);
+    if (l && b && fs.face[4]) put(fs.face[4], rb * H + cl);
+    if (r && b && fs.face[5]) put(fs.face[5], rb * H + cr);
+    if (l && t && fs.face[6]) put(fs.face[6], rt * H + cl);
+    if (r && t && fs.face[7]) put(fs.face[7], rt * H + cr);
+}
+
+#ifdef CSIM_TRACE
+// tools/wavetrace.hip only: start/end time (100 MHz wall clock) and placement of every wavefront
+__device__ unsigned long long* g_wave_trace = nullptr;
+struct WaveTrace {
+    int slot, lane;
+    unsigned long long t0;
+    __device__ WaveTrace(int s, int l) : slot(s), lane(l), t0(wall_clock64()) {}
+    __device__ ~WaveTrace() {
+        if (lane == 0 && g_wave_trace) {
+            g_wave_trace[3 * slot] = t0;
+            g_wave_trace[3 * slot + 1] = wall_clock64();
+            g_wave_trace[3 * slot + 2] = (static_cast<unsigned long long>(__builtin_amdgcn_s_getreg(63508)) << 32) |
+                                         static_cast<unsigned>(__builtin_amdgcn_s_getreg(63492));
+        }
+    }
+};
+#endif
+
+template <int DIV, int T, int SX, int SY>
+__global__ __launch_bounds__(256) void k_sweepO_dpp(const double* __restrict__ in, double* __restrict__ out, SweepArgs a) {
+    constexpr int TP = OverlapGeom<T>::TP;
+    constexpr int STRIDE = OverlapGeom<T>::STRIDE;
+    const int nx = a.nx, ny = a.ny, pitch = a.pitch, nstrips = a.nstrips;
+    const LateArgs late = LateArgs::get();
+    const int lane = threadIdx.x & 63;
+    // readfirstlane: tells the compiler the wave index (and the strip, edge kinds and row range
+    // derived from it) is wave-uniform, so those tests become scalar branches
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+#ifdef CSIM_TRACE
+    WaveTrace trace_scope(blockIdx.x * 4 + wave, lane);
+#endif
+    // blocks [0, frame_blocks): the frame tiles in plain order; the last tail_blocks blocks: the tail tiles in
+    // plain order; the blocks in between own the main tiles, XCD-remapped among themselves
+    int tile;
+    bool frame_tile = false;
+    {
+        const int b = blockIdx.x;
+        if (b < a.tl.frame_blocks) {
+            tile = 4 * b + wave;
+            if (tile >= a.tl.frame_tiles) return;  // padding of the last frame block
+            frame_tile = true;
+        } else {
+            const int lb = b - a.tl.frame_blocks, nb_mid = gridDim.x - a.tl.frame_blocks - a.tl.tail_blocks;
+            tile = a.tl.frame_tiles + (lb < nb_mid ? xcd_remap(lb, nb_mid, a.swz) : lb) * 4 + wave;
+        }
+    }
+    if (tile >= a.tl.ntiles) return;  // wave-uniform
+    int t0 = 0, strip0 = a.tl.r[0].strip0, nstrip = a.tl.r[0].nstrip, j0 = a.tl.r[0].j0, j1 = a.tl.r[0].j1, ry = a.tl.r[0].ry;
+#pragma unroll
+    for (int q = 1; q < 8; ++q)
+        if (q < a.tl.nregions && tile >= a.tl.r[q - 1].t_end) {
+            t0 = a.tl.r[q - 1].t_end;
+            strip0 = a.tl.r[q].strip0, nstrip = a.tl.r[q].nstrip, j0 = a.tl.r[q].j0, j1 = a.tl.r[q].j1, ry = a.tl.r[q].ry;
+        }
+    const int local = tile - t0;
+    const int strip = strip0 + local % nstrip;
+    const int chunk = local / nstrip;
+    const bool first = strip == 0, last = strip == nstrips - 1;
+    const int jb = j0 + chunk * ry;
+    const int je = min(jb + ry - 1, j1);
+    const int g0 = strip * STRIDE - TP;
+    // a strip meets the left ghost column iff it is the first one; the right ghost column (index
+    // nx) lies inside every strip whose 128 loaded columns reach it
+    const int kl = first ? a.bc.kind[CSIM_LEFT] : 3;
+    const int kr = g0 + WAVE_COLS > nx ? a.bc.kind[CSIM_RIGHT] : 3;
+    const int kb = a.bc.kind[CSIM_BOTTOM], kt = a.bc.kind[CSIM_TOP];
+    // on the last pass of a run the frame tiles also take the edge body: they emit the FinLines
+    const bool fin_frame = a.fin.line[CSIM_BOTTOM] != nullptr && (first || last || jb == 1 || je == ny);
+    const bool edge = kl != 3 || kr != 3 || (kb != 3 && jb - (T - 1) < 1) || (kt != 3 && je + (T - 1) > ny) || fin_frame;
+    if (frame_tile && a.fs.prio) __builtin_amdgcn_s_setprio(3);  // the faces wait for these: issue ahead of the co-resident bulk
+    const bool signalling = frame_tile && a.fs.flag != nullptr;  // merged launch: this wavefront counts itself below
+    const bool wt = signalling && a.fs.fence == 0;
+    if (edge) {
+        // Edge wavefronts run a little longer than interior ones and would finish last, leaving the rest of the chip
+        // idle (29 % of a 4096 x 8192 launch with round 1's edge body, tools/wavetrace.hip): give them issue priority.
+        __builtin_amdgcn_s_setprio(3);
+        const bool rows = (kb != 3 && jb - (T - 1) < 1) || (kt != 3 && je + (T - 1) > ny);
+        int col_case = 0;
+        if (kl != 3 && kr != 3)
+            col_case = 7;
+        else if (kl != 3)
+            col_case = kl == CSIM_BC_NEUMANN ? 2 : 1;
+        else if (kr != 3)
+            col_case = (kr == CSIM_BC_NEUMANN ? 5 : 3) + (nx & 1);  // g0 is even: the right ghost column is a .x iff nx is even
+        if (!SPECIALISE_EDGES<DIV, T>::value || rows || col_case == 7) col_case = -1;
+#define CSIM_MARCH(MODE_) \
+    sweepO_march<DIV, T, MODE_, SX, SY>(in, out, nx, ny, pitch, jb, je, g0, lane, kl, kr, a.p, kb, kt, late, fin_frame, first, last, wt)
+        switch (col_case) {
+            case 0: if (SPECIALISE_EDGES<DIV, T>::value) CSIM_MARCH(0); break;
+            case 1: if (SPECIALISE_EDGES<DIV, T>::value) CSIM_MARCH(1); break;
+            case 2: if (SPECIALISE_EDGES<DIV, T>::value) CSIM_MARCH(2); break;
+            case 3: if (SPECIALISE_EDGES<DIV, T>::value) CSIM_MARCH(3); break;
+            case 4: if (SPECIALISE_EDGES<DIV, T>::value) CSIM_MARCH(4); break;
+            case 5: if (SPECIALISE_EDGES<DIV, T>::value) CSIM_MARCH(5); break;
+            case 6: if (SPECIALISE_EDGES<DIV, T>::value) CSIM_MARCH(6); break;
+            default: CSIM_MARCH(M_GENERIC); break;
+        }
+    } else {
+        bool redo = true;
+        if (DIV != 3 && a.p.fast_thr > 0.0) redo = CSIM_MARCH(M_FAST);
+        if (redo) {
+            keep_branch();
+            CSIM_MARCH(M_PLAIN);
+        }
+    }
+#undef CSIM_MARCH
+    if (signalling) {
+        // Merged launch: the comm stream is parked on `flag` (hipStreamWaitValue64) and goes on to pack and
+        // send the next pass's faces as soon as EVERY frame tile is in memory — while this very kernel is
+        // still sweeping the bulk.  The consumers are later kernels on another stream and may run on any XCD,
+        // so a frame tile's outputs must be in memory, not in this XCD's write-back L2, before it counts
+        // itself: its result stores are write-through (store_pair_wt) and only have to be drained here.  (An
+        // agent-scope release fence, i.e. buffer_wbl2 per wavefront, also works but writes back the dirty
+        // output lines of the whole bulk each time: measured +40 us per 165 us pass; kept as fence = 1.)  The
+        // wavefront that completes the count re-arms the counter and publishes the pass number (system scope:
+        // the waiting side reads it through the command processor).
+        // Everything from here on is read from the kernel-argument segment NOW (LateArgs): nothing of FrameSync was
+        // alive during the march.
+        const LateArgs::Ptr ka = late.here();
+        FrameSync fs;
+        fs.counter = ka->fs.counter, fs.flag = ka->fs.flag, fs.pass = ka->fs.pass, fs.nframe = ka->fs.nframe;
+        fs.fence = ka->fs.fence, fs.face_depth = ka->fs.face_depth;
+#pragma unroll
+        for (int d = 0; d < 8; ++d) fs.face[d] = ka->fs.face[d];
+        if (fs.fence == 0)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (fs.fence == 0 && fs.face_depth > 0) {
+            // Direct faces: this wavefront copies the part of its tile that belongs to a face of the NEXT pass
+            // (and the ghost entries beside it) into the send buffers, so the comm stream can post the RCCL
+            // group at the flag without a pack kernel in between.  Done after the march by reading the tile
+            // back (its stores are drained and written through; the loads bypass the vector L1): the same
+            // stores inside the march loop cost 20 more VGPRs, i.e. one wavefront per SIMD.
+            const int H = fs.face_depth;
+            const int gx = g0 + 2 * lane;
+            const bool out_lane = 2 * lane >= TP && 2 * lane < TP + STRIDE && gx < nx;
+            const bool rows_near = jb <= H || je >= ny - H + 1;              // wave-uniform
+            const bool cols_near = g0 + TP < H || g0 + TP + STRIDE > nx - H;  // wave-uniform
+            if (rows_near || cols_near) {
+                const int jf0 = jb == 1 ? 0 : jb, jf1 = je == ny ? ny + 1 : je;
+                auto ldf = [&](const double* q) {
+                    return __longlong_as_double(static_cast<long long>(__hip_atomic_load(
+                        reinterpret_cast<const unsigned long long*>(q), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
+                };
+                for (int rho = jf0; rho <= jf1; ++rho) {
+                    if (!out_lane) continue;
+                    const double* src = out + static_cast<ptrdiff_t>(rho) * pitch + LPAD + gx;  // cell (gx + 1, rho)
+                    face_store_cell(fs, gx + 1, rho, ldf(src), nx, ny);
+                    if (gx + 1 < nx) face_store_cell(fs, gx + 2, rho, ldf(src + 1), nx, ny);
+                    if (gx == 0) face_store_cell(fs, 0, rho, ldf(src - 1), nx, ny);
+                    if (gx + 1 == nx) face_store_cell(fs, nx + 1, rho, ldf(src + 1), nx, ny);
+                    if (gx + 2 == nx) face_store_cell(fs, nx + 1, rho, ldf(src + 2), nx, ny);
+                }
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+        }
+        if (fs.fence == 1) __threadfence();  // plain result stores + agent-scope fence per wavefront (measured alternative)
+        // Ordering (ISA level; no C++ happens-before is claimed): every store of this wavefront that a consumer may
+        // read — tile results and face copies — is an agent-scope write-through store (global_store ... sc1), and the
+        // s_waitcnt vmcnt(0) above returns only once each of them has been acknowledged by memory.  The counter
+        // increment below is therefore issued after the data is globally visible; it can be relaxed, because the only
+        // thing ordered after it is the flag store of the LAST arriver, and that wavefront's own data was drained by
+        // its own s_waitcnt before its own increment — the increments of the others precede it in the counter's
+        // modification order, each issued after that wavefront's drain.  The flag itself is a system-scope release
+        // store; the waiting side is the command processor (hipStreamWaitValue64), and every kernel launched behind the
+        // wait begins with the usual acquire (L2 invalidate / write-back state of a kernel boundary).
+        if (lane == 0) {
+            const unsigned done = atomicAdd(fs.counter, 1u);
+            if (done == fs.nframe - 1) {
+                atomicExch(fs.counter, 0u);
+                __hip_atomic_store(fs.flag, fs.pass, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+    }
+}
+
+// ============================================================================================
+// launcher of the overlapped-strip sweep (templates: one depth per translation unit, see sweepO_inst.hip)
+// ============================================================================================
+
+template <int DIV, int T>
+hipError_t sweepO_div(const double* in, double* out, int nx, int ny, int pitch, const Phys& p,
+                             const SweepCfg& cfg, const Bc2& bc, const FinLines& fin, int part, hipStream_t st,
+                             FrameSync fs) {
+    constexpr int STRIDE = OverlapGeom<T>::STRIDE;
+    const int nstrips = cdiv(nx, STRIDE);
+    int ry = cfg.rows_per_chunk;
+    if (ry <= 0) {
+        if (cfg.tuned_rows > 0) {
+            ry = cfg.tuned_rows;
+        } else {
+            ry = 64;
+            while (ry > 16 && static_cast<long>(nstrips) * cdiv(ny, ry) < 8192) ry >>= 1;
+            // tiles too small for the on-device trial (< 4 M cells): a launch is at most a round or two of
+            // wavefronts and the length of a wavefront's march decides — the shortest chunks win although
+            // they double the overhead rows (512^2: +52 %, 1024^2: +37 %, 2048^2: +25 % against 18 rows)
+            if (static_cast<long>(nx) * ny < (1L << 22)) ry = 6;
+        }
+        // the march runs whole groups of six iterations: make ry + 2 (T - 1) a multiple of six so
+        // that only a ragged last chunk computes surplus rows
+        ry = whole_groups<T>(ry);
+    }
+    if (ry > ny) ry = ny;
+    if (cfg.rows_used && part != 1) *cfg.rows_used = ry;
+    // part 0: the whole field.  part 1 / 2 (multi-rank pass): FRAME / BULK.  The frame is the
+    // bottom and top bands (hf rows, all strips) plus the first strip and the last one or two
+    // strips (>= MAX_FUSE columns) over the rows in between, in chunks of hf rows: thin tiles,
+    // one short round of wavefronts, so the faces are ready ~15 us into the pass.
+    const int hf = whole_groups<T>(12);  // >= the deepest face (8-row bands were measured slower: more, even thinner tiles)
+    const int nright = (nx - (nstrips - 1) * STRIDE >= MAX_FUSE) ? 1 : 2;
+    const bool split = ny >= 2 * hf + 1 && nstrips >= nright + 2;
+    // A band along a PHYSICAL bottom / top edge runs the generic edge body (ghost rows), about twice as slow per
+    // iteration as the other frame tiles, and the frame launch lasts as long as its slowest tile (47 us instead of 34 on
+    // a 4096 x 8192 tile with one physical side): such a band is only as high as the ghost rows require (T-1 rows,
+    // rounded so that its march is whole groups of six: 18 iterations at T = 7 instead of 24).  The tiles above it then
+    // start at row T and read the ghost row itself as level-0 input — in a bulk-first pass BEFORE this pass's ghost
+    // fill has run: fine for Dirichlet and Periodic sides, whose ghost ring never changes, not for Neumann ones, which
+    // keep the band of hf >= T rows.
+    const int hphys = whole_groups<T>(T - 1);
+    auto thin = [&](int side) {
+        return SPECIALISE_EDGES<DIV, T>::value && bc.kind[side] != 3 && bc.kind[side] != CSIM_BC_NEUMANN;
+    };
+    const int hfb = thin(CSIM_BOTTOM) ? std::min(hf, hphys) : hf;
+    const int hft = thin(CSIM_TOP) ? std::min(hf, hphys) : hf;
+    Tiling tl{};
+    auto add = [&](int strip0, int nstrip, int j0, int j1, int rows) {
+        if (nstrip <= 0 || j1 < j0) return;
+        TileRegion& r = tl.r[tl.nregions++];
+        r.strip0 = strip0, r.nstrip = nstrip, r.j0 = j0, r.j1 = j1, r.ry = rows;
+        tl.ntiles += nstrip * cdiv(j1 - j0 + 1, rows);
+        r.t_end = tl.ntiles;
+    };
+    // rows j0..j1 of `nstrip` strips: full-height chunks, or — on launches of two or more rounds of wavefronts —
+    // a main region of 7/8 of the chunks (a multiple of four, so that its tiles fill whole blocks whatever the
+    // number of strips) followed by a tail region at half the height; returns the tail tiles
+    auto add_rows = [&](int strip0, int nstrip, int j0, int j1, int rows) -> int {
+        const int nrows = j1 - j0 + 1;
+        if (nstrip <= 0 || nrows <= 0) return 0;
+        const int nchunks = cdiv(nrows, rows);
+        if (!cfg.tail_split || rows < 48 || nchunks < 16 || static_cast<long>(nstrip) * nchunks < 8192) {
+            add(strip0, nstrip, j0, j1, rows);
+            return 0;
+        }
+        const bool two_level = cfg.tail_split != 2;  // default: 7/8 of the chunks full height + the rest at half height;
+                                                     // 2 (experiment): 3/4 + half + quarter height — measured no better
+        const int main_chunks = (nchunks * (two_level ? 7 : 3) / (two_level ? 8 : 4)) / 4 * 4;
+        const int j_main = j0 + main_chunks * rows - 1;
+        const int half = whole_groups<T>(rows / 2), quarter = whole_groups<T>(rows / 4);
+        const int rest = j1 - j_main;                       // rows left for the tail regions
+        const int j_half = two_level ? j1 : j_main + (rest * 2 / 3) / half * half;  // about two thirds of them at half height
+        add(strip0, nstrip, j0, j_main, rows);
+        const int before = tl.ntiles;
+        add(strip0, nstrip, j_main + 1, j_half, half);
+        add(strip0, nstrip, j_half + 1, j1, quarter);
+        return tl.ntiles - before;
+    };
+    int tail_tiles = 0;
+    if (part == 0 || ((part == 1 || part == 3) && !split)) {
+        // Physical bottom / top edges: the rows whose chunks can produce ghost ROWS of the intermediate levels (the
+        // first and last T-1) go into thin bands of their own, so that only those few short tiles run the generic
+        // edge body and every other tile of the first / last strips a straight-line column flavour (sweepO_march).
+        // The bands come last in the tile order, with the tail region: they are the shortest tiles of the launch.
+        const int hb = whole_groups<T>(T - 1);
+        const bool bands = SPECIALISE_EDGES<DIV, T>::value && ny >= 2 * hb + 6;
+        const bool band_b = bands && bc.kind[CSIM_BOTTOM] != 3, band_t = bands && bc.kind[CSIM_TOP] != 3;
+        tail_tiles = add_rows(0, nstrips, band_b ? hb + 1 : 1, band_t ? ny - hb : ny, ry);
+        const int before = tl.ntiles;
+        if (band_b) add(0, nstrips, 1, hb, hb);
+        if (band_t) add(0, nstrips, ny - hb + 1, ny, hb);
+        tail_tiles += tl.ntiles - before;
+    } else if (part == 1 || part == 3) {
+        add(0, nstrips, 1, hfb, hfb);
+        add(0, nstrips, ny - hft + 1, ny, hft);
+        int hs = hf;  // side strips: taller chunks waste fewer warm-up rows (2 (T - 1) per chunk) but finish later
+        if (cfg.frame_rows >= MAX_FUSE) hs = whole_groups<T>(cfg.frame_rows);
+        add(0, 1, hfb + 1, ny - hft, hs);
+        add(nstrips - nright, nright, hfb + 1, ny - hft, hs);
+    }
+    int nblocks;
+    if (part == 3 && split) {  // merged launch: the frame tiles above, then the bulk in the same grid
+        tl.frame_tiles = tl.ntiles;
+        tl.frame_blocks = cdiv(tl.ntiles, 4);
+        fs.nframe = static_cast<unsigned>(tl.frame_tiles);
+        const int before = tl.ntiles;
+        tail_tiles = add_rows(1, nstrips - 1 - nright, hfb + 1, ny - hft, std::min(ry, ny - hfb - hft));
+        nblocks = tl.frame_blocks + cdiv(tl.ntiles - before, 4);
+    } else if (part == 3) {  // a tile that is all frame: every tile counts for the flag
+        tl.frame_tiles = tl.ntiles;
+        tl.frame_blocks = cdiv(tl.ntiles, 4);
+        tl.tail_blocks = 0;
+        tail_tiles = 0;
+        fs.nframe = static_cast<unsigned>(tl.frame_tiles);
+        nblocks = tl.frame_blocks;
+    } else {
+        if (part == 2 && split) tail_tiles = add_rows(1, nstrips - 1 - nright, hfb + 1, ny - hft, std::min(ry, ny - hfb - hft));
+        if (tl.ntiles == 0) return hipSuccess;  // part 2 of a field that is all frame
+        nblocks = cdiv(tl.ntiles, 4);
+        fs = FrameSync{};
+    }
+    tl.tail_blocks = cdiv(tail_tiles, 4);
+    const dim3 grid(nblocks), block(256);
+    const int sw = cfg.xcd_swizzle;
+    SweepArgs ka;
+    ka.nx = nx, ka.ny = ny, ka.pitch = pitch, ka.nstrips = nstrips, ka.swz = sw;
+    ka.tl = tl, ka.p = p, ka.bc = bc, ka.fin = fin, ka.fs = fs;
+#define CSIM_LAUNCH_O(SXV, SYV) \
+    hipLaunchKernelGGL((k_sweepO_dpp<DIV, T, SXV, SYV>), grid, block, cfg.lds_bytes, st, in, out, ka)
+#ifdef CSIM_ISA_PROBE
+    CSIM_LAUNCH_O(1, 1);
+#else
+    if (DIV == 3) {  // coefficient form: the upwind directions are folded into the coefficients
+        CSIM_LAUNCH_O(1, 1);
+    } else {
+        // zero velocity components (DIV 0 / 1; the IEEE-division form keeps its four sign flavours): code 2 per axis
+        const bool screened = DIV <= 1 && p.fast_thr > 0.0;
+        const int cx = screened && p.vx == 0.0 ? 2 : (p.vx >= 0.0 ? 1 : 0), cy = screened && p.vy == 0.0 ? 2 : (p.vy >= 0.0 ? 1 : 0);
+        switch (3 * cx + cy) {
+            case 8: if constexpr (DIV <= 1) CSIM_LAUNCH_O(2, 2); break;
+            case 7: if constexpr (DIV <= 1) CSIM_LAUNCH_O(2, 1); break;
+            case 6: if constexpr (DIV <= 1) CSIM_LAUNCH_O(2, 0); break;
+            case 5: if constexpr (DIV <= 1) CSIM_LAUNCH_O(1, 2); break;
+            case 2: if constexpr (DIV <= 1) CSIM_LAUNCH_O(0, 2); break;
+            case 4: CSIM_LAUNCH_O(1, 1); break;
+            case 3: CSIM_LAUNCH_O(1, 0); break;
+            case 1: CSIM_LAUNCH_O(0, 1); break;
+            default: CSIM_LAUNCH_O(0, 0); break;
+        }
+    }
+#endif
+#undef CSIM_LAUNCH_O
+    return hipGetLastError();
+}
+
+template <int T>
+hipError_t sweepO_T(const double* in, double* out, int nx, int ny, int pitch, const Phys& p,
+                           const SweepCfg& cfg, const Bc2& bc, const FinLines& fin, int part, hipStream_t st,
+                           const FrameSync& fs) {
+#ifdef CSIM_ISA_PROBE  // tools: only the instantiation bench.py runs (dx = dy = 1, vx, vy >= 0), for a readable listing
+    return sweepO_div<0, T>(in, out, nx, ny, pitch, p, cfg, bc, fin, part, st, fs);
+#else
+    switch (p.div_mode) {
+        case 0: return sweepO_div<0, T>(in, out, nx, ny, pitch, p, cfg, bc, fin, part, st, fs);
+        case 1: return sweepO_div<1, T>(in, out, nx, ny, pitch, p, cfg, bc, fin, part, st, fs);
+        case 3: return sweepO_div<3, T>(in, out, nx, ny, pitch, p, cfg, bc, fin, part, st, fs);
+        default: return sweepO_div<2, T>(in, out, nx, ny, pitch, p, cfg, bc, fin, part, st, fs);
+    }
+#endif
+}
+
+}  // namespace csim

@@ -1,0 +1,14 @@
+// sweepO_inst.hip — one depth of the overlapped-strip sweep: sweepO.hpp plus the explicit instantiation of
+// sweepO_T<CSIM_INST_T>.  Built six times (csrc/Makefile, -DCSIM_INST_T=2..7) in parallel with kernels.hip.
+#ifndef CSIM_INST_T
+#error "sweepO_inst.hip is compiled with -DCSIM_INST_T=<2..7>, once per depth of the fused sweep"
+#endif
+#include "sweepO.hpp"
+
+namespace csim {
+
+template hipError_t sweepO_T<CSIM_INST_T>(const double* in, double* out, int nx, int ny, int pitch, const Phys& p,
+                                    const SweepCfg& cfg, const Bc2& bc, const FinLines& fin, int part, hipStream_t st,
+                                    const FrameSync& fs);
+
+}  // namespace csim

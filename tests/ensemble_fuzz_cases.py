@@ -17,7 +17,7 @@ VX_SET = [0.0, -0.0, 0.5, -0.5, 0.25, -1.0]
 VY_SET = [0.0, -0.0, 0.25, -0.25, 0.75]
 DT_FRACTION = [0.8, 0.5, 0.2]
 VALUES = [0.0, 1.5, -0.0]
-# output columns per strip of the multi-step sweep at pass depth T (OverlapGeom<T>::STRIDE, kernels.hip)
+# output columns per strip of the multi-step sweep at pass depth T (OverlapGeom<T>::STRIDE, sweep_core.hpp)
 STRIDE = {2: 124, 3: 120, 4: 120, 5: 116, 6: 116, 7: 112}
 
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """tools/isa_summary.py — per-kernel and per-loop instruction census of a gfx950 assembly listing.
 
-  hipcc ... -S --cuda-device-only -o k.s kernels.hip -Rpass-analysis=kernel-resource-usage 2> k.res.txt
+  make -C climate-sim-mpi-cpp_amd/csrc asm [T=7] [ISA_PROBE=1]    (hipcc ... -S --cuda-device-only of kernels.hip and of
+  sweepO_inst.hip at depth T with -Rpass-analysis=kernel-resource-usage: kernels.s, sweepO_T7.s and their .resource.txt)
   python tools/isa_summary.py k.s k.res.txt [--kernel SUBSTR] > profiles/rNN_isa_summary.txt
 
 For every kernel whose mangled name contains SUBSTR: VGPRs / SGPR spills / occupancy from the resource remarks, and for

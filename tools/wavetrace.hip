@@ -5,6 +5,7 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DCSIM_TRACE \
 //              -I../include -I../climate-sim-mpi-cpp_amd/csrc -o wavetrace wavetrace.hip
 // Usage: ./wavetrace NX NY T RY [reps] [boundary kind: 0 dirichlet, 1 neumann, 2 periodic, 3 none]
+#include "../climate-sim-mpi-cpp_amd/csrc/sweepO.hpp"  // every depth of the fused sweep, in this one unit
 #include "../climate-sim-mpi-cpp_amd/csrc/kernels.hip"
 
 #include <cstdlib>
