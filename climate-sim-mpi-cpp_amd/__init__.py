@@ -213,6 +213,11 @@ def lib() -> C.CDLL:
         "csim_obs_network_fetch": (i, [vp, dp, dp, dp, dp, dp, dp]),
         "csim_obs_network_log": (i, [vp, i, C.POINTER(CsimObsCycle), ip]),
         "csim_obs_network_log_reset": (i, [vp]),
+        "csim_obs_network_create_linear": (i, [vp, i, ip, ip, ip, ip, ip, dp, dp, d, i, i, C.POINTER(vp)]),
+        "csim_obs_network_taps": (i, [vp, ip]),
+        "csim_obs_linear_check": (i, [i, i, i, i, i, ip, ip, ip, ip, ip, dp]),
+        "csim_obs_taps_bilinear": (i, [i, i, d, d, ip, ip, ip, ip, dp]),
+        "csim_obs_taps_box": (i, [i, i, i, i, i, i, ip, ip, ip, dp]),
         "csim_ensemble_set_option": (i, [vp, C.c_char_p, C.c_long]),
         "csim_ensemble_get_option": (i, [vp, C.c_char_p, C.POINTER(C.c_long)]),
         "csim_ensemble_plan": (i, [i, i, i, i, ip]),
@@ -723,6 +728,75 @@ def obs_noise(seed, draw, o):
     return out if out.ndim else float(out)
 
 
+OBS_MAX_TAPS = 64  # CSIM_OBS_MAX_TAPS
+ObsTaps = collections.namedtuple("ObsTaps", "start di dj w")
+ObsTaps.__doc__ = """the taps of linear observations (csim_obs_network_create_linear): observation o observes
+sum_s w[s] x(i[o] + di[s], j[o] + dj[s]) over s = start[o] .. start[o + 1] - 1"""
+
+
+def _taps(taps, n):
+    """(start, di, dj, w) as contiguous arrays of the C types; start has n + 1 values, the others start[n] each"""
+    start, di, dj, w = taps
+    start = _ints(start, n + 1)
+    di, dj = _ints(di), _ints(dj)
+    w = np.ascontiguousarray(np.atleast_1d(np.asarray(w, dtype=np.float64)))
+    # the library checks start itself, before it reads a tap; where start is in order the arrays must be as long as
+    # it says
+    in_order = start[0] == 0 and np.all(np.diff(start) >= 0)
+    if not (len(di) == len(dj) == len(w)) or (in_order and len(w) != start[-1]):
+        raise ValueError("taps: di, dj and w need start[-1] values each")
+    return ObsTaps(start, di, dj, w)
+
+
+def obs_linear_check(nx, ny, lx, ly, i, j, taps):
+    """raises CsimError unless (i, j, taps) are valid linear observations on an nx x ny grid with localisation
+    half-widths lx, ly (csim_obs_linear_check) — host only"""
+    ii = _ints(i)
+    jj = _ints(j, len(ii))
+    t = _taps(taps, len(ii))
+    _ck(lib().csim_obs_linear_check(int(nx), int(ny), int(lx), int(ly), len(ii), _ip(ii), _ip(jj), _ip(t.start),
+                                    _ip(t.di), _ip(t.dj), _dp(t.w)))
+
+
+def bilinear_taps(nx, ny, x, y):
+    """(i, j, ObsTaps) of bilinear interpolation to the positions (x, y), arrays in cell-index units, 1 <= x <= nx,
+    1 <= y <= ny: four taps per observation (csim_obs_taps_bilinear) — host only"""
+    xx = np.atleast_1d(np.asarray(x, dtype=np.float64))
+    yy = np.atleast_1d(np.asarray(y, dtype=np.float64))
+    if xx.shape != yy.shape or xx.ndim != 1:
+        raise ValueError("x and y must be arrays of one length")
+    n = len(xx)
+    i, j = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+    di, dj, w = np.empty(4 * n, dtype=np.int32), np.empty(4 * n, dtype=np.int32), np.empty(4 * n)
+    ci, cj, cdi, cdj, cw = C.c_int(), C.c_int(), (C.c_int * 4)(), (C.c_int * 4)(), (C.c_double * 4)()
+    fn = lib().csim_obs_taps_bilinear
+    for o in range(n):
+        _ck(fn(int(nx), int(ny), float(xx[o]), float(yy[o]), C.byref(ci), C.byref(cj), cdi, cdj, cw))
+        i[o], j[o] = ci.value, cj.value
+        di[4 * o:4 * o + 4], dj[4 * o:4 * o + 4], w[4 * o:4 * o + 4] = cdi[:], cdj[:], cw[:]
+    return i, j, ObsTaps(np.arange(0, 4 * n + 1, 4, dtype=np.int32), di, dj, w)
+
+
+def box_taps(nx, ny, i, j, a, b):
+    """(i, j, ObsTaps) of the means over the (2a+1) x (2b+1) boxes around the interior cells (i, j), clipped to the
+    interior, at most 64 taps each (csim_obs_taps_box) — host only"""
+    ii = _ints(i)
+    jj = _ints(j, len(ii))
+    start, di, dj, w = [0], [], [], []
+    cn = C.c_int()
+    cdi, cdj, cw = (C.c_int * OBS_MAX_TAPS)(), (C.c_int * OBS_MAX_TAPS)(), (C.c_double * OBS_MAX_TAPS)()
+    fn = lib().csim_obs_taps_box
+    for o in range(len(ii)):
+        _ck(fn(int(nx), int(ny), int(ii[o]), int(jj[o]), int(a), int(b), C.byref(cn), cdi, cdj, cw))
+        k = cn.value
+        di += cdi[:k]
+        dj += cdj[:k]
+        w += cw[:k]
+        start.append(len(w))
+    return ii, jj, ObsTaps(np.array(start, dtype=np.int32), np.array(di, dtype=np.int32), np.array(dj, dtype=np.int32),
+                           np.array(w, dtype=np.float64))
+
+
 ObsNetworkInfo = collections.namedtuple("ObsNetworkInfo", "nobs nlevels lx ly")
 ObsValues = collections.namedtuple("ObsValues", "y truth bg_mean bg_var post_mean post_var")
 ObsValues.__doc__ = """what ObsNetwork.fetch() returns, each per observation in input order or None where the network
@@ -732,18 +806,25 @@ OBS_CYCLE_FIELDS = tuple(k for k, _ in CsimObsCycle._fields_)
 
 
 class ObsNetwork:
-    """point observations that live on the device (csim_obs_network_*): planned once, their values drawn on the GPU
-    from a member or set from the host, read by Ensemble.assimilate_network without staging.  Made by
-    Ensemble.obs_network(); closing the ensemble closes its networks."""
+    """observations that live on the device (csim_obs_network_*): planned once, their values drawn on the GPU
+    from a member or set from the host, read by Ensemble.assimilate_network without staging.  Point observations of
+    the cells (i, j), or with taps = (start, di, dj, w) linear observations anchored there
+    (csim_obs_network_create_linear).  Made by Ensemble.obs_network(); closing the ensemble closes its networks."""
 
-    def __init__(self, ens, i, j, r, loc, ordered=False, log_cycles=0):
+    def __init__(self, ens, i, j, r, loc, ordered=False, log_cycles=0, taps=None):
         ii = _ints(i)
         n = len(ii)
         jj = _ints(j, n)
         rr = np.ascontiguousarray(np.broadcast_to(np.asarray(r, dtype=np.float64), (n,)))
         h = C.c_void_p()
-        _ck(lib().csim_obs_network_create(ens._h, n, _ip(ii), _ip(jj), _dp(rr), float(loc), int(bool(ordered)),
-                                          int(log_cycles), C.byref(h)))
+        if taps is None:
+            _ck(lib().csim_obs_network_create(ens._h, n, _ip(ii), _ip(jj), _dp(rr), float(loc), int(bool(ordered)),
+                                              int(log_cycles), C.byref(h)))
+        else:
+            t = _taps(taps, n)
+            _ck(lib().csim_obs_network_create_linear(ens._h, n, _ip(ii), _ip(jj), _ip(t.start), _ip(t.di), _ip(t.dj),
+                                                     _dp(t.w), _dp(rr), float(loc), int(bool(ordered)),
+                                                     int(log_cycles), C.byref(h)))
         self._h, self._ens, self.nobs = h, ens, n
         ens._nets.add(self)
 
@@ -761,6 +842,13 @@ class ObsNetwork:
         v = [C.c_int() for _ in range(4)]
         _ck(lib().csim_obs_network_info(self._h, *[C.byref(x) for x in v]))
         return ObsNetworkInfo(*[x.value for x in v])
+
+    @property
+    def ntaps(self) -> int:
+        """taps of all observations of a linear network, 0 for point observations (csim_obs_network_taps)"""
+        v = C.c_int()
+        _ck(lib().csim_obs_network_taps(self._h, C.byref(v)))
+        return v.value
 
     def set_values(self, y):
         """the values, one per observation in input order; copied before the call returns, enqueued without waiting"""
@@ -995,11 +1083,12 @@ class Ensemble:
             return nl.value
         return EnsembleAnalysis(nl.value, *outs)
 
-    def obs_network(self, i, j, r, loc, ordered=False, log_cycles=0) -> ObsNetwork:
+    def obs_network(self, i, j, r, loc, ordered=False, log_cycles=0, taps=None) -> ObsNetwork:
         """an observation network on the device: cells (i, j), error variances r (a scalar broadcasts), Gaspari-Cohn
         length loc and the plan of assimilate(), made once; log_cycles: room for that many recorded analyses
-        (csim_obs_network_create)"""
-        return ObsNetwork(self, i, j, r, loc, ordered, log_cycles)
+        (csim_obs_network_create).  taps=(start, di, dj, w), as bilinear_taps() and box_taps() return them: linear
+        observations sum_s w_s x(i + di_s, j + dj_s) anchored at (i, j) (csim_obs_network_create_linear)"""
+        return ObsNetwork(self, i, j, r, loc, ordered, log_cycles, taps)
 
     def assimilate_network(self, net: ObsNetwork, inflation=1.0, truth_member=None, record=False):
         """the analysis of assimilate() with the network's observations, always enqueued without waiting; record=True

@@ -127,8 +127,16 @@ struct AssimArgs {
     double* scal;                 // 3 per plan position: d, alpha, delta
     double* hp;                   // M per observation of the batch: h'_k
     double* prior;                // 2 per input index: hbar, p (null: not wanted)
+    // linear observations (csim_obs_network_create_linear); null / 0: point observations.  Last, so that the
+    // arguments of the point kernels stay where they were
+    const int* tstart;            // plan order, one more than observations: the taps of position q are
+                                  // tstart[q] .. tstart[q + 1] - 1
+    const int* toff;              // per tap: dj * pitch + di, the cell's offset from the anchor in a member's slab
+    const double* tw;             // per tap: w
+    int tmax;                     // the most taps of one observation (sizes the linear prior's LDS tile)
 };
-// the batch's h'_k and scalars, then its window updates; wcells: the largest clipped window of the batch in cells
+// the batch's h'_k and scalars, then its window updates; wcells: the largest clipped window of the batch in cells.
+// With taps (a.tstart) the prior is the linear one: h_k = sum_s w_s x_k(anchor + tap s)
 hipError_t ens_launch_assim_prior(const EnsGeom& g, const double* f, const AssimArgs& a, int first, int count,
                                   hipStream_t st);
 hipError_t ens_launch_assim_update(const EnsGeom& g, double* f, const AssimArgs& a, int first, int count,
@@ -136,7 +144,7 @@ hipError_t ens_launch_assim_update(const EnsGeom& g, double* f, const AssimArgs&
 // x_k <- x_k + lm1 (x_k - xbar) on every interior cell of the forecast members
 hipError_t ens_launch_assim_inflate(const EnsGeom& g, double* f, int forecast, int truth_member, double lm1,
                                     hipStream_t st);
-// the posterior mean and variance at each observation's cell, 2 per input index
+// the posterior mean and variance at each observation's cell (with taps: of its h_k), 2 per input index
 hipError_t ens_launch_assim_post(const EnsGeom& g, const double* f, const AssimArgs& a, int nobs, double* post,
                                  hipStream_t st);
 
@@ -174,6 +182,7 @@ hipError_t ens_launch_relax_pert(const EnsGeom& g, double* f, const double* fb, 
 constexpr int OBS_CHUNK = 256;       // input indices per chunk of the log's sums
 constexpr int OBS_CYCLE_FIELDS = 13; // doubles of a csim_obs_cycle: n, has_truth and the 11 sums
 constexpr int OBS_SUMS = 11;
+constexpr int OBS_MAX_TAPS = 64;     // CSIM_OBS_MAX_TAPS: taps of one linear observation
 struct ObsArgs {
     int nobs;
     const int* i;
@@ -187,8 +196,11 @@ struct ObsArgs {
     const double* bg;             // 2 per input index: hb, vb
     const double* post;           // 2 per input index: ha, va
     double* part;                 // OBS_SUMS per chunk: T_c
+    const int* tstart;            // the taps, as in AssimArgs; null: point observations
+    const int* toff;
+    const double* tw;
 };
-// y and xt of every observation from member `member`; noise: y = xt + sr z, z the deviate of (seed, draw, input index)
+// y and xt of every observation from member `member` (with taps: xt = h of that member); noise: y = xt + sr z, z the deviate of (seed, draw, input index)
 hipError_t ens_launch_obs_observe(const EnsGeom& g, const double* f, const ObsArgs& a, int member, unsigned seed_lo,
                                   unsigned seed_hi, unsigned draw, bool noise, hipStream_t st);
 // the chunk sums T_c, then their fold in chunk order into the record `slot` (OBS_CYCLE_FIELDS doubles)

@@ -6,7 +6,9 @@
 // windows and none lies in another's window, so each level is one batch of independent rank-1 updates, two launches:
 //   assim_prior   one wave per observation: h_k of the M forecast members, hbar, h'_k (to `hp`), p, d, alpha, delta.
 //                 It runs apart from the update so that no workgroup of an observation can overwrite the observed cell
-//                 while another workgroup of that observation still reads it.
+//                 while another workgroup of that observation still reads it.  Linear observations (a.tstart, the
+//                 taps of csim_obs_network_create_linear) differ only in h_k = sum_s w_s x_k(anchor + tap s):
+//                 linear_h below; the taps lie outside every other window of the level, so the same holds for them.
 //   assim_update  one wave per 64 cells of one observation's window (blockIdx.y: the observation, blockIdx.x: which
 //                 64 cells of its window clipped to the interior, row-major), so h'_k and the scalars are the same in
 //                 every lane of a wave, and lanes that follow i within a window row load each member coalesced.
@@ -32,15 +34,62 @@ __device__ __forceinline__ double* cell(double* f, int i, int j, int pitch) {
     return f + static_cast<ptrdiff_t>(j) * pitch + (LPAD - 1) + i;
 }
 
+// LDS of a wave that runs linear_h: M values of h, the tile of 64 members x (tmax | 1) values, 64 tap offsets
+size_t linear_lds(const AssimArgs& a) {
+    return sizeof(double) * a.forecast + sizeof(double) * 64 * (a.tmax | 1) + sizeof(int) * 64;
+}
+
+// One wave: h_k = sum_s w_s x_k(anchor + tap s) of the M forecast members for the observation at plan position q, into
+// sh[0 .. M); p: the anchor's cell in member 0; tile: 64 (tmax | 1) doubles and 64 ints behind sh.  64 members at a
+// time: the 64 x nt values go to the tile with the lanes along the taps (element e = m nt + s in lane e % 64), so the
+// lanes of a load read runs of neighbouring cells of a few members: a footprint's row is one or two cache lines per
+// member, where one lane per member would make every load 64 lines `slab` apart.  Then lane m folds row m of the tile
+// in tap order, a running sum from +0, every product rounded.  Rows are ld = nt | 1 doubles apart: odd, so the 32
+// lanes of a ds_read_b64 group hit 32 different bank pairs.  Ends with a barrier.
+__device__ __forceinline__ void linear_h(const double* __restrict__ p, long slab, const AssimArgs& a, int q,
+                                         double* __restrict__ sh, double* __restrict__ tile) {
+    const int lane = threadIdx.x;
+    const int M = a.forecast, t = a.truth_member;
+    const int s0 = a.tstart[q], nt = a.tstart[q + 1] - s0, ld = nt | 1;
+    const double* __restrict__ w = a.tw + s0;
+    int* offs = reinterpret_cast<int*>(tile + 64 * (a.tmax | 1));
+    if (lane < nt) offs[lane] = a.toff[s0 + lane];
+    __syncthreads();
+    const int dm = 64 / nt, ds = 64 - dm * nt;  // what 64 elements further means for (m, s)
+    for (int k0 = 0; k0 < M; k0 += 64) {
+        const int nm = min(64, M - k0), n = nm * nt;
+        int m = lane / nt, s = lane - m * nt;
+        for (int e = lane; e < n; e += 64) {
+            const int k = k0 + m;
+            tile[m * ld + s] = p[static_cast<ptrdiff_t>(k + (k >= t)) * slab + offs[s]];
+            m += dm, s += ds;
+            if (s >= nt) s -= nt, ++m;
+        }
+        __syncthreads();
+        if (lane < nm) {
+            double h = 0.0;
+            for (int u = 0; u < nt; ++u) h = h + w[u] * tile[lane * ld + u];
+            sh[k0 + lane] = h;
+        }
+        __syncthreads();  // sh is complete, and the tile is free for the next 64 members
+    }
+}
+
+// LIN: linear observations (h_k from linear_h); the point instantiation is the kernel as it was before they existed
+template <bool LIN>
 __global__ __launch_bounds__(64) void k_assim_prior(const double* __restrict__ f, int pitch, long slab, AssimArgs a,
                                                     int first) {
-    extern __shared__ double sh[];  // M values (dynamic: a small ensemble does not pay for 1024)
+    extern __shared__ double sh[];  // M values (dynamic: a small ensemble does not pay for 1024); LIN: linear_lds
     const int lane = threadIdx.x;
     const int M = a.forecast, t = a.truth_member;
     const int q = first + blockIdx.x;
     const double* p = f + static_cast<ptrdiff_t>(a.obs.j[q]) * pitch + (LPAD - 1) + a.obs.i[q];
-    for (int k = lane; k < M; k += 64) sh[k] = p[static_cast<ptrdiff_t>(k + (k >= t)) * slab];
-    __syncthreads();
+    if constexpr (LIN) {
+        linear_h(p, slab, a, q, sh, sh + M);
+    } else {
+        for (int k = lane; k < M; k += 64) sh[k] = p[static_cast<ptrdiff_t>(k + (k >= t)) * slab];
+        __syncthreads();
+    }
     double s = 0.0;
     for (int k = 0; k < M; ++k) s = s + sh[k];
     const double hbar = s / static_cast<double>(M);
@@ -182,6 +231,28 @@ __global__ __launch_bounds__(256) void k_assim_post(const double* __restrict__ f
     post[o + 1] = v / static_cast<double>(M - 1);
 }
 
+// the same for linear observations, one wave per observation: mv of csim_ensemble_relax applied to h_k
+__global__ __launch_bounds__(64) void k_assim_post_linear(const double* __restrict__ f, int pitch, long slab,
+                                                          AssimArgs a, double* __restrict__ post) {
+    extern __shared__ double sh[];  // linear_lds
+    const int M = a.forecast;
+    const int q = blockIdx.x;
+    linear_h(f + static_cast<ptrdiff_t>(a.obs.j[q]) * pitch + (LPAD - 1) + a.obs.i[q], slab, a, q, sh, sh + M);
+    double s = 0.0;
+    for (int k = 0; k < M; ++k) s = s + sh[k];
+    const double m = s / static_cast<double>(M);
+    double v = 0.0;
+    for (int k = 0; k < M; ++k) {
+        const double dx = sh[k] - m;
+        v = v + dx * dx;
+    }
+    if (threadIdx.x == 0) {
+        const size_t o = 2 * static_cast<size_t>(a.obs.idx[q]);
+        post[o] = m;
+        post[o + 1] = v / static_cast<double>(M - 1);
+    }
+}
+
 template <int P>
 hipError_t launch_update(const EnsGeom& g, double* f, const AssimArgs& a, int first, int count, long wcells,
                          hipStream_t st) {
@@ -196,7 +267,13 @@ hipError_t ens_launch_assim_prior(const EnsGeom& g, const double* f, const Assim
                                   hipStream_t st) {
     if (count <= 0) return hipSuccess;
     if (a.forecast < 2 || a.forecast > ASSIM_MAX_MEMBERS) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_assim_prior, dim3(count), dim3(64), sizeof(double) * a.forecast, st, f, g.pitch, g.slab, a, first);
+    if (a.tstart) {
+        if (a.tmax < 1 || a.tmax > OBS_MAX_TAPS) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_assim_prior<true>, dim3(count), dim3(64), linear_lds(a), st, f, g.pitch, g.slab, a, first);
+    } else {
+        hipLaunchKernelGGL(k_assim_prior<false>, dim3(count), dim3(64), sizeof(double) * a.forecast, st, f, g.pitch,
+                           g.slab, a, first);
+    }
     return hipGetLastError();
 }
 
@@ -226,6 +303,11 @@ hipError_t ens_launch_assim_inflate(const EnsGeom& g, double* f, int forecast, i
 hipError_t ens_launch_assim_post(const EnsGeom& g, const double* f, const AssimArgs& a, int nobs, double* post,
                                  hipStream_t st) {
     if (nobs <= 0) return hipSuccess;
+    if (a.tstart) {
+        if (a.tmax < 1 || a.tmax > OBS_MAX_TAPS) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_assim_post_linear, dim3(nobs), dim3(64), linear_lds(a), st, f, g.pitch, g.slab, a, post);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_assim_post, dim3((nobs + 255) / 256), dim3(256), 0, st, f, g.pitch, g.slab, a, nobs, post);
     return hipGetLastError();
 }

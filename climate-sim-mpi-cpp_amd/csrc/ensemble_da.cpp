@@ -281,6 +281,7 @@ int csim_ensemble_assimilate(csim_ensemble* e, int nobs, const int* i, const int
     a.scal = reinterpret_cast<double*>(d + l.scal);
     a.hp = reinterpret_cast<double*>(d + l.hp);
     a.prior = prior_mean || prior_var ? reinterpret_cast<double*>(d + l.prior) : nullptr;
+    // a.tstart stays null: point observations
     std::vector<AssimBatch> batches;
     assim_batches(g, nl, off.data(), hi, hj, lx, ly, batch, &batches);
     CSIM_TRY(assim_enqueue(e, a, inflation, batches));

@@ -9,40 +9,11 @@
 
 #include "ensemble_host.hpp"
 #include "ensemble_noise.hpp"
+#include "obs_taps.hpp"
 
 using namespace csim;
 
 namespace {
-
-// byte layout of a network's device buffer.  Written once at create: i, j, idx, r, sr (plan order), pos (by input
-// index) and the table.  Then y and xt (plan order), the analysis's scalars and one batch's h'_k, the background and
-// posterior diagnostics (2 per input index each), the chunk sums of the last record and the log.
-struct ObsLayout {
-    size_t i, j, idx, pos, r, sr, rho, fixed, y, xt, scal, bg, post, part, hp, log, total;
-};
-ObsLayout obs_layout(size_t n, size_t tcells, size_t hp, size_t log_cycles) {
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t chunks = (n + OBS_CHUNK - 1) / OBS_CHUNK;
-    ObsLayout l{};
-    l.i = 0;
-    l.j = up(l.i + 4 * n);
-    l.idx = up(l.j + 4 * n);
-    l.pos = up(l.idx + 4 * n);
-    l.r = up(l.pos + 4 * n);
-    l.sr = up(l.r + 8 * n);
-    l.rho = up(l.sr + 8 * n);
-    l.fixed = up(l.rho + 8 * tcells);
-    l.y = l.fixed;
-    l.xt = up(l.y + 8 * n);
-    l.scal = up(l.xt + 8 * n);
-    l.bg = up(l.scal + 24 * n);
-    l.post = up(l.bg + 16 * n);
-    l.part = up(l.post + 16 * n);
-    l.hp = up(l.part + 8 * OBS_SUMS * chunks);
-    l.log = up(l.hp + 8 * hp);
-    l.total = up(l.log + 8 * OBS_CYCLE_FIELDS * log_cycles);
-    return l;
-}
 
 static_assert(sizeof(csim_obs_cycle) == sizeof(double) * OBS_CYCLE_FIELDS, "csim_obs_cycle is 13 doubles");
 
@@ -51,6 +22,7 @@ static_assert(sizeof(csim_obs_cycle) == sizeof(double) * OBS_CYCLE_FIELDS, "csim
 struct csim_obs_network {
     csim_ensemble* e = nullptr;
     int nobs = 0, nlevels = 0, lx = 0, ly = 0, log_cycles = 0;
+    int ntaps = 0, tmax = 0;            // of a linear network: taps in all, the most of one observation; else 0
     std::vector<int> off, pi, pj, idx;  // the plan: level offsets; cells and input index of every plan position
     std::vector<AssimBatch> batches;    // its launches for batches_m forecast members (made at the first analysis)
     int batches_m = 0;
@@ -67,6 +39,7 @@ struct csim_obs_network {
         a.r = at<double>(l.r), a.sr = at<double>(l.sr);
         a.y = at<double>(l.y), a.xt = at<double>(l.xt);
         a.bg = at<double>(l.bg), a.post = at<double>(l.post), a.part = at<double>(l.part);
+        if (ntaps) a.tstart = at<int>(l.tstart), a.toff = at<int>(l.toff), a.tw = at<double>(l.tw);
         return a;
     }
     void release() { dev.release(), stage.release(); }
@@ -104,18 +77,23 @@ int fetch_pairs(const csim_obs_network* n, size_t byte, double* mean, double* va
     return CSIM_OK;
 }
 
-}  // namespace
+// the taps of csim_obs_network_create_linear, input order
+struct Taps {
+    const int *start, *di, *dj;
+    const double* w;
+};
 
-extern "C" {
-
-int csim_obs_network_create(csim_ensemble* e, int nobs, const int* i, const int* j, const double* r, double loc,
-                            int ordered, int log_cycles, csim_obs_network** out) {
+// csim_obs_network_create (taps null) and csim_obs_network_create_linear
+int network_create(csim_ensemble* e, int nobs, const int* i, const int* j, const Taps* taps, const double* r, double loc,
+                   int ordered, int log_cycles, csim_obs_network** out) {
     CSIM_REQUIRE(out, "out is null");
     *out = nullptr;
     CSIM_REQUIRE(e, "null ensemble");
     const EnsGeom& g = e->g;
     CSIM_REQUIRE(nobs >= 1, "nobs must be >= 1");
     CSIM_REQUIRE(i && j && r, "null observation array");
+    CSIM_REQUIRE(!taps || (taps->start && taps->di && taps->dj && taps->w), "null tap array");
+    CSIM_REQUIRE(!taps || g.slab <= 0x7fffffffL, "grid too large for packed tap offsets");
     CSIM_REQUIRE(std::isfinite(loc) && loc > 0, "loc must be finite and > 0");
     CSIM_REQUIRE(ordered == 0 || ordered == 1, "ordered must be 0 or 1");
     CSIM_REQUIRE(log_cycles >= 0 && log_cycles <= 65536, "log_cycles must be in 0 .. 65536");
@@ -134,6 +112,7 @@ int csim_obs_network_create(csim_ensemble* e, int nobs, const int* i, const int*
     try {
         int lx = 0, ly = 0, nl = 0;
         CSIM_TRY(csim_ensemble_gc_table(e->dx, e->dy, loc, g.nx, g.ny, &lx, &ly, nullptr));
+        if (taps) CSIM_TRY(csim_obs_linear_check(g.nx, g.ny, lx, ly, nobs, i, j, taps->start, taps->di, taps->dj, taps->w));
         std::vector<int> level(nobs);
         CSIM_TRY(csim_ensemble_assim_plan(nobs, i, j, lx, ly, ordered, level.data(), &nl));
 
@@ -154,7 +133,13 @@ int csim_obs_network_create(csim_ensemble* e, int nobs, const int* i, const int*
             if (M >= 2 && M <= ASSIM_MAX_MEMBERS)
                 hp = std::max(hp, static_cast<size_t>(std::min(nobs, assim_batch_size(M))) * M);
         const size_t tcells = static_cast<size_t>(2 * lx + 1) * (2 * ly + 1);
-        n->l = obs_layout(nobs, tcells, hp, log_cycles);
+        if (taps) {
+            n->ntaps = taps->start[nobs];
+            for (int o = 0; o < nobs; ++o) n->tmax = std::max(n->tmax, taps->start[o + 1] - taps->start[o]);
+        }
+        const size_t chunks = (static_cast<size_t>(nobs) + OBS_CHUNK - 1) / OBS_CHUNK;
+        n->l = obs_layout(nobs, n->ntaps, tcells, hp, OBS_SUMS * chunks,
+                          static_cast<size_t>(OBS_CYCLE_FIELDS) * log_cycles);
         const ObsLayout& l = n->l;
         std::vector<char> h(l.fixed, 0);
         auto* hi = reinterpret_cast<int*>(h.data() + l.i);
@@ -168,6 +153,10 @@ int csim_obs_network_create(csim_ensemble* e, int nobs, const int* i, const int*
             n->pi[q] = hi[q] = i[o], n->pj[q] = hj[q] = j[o], hx[q] = o, hpos[o] = q;
             hr[q] = r[o], hs[q] = std::sqrt(r[o]);
         }
+        if (taps)
+            obs_taps_plan_order(nobs, n->idx.data(), taps->start, taps->di, taps->dj, taps->w, g.pitch,
+                                reinterpret_cast<int*>(h.data() + l.tstart), reinterpret_cast<int*>(h.data() + l.toff),
+                                reinterpret_cast<double*>(h.data() + l.tw));
         int rc = csim_ensemble_gc_table(e->dx, e->dy, loc, g.nx, g.ny, &lx, &ly, reinterpret_cast<double*>(h.data() + l.rho));
         if (rc == CSIM_OK) rc = n->dev.reserve(l.total);
         hipError_t err = hipSuccess;
@@ -184,6 +173,29 @@ int csim_obs_network_create(csim_ensemble* e, int nobs, const int* i, const int*
     } catch (const std::bad_alloc&) {
         return fail(CSIM_ERR_STATE, "csim_obs_network_create: out of host memory");
     }
+}
+
+}  // namespace
+
+extern "C" {
+
+int csim_obs_network_create(csim_ensemble* e, int nobs, const int* i, const int* j, const double* r, double loc,
+                            int ordered, int log_cycles, csim_obs_network** out) {
+    return network_create(e, nobs, i, j, nullptr, r, loc, ordered, log_cycles, out);
+}
+
+int csim_obs_network_create_linear(csim_ensemble* e, int nobs, const int* i, const int* j, const int* start,
+                                   const int* di, const int* dj, const double* w, const double* r, double loc,
+                                   int ordered, int log_cycles, csim_obs_network** out) {
+    const Taps taps{start, di, dj, w};
+    return network_create(e, nobs, i, j, &taps, r, loc, ordered, log_cycles, out);
+}
+
+int csim_obs_network_taps(const csim_obs_network* n, int* ntaps_total) {
+    CSIM_REQUIRE(n, "null network");
+    CSIM_REQUIRE(ntaps_total, "null argument");
+    *ntaps_total = n->ntaps;
+    return CSIM_OK;
 }
 
 int csim_obs_network_destroy(csim_obs_network* n) {
@@ -271,6 +283,7 @@ int csim_ensemble_assimilate_network(csim_ensemble* e, csim_obs_network* n, doub
     a.lx = n->lx, a.ly = n->ly;
     a.rho = n->at<double>(n->l.rho);
     a.obs.i = oa.i, a.obs.j = oa.j, a.obs.idx = oa.idx, a.obs.y = oa.y, a.obs.r = oa.r;
+    a.tstart = oa.tstart, a.toff = oa.toff, a.tw = oa.tw, a.tmax = n->tmax;  // null / 0: point observations
     a.scal = n->at<double>(n->l.scal);
     a.hp = n->at<double>(n->l.hp);
     a.prior = nullptr;

@@ -4,7 +4,9 @@
 //   k_obs_observe  one lane per observation (plan position q): the gather of x_s(i, j) from the source member, and
 //                  with noise one Philox call on the counter (input index, 0, 0xFFFFFFFF, draw) and the normal
 //                  quantile of its first 64 bits; stores y and xt in plan order.  The deviate depends on the input
-//                  index alone, so neither the plan nor the launch geometry shows in the result.
+//                  index alone, so neither the plan nor the launch geometry shows in the result.  Linear
+//                  observations (a.tstart): xt = h of the source member, sum_s w_s x(anchor + tap s) in tap order
+//                  from +0; the taps of a footprint are neighbours, so a lane's loads stay in a few cache lines.
 //   k_obs_chunks   one lane per chunk of OBS_CHUNK consecutive input indices: T_c of the eleven sums of a
 //                  csim_obs_cycle, each a running sum from +0 in input order.
 //   k_obs_cycle    one wave: lane f folds T_c of sum f in chunk order from +0 into the log's record.
@@ -19,13 +21,21 @@ namespace csim {
 
 namespace {
 
+template <bool LIN>
 __global__ __launch_bounds__(256) void k_obs_observe(const double* __restrict__ f, int pitch, long slab, ObsArgs a,
                                                      int member, unsigned seed_lo, unsigned seed_hi, unsigned draw,
                                                      int noise) {
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= a.nobs) return;
-    const double xt = f[static_cast<ptrdiff_t>(member) * slab + static_cast<ptrdiff_t>(a.j[q]) * pitch + (LPAD - 1) +
-                        a.i[q]];
+    const double* p = f + static_cast<ptrdiff_t>(member) * slab + static_cast<ptrdiff_t>(a.j[q]) * pitch + (LPAD - 1) +
+                      a.i[q];
+    double xt;
+    if constexpr (LIN) {
+        xt = 0.0;
+        for (int s = a.tstart[q]; s < a.tstart[q + 1]; ++s) xt = xt + a.tw[s] * p[a.toff[s]];
+    } else {
+        xt = *p;
+    }
     double y = xt;
     if (noise) {
         unsigned c[4] = {static_cast<unsigned>(a.idx[q]), 0u, 0xFFFFFFFFu, draw};
@@ -89,8 +99,12 @@ __global__ __launch_bounds__(64) void k_obs_cycle(const double* __restrict__ par
 hipError_t ens_launch_obs_observe(const EnsGeom& g, const double* f, const ObsArgs& a, int member, unsigned seed_lo,
                                   unsigned seed_hi, unsigned draw, bool noise, hipStream_t st) {
     if (a.nobs <= 0 || member < 0 || member >= g.members) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_obs_observe, dim3((a.nobs + 255) / 256), dim3(256), 0, st, f, g.pitch, g.slab, a, member,
-                       seed_lo, seed_hi, draw, noise ? 1 : 0);
+    if (a.tstart)
+        hipLaunchKernelGGL(k_obs_observe<true>, dim3((a.nobs + 255) / 256), dim3(256), 0, st, f, g.pitch, g.slab, a,
+                           member, seed_lo, seed_hi, draw, noise ? 1 : 0);
+    else
+        hipLaunchKernelGGL(k_obs_observe<false>, dim3((a.nobs + 255) / 256), dim3(256), 0, st, f, g.pitch, g.slab, a,
+                           member, seed_lo, seed_hi, draw, noise ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -45,9 +45,17 @@ struct ObsValues {
     std::vector<double> y, truth, bg_mean, bg_var, post_mean, post_var;
 };
 
+// the taps of linear observations (see csim_obs_network_create_linear): observation o observes
+// sum_s w[s] x(i[o] + di[s], j[o] + dj[s]) over s = start[o] .. start[o + 1] - 1; i, j are the anchors
+struct ObsTaps {
+    std::vector<int> i, j, start{0}, di, dj;
+    std::vector<double> w;
+    std::size_t size() const { return i.size(); }
+};
+
 class Ensemble;
 
-// point observations that live on the device (csim_obs_network_*): planned once, their values drawn on the GPU from a
+// observations that live on the device (csim_obs_network_*): planned once, their values drawn on the GPU from a
 // member or set from the host, read by Ensemble::assimilate(ObsNetwork&, ...) without staging.  Move-only; made by
 // Ensemble::obs_network().  The library destroys the networks of an ensemble with it; the ensemble then empties the
 // handle this class shares with it, so a network that outlives its ensemble is safe to destroy or move, and every
@@ -67,6 +75,12 @@ public:
     ObsNetwork& operator=(const ObsNetwork&) = delete;
 
     std::size_t size() const { return nobs_; }
+    // taps of all observations of a linear network, 0 for point observations
+    int taps() const {
+        int n = 0;
+        check(csim_obs_network_taps(handle(), &n));
+        return n;
+    }
     int levels() const {
         int nl = 0;
         check(csim_obs_network_info(handle(), nullptr, &nl, nullptr, nullptr));
@@ -295,6 +309,51 @@ public:
                                       ordered ? 1 : 0, log_cycles, &slot->h));
         nets_.push_back(slot);
         return ObsNetwork(std::move(slot), i.size());
+    }
+    // the same for linear observations (see csim_obs_network_create_linear): taps from bilinear_taps() / box_taps() or
+    // the caller's own
+    ObsNetwork obs_network(const ObsTaps& t, const std::vector<double>& r, double loc, bool ordered = false,
+                           int log_cycles = 0) {
+        if (t.j.size() != t.i.size() || r.size() != t.i.size() || t.start.size() != t.i.size() + 1 ||
+            t.start.back() < 0 || t.di.size() != t.w.size() || t.dj.size() != t.w.size() ||
+            t.w.size() < static_cast<std::size_t>(t.start.back()))
+            throw std::invalid_argument("ensemble: observation arrays of different sizes");
+        nets_.erase(std::remove_if(nets_.begin(), nets_.end(), [](const auto& slot) { return !slot->h; }), nets_.end());
+        auto slot = std::make_shared<ObsNetwork::Slot>();
+        check(csim_obs_network_create_linear(h_, static_cast<int>(t.i.size()), t.i.data(), t.j.data(), t.start.data(),
+                                             t.di.data(), t.dj.data(), t.w.data(), r.data(), loc, ordered ? 1 : 0,
+                                             log_cycles, &slot->h));
+        nets_.push_back(slot);
+        return ObsNetwork(std::move(slot), t.i.size());
+    }
+    // host-only builders of taps: bilinear interpolation to the positions (x, y) in cell-index units, 1 <= x <= nx,
+    // 1 <= y <= ny (csim_obs_taps_bilinear), and the means over (2a+1) x (2b+1) boxes around the cells (i, j), clipped
+    // to the interior (csim_obs_taps_box)
+    static ObsTaps bilinear_taps(int nx, int ny, const std::vector<double>& x, const std::vector<double>& y) {
+        if (x.size() != y.size()) throw std::invalid_argument("ensemble: observation arrays of different sizes");
+        ObsTaps t;
+        for (std::size_t o = 0; o < x.size(); ++o) {
+            int i = 0, j = 0, di[4], dj[4];
+            double w[4];
+            check(csim_obs_taps_bilinear(nx, ny, x[o], y[o], &i, &j, di, dj, w));
+            t.i.push_back(i), t.j.push_back(j);
+            t.di.insert(t.di.end(), di, di + 4), t.dj.insert(t.dj.end(), dj, dj + 4), t.w.insert(t.w.end(), w, w + 4);
+            t.start.push_back(static_cast<int>(t.w.size()));
+        }
+        return t;
+    }
+    static ObsTaps box_taps(int nx, int ny, const std::vector<int>& i, const std::vector<int>& j, int a, int b) {
+        if (i.size() != j.size()) throw std::invalid_argument("ensemble: observation arrays of different sizes");
+        ObsTaps t;
+        for (std::size_t o = 0; o < i.size(); ++o) {
+            int n = 0, di[CSIM_OBS_MAX_TAPS], dj[CSIM_OBS_MAX_TAPS];
+            double w[CSIM_OBS_MAX_TAPS];
+            check(csim_obs_taps_box(nx, ny, i[o], j[o], a, b, &n, di, dj, w));
+            t.i.push_back(i[o]), t.j.push_back(j[o]);
+            t.di.insert(t.di.end(), di, di + n), t.dj.insert(t.dj.end(), dj, dj + n), t.w.insert(t.w.end(), w, w + n);
+            t.start.push_back(static_cast<int>(t.w.size()));
+        }
+        return t;
     }
     // the analysis with the network's observations, always enqueued; record: also append the cycle's innovation
     // statistics to the network's log on the device (see csim_ensemble_assimilate_network)

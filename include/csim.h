@@ -599,6 +599,58 @@ typedef struct csim_obs_cycle {
 } csim_obs_cycle;
 int csim_obs_network_log(csim_obs_network* n, int max, csim_obs_cycle* out, int* ncycles);
 int csim_obs_network_log_reset(csim_obs_network* n);
+/* linear observations: a network whose observations are linear functionals of the state, a station between grid
+ * points (interpolated) or a footprint (an area average), instead of one cell each.  Observation o has an anchor
+ * (i_o, j_o) in the interior, an error variance r_o and the taps s = start[o] .. start[o+1]-1, each (di_s, dj_s, w_s).
+ * The anchor centres the localisation window and enters the level plan, exactly as the observed cell of a point
+ * observation does; the taps define what is observed.  Operator value, without FMA contraction, every product rounded,
+ * a running sum from +0 in tap order:
+ *
+ *     h_k = sum_s  w_s * x_k(i_o + di_s, j_o + dj_s)
+ *
+ * Everything after h_k is the text of csim_ensemble_assimilate: hbar = sum h_k / M;  h'_k = h_k - hbar;
+ * p = sum h'_k h'_k / (M-1);  d = p + r_o;  alpha = 1 / (1 + sqrt(r_o / d));  delta = y_o - hbar;  the window update
+ * for every interior cell c = (i_o+a, j_o+b), |a| <= lx, |b| <= ly, with rho > 0, centred on the anchor; the levels of
+ * csim_ensemble_assim_plan on the anchors; plan order (level, input index).
+ * Constraints, checked before anything is enqueued (CSIM_ERR_ARG): 1 <= taps per observation <= CSIM_OBS_MAX_TAPS;
+ * start[0] == 0 and start non-decreasing; every tapped cell interior; every w_s finite; |di_s| <= lx and |dj_s| <= ly,
+ * lx and ly those of csim_ensemble_gc_table.  The last constraint is what keeps the plan valid unchanged: two
+ * observations of one level have anchors more than 2 lx apart along x or more than 2 ly apart along y, so a tap at
+ * most lx / ly from its anchor lies outside every other window of that level, no observation of a level reads a cell
+ * that another one of that level writes, and the observations of a level still commute exactly.  Repeated cells and
+ * negative weights are allowed.  A one-tap observation (0, 0, 1.0) gives h_k = +0 + 1.0 x_k = x_k: the point
+ * observation bit for bit, except that a -0 in the field becomes +0.
+ * Diagnostics and the log follow the operator: observe gives xt_o = h of the source member (noise as before:
+ * y_o = xt_o + sqrt(r_o) z_o, z_o = csim_obs_noise of the input index; noise = 0: y_o = xt_o); (hb, vb) and (ha, va)
+ * are mv of csim_ensemble_relax applied to h_k over the forecast members, before the inflation and after the last
+ * observation; csim_obs_cycle keeps its thirteen fields and their chunked sums.
+ * create_linear: as csim_obs_network_create with (i, j) the anchors, plus start (nobs + 1 values), di, dj, w
+ *   (start[nobs] values each); the constraints above are those of csim_obs_linear_check with the ensemble's nx, ny and
+ *   the lx, ly of loc.  The result is a csim_obs_network: set_values, observe, csim_ensemble_assimilate_network, fetch,
+ *   log, log_reset, info and destroy work on it unchanged.  An error leaves the ensemble and every existing network as
+ *   they were.  CSIM_ERR_ARG also for a null start / di / dj / w.
+ * taps: *ntaps_total = start[nobs] of a linear network, 0 of a point network.
+ * linear_check (host-only, needs no device): CSIM_OK or CSIM_ERR_ARG with the first violated constraint in
+ *   csim_last_error; also CSIM_ERR_ARG for nobs < 1, nx or ny < 1, lx or ly < 0, a null array, an anchor outside the
+ *   interior.
+ * taps_bilinear (host-only): the four taps of bilinear interpolation to (x, y) in cell-index units, 1 <= x <= nx,
+ *   1 <= y <= ny (else CSIM_ERR_ARG).  *i = min(floor(x), nx - 1), and max(., 1) when nx == 1, where the x taps
+ *   collapse onto the one column (di = 0 for all four); fx = x - *i; *j and fy the same from y and ny.  Taps in the
+ *   order (0,0) (1,0) (0,1) (1,1) with weights (1-fx)(1-fy), fx (1-fy), (1-fx) fy, fx fy, each difference and product
+ *   rounded in that order.
+ * taps_box (host-only): the mean over the (2a+1) x (2b+1) box around the interior cell (i, j), a, b >= 0, clipped to
+ *   the interior: rows in increasing dj, then increasing di; every weight 1 / count, the rounded quotient; *ntaps =
+ *   count; di, dj, w have room for CSIM_OBS_MAX_TAPS.  CSIM_ERR_UNSUPPORTED above CSIM_OBS_MAX_TAPS taps,
+ *   CSIM_ERR_ARG for (i, j) outside the interior, a or b < 0, a null pointer. */
+#define CSIM_OBS_MAX_TAPS 64
+int csim_obs_network_create_linear(csim_ensemble* e, int nobs, const int* i, const int* j, const int* start,
+                                   const int* di, const int* dj, const double* w, const double* r, double loc,
+                                   int ordered, int log_cycles, csim_obs_network** out);
+int csim_obs_network_taps(const csim_obs_network* n, int* ntaps_total);
+int csim_obs_linear_check(int nx, int ny, int lx, int ly, int nobs, const int* i, const int* j, const int* start,
+                          const int* di, const int* dj, const double* w);
+int csim_obs_taps_bilinear(int nx, int ny, double x, double y, int* i, int* j, int di[4], int dj[4], double w[4]);
+int csim_obs_taps_box(int nx, int ny, int i, int j, int a, int b, int* ntaps, int* di, int* dj, double* w);
 /* options (unknown keys: CSIM_ERR_ARG; "contract": CSIM_ERR_UNSUPPORTED), results never depend on them:
  *   "fuse"        -1 (default) passes of the ensemble depth where the grid allows; 0 / 1 single steps only
  *   "fused_2c"    0/1 (default 1), as for csim_stepper_set_option
