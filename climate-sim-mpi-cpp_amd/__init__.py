@@ -75,6 +75,11 @@ class CsimObsCycle(C.Structure):
                                           "sum_ab_ob", "sum_vb", "sum_va", "sum_r", "sum_eb2", "sum_ea2")]
 
 
+class CsimObsScreenCycle(C.Structure):
+    """csim_obs_screen_cycle of include/csim.h: the used / inactive / rejected counts of one recorded analysis"""
+    _fields_ = [(k, C.c_double) for k in ("n_used", "n_inactive", "n_rejected")]
+
+
 class CsimVerifyScores(C.Structure):
     """csim_verify_scores of include/csim.h"""
     _fields_ = [("cells", C.c_longlong), ("nan_cells", C.c_longlong), ("crps", C.c_double), ("rmse", C.c_double),
@@ -218,6 +223,11 @@ def lib() -> C.CDLL:
         "csim_obs_linear_check": (i, [i, i, i, i, i, ip, ip, ip, ip, ip, dp]),
         "csim_obs_taps_bilinear": (i, [i, i, d, d, ip, ip, ip, ip, dp]),
         "csim_obs_taps_box": (i, [i, i, i, i, i, i, ip, ip, ip, dp]),
+        "csim_obs_network_set_active": (i, [vp, C.POINTER(C.c_ubyte)]),
+        "csim_ensemble_assimilate_screened": (i, [vp, vp, d, i, i, d]),
+        "csim_obs_network_screen_log": (i, [vp, i, C.POINTER(CsimObsScreenCycle), ip]),
+        "csim_obs_network_status": (i, [vp, C.POINTER(C.c_ubyte)]),
+        "csim_obs_screen_decide": (i, [d, d, d, d, d, i, ip]),
         "csim_ensemble_set_option": (i, [vp, C.c_char_p, C.c_long]),
         "csim_ensemble_get_option": (i, [vp, C.c_char_p, C.POINTER(C.c_long)]),
         "csim_ensemble_plan": (i, [i, i, i, i, ip]),
@@ -803,6 +813,18 @@ ObsValues.__doc__ = """what ObsNetwork.fetch() returns, each per observation in 
 does not hold it: the values, the source member's own values (after observe), and the forecast members' mean and
 variance at the cell before and after the last recorded analysis"""
 OBS_CYCLE_FIELDS = tuple(k for k, _ in CsimObsCycle._fields_)
+OBS_SCREEN_FIELDS = tuple(k for k, _ in CsimObsScreenCycle._fields_)
+OBS_USED, OBS_INACTIVE, OBS_REJECTED = 0, 1, 2
+
+
+def obs_screen_decide(y, hb, vb, r, tol, active=True) -> int:
+    """the status (OBS_USED / OBS_INACTIVE / OBS_REJECTED) that a screened analysis gives one observation with value y,
+    background mean hb and variance vb, error variance r, under tolerance tol and its mask byte
+    (csim_obs_screen_decide) — host only"""
+    st = C.c_int()
+    _ck(lib().csim_obs_screen_decide(float(y), float(hb), float(vb), float(r), float(tol),
+                                     active if isinstance(active, int) else int(bool(active)), C.byref(st)))
+    return st.value
 
 
 class ObsNetwork:
@@ -856,6 +878,47 @@ class ObsNetwork:
         if yy.shape != (self.nobs,):
             raise ValueError(f"expected {self.nobs} values")
         _ck(lib().csim_obs_network_set_values(self._h, _dp(yy)))
+
+    def set_active(self, mask=None):
+        """which observations the analyses use from now on: one 0 / 1 per observation in input order, None: all;
+        copied before the call returns, enqueued without waiting, kept until replaced (csim_obs_network_set_active)"""
+        if mask is None:
+            _ck(lib().csim_obs_network_set_active(self._h, None))
+            return
+        m = np.asarray(mask)
+        if m.shape != (self.nobs,):
+            raise ValueError(f"expected {self.nobs} mask bytes")
+        m = np.ascontiguousarray(m.astype(np.uint8) if m.dtype == np.bool_ else m, dtype=np.uint8)
+        _ck(lib().csim_obs_network_set_active(self._h, m.ctypes.data_as(C.POINTER(C.c_ubyte))))
+
+    def set_reports(self, y):
+        """this cycle's reports, NaN (or any non-finite value) where a station did not report: the mask becomes
+        isfinite(y) and the values y with 0.0 in place of the missing ones (set_active, then set_values)"""
+        yy = np.asarray(y, dtype=np.float64)
+        if yy.shape != (self.nobs,):
+            raise ValueError(f"expected {self.nobs} values")
+        ok = np.isfinite(yy)
+        self.set_active(ok)
+        self.set_values(np.where(ok, yy, 0.0))
+
+    def status(self) -> np.ndarray:
+        """waits for the ensemble's stream; OBS_USED / OBS_INACTIVE / OBS_REJECTED per observation in input order for
+        the last analysis of this network (csim_obs_network_status)"""
+        out = np.empty(self.nobs, dtype=np.uint8)
+        _ck(lib().csim_obs_network_status(self._h, out.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return out
+
+    def screen_log(self) -> np.ndarray:
+        """waits for the ensemble's stream; n_used, n_inactive and n_rejected of the recorded analyses, oldest first,
+        as a structured array parallel to log() (csim_obs_network_screen_log)"""
+        k = C.c_int()
+        _ck(lib().csim_obs_network_screen_log(self._h, 0, None, C.byref(k)))
+        rec = (CsimObsScreenCycle * max(k.value, 1))()
+        _ck(lib().csim_obs_network_screen_log(self._h, k.value, rec, C.byref(k)))
+        out = np.zeros(k.value, dtype=[(f, np.float64) for f in OBS_SCREEN_FIELDS])
+        for c in range(k.value):
+            out[c] = tuple(getattr(rec[c], f) for f in OBS_SCREEN_FIELDS)
+        return out
 
     def observe(self, source_member, seed, draw=0, noise=True):
         """the values from member source_member at the observed cells, with noise plus sqrt(r) times the seeded
@@ -1090,13 +1153,18 @@ class Ensemble:
         observations sum_s w_s x(i + di_s, j + dj_s) anchored at (i, j) (csim_obs_network_create_linear)"""
         return ObsNetwork(self, i, j, r, loc, ordered, log_cycles, taps)
 
-    def assimilate_network(self, net: ObsNetwork, inflation=1.0, truth_member=None, record=False):
+    def assimilate_network(self, net: ObsNetwork, inflation=1.0, truth_member=None, record=False, screen=None):
         """the analysis of assimilate() with the network's observations, always enqueued without waiting; record=True
         also appends the cycle's innovation statistics to the network's log on the device
-        (csim_ensemble_assimilate_network)"""
+        (csim_ensemble_assimilate_network).  Observations that net.set_active() masks out take no part.  screen=tol > 0
+        adds the background check on the device: an observation with (y - hb)^2 > tol^2 (vb + r) is rejected
+        (csim_ensemble_assimilate_screened); net.status() tells which were used"""
         tm = -1 if truth_member is None else int(truth_member)
-        _ck(lib().csim_ensemble_assimilate_network(self._h, net._h, float(inflation), tm,
-                                                   record if isinstance(record, int) else int(bool(record))))
+        rec = record if isinstance(record, int) else int(bool(record))
+        if screen is None or screen == 0:
+            _ck(lib().csim_ensemble_assimilate_network(self._h, net._h, float(inflation), tm, rec))
+        else:
+            _ck(lib().csim_ensemble_assimilate_screened(self._h, net._h, float(inflation), tm, rec, float(screen)))
 
     def perturb(self, sigma, corr_len, seed, draw=0, centered=False, truth_member=None):
         """adds sigma times a seeded Gaussian random field of correlation length corr_len to the interior of every

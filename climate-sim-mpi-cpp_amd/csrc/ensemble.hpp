@@ -134,6 +134,9 @@ struct AssimArgs {
     const int* toff;              // per tap: dj * pitch + di, the cell's offset from the anchor in a member's slab
     const double* tw;             // per tap: w
     int tmax;                     // the most taps of one observation (sizes the linear prior's LDS tile)
+    // screening (csim_ensemble_assimilate_screened): one byte per plan position, an observation whose byte is not 0
+    // (CSIM_OBS_USED) takes no turn; null: every observation is used.  After the taps, for the same reason
+    const unsigned char* status;
 };
 // the batch's h'_k and scalars, then its window updates; wcells: the largest clipped window of the batch in cells.
 // With taps (a.tstart) the prior is the linear one: h_k = sum_s w_s x_k(anchor + tap s)
@@ -200,11 +203,29 @@ struct ObsArgs {
     const int* toff;
     const double* tw;
 };
+// screening (csim_obs_network_set_active, csim_ensemble_assimilate_screened); mask and status in plan order
+constexpr int OBS_SCREEN_FIELDS = 3; // doubles of a csim_obs_screen_cycle, and counts per chunk: used, inactive, rejected
+struct ObsScreen {
+    const unsigned char* mask;    // 1: active; null: all active
+    unsigned char* status;        // CSIM_OBS_USED / _INACTIVE / _REJECTED of the analysis that follows
+    const double* bg;             // 2 per input index: hb, vb (read only with check)
+    int check;                    // tol > 0: the background check is made
+    double k2;                    // tol * tol, rounded on the host
+    int* cnt;                     // OBS_SCREEN_FIELDS per chunk: the counts of the last recorded, screened analysis
+};
 // y and xt of every observation from member `member` (with taps: xt = h of that member); noise: y = xt + sr z, z the deviate of (seed, draw, input index)
 hipError_t ens_launch_obs_observe(const EnsGeom& g, const double* f, const ObsArgs& a, int member, unsigned seed_lo,
                                   unsigned seed_hi, unsigned draw, bool noise, hipStream_t st);
 // the chunk sums T_c, then their fold in chunk order into the record `slot` (OBS_CYCLE_FIELDS doubles)
 hipError_t ens_launch_obs_cycle(const ObsArgs& a, bool has_truth, double* slot, hipStream_t st);
+// the status of every observation from the mask and, with s.check, (y, hb, vb, r)
+hipError_t ens_launch_obs_screen(const ObsArgs& a, const ObsScreen& s, hipStream_t st);
+// ens_launch_obs_cycle of a screened analysis: the terms of observations that are not used are +0, slot[0] is the
+// number used, and `sslot` (OBS_SCREEN_FIELDS doubles) gets the three counts
+hipError_t ens_launch_obs_cycle_screened(const ObsArgs& a, const ObsScreen& s, bool has_truth, double* slot,
+                                         double* sslot, hipStream_t st);
+// (nobs, 0, 0) into each of `cycles` records of a screen log: what a cycle that is not screened leaves there
+hipError_t ens_launch_obs_screen_log_fill(double* slog, int cycles, int nobs, hipStream_t st);
 
 // the rank histogram's tie-break: splitmix64's finaliser of the interior index g; a cell with `eq` members equal to the
 // truth goes to bin lt + mix(g) mod (eq + 1)

@@ -14,6 +14,9 @@
 //                 every lane of a wave, and lanes that follow i within a window row load each member coalesced.
 //                 M <= 64: each lane reads its cell of every member once into registers and writes it once.  M > 64:
 //                 three passes over the members (mean, covariance, update); a window's members stay in L2 between them.
+// Screening (a.status, csim_ensemble_assimilate_screened): a byte per plan position; the block of an observation whose
+// byte is not 0 leaves at once in assim_prior and skips it in assim_update, so it reads and writes nothing.  The
+// pointer is a kernel argument (null: as before), the test a scalar one: no instantiation of its own is needed.
 // Forecast member k is member k + (k >= t) of the ensemble (t = B: none skipped).  Every sum is a running sum from +0
 // in member order, without FMA contraction; / and sqrt are IEEE fp64 (no fast-math), so the numpy restatement of the
 // csim.h block gives the same bits.  Only interior cells of the forecast members are written; ghost rings, member t
@@ -83,6 +86,7 @@ __global__ __launch_bounds__(64) void k_assim_prior(const double* __restrict__ f
     const int lane = threadIdx.x;
     const int M = a.forecast, t = a.truth_member;
     const int q = first + blockIdx.x;
+    if (a.status && a.status[q]) return;  // screened out: the whole block, before any barrier
     const double* p = f + static_cast<ptrdiff_t>(a.obs.j[q]) * pitch + (LPAD - 1) + a.obs.i[q];
     if constexpr (LIN) {
         linear_h(p, slab, a, q, sh, sh + M);
@@ -132,6 +136,7 @@ __global__ __launch_bounds__(64) void k_assim_update(double* __restrict__ f, int
     const double den = static_cast<double>(M), cden = static_cast<double>(M - 1);
     for (int o = blockIdx.y; o < count; o += gridDim.y) {
         const int q = first + o;
+        if (a.status && a.status[q]) continue;  // screened out: the same in every lane, nothing of it is read
         const int io = a.obs.i[q], jo = a.obs.j[q];
         const int i0 = max(1, io - lx), i1 = min(nx, io + lx), j0 = max(1, jo - ly), j1 = min(ny, jo + ly);
         const long W = i1 - i0 + 1, cells = W * (j1 - j0 + 1);

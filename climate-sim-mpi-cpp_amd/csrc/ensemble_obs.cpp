@@ -2,6 +2,8 @@
 // kernels in ensemble_obs.hip): observations that are planned once and live on the device.  create does what
 // csim_ensemble_assimilate does per call (checks, Gaspari-Cohn table, levels, plan order, upload); the analysis then
 // only points an AssimArgs into the network's buffer and enqueues the launches of ensemble_da.cpp's assim_enqueue.
+// Screening (csim_obs_network_set_active, csim_ensemble_assimilate_screened) adds a mask and a status byte per plan
+// position: one k_obs_screen launch ahead of the analysis, whose kernels then skip what is not used.
 #include <cmath>
 #include <memory>
 #include <new>
@@ -16,6 +18,18 @@ using namespace csim;
 namespace {
 
 static_assert(sizeof(csim_obs_cycle) == sizeof(double) * OBS_CYCLE_FIELDS, "csim_obs_cycle is 13 doubles");
+static_assert(sizeof(csim_obs_screen_cycle) == sizeof(double) * OBS_SCREEN_FIELDS, "csim_obs_screen_cycle is 3 doubles");
+
+// the decision of csim_ensemble_assimilate_screened for one observation, as k_obs_screen makes it
+int screen_decide(double y, double hb, double vb, double r, double tol, bool active) {
+    if (!active) return CSIM_OBS_INACTIVE;
+    if (!(tol > 0)) return CSIM_OBS_USED;
+    const double k2 = tol * tol;
+    const double t = y - hb;
+    const double lhs = t * t;
+    const double rhs = k2 * (vb + r);
+    return lhs <= rhs ? CSIM_OBS_USED : CSIM_OBS_REJECTED;
+}
 
 }  // namespace
 
@@ -29,8 +43,11 @@ struct csim_obs_network {
     ObsLayout l{};
     DeviceBuf dev;
     Staging stage;                      // of set_values
+    Staging mstage;                     // of set_active
     bool has_values = false, has_truth = false, has_diag = false;
-    int cycles = 0;                     // records in the log
+    bool masked = false;                // the mask on the device has an inactive observation (else it is not read)
+    bool analysed = false, screened = false;  // there was an analysis; the last one launched the screening
+    int cycles = 0;                     // records in both logs
     template <class T> T* at(size_t byte) const { return reinterpret_cast<T*>(dev.as<char>() + byte); }
     ObsArgs args() const {
         ObsArgs a{};
@@ -42,7 +59,7 @@ struct csim_obs_network {
         if (ntaps) a.tstart = at<int>(l.tstart), a.toff = at<int>(l.toff), a.tw = at<double>(l.tw);
         return a;
     }
-    void release() { dev.release(), stage.release(); }
+    void release() { dev.release(), stage.release(), mstage.release(); }
 };
 
 void csim_ensemble::Obs::release() {
@@ -139,7 +156,8 @@ int network_create(csim_ensemble* e, int nobs, const int* i, const int* j, const
         }
         const size_t chunks = (static_cast<size_t>(nobs) + OBS_CHUNK - 1) / OBS_CHUNK;
         n->l = obs_layout(nobs, n->ntaps, tcells, hp, OBS_SUMS * chunks,
-                          static_cast<size_t>(OBS_CYCLE_FIELDS) * log_cycles);
+                          static_cast<size_t>(OBS_CYCLE_FIELDS) * log_cycles, OBS_SCREEN_FIELDS * chunks,
+                          static_cast<size_t>(OBS_SCREEN_FIELDS) * log_cycles);
         const ObsLayout& l = n->l;
         std::vector<char> h(l.fixed, 0);
         auto* hi = reinterpret_cast<int*>(h.data() + l.i);
@@ -163,6 +181,7 @@ int network_create(csim_ensemble* e, int nobs, const int* i, const int* j, const
         if (rc == CSIM_OK) {
             err = hipMemsetAsync(n->dev.p, 0, l.total, e->st);
             if (err == hipSuccess) err = hipMemcpyAsync(n->dev.p, h.data(), l.fixed, hipMemcpyHostToDevice, e->st);
+            if (err == hipSuccess) err = ens_launch_obs_screen_log_fill(n->at<double>(l.slog), log_cycles, nobs, e->st);
             if (err == hipSuccess) err = hipStreamSynchronize(e->st);  // h goes away
         }
         if (rc != CSIM_OK) return rc;
@@ -231,6 +250,27 @@ int csim_obs_network_set_values(csim_obs_network* n, const double* y) {
     return CSIM_OK;
 }
 
+int csim_obs_network_set_active(csim_obs_network* n, const unsigned char* active) {
+    CSIM_REQUIRE(n, "null network");
+    bool any = false;
+    if (active)
+        for (int o = 0; o < n->nobs; ++o) {
+            CSIM_REQUIRE(active[o] <= 1, "a mask byte must be 0 or 1");
+            any = any || !active[o];
+        }
+    if (!any) {  // all active: the mask on the device is not read
+        n->masked = false;
+        return CSIM_OK;
+    }
+    void* staged = nullptr;
+    CSIM_TRY(n->mstage.acquire(n->nobs, &staged));
+    auto* hm = static_cast<unsigned char*>(staged);
+    for (int q = 0; q < n->nobs; ++q) hm[q] = active[n->idx[q]];
+    CSIM_TRY(n->mstage.send(n->at<char>(n->l.mask), n->nobs, n->e->st));
+    n->masked = true;
+    return CSIM_OK;
+}
+
 int csim_obs_network_observe(csim_obs_network* n, int source_member, unsigned long long seed, unsigned draw,
                              int noise) {
     CSIM_REQUIRE(n, "null network");
@@ -252,8 +292,21 @@ int csim_obs_noise(unsigned long long seed, unsigned draw, unsigned o, double* z
     return CSIM_OK;
 }
 
+int csim_obs_screen_decide(double y, double hb, double vb, double r, double tol, int active, int* status) {
+    CSIM_REQUIRE(status, "null argument");
+    CSIM_REQUIRE(std::isfinite(tol) && tol >= 0, "tol must be finite and >= 0");
+    CSIM_REQUIRE(active == 0 || active == 1, "active must be 0 or 1");
+    *status = screen_decide(y, hb, vb, r, tol, active == 1);
+    return CSIM_OK;
+}
+
 int csim_ensemble_assimilate_network(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
                                      int record) {
+    return csim_ensemble_assimilate_screened(e, n, inflation, truth_member, record, 0.0);
+}
+
+int csim_ensemble_assimilate_screened(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
+                                      int record, double tol) {
     CSIM_REQUIRE(e, "null ensemble");
     CSIM_REQUIRE(n, "null network");
     CSIM_REQUIRE(n->e == e, "the network belongs to another ensemble");
@@ -265,6 +318,7 @@ int csim_ensemble_assimilate_network(csim_ensemble* e, csim_obs_network* n, doub
     if (M > ASSIM_MAX_MEMBERS)
         return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_network: at most 1024 forecast members");
     CSIM_REQUIRE(record == 0 || record == 1, "record must be 0 or 1");
+    CSIM_REQUIRE(std::isfinite(tol) && tol >= 0, "tol must be finite and >= 0");
     if (!n->has_values)
         return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_network: the network has no values yet "
                                     "(csim_obs_network_set_values or csim_obs_network_observe)");
@@ -288,12 +342,30 @@ int csim_ensemble_assimilate_network(csim_ensemble* e, csim_obs_network* n, doub
     a.hp = n->at<double>(n->l.hp);
     a.prior = nullptr;
     const double* f = e->base(e->cur);
-    if (record) CSIM_HIP(ens_launch_assim_post(g, f, a, n->nobs, n->at<double>(n->l.bg), e->st));
+    // (hb, vb): of a recorded analysis where fetch reads them, of an unrecorded background check where it does not
+    const bool check = tol > 0, screen = check || n->masked;
+    double* bg = n->at<double>(record ? n->l.bg : n->l.sbg);
+    if (record || check) CSIM_HIP(ens_launch_assim_post(g, f, a, n->nobs, bg, e->st));
+    ObsScreen s{};
+    if (screen) {
+        s.mask = n->masked ? n->at<unsigned char>(n->l.mask) : nullptr;
+        s.status = n->at<unsigned char>(n->l.status);
+        s.bg = bg, s.check = check ? 1 : 0, s.k2 = tol * tol;
+        s.cnt = n->at<int>(n->l.cnt);
+        CSIM_HIP(ens_launch_obs_screen(oa, s, e->st));
+        a.status = s.status;
+    }
+    n->analysed = true, n->screened = screen;
     CSIM_TRY(assim_enqueue(e, a, inflation, n->batches));
     if (!record) return CSIM_OK;
     CSIM_HIP(ens_launch_assim_post(g, f, a, n->nobs, n->at<double>(n->l.post), e->st));
-    CSIM_HIP(ens_launch_obs_cycle(oa, n->has_truth,
-                                  n->at<double>(n->l.log) + static_cast<size_t>(OBS_CYCLE_FIELDS) * n->cycles, e->st));
+    double* slot = n->at<double>(n->l.log) + static_cast<size_t>(OBS_CYCLE_FIELDS) * n->cycles;
+    // the screen record of a cycle that is not screened is the (nobs, 0, 0) that create and log_reset put there
+    if (screen)
+        CSIM_HIP(ens_launch_obs_cycle_screened(oa, s, n->has_truth, slot, n->at<double>(n->l.slog) +
+                                               static_cast<size_t>(OBS_SCREEN_FIELDS) * n->cycles, e->st));
+    else
+        CSIM_HIP(ens_launch_obs_cycle(oa, n->has_truth, slot, e->st));
     ++n->cycles;
     n->has_diag = true;
     return CSIM_OK;
@@ -330,9 +402,41 @@ int csim_obs_network_log(csim_obs_network* n, int max, csim_obs_cycle* out, int*
 
 int csim_obs_network_log_reset(csim_obs_network* n) {
     CSIM_REQUIRE(n, "null network");
-    if (n->log_cycles)
+    if (n->log_cycles) {
         CSIM_HIP(hipMemsetAsync(n->at<char>(n->l.log), 0, sizeof(csim_obs_cycle) * n->log_cycles, n->e->st));
+        CSIM_HIP(ens_launch_obs_screen_log_fill(n->at<double>(n->l.slog), n->log_cycles, n->nobs, n->e->st));
+    }
     n->cycles = 0;
+    return CSIM_OK;
+}
+
+int csim_obs_network_screen_log(csim_obs_network* n, int max, csim_obs_screen_cycle* out, int* ncycles) {
+    CSIM_REQUIRE(n, "null network");
+    CSIM_REQUIRE(max >= 0 && (max == 0 || out), "max must be >= 0, with room for that many records");
+    CSIM_HIP(hipStreamSynchronize(n->e->st));
+    const int k = std::min(max, n->cycles);
+    if (k > 0) {
+        CSIM_HIP(hipMemcpyAsync(out, n->at<char>(n->l.slog), sizeof(csim_obs_screen_cycle) * k, hipMemcpyDeviceToHost,
+                                n->e->st));
+        CSIM_HIP(hipStreamSynchronize(n->e->st));
+    }
+    if (ncycles) *ncycles = n->cycles;
+    return CSIM_OK;
+}
+
+int csim_obs_network_status(csim_obs_network* n, unsigned char* status) {
+    CSIM_REQUIRE(n, "null network");
+    CSIM_REQUIRE(status, "null argument");
+    if (!n->analysed) return fail(CSIM_ERR_STATE, "csim_obs_network_status: the network has not been analysed yet");
+    CSIM_HIP(hipStreamSynchronize(n->e->st));
+    if (!n->screened) {  // nothing was screened: every observation was used
+        std::fill(status, status + n->nobs, static_cast<unsigned char>(CSIM_OBS_USED));
+        return CSIM_OK;
+    }
+    std::vector<unsigned char> buf(n->nobs);
+    CSIM_HIP(hipMemcpyAsync(buf.data(), n->at<char>(n->l.status), buf.size(), hipMemcpyDeviceToHost, n->e->st));
+    CSIM_HIP(hipStreamSynchronize(n->e->st));
+    for (int q = 0; q < n->nobs; ++q) status[n->idx[q]] = buf[q];
     return CSIM_OK;
 }
 

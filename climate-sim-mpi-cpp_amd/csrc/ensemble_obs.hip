@@ -10,6 +10,11 @@
 //   k_obs_chunks   one lane per chunk of OBS_CHUNK consecutive input indices: T_c of the eleven sums of a
 //                  csim_obs_cycle, each a running sum from +0 in input order.
 //   k_obs_cycle    one wave: lane f folds T_c of sum f in chunk order from +0 into the log's record.
+//   k_obs_screen   one lane per plan position: the status byte of csim_ensemble_assimilate_screened, plan order, from
+//                  the mask and, with the background check, y, r and the (hb, vb) that k_assim_post has just written.
+// SCR instantiations of k_obs_chunks / k_obs_cycle: an observation whose status is not 0 adds nothing (a running sum
+// that started from +0 is never -0, so adding +0 leaves its bits) and y of it is not read; three counts per chunk are
+// folded in chunk order into n and the screen record.  The SCR = false ones compute what the kernels computed before.
 // The background and posterior diagnostics that k_obs_chunks reads are written by the analysis's own k_assim_post
 // (ens_launch_assim_post), before and after the analysis.  Every product is rounded, no FMA contraction.
 #include "ensemble.hpp"
@@ -48,15 +53,23 @@ __global__ __launch_bounds__(256) void k_obs_observe(const double* __restrict__ 
     a.xt[q] = xt;
 }
 
-__global__ __launch_bounds__(64) void k_obs_chunks(ObsArgs a, int nchunks, int has_truth) {
+template <bool SCR>
+__global__ __launch_bounds__(64) void k_obs_chunks(ObsArgs a, int nchunks, int has_truth,
+                                                   const unsigned char* __restrict__ status, int* __restrict__ cnt) {
     const int c = blockIdx.x * 64 + threadIdx.x;
     if (c >= nchunks) return;
     double s[OBS_SUMS];
 #pragma unroll
     for (int k = 0; k < OBS_SUMS; ++k) s[k] = 0.0;
+    int n[OBS_SCREEN_FIELDS] = {0, 0, 0};
     const int o1 = min(a.nobs, (c + 1) * OBS_CHUNK);
     for (int o = c * OBS_CHUNK; o < o1; ++o) {
         const int q = a.pos[o];
+        if constexpr (SCR) {
+            const int st = status[q];
+            n[0] += st == 0, n[1] += st == 1, n[2] += st >= 2;
+            if (st) continue;
+        }
         const double y = a.y[q];
         const double hb = a.bg[2 * static_cast<size_t>(o)], vb = a.bg[2 * static_cast<size_t>(o) + 1];
         const double ha = a.post[2 * static_cast<size_t>(o)], va = a.post[2 * static_cast<size_t>(o) + 1];
@@ -79,12 +92,26 @@ __global__ __launch_bounds__(64) void k_obs_chunks(ObsArgs a, int nchunks, int h
     }
 #pragma unroll
     for (int k = 0; k < OBS_SUMS; ++k) a.part[static_cast<size_t>(c) * OBS_SUMS + k] = s[k];
+    if constexpr (SCR) {
+#pragma unroll
+        for (int k = 0; k < OBS_SCREEN_FIELDS; ++k) cnt[static_cast<size_t>(c) * OBS_SCREEN_FIELDS + k] = n[k];
+    }
 }
 
+template <bool SCR>
 __global__ __launch_bounds__(64) void k_obs_cycle(const double* __restrict__ part, int nchunks, int nobs, int has_truth,
-                                                  double* __restrict__ slot) {
+                                                  double* __restrict__ slot, const int* __restrict__ cnt,
+                                                  double* __restrict__ sslot) {
     const int k = threadIdx.x;
-    if (k == 0) {
+    if constexpr (SCR) {
+        if (k < OBS_SCREEN_FIELDS) {
+            int n = 0;
+            for (int c = 0; c < nchunks; ++c) n += cnt[static_cast<size_t>(c) * OBS_SCREEN_FIELDS + k];
+            sslot[k] = static_cast<double>(n);
+            if (k == 0) slot[0] = static_cast<double>(n);
+        }
+        if (k == 0) slot[1] = has_truth ? 1.0 : 0.0;
+    } else if (k == 0) {
         slot[0] = static_cast<double>(nobs);
         slot[1] = has_truth ? 1.0 : 0.0;
     }
@@ -92,6 +119,32 @@ __global__ __launch_bounds__(64) void k_obs_cycle(const double* __restrict__ par
     double s = 0.0;
     for (int c = 0; c < nchunks; ++c) s = s + part[static_cast<size_t>(c) * OBS_SUMS + k];
     slot[2 + k] = s;
+}
+
+// status: INACTIVE where the mask says so (y is not looked at), else REJECTED iff the check is made and
+// !(t t <= k2 (vb + r)), t = y - hb: a NaN rejects, equality keeps; every product rounded
+__global__ __launch_bounds__(256) void k_obs_screen(ObsArgs a, ObsScreen s) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= a.nobs) return;
+    unsigned char st = 0;
+    if (s.mask && !s.mask[q]) {
+        st = 1;
+    } else if (s.check) {
+        const size_t o = 2 * static_cast<size_t>(a.idx[q]);
+        const double t = a.y[q] - s.bg[o];
+        const double lhs = t * t;
+        const double rhs = s.k2 * (s.bg[o + 1] + a.r[q]);
+        if (!(lhs <= rhs)) st = 2;
+    }
+    s.status[q] = st;
+}
+
+__global__ __launch_bounds__(256) void k_obs_screen_log_fill(double* __restrict__ slog, int cycles, int nobs) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= cycles) return;
+    slog[static_cast<size_t>(c) * OBS_SCREEN_FIELDS] = static_cast<double>(nobs);
+    slog[static_cast<size_t>(c) * OBS_SCREEN_FIELDS + 1] = 0.0;
+    slog[static_cast<size_t>(c) * OBS_SCREEN_FIELDS + 2] = 0.0;
 }
 
 }  // namespace
@@ -111,10 +164,37 @@ hipError_t ens_launch_obs_observe(const EnsGeom& g, const double* f, const ObsAr
 hipError_t ens_launch_obs_cycle(const ObsArgs& a, bool has_truth, double* slot, hipStream_t st) {
     if (a.nobs <= 0) return hipErrorInvalidValue;
     const int nchunks = (a.nobs + OBS_CHUNK - 1) / OBS_CHUNK;
-    hipLaunchKernelGGL(k_obs_chunks, dim3((nchunks + 63) / 64), dim3(64), 0, st, a, nchunks, has_truth ? 1 : 0);
+    hipLaunchKernelGGL(k_obs_chunks<false>, dim3((nchunks + 63) / 64), dim3(64), 0, st, a, nchunks, has_truth ? 1 : 0,
+                       nullptr, nullptr);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(k_obs_cycle, dim3(1), dim3(64), 0, st, a.part, nchunks, a.nobs, has_truth ? 1 : 0, slot);
+    hipLaunchKernelGGL(k_obs_cycle<false>, dim3(1), dim3(64), 0, st, a.part, nchunks, a.nobs, has_truth ? 1 : 0, slot,
+                       nullptr, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t ens_launch_obs_screen(const ObsArgs& a, const ObsScreen& s, hipStream_t st) {
+    if (a.nobs <= 0 || !s.status || (s.check && !s.bg)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_obs_screen, dim3((a.nobs + 255) / 256), dim3(256), 0, st, a, s);
+    return hipGetLastError();
+}
+
+hipError_t ens_launch_obs_cycle_screened(const ObsArgs& a, const ObsScreen& s, bool has_truth, double* slot,
+                                         double* sslot, hipStream_t st) {
+    if (a.nobs <= 0 || !s.status || !s.cnt || !sslot) return hipErrorInvalidValue;
+    const int nchunks = (a.nobs + OBS_CHUNK - 1) / OBS_CHUNK;
+    hipLaunchKernelGGL(k_obs_chunks<true>, dim3((nchunks + 63) / 64), dim3(64), 0, st, a, nchunks, has_truth ? 1 : 0,
+                       s.status, s.cnt);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL(k_obs_cycle<true>, dim3(1), dim3(64), 0, st, a.part, nchunks, a.nobs, has_truth ? 1 : 0, slot,
+                       s.cnt, sslot);
+    return hipGetLastError();
+}
+
+hipError_t ens_launch_obs_screen_log_fill(double* slog, int cycles, int nobs, hipStream_t st) {
+    if (cycles <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_obs_screen_log_fill, dim3((cycles + 255) / 256), dim3(256), 0, st, slog, cycles, nobs);
     return hipGetLastError();
 }
 

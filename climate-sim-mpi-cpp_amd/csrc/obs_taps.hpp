@@ -16,12 +16,17 @@ int fail(int code, const std::string& msg);  // api.cpp
 // taps: tstart (plan order, n + 1 values), toff (the packed cell offset dj * pitch + di of each tap) and tw, both in
 // plan order of their observations.  Then y and xt (plan order), the analysis's scalars and one batch's h'_k, the
 // background and posterior diagnostics (2 per input index each), the chunk sums of the last record and the log.
+// Screening comes last, so that everything before it stays where it was: the active mask and the status bytes (plan
+// order), (hb, vb) of an unrecorded background check (2 per input index, never fetched), the chunk counts and the
+// screen log.
 struct ObsLayout {
-    size_t i, j, idx, pos, r, sr, rho, tstart, toff, tw, fixed, y, xt, scal, bg, post, part, hp, log, total;
+    size_t i, j, idx, pos, r, sr, rho, tstart, toff, tw, fixed, y, xt, scal, bg, post, part, hp, log, mask, status, sbg,
+        cnt, slog, total;
 };
 // n observations, ntaps taps in all (0: a point network, which has no tap arrays), tcells table cells, hp doubles of
-// h'_k, part doubles of chunk sums, logd doubles of log
-inline ObsLayout obs_layout(size_t n, size_t ntaps, size_t tcells, size_t hp, size_t part, size_t logd) {
+// h'_k, part doubles of chunk sums, logd doubles of log, cnt ints of chunk counts, slogd doubles of screen log
+inline ObsLayout obs_layout(size_t n, size_t ntaps, size_t tcells, size_t hp, size_t part, size_t logd, size_t cnt = 0,
+                            size_t slogd = 0) {
     auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
     ObsLayout l{};
     l.i = 0;
@@ -43,7 +48,12 @@ inline ObsLayout obs_layout(size_t n, size_t ntaps, size_t tcells, size_t hp, si
     l.part = up(l.post + 16 * n);
     l.hp = up(l.part + 8 * part);
     l.log = up(l.hp + 8 * hp);
-    l.total = up(l.log + 8 * logd);
+    l.mask = up(l.log + 8 * logd);
+    l.status = up(l.mask + n);
+    l.sbg = up(l.status + n);
+    l.cnt = up(l.sbg + 16 * n);
+    l.slog = up(l.cnt + 4 * cnt);
+    l.total = up(l.slog + 8 * slogd);
     return l;
 }
 

@@ -117,6 +117,27 @@ public:
         return out;
     }
     void log_reset() { check(csim_obs_network_log_reset(handle())); }
+    // screening (see csim_obs_network_set_active): one byte per observation, 1 active, 0 a missing report; copied
+    // before the call returns, enqueued, and kept until it is replaced
+    void set_active(const std::vector<unsigned char>& active) {
+        if (active.size() != nobs_) throw std::invalid_argument("obs network: one mask byte per observation");
+        check(csim_obs_network_set_active(handle(), active.data()));
+    }
+    void set_all_active() { check(csim_obs_network_set_active(handle(), nullptr)); }
+    // waits for the ensemble's stream: CSIM_OBS_USED / _INACTIVE / _REJECTED per observation for the last analysis
+    std::vector<unsigned char> status() {
+        std::vector<unsigned char> s(nobs_);
+        check(csim_obs_network_status(handle(), s.data()));
+        return s;
+    }
+    // waits for the ensemble's stream: the used / inactive / rejected counts of the recorded analyses, oldest first
+    std::vector<csim_obs_screen_cycle> screen_log() {
+        int k = 0;
+        check(csim_obs_network_screen_log(handle(), 0, nullptr, &k));
+        std::vector<csim_obs_screen_cycle> out(static_cast<std::size_t>(k));
+        check(csim_obs_network_screen_log(handle(), k, out.data(), &k));
+        return out;
+    }
 
 private:
     friend class Ensemble;
@@ -356,9 +377,11 @@ public:
         return t;
     }
     // the analysis with the network's observations, always enqueued; record: also append the cycle's innovation
-    // statistics to the network's log on the device (see csim_ensemble_assimilate_network)
-    void assimilate(ObsNetwork& net, double inflation = 1.0, int t = -1, bool record = false) {
-        check(csim_ensemble_assimilate_network(h_, net.handle(), inflation, t, record ? 1 : 0));
+    // statistics to the network's log on the device (see csim_ensemble_assimilate_network).  screen_tol > 0: the
+    // background check of csim_ensemble_assimilate_screened, which rejects an observation with
+    // (y - hb)^2 > screen_tol^2 (vb + r); the network's active mask acts either way
+    void assimilate(ObsNetwork& net, double inflation = 1.0, int t = -1, bool record = false, double screen_tol = 0.0) {
+        check(csim_ensemble_assimilate_screened(h_, net.handle(), inflation, t, record ? 1 : 0, screen_tol));
     }
     // adds sigma times a seeded Gaussian random field of correlation length corr_len to the interior of every forecast
     // member (t = -1: all members, else member t is left alone); enqueued on the ensemble's stream, so that run() follows

@@ -651,6 +651,60 @@ int csim_obs_linear_check(int nx, int ny, int lx, int ly, int nobs, const int* i
                           const int* di, const int* dj, const double* w);
 int csim_obs_taps_bilinear(int nx, int ny, double x, double y, int* i, int* j, int di[4], int dj[4], double w[4]);
 int csim_obs_taps_box(int nx, int ny, int i, int j, int a, int b, int* ntaps, int* di, int* dj, double* w);
+/* screening: which observations of a network an analysis uses, decided per cycle on the device without a host round
+ * trip: a mask for reports that are missing, and a background (gross-error) check that rejects an observation whose
+ * innovation is large against background variance + r.  Each observation has a status byte for the last analysis:
+ * CSIM_OBS_USED 0, CSIM_OBS_INACTIVE 1, CSIM_OBS_REJECTED 2.  Point and linear networks alike.
+ * set_active: active[o], nobs bytes in input order, each 0 or 1 (any other value: CSIM_ERR_ARG, before anything is
+ *   enqueued); NULL: all active.  Copied before the call returns; the call only enqueues.  The mask belongs to the
+ *   network and stays until it is replaced; a new network is all active.  Values, has_truth, the log and the
+ *   diagnostics are not touched.
+ * assimilate_screened: tol finite and >= 0; tol == 0: no background check, only the mask acts.
+ *   1. (hb_o, vb_o) = mv of csim_ensemble_relax applied to h_k of the observation (point or linear) over the forecast
+ *      members, before the inflation and the first observation: what record = 1 stores.
+ *   2. k2 = tol * tol, the rounded product, formed on the host.  Per observation, without FMA contraction:
+ *          t = y_o - hb_o;   lhs = t * t;   rhs = k2 * (vb_o + r_o)
+ *   3. status_o = INACTIVE where the mask says so (the mask wins; y_o of an inactive observation is never looked at);
+ *      else REJECTED iff tol > 0 and !(lhs <= rhs): a NaN rejects, equality keeps; else USED.
+ *   4. The analysis of csim_ensemble_assimilate follows.  The inflation is applied as before to every interior cell,
+ *      whatever the statuses; the serial filter runs over the USED observations only, in the plan order
+ *      (level, input index) of the full network.  An observation that is not USED takes no turn: it reads nothing and
+ *      writes nothing.  Observations of one level commute exactly, so a subset of a level still does, and the levels and
+ *      launches of the full plan stay valid.
+ *   Two consequences.  ordered = 1: the result is that of csim_ensemble_assimilate with just the USED observations, in
+ *   input order, ordered = 1, bit for bit (conflicting pairs keep their input order in both plans, the others commute
+ *   exactly).  ordered = 0: the order is that of the full plan; a first-fit plan of the subset may order a conflicting
+ *   pair differently, so that identity is not claimed.
+ *   csim_ensemble_assimilate_network(e, n, lambda, t, record) is this call with tol = 0.  With an all-active mask
+ *   (never set, NULL, or all ones) and tol == 0 nothing is screened: no status is computed, the analysis launches what
+ *   it launched before this block existed, and gives the same bits.
+ *   record = 1: (hb, vb) and (ha, va) are stored for every observation, whatever its status.  Every sum_ field of
+ *   csim_obs_cycle keeps its chunks of 256 consecutive input indices; the term of an observation that is not USED is
+ *   +0, which leaves the bits of a running sum that started from +0: the sums over the USED observations.  n = the
+ *   number of USED observations.  A second log runs parallel to the first: per recorded cycle one
+ *   csim_obs_screen_cycle, the counts n_used (== n), n_inactive and n_rejected as doubles, with room for log_cycles
+ *   records; log_reset resets both.  record = 0 with tol > 0 computes (hb, vb) into storage that fetch does not read: bg_* / post_* of
+ *   fetch stay those of the last recorded analysis.
+ *   Errors, all before anything is enqueued, leaving members, values, mask, log and diagnostics as they were: those of
+ *   csim_ensemble_assimilate_network; CSIM_ERR_ARG for tol not finite or < 0.
+ * screen_log: as log, for the csim_obs_screen_cycle records.
+ * status: synchronises the ensemble's stream; nobs bytes in input order for the last analysis of this network, recorded
+ *   or not.  CSIM_ERR_STATE before the first analysis; after an analysis that screened nothing every byte is 0.
+ *   CSIM_ERR_ARG for a null pointer.
+ * screen_decide (host-only, needs no device): *status of steps 2 and 3 for one observation; active is 0 or 1
+ *   (CSIM_ERR_ARG otherwise, and for tol not finite or < 0, and a null status). */
+#define CSIM_OBS_USED 0
+#define CSIM_OBS_INACTIVE 1
+#define CSIM_OBS_REJECTED 2
+int csim_obs_network_set_active(csim_obs_network* n, const unsigned char* active);
+int csim_ensemble_assimilate_screened(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
+                                      int record, double tol);
+typedef struct csim_obs_screen_cycle {
+    double n_used, n_inactive, n_rejected;
+} csim_obs_screen_cycle;
+int csim_obs_network_screen_log(csim_obs_network* n, int max, csim_obs_screen_cycle* out, int* ncycles);
+int csim_obs_network_status(csim_obs_network* n, unsigned char* status);
+int csim_obs_screen_decide(double y, double hb, double vb, double r, double tol, int active, int* status);
 /* options (unknown keys: CSIM_ERR_ARG; "contract": CSIM_ERR_UNSUPPORTED), results never depend on them:
  *   "fuse"        -1 (default) passes of the ensemble depth where the grid allows; 0 / 1 single steps only
  *   "fused_2c"    0/1 (default 1), as for csim_stepper_set_option
