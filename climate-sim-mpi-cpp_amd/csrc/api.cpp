@@ -78,7 +78,7 @@ int finish_partials(const double* scratch_dev, int nblocks, int kind, double out
         } else if (kind == 1) {
             r0 += h[k];
         } else {
-            r0 = std::fmax(r0, h[k]);
+            r0 = max_nan(r0, h[k]);  // fmax would drop the NaN the kernel kept
         }
     }
     out[0] = r0;

@@ -161,6 +161,9 @@ hipError_t launch_minmax(const double* f, int nx, int ny, int pitch, double* scr
 hipError_t launch_sum(const double* f, int nx, int ny, int pitch, double* scratch, hipStream_t st);
 hipError_t launch_linf(const double* a, const double* b, int nx, int ny, int pitch, double* scratch,
                        hipStream_t st);
+// max that keeps a NaN (fmax drops one): every stage of the L-inf reduction — lane, wave, block (k_reduce<2>) and the
+// host merge (finish_partials) — goes through it, so max |a-b| is NaN as soon as one |a-b| is
+__host__ __device__ __forceinline__ double max_nan(double r, double d) { return (d > r || d != d) ? d : r; }
 // position-weighted 64-bit checksum of the interior (k_checksum): min(ny, REDUCE_BLOCKS) u64 partials in `scratch`
 hipError_t launch_checksum(const double* f, int nx, int ny, int pitch, long x_off, long y_off, long nx_global,
                            double* scratch, hipStream_t st);

@@ -380,6 +380,15 @@ __global__ __launch_bounds__(256) void k_gaussian(double* __restrict__ f, int nx
 
 // ---- reductions (wave_min / wave_max / wave_sum: sweep_core.hpp) ---------------------------
 // KIND 0: min/max over i0..i1, j0..j1 ; KIND 1: sum ; KIND 2: max |a-b|
+// NaN: min/max skip it (fmin / fmax; all NaN gives +inf, -inf), the sum carries it, and max |a-b| is NaN as soon as
+// one |a-b| is — max_nan (internal.hpp) at all of its stages, and again on the host (finish_partials), where fmax would lose it.
+// The sum's order is fixed (tests/reduce_restatement.py restates it): a lane adds its columns of its rows serially,
+// then the xor butterfly of wave_sum, the four waves in order, the blocks in order on the host.
+__device__ __forceinline__ double wave_max_nan(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = max_nan(v, __shfl_xor(v, m, 64));
+    return v;
+}
 template <int KIND>
 __global__ __launch_bounds__(256) void k_reduce(const double* __restrict__ a,
                                                 const double* __restrict__ b, int i0, int i1,
@@ -398,7 +407,7 @@ __global__ __launch_bounds__(256) void k_reduce(const double* __restrict__ a,
             } else if (KIND == 1) {
                 r0 = r0 + v;
             } else {
-                r0 = fmax(r0, fabs(v - b[o]));
+                r0 = max_nan(r0, fabs(v - b[o]));
             }
         }
     }
@@ -408,7 +417,7 @@ __global__ __launch_bounds__(256) void k_reduce(const double* __restrict__ a,
     } else if (KIND == 1) {
         r0 = wave_sum(r0);
     } else {
-        r0 = wave_max(r0);
+        r0 = wave_max_nan(r0);
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) {
@@ -425,7 +434,7 @@ __global__ __launch_bounds__(256) void k_reduce(const double* __restrict__ a,
             } else if (KIND == 1) {
                 x0 = x0 + sh[0][w];
             } else {
-                x0 = fmax(x0, sh[0][w]);
+                x0 = max_nan(x0, sh[0][w]);
             }
         }
         partial[blockIdx.x] = x0;

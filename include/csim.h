@@ -103,7 +103,18 @@ int csim_field_fill(csim_field* f, double value);                 /* Field::fill
 int csim_field_copy(csim_field* dst, const csim_field* src);      /* std::copy, main.cpp:104 */
 int csim_field_swap(csim_field* a, csim_field* b);                /* std::swap, main.cpp:109 */
 /* wavefront-level reductions.  minmax spans the whole array, ghosts included, like
- * reference src/main.cpp:73-77; sum/linf span the interior. */
+ * reference src/main.cpp:73-77; sum/linf span the interior.  NaN and Inf are data:
+ *  - minmax skips NaN cells (the reference's std::min_element / max_element skip them too, unless
+ *    the NaN is element 0); an array of nothing but NaN gives (+inf, -inf); +-Inf are values;
+ *    +0 and -0 compare equal, either may be returned.  csim_stepper_minmax and
+ *    csim_ensemble_minmax follow the same rule.
+ *  - sum carries them as IEEE addition does (one NaN -> NaN; +Inf -> +Inf; +Inf and -Inf -> NaN).
+ *    Its order of additions is fixed, so the same field gives the same bits on every call;
+ *    tests/reduce_restatement.py restates it (csim_stepper_sum, csim_ensemble_sum likewise).
+ *  - linf_diff is max |a - b| with NaN propagated: if |a - b| is NaN in any interior cell (NaN in
+ *    one field, NaN in both, Inf of one sign in both) the result is NaN, as numpy's
+ *    abs(a - b).max(); otherwise it is the maximum, +Inf included.  0.0 therefore means that the
+ *    interiors are equal number for number (+0 == -0). */
 int csim_field_minmax(const csim_field* f, double out_min_max[2]);
 int csim_field_sum(const csim_field* f, double* out);
 int csim_field_linf_diff(const csim_field* a, const csim_field* b, double* out);
