@@ -687,17 +687,22 @@ def philox4x32(ctr, key):
     return np.array(o[:], dtype=np.uint32)
 
 
+def _per_element(values, call):
+    """call(v, z) for every element v of an array, z a double the library writes: the doubles as an array of the same
+    shape, a float for a scalar"""
+    out = np.empty(values.shape)
+    z = C.c_double()
+    flat = out.reshape(-1)
+    for n, v in enumerate(values.reshape(-1).tolist()):
+        _ck(call(v, C.byref(z)))
+        flat[n] = z.value
+    return out if out.ndim else float(out)
+
+
 def normal_from_bits(bits):
     """the normal deviate csim_ensemble_perturb makes of 64 random bits (csim_normal_from_bits); a scalar or an array
     of uint64 — host only"""
-    b = np.asarray(bits, dtype=np.uint64)
-    out = np.empty(b.shape)
-    z, fn = C.c_double(), lib().csim_normal_from_bits
-    flat = out.reshape(-1)
-    for n, v in enumerate(b.reshape(-1).tolist()):
-        _ck(fn(v, C.byref(z)))
-        flat[n] = z.value
-    return out if out.ndim else float(out)
+    return _per_element(np.asarray(bits, dtype=np.uint64), lib().csim_normal_from_bits)
 
 
 def ensemble_perturb_taps(d, corr_len, n, periodic=False) -> np.ndarray:
@@ -728,14 +733,8 @@ def obs_noise(seed, draw, o):
     seed, draw = int(seed), int(draw)
     if not (0 <= seed < 1 << 64 and 0 <= draw < 1 << 32):
         raise ValueError("seed must fit 64 bits and draw 32 bits, unsigned")
-    idx = np.asarray(o, dtype=np.uint32)
-    out = np.empty(idx.shape)
-    z, fn = C.c_double(), lib().csim_obs_noise
-    flat = out.reshape(-1)
-    for n, v in enumerate(idx.reshape(-1).tolist()):
-        _ck(fn(seed, draw, v, C.byref(z)))
-        flat[n] = z.value
-    return out if out.ndim else float(out)
+    fn = lib().csim_obs_noise
+    return _per_element(np.asarray(o, dtype=np.uint32), lambda v, z: fn(seed, draw, v, z))
 
 
 OBS_MAX_TAPS = 64  # CSIM_OBS_MAX_TAPS
@@ -908,17 +907,21 @@ class ObsNetwork:
         _ck(lib().csim_obs_network_status(self._h, out.ctypes.data_as(C.POINTER(C.c_ubyte))))
         return out
 
+    def _log(self, fn, record, fields) -> np.ndarray:
+        """the records of one of the two logs as a structured array: their number first, then that many"""
+        k = C.c_int()
+        _ck(fn(self._h, 0, None, C.byref(k)))
+        rec = (record * max(k.value, 1))()
+        _ck(fn(self._h, k.value, rec, C.byref(k)))
+        out = np.zeros(k.value, dtype=[(f, np.float64) for f in fields])
+        for c in range(k.value):
+            out[c] = tuple(getattr(rec[c], f) for f in fields)
+        return out
+
     def screen_log(self) -> np.ndarray:
         """waits for the ensemble's stream; n_used, n_inactive and n_rejected of the recorded analyses, oldest first,
         as a structured array parallel to log() (csim_obs_network_screen_log)"""
-        k = C.c_int()
-        _ck(lib().csim_obs_network_screen_log(self._h, 0, None, C.byref(k)))
-        rec = (CsimObsScreenCycle * max(k.value, 1))()
-        _ck(lib().csim_obs_network_screen_log(self._h, k.value, rec, C.byref(k)))
-        out = np.zeros(k.value, dtype=[(f, np.float64) for f in OBS_SCREEN_FIELDS])
-        for c in range(k.value):
-            out[c] = tuple(getattr(rec[c], f) for f in OBS_SCREEN_FIELDS)
-        return out
+        return self._log(lib().csim_obs_network_screen_log, CsimObsScreenCycle, OBS_SCREEN_FIELDS)
 
     def observe(self, source_member, seed, draw=0, noise=True):
         """the values from member source_member at the observed cells, with noise plus sqrt(r) times the seeded
@@ -949,14 +952,7 @@ class ObsNetwork:
     def log(self) -> np.ndarray:
         """waits for the ensemble's stream; the recorded analyses, oldest first, as a structured array with the fields
         of csim_obs_cycle (csim_obs_network_log)"""
-        k = C.c_int()
-        _ck(lib().csim_obs_network_log(self._h, 0, None, C.byref(k)))
-        rec = (CsimObsCycle * max(k.value, 1))()
-        _ck(lib().csim_obs_network_log(self._h, k.value, rec, C.byref(k)))
-        out = np.zeros(k.value, dtype=[(f, np.float64) for f in OBS_CYCLE_FIELDS])
-        for c in range(k.value):
-            out[c] = tuple(getattr(rec[c], f) for f in OBS_CYCLE_FIELDS)
-        return out
+        return self._log(lib().csim_obs_network_log, CsimObsCycle, OBS_CYCLE_FIELDS)
 
     def log_reset(self):
         _ck(lib().csim_obs_network_log_reset(self._h))

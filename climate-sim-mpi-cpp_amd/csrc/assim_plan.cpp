@@ -1,0 +1,197 @@
+// assim_plan.cpp — the analysis plan on the host (assim_plan.hpp): the Gaspari-Cohn table that the analysis and the
+// perturbation taps share, the levels, the plan order and its batches.  No device, no HIP headers.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <unordered_map>
+
+#include "assim_plan.hpp"
+
+using namespace csim;
+
+namespace {
+
+// the localisation half-width along one axis: the largest a >= 0 with a * h < 2 loc, at most n - 1
+int gc_half(double h, double loc, int n) {
+    const double s = 2.0 * loc;
+    if (static_cast<double>(n - 1) * h < s) return n - 1;
+    int a = static_cast<int>(std::min(std::floor(s / h), static_cast<double>(n - 1)));
+    while (a > 0 && static_cast<double>(a) * h >= s) --a;
+    while (a + 1 < n && static_cast<double>(a + 1) * h < s) ++a;
+    return a;
+}
+
+// Gaspari-Cohn in the Horner forms of csim.h, clamped at +0
+double gc_value(double z) {
+    double v = 0.0;
+    if (z <= 1.0)
+        v = ((((-0.25 * z + 0.5) * z + 0.625) * z - 5.0 / 3.0) * z) * z + 1.0;
+    else if (z < 2.0)
+        v = ((((z / 12.0 - 0.5) * z + 0.625) * z + 5.0 / 3.0) * z - 5.0) * z + 4.0 - 2.0 / (3.0 * z);
+    return v > 0.0 ? v : 0.0;
+}
+
+// the smoothing taps of csim_ensemble_perturb along one axis (csim_ensemble_perturb_taps): the radius, and with `taps`
+// the 2 R + 1 Gaspari-Cohn weights scaled to unit sum of squares
+int perturb_radius(double d, double c, int n, bool periodic) {
+    return c == 0.0 ? 0 : gc_half(d, c, periodic ? (n - 1) / 2 + 1 : n);
+}
+
+void perturb_fill(double d, double c, int R, double* taps) {
+    if (c == 0.0) {
+        taps[0] = 1.0;
+        return;
+    }
+    for (int o = -R; o <= R; ++o) taps[o + R] = gc_value(static_cast<double>(std::abs(o)) * d / c);
+    double S = 0.0;
+    for (int o = 0; o <= 2 * R; ++o) S = S + taps[o] * taps[o];
+    const double norm = std::sqrt(S);
+    for (int o = 0; o <= 2 * R; ++o) taps[o] = taps[o] / norm;
+}
+
+// the levels of csim_ensemble_assim_plan.  Spatial buckets of (2 lx + 1) x (2 ly + 1) cells: observations that
+// conflict lie in the same bucket or in one of its eight neighbours.  First fit keeps one bucket map per level,
+// ordered mode one for all earlier observations.
+int assim_levels(int n, const int* oi, const int* oj, int lx, int ly, bool ordered, int* level) {
+    const long long wx = 2LL * lx, wy = 2LL * ly;
+    auto bucket = [&](long long v, long long w) { return v >= 0 ? v / (w + 1) : -((-v + w) / (w + 1)); };
+    auto key = [](long long bi, long long bj) { return static_cast<unsigned long long>(bi) * 0x9E3779B97F4A7C15ull ^
+                                                       static_cast<unsigned long long>(bj); };
+    using Map = std::unordered_map<unsigned long long, std::vector<int>>;
+    // calls f(p) for every observation p of map m in the 3 x 3 buckets around o that conflicts with o; stops when f
+    // returns true
+    auto scan = [&](const Map& m, int o, auto&& f) {
+        const long long bi = bucket(oi[o], wx), bj = bucket(oj[o], wy);
+        for (long long u = bi - 1; u <= bi + 1; ++u)
+            for (long long v = bj - 1; v <= bj + 1; ++v) {
+                auto it = m.find(key(u, v));
+                if (it == m.end()) continue;
+                for (int p : it->second)
+                    if (std::llabs(static_cast<long long>(oi[p]) - oi[o]) <= wx &&
+                        std::llabs(static_cast<long long>(oj[p]) - oj[o]) <= wy && f(p))
+                        return;
+            }
+    };
+    int nl = 0;
+    if (ordered) {
+        Map all;
+        for (int o = 0; o < n; ++o) {
+            int lv = 0;
+            scan(all, o, [&](int p) {
+                lv = std::max(lv, level[p] + 1);
+                return false;
+            });
+            level[o] = lv;
+            nl = std::max(nl, lv + 1);
+            all[key(bucket(oi[o], wx), bucket(oj[o], wy))].push_back(o);
+        }
+        return nl;
+    }
+    std::vector<Map> per;
+    for (int o = 0; o < n; ++o) {
+        int lv = 0;
+        for (;; ++lv) {
+            if (lv == static_cast<int>(per.size())) break;
+            bool hit = false;
+            scan(per[lv], o, [&](int) { return hit = true; });
+            if (!hit) break;
+        }
+        if (lv == static_cast<int>(per.size())) per.emplace_back();
+        per[lv][key(bucket(oi[o], wx), bucket(oj[o], wy))].push_back(o);
+        level[o] = lv;
+    }
+    return static_cast<int>(per.size());
+}
+
+}  // namespace
+
+namespace csim {
+
+void gc_fill(double dx, double dy, double loc, int lx, int ly, double* table) {
+    const int tw = 2 * lx + 1;
+    for (int b = -ly; b <= ly; ++b)
+        for (int a = -lx; a <= lx; ++a) {
+            const double ax = static_cast<double>(a) * dx, by = static_cast<double>(b) * dy;
+            table[static_cast<size_t>(b + ly) * tw + (a + lx)] = gc_value(std::sqrt(ax * ax + by * by) / loc);
+        }
+}
+
+int assim_plan_build(int nx, int ny, double dx, double dy, double loc, bool ordered, int nobs, const int* i,
+                     const int* j, const double* r, const double* y, AssimPlan* p) {
+    for (int o = 0; o < nobs; ++o) {
+        OBS_REQUIRE(i[o] >= 1 && i[o] <= nx && j[o] >= 1 && j[o] <= ny, "observation outside the interior");
+        OBS_REQUIRE(!y || std::isfinite(y[o]), "observation value must be finite");
+        OBS_REQUIRE(std::isfinite(r[o]) && r[o] > 0, "observation error variance must be finite and > 0");
+    }
+    if (int rc = csim_ensemble_gc_table(dx, dy, loc, nx, ny, &p->lx, &p->ly, nullptr)) return rc;
+    std::vector<int> level(nobs);
+    p->nobs = nobs;
+    p->nlevels = nobs ? assim_levels(nobs, i, j, p->lx, p->ly, ordered, level.data()) : 0;
+    // plan order: by level, then input index (a counting sort)
+    p->off.assign(p->nlevels + 1, 0);
+    for (int o = 0; o < nobs; ++o) ++p->off[level[o] + 1];
+    for (int L = 0; L < p->nlevels; ++L) p->off[L + 1] += p->off[L];
+    p->idx.resize(nobs), p->pi.resize(nobs), p->pj.resize(nobs);
+    std::vector<int> fill(p->off.begin(), p->off.end() - 1);
+    for (int o = 0; o < nobs; ++o) p->idx[fill[level[o]]++] = o;
+    for (int q = 0; q < nobs; ++q) p->pi[q] = i[p->idx[q]], p->pj[q] = j[p->idx[q]];
+    return CSIM_OK;
+}
+
+void assim_batches(int nx, int ny, const AssimPlan& p, int batch, std::vector<AssimBatch>* out) {
+    out->clear();
+    for (int L = 0; L < p.nlevels; ++L)
+        for (int q0 = p.off[L]; q0 < p.off[L + 1]; q0 += batch) {
+            const int n = std::min(batch, p.off[L + 1] - q0);
+            long wcells = 0;
+            for (int q = q0; q < q0 + n; ++q) {
+                const long w = std::min(nx, p.pi[q] + p.lx) - std::max(1, p.pi[q] - p.lx) + 1;
+                const long hgt = std::min(ny, p.pj[q] + p.ly) - std::max(1, p.pj[q] - p.ly) + 1;
+                wcells = std::max(wcells, w * hgt);
+            }
+            out->push_back({q0, n, wcells});
+        }
+}
+
+}  // namespace csim
+
+extern "C" {
+
+int csim_ensemble_gc_table(double dx, double dy, double loc, int nx, int ny, int* lx, int* ly, double* table) {
+    OBS_REQUIRE(lx && ly, "null argument");
+    OBS_REQUIRE(std::isfinite(dx) && dx > 0 && std::isfinite(dy) && dy > 0, "dx/dy must be finite and > 0");
+    OBS_REQUIRE(std::isfinite(loc) && loc > 0, "loc must be finite and > 0");
+    OBS_REQUIRE(nx >= 1 && ny >= 1, "empty grid");
+    *lx = gc_half(dx, loc, nx);
+    *ly = gc_half(dy, loc, ny);
+    if (table) gc_fill(dx, dy, loc, *lx, *ly, table);
+    return CSIM_OK;
+}
+
+int csim_ensemble_assim_plan(int nobs, const int* i, const int* j, int lx, int ly, int ordered, int* level,
+                             int* nlevels) {
+    OBS_REQUIRE(nlevels, "null nlevels");
+    OBS_REQUIRE(nobs >= 0, "nobs must be >= 0");
+    OBS_REQUIRE(nobs == 0 || (i && j && level), "null array");
+    OBS_REQUIRE(lx >= 0 && ly >= 0, "lx and ly must be >= 0");
+    OBS_REQUIRE(ordered == 0 || ordered == 1, "ordered must be 0 or 1");
+    if (nobs > CSIM_ASSIM_MAX_OBS)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assim_plan: at most 2^20 observations");
+    *nlevels = assim_levels(nobs, i, j, lx, ly, ordered == 1, level);
+    return CSIM_OK;
+}
+
+int csim_ensemble_perturb_taps(double d, double corr_len, int n, int periodic, int* R, double* taps) {
+    OBS_REQUIRE(R, "null argument");
+    OBS_REQUIRE(std::isfinite(d) && d > 0, "the spacing must be finite and > 0");
+    OBS_REQUIRE(std::isfinite(corr_len) && corr_len >= 0, "corr_len must be finite and >= 0");
+    OBS_REQUIRE(n >= 1, "empty axis");
+    OBS_REQUIRE(periodic == 0 || periodic == 1, "periodic must be 0 or 1");
+    *R = perturb_radius(d, corr_len, n, periodic == 1);
+    if (*R > CSIM_PERTURB_MAX_RADIUS)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_perturb_taps: the radius exceeds CSIM_PERTURB_MAX_RADIUS");
+    if (taps) perturb_fill(d, corr_len, *R, taps);
+    return CSIM_OK;
+}
+
+}  // extern "C"

@@ -6,8 +6,8 @@
 //                      the pass plan and sign classes, run / sync, per-member reductions, options
 //   ensemble_diag.cpp  diagnostics, synchronous and as _begin / _wait captures: statistics, quantiles (and their
 //                      plan), verification (and its rank slot)
-//   ensemble_da.cpp    data assimilation: the Gaspari-Cohn table, the analysis and its plan, Philox / normal numbers,
-//                      perturbations and their taps, relaxation (prior capture, relax)
+//   ensemble_da.cpp    data assimilation: the analysis of a plan, Philox / normal numbers, perturbations, relaxation
+//                      (prior capture, relax); the plan, the Gaspari-Cohn table and the taps: assim_plan.cpp, without HIP
 //   ensemble_obs.cpp   observation networks: create / destroy, values from the host or from a member, the analysis that
 //                      reads a network, its diagnostics and log
 #include <cmath>

@@ -1,10 +1,8 @@
-// ensemble_da.cpp — the ensemble's data assimilation: the EnSRF analysis and its plan, the seeded perturbations and the
+// ensemble_da.cpp — the ensemble's data assimilation: the EnSRF analysis of a plan, the seeded perturbations and the
 // RTPS / RTPP relaxation (kernels in ensemble_assim.hip, ensemble_perturb.hip, ensemble_relax.hip; random numbers in
-// ensemble_noise.hpp), with the Gaspari-Cohn table that the analysis and the perturbation taps share.
+// ensemble_noise.hpp).  The plan, the Gaspari-Cohn table and the perturbation taps are made in assim_plan.cpp.
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <unordered_map>
 #include <vector>
 
 #include "ensemble_host.hpp"
@@ -13,130 +11,6 @@
 using namespace csim;
 
 namespace {
-
-// the localisation half-width along one axis: the largest a >= 0 with a * h < 2 loc, at most n - 1
-int gc_half(double h, double loc, int n) {
-    const double s = 2.0 * loc;
-    if (static_cast<double>(n - 1) * h < s) return n - 1;
-    int a = static_cast<int>(std::min(std::floor(s / h), static_cast<double>(n - 1)));
-    while (a > 0 && static_cast<double>(a) * h >= s) --a;
-    while (a + 1 < n && static_cast<double>(a + 1) * h < s) ++a;
-    return a;
-}
-
-// Gaspari-Cohn in the Horner forms of csim.h, clamped at +0
-double gc_value(double z) {
-    double v = 0.0;
-    if (z <= 1.0)
-        v = ((((-0.25 * z + 0.5) * z + 0.625) * z - 5.0 / 3.0) * z) * z + 1.0;
-    else if (z < 2.0)
-        v = ((((z / 12.0 - 0.5) * z + 0.625) * z + 5.0 / 3.0) * z - 5.0) * z + 4.0 - 2.0 / (3.0 * z);
-    return v > 0.0 ? v : 0.0;
-}
-
-void gc_fill(double dx, double dy, double loc, int lx, int ly, double* table) {
-    const int tw = 2 * lx + 1;
-    for (int b = -ly; b <= ly; ++b)
-        for (int a = -lx; a <= lx; ++a) {
-            const double ax = static_cast<double>(a) * dx, by = static_cast<double>(b) * dy;
-            table[static_cast<size_t>(b + ly) * tw + (a + lx)] = gc_value(std::sqrt(ax * ax + by * by) / loc);
-        }
-}
-
-// the smoothing taps of csim_ensemble_perturb along one axis (csim_ensemble_perturb_taps): the radius, and with `taps`
-// the 2 R + 1 Gaspari-Cohn weights scaled to unit sum of squares
-int perturb_radius(double d, double c, int n, bool periodic) {
-    return c == 0.0 ? 0 : gc_half(d, c, periodic ? (n - 1) / 2 + 1 : n);
-}
-
-void perturb_fill(double d, double c, int R, double* taps) {
-    if (c == 0.0) {
-        taps[0] = 1.0;
-        return;
-    }
-    for (int o = -R; o <= R; ++o) taps[o + R] = gc_value(static_cast<double>(std::abs(o)) * d / c);
-    double S = 0.0;
-    for (int o = 0; o <= 2 * R; ++o) S = S + taps[o] * taps[o];
-    const double norm = std::sqrt(S);
-    for (int o = 0; o <= 2 * R; ++o) taps[o] = taps[o] / norm;
-}
-
-// the levels of csim_ensemble_assim_plan.  Spatial buckets of (2 lx + 1) x (2 ly + 1) cells: observations that
-// conflict lie in the same bucket or in one of its eight neighbours.  First fit keeps one bucket map per level,
-// ordered mode one for all earlier observations.
-int assim_levels(int n, const int* oi, const int* oj, int lx, int ly, bool ordered, int* level) {
-    const long long wx = 2LL * lx, wy = 2LL * ly;
-    auto bucket = [&](long long v, long long w) { return v >= 0 ? v / (w + 1) : -((-v + w) / (w + 1)); };
-    auto key = [](long long bi, long long bj) { return static_cast<unsigned long long>(bi) * 0x9E3779B97F4A7C15ull ^
-                                                       static_cast<unsigned long long>(bj); };
-    using Map = std::unordered_map<unsigned long long, std::vector<int>>;
-    // calls f(p) for every observation p of map m in the 3 x 3 buckets around o that conflicts with o; stops when f
-    // returns true
-    auto scan = [&](const Map& m, int o, auto&& f) {
-        const long long bi = bucket(oi[o], wx), bj = bucket(oj[o], wy);
-        for (long long u = bi - 1; u <= bi + 1; ++u)
-            for (long long v = bj - 1; v <= bj + 1; ++v) {
-                auto it = m.find(key(u, v));
-                if (it == m.end()) continue;
-                for (int p : it->second)
-                    if (std::llabs(static_cast<long long>(oi[p]) - oi[o]) <= wx &&
-                        std::llabs(static_cast<long long>(oj[p]) - oj[o]) <= wy && f(p))
-                        return;
-            }
-    };
-    int nl = 0;
-    if (ordered) {
-        Map all;
-        for (int o = 0; o < n; ++o) {
-            int lv = 0;
-            scan(all, o, [&](int p) {
-                lv = std::max(lv, level[p] + 1);
-                return false;
-            });
-            level[o] = lv;
-            nl = std::max(nl, lv + 1);
-            all[key(bucket(oi[o], wx), bucket(oj[o], wy))].push_back(o);
-        }
-        return nl;
-    }
-    std::vector<Map> per;
-    for (int o = 0; o < n; ++o) {
-        int lv = 0;
-        for (;; ++lv) {
-            if (lv == static_cast<int>(per.size())) break;
-            bool hit = false;
-            scan(per[lv], o, [&](int) { return hit = true; });
-            if (!hit) break;
-        }
-        if (lv == static_cast<int>(per.size())) per.emplace_back();
-        per[lv][key(bucket(oi[o], wx), bucket(oj[o], wy))].push_back(o);
-        level[o] = lv;
-    }
-    return static_cast<int>(per.size());
-}
-
-// byte layout of the analysis buffer: the staged inputs (y, r, table, i, j, input index), then the device-only
-// scalars (3 per observation), prior and posterior diagnostics (2 each per observation) and one batch's h'_k
-struct AssimLayout {
-    size_t y, r, rho, i, j, idx, staged, scal, prior, post, hp, total;
-};
-AssimLayout assim_layout(size_t n, size_t tcells, size_t hp) {
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-    AssimLayout l{};
-    l.y = 0;
-    l.r = up(l.y + 8 * n);
-    l.rho = up(l.r + 8 * n);
-    l.i = up(l.rho + 8 * tcells);
-    l.j = up(l.i + 4 * n);
-    l.idx = up(l.j + 4 * n);
-    l.staged = up(l.idx + 4 * n);
-    l.scal = l.staged;
-    l.prior = up(l.scal + 24 * n);
-    l.post = up(l.prior + 16 * n);
-    l.hp = up(l.post + 16 * n);
-    l.total = up(l.hp + 8 * hp);
-    return l;
-}
 
 // the checks csim_ensemble_prior_capture and csim_ensemble_relax share
 int relax_check(const csim_ensemble* e, int mode, int truth_member, int* M, int* t) {
@@ -150,22 +24,6 @@ int relax_check(const csim_ensemble* e, int mode, int truth_member, int* M, int*
 }  // namespace
 
 namespace csim {
-
-void assim_batches(const EnsGeom& g, int nlevels, const int* off, const int* pi, const int* pj, int lx, int ly,
-                   int batch, std::vector<AssimBatch>* out) {
-    out->clear();
-    for (int L = 0; L < nlevels; ++L)
-        for (int q0 = off[L]; q0 < off[L + 1]; q0 += batch) {
-            const int n = std::min(batch, off[L + 1] - q0);
-            long wcells = 0;
-            for (int q = q0; q < q0 + n; ++q) {
-                const long w = std::min(g.nx, pi[q] + lx) - std::max(1, pi[q] - lx) + 1;
-                const long hgt = std::min(g.ny, pj[q] + ly) - std::max(1, pj[q] - ly) + 1;
-                wcells = std::max(wcells, w * hgt);
-            }
-            out->push_back({q0, n, wcells});
-        }
-}
 
 int assim_enqueue(csim_ensemble* e, const AssimArgs& a, double inflation, const std::vector<AssimBatch>& batches) {
     const EnsGeom& g = e->g;
@@ -183,124 +41,66 @@ int assim_enqueue(csim_ensemble* e, const AssimArgs& a, double inflation, const 
 
 extern "C" {
 
-int csim_ensemble_gc_table(double dx, double dy, double loc, int nx, int ny, int* lx, int* ly, double* table) {
-    CSIM_REQUIRE(lx && ly, "null argument");
-    CSIM_REQUIRE(std::isfinite(dx) && dx > 0 && std::isfinite(dy) && dy > 0, "dx/dy must be finite and > 0");
-    CSIM_REQUIRE(std::isfinite(loc) && loc > 0, "loc must be finite and > 0");
-    CSIM_REQUIRE(nx >= 1 && ny >= 1, "empty grid");
-    *lx = gc_half(dx, loc, nx);
-    *ly = gc_half(dy, loc, ny);
-    if (table) gc_fill(dx, dy, loc, *lx, *ly, table);
-    return CSIM_OK;
-}
-
-int csim_ensemble_assim_plan(int nobs, const int* i, const int* j, int lx, int ly, int ordered, int* level,
-                             int* nlevels) {
-    CSIM_REQUIRE(nlevels, "null nlevels");
-    CSIM_REQUIRE(nobs >= 0, "nobs must be >= 0");
-    CSIM_REQUIRE(nobs == 0 || (i && j && level), "null array");
-    CSIM_REQUIRE(lx >= 0 && ly >= 0, "lx and ly must be >= 0");
-    CSIM_REQUIRE(ordered == 0 || ordered == 1, "ordered must be 0 or 1");
-    if (nobs > ASSIM_MAX_OBS) return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assim_plan: at most 2^20 observations");
-    *nlevels = assim_levels(nobs, i, j, lx, ly, ordered == 1, level);
-    return CSIM_OK;
-}
-
 int csim_ensemble_assimilate(csim_ensemble* e, int nobs, const int* i, const int* j, const double* y, const double* r,
                              double loc, double inflation, int truth_member, int ordered, double* prior_mean,
                              double* prior_var, double* post_mean, double* post_var, int* nlevels) {
     CSIM_REQUIRE(e, "null ensemble");
     const EnsGeom& g = e->g;
-    const int B = g.members;
     CSIM_REQUIRE(nobs >= 0, "nobs must be >= 0");
     CSIM_REQUIRE(nobs == 0 || (i && j && y && r), "null observation array");
     CSIM_REQUIRE(std::isfinite(loc) && loc > 0, "loc must be finite and > 0");
     CSIM_REQUIRE(std::isfinite(inflation) && inflation >= 1.0, "inflation must be finite and >= 1");
     int M = 0, t = 0;
-    CSIM_TRY(forecast_split(B, truth_member, &M, &t));
+    CSIM_TRY(forecast_split(g.members, truth_member, &M, &t));
     CSIM_REQUIRE(ordered == 0 || ordered == 1, "ordered must be 0 or 1");
     CSIM_REQUIRE(M >= 2, "the analysis needs at least two forecast members");
     if (M > ASSIM_MAX_MEMBERS)
         return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate: at most 1024 forecast members");
     if (nobs > ASSIM_MAX_OBS) return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate: at most 2^20 observations");
-    for (int o = 0; o < nobs; ++o) {
-        CSIM_REQUIRE(i[o] >= 1 && i[o] <= g.nx && j[o] >= 1 && j[o] <= g.ny, "observation outside the interior");
-        CSIM_REQUIRE(std::isfinite(y[o]), "observation value must be finite");
-        CSIM_REQUIRE(std::isfinite(r[o]) && r[o] > 0, "observation error variance must be finite and > 0");
-    }
-    int lx = 0, ly = 0;
-    CSIM_TRY(csim_ensemble_gc_table(e->dx, e->dy, loc, g.nx, g.ny, &lx, &ly, nullptr));
-    std::vector<int> level(nobs);
-    int nl = nobs ? assim_levels(nobs, i, j, lx, ly, ordered == 1, level.data()) : 0;
-    if (nlevels) *nlevels = nl;
+    AssimPlan p;
+    CSIM_TRY(assim_plan_build(g.nx, g.ny, e->dx, e->dy, loc, ordered == 1, nobs, i, j, r, y, &p));
+    if (nlevels) *nlevels = p.nlevels;
     const bool diag = prior_mean || prior_var || post_mean || post_var;
     if (nobs == 0 && inflation == 1.0) return diag ? csim_ensemble_sync(e) : CSIM_OK;
 
-    // plan order: by level, then input index (a counting sort)
-    std::vector<int> off(nl + 1, 0), ord(nobs);
-    for (int o = 0; o < nobs; ++o) ++off[level[o] + 1];
-    for (int L = 0; L < nl; ++L) off[L + 1] += off[L];
-    {
-        std::vector<int> fill(off.begin(), off.end() - 1);
-        for (int o = 0; o < nobs; ++o) ord[fill[level[o]]++] = o;
-    }
-    const size_t tcells = static_cast<size_t>(2 * lx + 1) * (2 * ly + 1);
+    const size_t tcells = static_cast<size_t>(2 * p.lx + 1) * (2 * p.ly + 1);
     const int batch = assim_batch_size(M);
     const size_t hp = static_cast<size_t>(std::min(nobs, batch)) * M;
     const AssimLayout l = assim_layout(nobs, tcells, hp);
 
     // resources: the device buffer grows after the work already enqueued is done with it, the staging buffer after
     // its last copy has run
-    void* staged = nullptr;
+    void* h = nullptr;
     CSIM_TRY(e->assim.dev.reserve(l.total, e->st));
-    CSIM_TRY(e->assim.stage.acquire(l.staged, &staged));
-    char* const h = static_cast<char*>(staged);
-    char* const d = e->assim.dev.as<char>();
-    auto* hy = reinterpret_cast<double*>(h + l.y);
-    auto* hr = reinterpret_cast<double*>(h + l.r);
-    auto* hi = reinterpret_cast<int*>(h + l.i);
-    auto* hj = reinterpret_cast<int*>(h + l.j);
-    auto* hx = reinterpret_cast<int*>(h + l.idx);
-    for (int q = 0; q < nobs; ++q) {
-        const int o = ord[q];
-        hy[q] = y[o], hr[q] = r[o], hi[q] = i[o], hj[q] = j[o], hx[q] = o;
-    }
-    gc_fill(e->dx, e->dy, loc, lx, ly, reinterpret_cast<double*>(h + l.rho));
+    CSIM_TRY(e->assim.stage.acquire(l.staged, &h));
+    void* const d = e->assim.dev.p;
+    double *hy = buf_at<double>(h, l.y), *hr = buf_at<double>(h, l.r);
+    for (int q = 0; q < nobs; ++q) hy[q] = y[p.idx[q]], hr[q] = r[p.idx[q]];
+    std::copy(p.pi.begin(), p.pi.end(), buf_at<int>(h, l.i));
+    std::copy(p.pj.begin(), p.pj.end(), buf_at<int>(h, l.j));
+    std::copy(p.idx.begin(), p.idx.end(), buf_at<int>(h, l.idx));
+    gc_fill(e->dx, e->dy, loc, p.lx, p.ly, buf_at<double>(h, l.rho));
     CSIM_TRY(e->assim.stage.send(d, l.staged, e->st));
 
-    AssimArgs a{};
-    a.forecast = M;
-    a.truth_member = t;
-    a.lx = lx, a.ly = ly;
-    a.rho = reinterpret_cast<const double*>(d + l.rho);
-    a.obs.i = reinterpret_cast<const int*>(d + l.i);
-    a.obs.j = reinterpret_cast<const int*>(d + l.j);
-    a.obs.idx = reinterpret_cast<const int*>(d + l.idx);
-    a.obs.y = reinterpret_cast<const double*>(d + l.y);
-    a.obs.r = reinterpret_cast<const double*>(d + l.r);
-    a.scal = reinterpret_cast<double*>(d + l.scal);
-    a.hp = reinterpret_cast<double*>(d + l.hp);
-    a.prior = prior_mean || prior_var ? reinterpret_cast<double*>(d + l.prior) : nullptr;
-    // a.tstart stays null: point observations
+    const AssimObs obs{buf_at<int>(d, l.i), buf_at<int>(d, l.j), buf_at<int>(d, l.idx), buf_at<double>(d, l.y),
+                       buf_at<double>(d, l.r)};
+    const AssimArgs a = assim_args(M, t, p, buf_at<double>(d, l.rho), obs, buf_at<double>(d, l.scal),
+                                   buf_at<double>(d, l.hp), prior_mean || prior_var ? buf_at<double>(d, l.prior) : nullptr);
     std::vector<AssimBatch> batches;
-    assim_batches(g, nl, off.data(), hi, hj, lx, ly, batch, &batches);
+    assim_batches(g.nx, g.ny, p, batch, &batches);
     CSIM_TRY(assim_enqueue(e, a, inflation, batches));
-    double* f = e->base(e->cur);
     if (!diag) return CSIM_OK;
-    auto* post = reinterpret_cast<double*>(d + l.post);
-    if (post_mean || post_var) CSIM_HIP(ens_launch_assim_post(g, f, a, nobs, post, e->st));
+    double* post = buf_at<double>(d, l.post);
+    if (post_mean || post_var) CSIM_HIP(ens_launch_assim_post(g, e->base(e->cur), a, nobs, post, e->st));
+    // both copies are enqueued, then the call waits once
     std::vector<double> pr(2 * static_cast<size_t>(nobs)), po(2 * static_cast<size_t>(nobs));
     if (a.prior && nobs)
         CSIM_HIP(hipMemcpyAsync(pr.data(), a.prior, sizeof(double) * pr.size(), hipMemcpyDeviceToHost, e->st));
     if ((post_mean || post_var) && nobs)
         CSIM_HIP(hipMemcpyAsync(po.data(), post, sizeof(double) * po.size(), hipMemcpyDeviceToHost, e->st));
     CSIM_HIP(hipStreamSynchronize(e->st));
-    for (int o = 0; o < nobs; ++o) {
-        if (prior_mean) prior_mean[o] = pr[2 * static_cast<size_t>(o)];
-        if (prior_var) prior_var[o] = pr[2 * static_cast<size_t>(o) + 1];
-        if (post_mean) post_mean[o] = po[2 * static_cast<size_t>(o)];
-        if (post_var) post_var[o] = po[2 * static_cast<size_t>(o) + 1];
-    }
+    split_pairs(pr.data(), nobs, prior_mean, prior_var);
+    split_pairs(po.data(), nobs, post_mean, post_var);
     return CSIM_OK;
 }
 
@@ -315,19 +115,6 @@ int csim_philox4x32(const unsigned ctr[4], const unsigned key[2], unsigned out[4
 int csim_normal_from_bits(unsigned long long bits, double* z) {
     CSIM_REQUIRE(z, "null argument");
     *z = normal_from_bits(bits);
-    return CSIM_OK;
-}
-
-int csim_ensemble_perturb_taps(double d, double corr_len, int n, int periodic, int* R, double* taps) {
-    CSIM_REQUIRE(R, "null argument");
-    CSIM_REQUIRE(std::isfinite(d) && d > 0, "the spacing must be finite and > 0");
-    CSIM_REQUIRE(std::isfinite(corr_len) && corr_len >= 0, "corr_len must be finite and >= 0");
-    CSIM_REQUIRE(n >= 1, "empty axis");
-    CSIM_REQUIRE(periodic == 0 || periodic == 1, "periodic must be 0 or 1");
-    *R = perturb_radius(d, corr_len, n, periodic == 1);
-    if (*R > PERTURB_MAX_RADIUS)
-        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_perturb_taps: the radius exceeds CSIM_PERTURB_MAX_RADIUS");
-    if (taps) perturb_fill(d, corr_len, *R, taps);
     return CSIM_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "assim_plan.hpp"
 #include "ensemble.hpp"
 #include "stepper.hpp"
 
@@ -16,6 +17,9 @@
     } while (0)
 
 namespace csim {
+
+// the array of T that starts `byte` bytes into a buffer (the layouts of obs_taps.hpp give the offsets)
+template <class T> T* buf_at(void* base, size_t byte) { return reinterpret_cast<T*>(static_cast<char*>(base) + byte); }
 
 // A device buffer, made on first use and grown to the largest request.  reserve: a buffer that is large enough is
 // untouched; one that is too small is replaced, after `idle` (if given) has drained, since work enqueued there may
@@ -220,17 +224,27 @@ namespace csim {
 // cells of a dense per-cell field, ghost ring included
 inline size_t stats_cells(const csim_ensemble* e) { return static_cast<size_t>(e->g.nx + 2) * (e->g.ny + 2); }
 
-// The launches of an analysis (ensemble_da.cpp), shared by csim_ensemble_assimilate and
+// The launches of an analysis (ensemble_da.cpp) of a plan (assim_plan.hpp), shared by csim_ensemble_assimilate and
 // csim_ensemble_assimilate_network.  h'_k of one batch: 64 MiB, at least 8192 observations
 constexpr size_t ASSIM_HP_DOUBLES = size_t(1) << 23;
 inline int assim_batch_size(int M) { return static_cast<int>(std::min<size_t>(ASSIM_HP_DOUBLES / M, ASSIM_MAX_OBS)); }
-struct AssimBatch {
-    int first, count;  // plan positions
-    long wcells;       // the largest clipped window of the batch in cells
-};
-// the batches of a plan: level L holds the plan positions off[L] .. off[L + 1), (pi, pj) the cells in plan order
-void assim_batches(const EnsGeom& g, int nlevels, const int* off, const int* pi, const int* pj, int lx, int ly,
-                   int batch, std::vector<AssimBatch>* out);
+// the arguments of the analysis kernels for M forecast members without member t, from the device arrays of a plan's
+// observations; a linear network adds its taps, a screened analysis sets `status` afterwards
+inline AssimArgs assim_args(int M, int t, const AssimPlan& p, const double* rho, const AssimObs& obs, double* scal,
+                            double* hp, double* prior, const int* tstart = nullptr, const int* toff = nullptr,
+                            const double* tw = nullptr, int tmax = 0) {
+    AssimArgs a{};
+    a.forecast = M, a.truth_member = t, a.lx = p.lx, a.ly = p.ly;
+    a.rho = rho, a.obs = obs;
+    a.scal = scal, a.hp = hp, a.prior = prior;
+    a.tstart = tstart, a.toff = toff, a.tw = tw, a.tmax = tmax;  // null / 0: point observations
+    return a;
+}
+// n (mean, variance) pairs by input index, already on the host -> two arrays, either may be null
+inline void split_pairs(const double* pairs, int n, double* mean, double* var) {
+    for (int o = 0; mean && o < n; ++o) mean[o] = pairs[2 * static_cast<size_t>(o)];
+    for (int o = 0; var && o < n; ++o) var[o] = pairs[2 * static_cast<size_t>(o) + 1];
+}
 // the inflation (when != 1), then assim_prior and assim_update of every batch in turn, on the ensemble's stream
 int assim_enqueue(csim_ensemble* e, const AssimArgs& a, double inflation, const std::vector<AssimBatch>& batches);
 }  // namespace csim

@@ -1,7 +1,7 @@
 // ensemble_obs.cpp — the observation network (csim_obs_network_* and csim_ensemble_assimilate_network of include/csim.h;
-// kernels in ensemble_obs.hip): observations that are planned once and live on the device.  create does what
-// csim_ensemble_assimilate does per call (checks, Gaspari-Cohn table, levels, plan order, upload); the analysis then
-// only points an AssimArgs into the network's buffer and enqueues the launches of ensemble_da.cpp's assim_enqueue.
+// kernels in ensemble_obs.hip): observations that are planned once and live on the device.  create builds the
+// plan that csim_ensemble_assimilate builds per call (assim_plan_build of assim_plan.hpp) and uploads it; the analysis
+// then only points an AssimArgs into the network's buffer and enqueues the launches of ensemble_da.cpp's assim_enqueue.
 // Screening (csim_obs_network_set_active, csim_ensemble_assimilate_screened) adds a mask and a status byte per plan
 // position: one k_obs_screen launch ahead of the analysis, whose kernels then skip what is not used.
 #include <cmath>
@@ -11,7 +11,6 @@
 
 #include "ensemble_host.hpp"
 #include "ensemble_noise.hpp"
-#include "obs_taps.hpp"
 
 using namespace csim;
 
@@ -33,11 +32,9 @@ int screen_decide(double y, double hb, double vb, double r, double tol, bool act
 
 }  // namespace
 
-struct csim_obs_network {
+struct csim_obs_network : AssimPlan {   // the plan: nobs, nlevels, lx, ly, off, idx, pi, pj
     csim_ensemble* e = nullptr;
-    int nobs = 0, nlevels = 0, lx = 0, ly = 0, log_cycles = 0;
-    int ntaps = 0, tmax = 0;            // of a linear network: taps in all, the most of one observation; else 0
-    std::vector<int> off, pi, pj, idx;  // the plan: level offsets; cells and input index of every plan position
+    int log_cycles = 0, ntaps = 0, tmax = 0;  // ntaps, tmax: a linear network's taps in all, the most of one observation
     std::vector<AssimBatch> batches;    // its launches for batches_m forecast members (made at the first analysis)
     int batches_m = 0;
     ObsLayout l{};
@@ -48,7 +45,7 @@ struct csim_obs_network {
     bool masked = false;                // the mask on the device has an inactive observation (else it is not read)
     bool analysed = false, screened = false;  // there was an analysis; the last one launched the screening
     int cycles = 0;                     // records in both logs
-    template <class T> T* at(size_t byte) const { return reinterpret_cast<T*>(dev.as<char>() + byte); }
+    template <class T> T* at(size_t byte) const { return buf_at<T>(dev.p, byte); }
     ObsArgs args() const {
         ObsArgs a{};
         a.nobs = nobs;
@@ -59,23 +56,20 @@ struct csim_obs_network {
         if (ntaps) a.tstart = at<int>(l.tstart), a.toff = at<int>(l.toff), a.tw = at<double>(l.tw);
         return a;
     }
-    void release() { dev.release(), stage.release(), mstage.release(); }
+    ~csim_obs_network() { dev.release(), stage.release(), mstage.release(); }
 };
 
 void csim_ensemble::Obs::release() {
-    for (csim_obs_network* n : nets) {
-        n->release();
-        delete n;
-    }
+    for (csim_obs_network* n : nets) delete n;
     nets.clear();
 }
 
 namespace {
 
-// nobs values in plan order on the device -> input order on the host; the stream must be idle afterwards
-int fetch_plan_order(const csim_obs_network* n, size_t byte, double* out) {
-    std::vector<double> buf(n->nobs);
-    CSIM_HIP(hipMemcpyAsync(buf.data(), n->at<char>(byte), sizeof(double) * buf.size(), hipMemcpyDeviceToHost, n->e->st));
+// nobs values in plan order on the device -> input order on the host; the stream is idle afterwards
+template <class T> int fetch_plan_order(const csim_obs_network* n, size_t byte, T* out) {
+    std::vector<T> buf(n->nobs);
+    CSIM_HIP(hipMemcpyAsync(buf.data(), n->at<char>(byte), sizeof(T) * buf.size(), hipMemcpyDeviceToHost, n->e->st));
     CSIM_HIP(hipStreamSynchronize(n->e->st));
     for (int q = 0; q < n->nobs; ++q) out[n->idx[q]] = buf[q];
     return CSIM_OK;
@@ -87,10 +81,21 @@ int fetch_pairs(const csim_obs_network* n, size_t byte, double* mean, double* va
     std::vector<double> buf(2 * static_cast<size_t>(n->nobs));
     CSIM_HIP(hipMemcpyAsync(buf.data(), n->at<char>(byte), sizeof(double) * buf.size(), hipMemcpyDeviceToHost, n->e->st));
     CSIM_HIP(hipStreamSynchronize(n->e->st));
-    for (int o = 0; o < n->nobs; ++o) {
-        if (mean) mean[o] = buf[2 * static_cast<size_t>(o)];
-        if (var) var[o] = buf[2 * static_cast<size_t>(o) + 1];
+    split_pairs(buf.data(), n->nobs, mean, var);
+    return CSIM_OK;
+}
+
+// csim_obs_network_log and _screen_log: the first min(max, cycles) records, `record` bytes each, of the log at l.*log
+int fetch_log(csim_obs_network* n, size_t ObsLayout::*log, size_t record, int max, void* out, int* ncycles) {
+    CSIM_REQUIRE(n, "null network");
+    CSIM_REQUIRE(max >= 0 && (max == 0 || out), "max must be >= 0, with room for that many records");
+    CSIM_HIP(hipStreamSynchronize(n->e->st));
+    const int k = std::min(max, n->cycles);
+    if (k > 0) {
+        CSIM_HIP(hipMemcpyAsync(out, n->at<char>(n->l.*log), record * k, hipMemcpyDeviceToHost, n->e->st));
+        CSIM_HIP(hipStreamSynchronize(n->e->st));
     }
+    if (ncycles) *ncycles = n->cycles;
     return CSIM_OK;
 }
 
@@ -115,41 +120,21 @@ int network_create(csim_ensemble* e, int nobs, const int* i, const int* j, const
     CSIM_REQUIRE(ordered == 0 || ordered == 1, "ordered must be 0 or 1");
     CSIM_REQUIRE(log_cycles >= 0 && log_cycles <= 65536, "log_cycles must be in 0 .. 65536");
     if (nobs > ASSIM_MAX_OBS) return fail(CSIM_ERR_UNSUPPORTED, "csim_obs_network_create: at most 2^20 observations");
-    for (int o = 0; o < nobs; ++o) {
-        CSIM_REQUIRE(i[o] >= 1 && i[o] <= g.nx && j[o] >= 1 && j[o] <= g.ny, "observation outside the interior");
-        CSIM_REQUIRE(std::isfinite(r[o]) && r[o] > 0, "observation error variance must be finite and > 0");
-    }
     // the network is the caller's only once everything has worked; no exception crosses the C ABI
-    struct Drop {
-        void operator()(csim_obs_network* p) const {
-            p->release();
-            delete p;
-        }
-    };
     try {
-        int lx = 0, ly = 0, nl = 0;
-        CSIM_TRY(csim_ensemble_gc_table(e->dx, e->dy, loc, g.nx, g.ny, &lx, &ly, nullptr));
-        if (taps) CSIM_TRY(csim_obs_linear_check(g.nx, g.ny, lx, ly, nobs, i, j, taps->start, taps->di, taps->dj, taps->w));
-        std::vector<int> level(nobs);
-        CSIM_TRY(csim_ensemble_assim_plan(nobs, i, j, lx, ly, ordered, level.data(), &nl));
-
-        std::unique_ptr<csim_obs_network, Drop> n(new csim_obs_network);
-        n->e = e, n->nobs = nobs, n->nlevels = nl, n->lx = lx, n->ly = ly, n->log_cycles = log_cycles;
-        // plan order: by level, then input index (a counting sort), as csim_ensemble_assimilate
-        n->off.assign(nl + 1, 0);
-        for (int o = 0; o < nobs; ++o) ++n->off[level[o] + 1];
-        for (int L = 0; L < nl; ++L) n->off[L + 1] += n->off[L];
-        n->pi.resize(nobs), n->pj.resize(nobs), n->idx.resize(nobs);
-        {
-            std::vector<int> fill(n->off.begin(), n->off.end() - 1);
-            for (int o = 0; o < nobs; ++o) n->idx[fill[level[o]]++] = o;
-        }
+        std::unique_ptr<csim_obs_network> n(new csim_obs_network);
+        CSIM_TRY(assim_plan_build(g.nx, g.ny, e->dx, e->dy, loc, ordered == 1, nobs, i, j, r, nullptr, n.get()));
+        // the taps need the half-widths; nothing that the builder does after its checks of the observations can fail,
+        // so their check fires where it did, after those
+        if (taps)
+            CSIM_TRY(csim_obs_linear_check(g.nx, g.ny, n->lx, n->ly, nobs, i, j, taps->start, taps->di, taps->dj, taps->w));
+        n->e = e, n->log_cycles = log_cycles;
         // h'_k of the largest batch of either number of forecast members
         size_t hp = 0;
         for (int M = g.members - 1; M <= g.members; ++M)
             if (M >= 2 && M <= ASSIM_MAX_MEMBERS)
                 hp = std::max(hp, static_cast<size_t>(std::min(nobs, assim_batch_size(M))) * M);
-        const size_t tcells = static_cast<size_t>(2 * lx + 1) * (2 * ly + 1);
+        const size_t tcells = static_cast<size_t>(2 * n->lx + 1) * (2 * n->ly + 1);
         if (taps) {
             n->ntaps = taps->start[nobs];
             for (int o = 0; o < nobs; ++o) n->tmax = std::max(n->tmax, taps->start[o + 1] - taps->start[o]);
@@ -160,31 +145,25 @@ int network_create(csim_ensemble* e, int nobs, const int* i, const int* j, const
                           static_cast<size_t>(OBS_SCREEN_FIELDS) * log_cycles);
         const ObsLayout& l = n->l;
         std::vector<char> h(l.fixed, 0);
-        auto* hi = reinterpret_cast<int*>(h.data() + l.i);
-        auto* hj = reinterpret_cast<int*>(h.data() + l.j);
-        auto* hx = reinterpret_cast<int*>(h.data() + l.idx);
-        auto* hpos = reinterpret_cast<int*>(h.data() + l.pos);
-        auto* hr = reinterpret_cast<double*>(h.data() + l.r);
-        auto* hs = reinterpret_cast<double*>(h.data() + l.sr);
+        std::copy(n->pi.begin(), n->pi.end(), buf_at<int>(h.data(), l.i));
+        std::copy(n->pj.begin(), n->pj.end(), buf_at<int>(h.data(), l.j));
+        std::copy(n->idx.begin(), n->idx.end(), buf_at<int>(h.data(), l.idx));
+        int* hpos = buf_at<int>(h.data(), l.pos);
+        double *hr = buf_at<double>(h.data(), l.r), *hs = buf_at<double>(h.data(), l.sr);
         for (int q = 0; q < nobs; ++q) {
             const int o = n->idx[q];
-            n->pi[q] = hi[q] = i[o], n->pj[q] = hj[q] = j[o], hx[q] = o, hpos[o] = q;
-            hr[q] = r[o], hs[q] = std::sqrt(r[o]);
+            hpos[o] = q, hr[q] = r[o], hs[q] = std::sqrt(r[o]);
         }
         if (taps)
             obs_taps_plan_order(nobs, n->idx.data(), taps->start, taps->di, taps->dj, taps->w, g.pitch,
-                                reinterpret_cast<int*>(h.data() + l.tstart), reinterpret_cast<int*>(h.data() + l.toff),
-                                reinterpret_cast<double*>(h.data() + l.tw));
-        int rc = csim_ensemble_gc_table(e->dx, e->dy, loc, g.nx, g.ny, &lx, &ly, reinterpret_cast<double*>(h.data() + l.rho));
-        if (rc == CSIM_OK) rc = n->dev.reserve(l.total);
-        hipError_t err = hipSuccess;
-        if (rc == CSIM_OK) {
-            err = hipMemsetAsync(n->dev.p, 0, l.total, e->st);
-            if (err == hipSuccess) err = hipMemcpyAsync(n->dev.p, h.data(), l.fixed, hipMemcpyHostToDevice, e->st);
-            if (err == hipSuccess) err = ens_launch_obs_screen_log_fill(n->at<double>(l.slog), log_cycles, nobs, e->st);
-            if (err == hipSuccess) err = hipStreamSynchronize(e->st);  // h goes away
-        }
-        if (rc != CSIM_OK) return rc;
+                                buf_at<int>(h.data(), l.tstart), buf_at<int>(h.data(), l.toff),
+                                buf_at<double>(h.data(), l.tw));
+        gc_fill(e->dx, e->dy, loc, n->lx, n->ly, buf_at<double>(h.data(), l.rho));
+        CSIM_TRY(n->dev.reserve(l.total));
+        hipError_t err = hipMemsetAsync(n->dev.p, 0, l.total, e->st);
+        if (err == hipSuccess) err = hipMemcpyAsync(n->dev.p, h.data(), l.fixed, hipMemcpyHostToDevice, e->st);
+        if (err == hipSuccess) err = ens_launch_obs_screen_log_fill(n->at<double>(l.slog), log_cycles, nobs, e->st);
+        if (err == hipSuccess) err = hipStreamSynchronize(e->st);  // h goes away
         if (err != hipSuccess) return fail(CSIM_ERR_HIP, std::string("csim_obs_network_create: ") + hipGetErrorString(err));
         e->obs.nets.push_back(n.get());
         *out = n.release();
@@ -222,7 +201,6 @@ int csim_obs_network_destroy(csim_obs_network* n) {
     csim_ensemble* e = n->e;
     if (e->st) (void)hipStreamSynchronize(e->st);  // work enqueued there may still use the buffer
     e->obs.nets.erase(std::remove(e->obs.nets.begin(), e->obs.nets.end(), n), e->obs.nets.end());
-    n->release();
     delete n;
     return CSIM_OK;
 }
@@ -313,10 +291,8 @@ int csim_ensemble_assimilate_screened(csim_ensemble* e, csim_obs_network* n, dou
     const EnsGeom& g = e->g;
     CSIM_REQUIRE(std::isfinite(inflation) && inflation >= 1.0, "inflation must be finite and >= 1");
     int M = 0, t = 0;
-    CSIM_TRY(forecast_split(g.members, truth_member, &M, &t));
-    CSIM_REQUIRE(M >= 2, "the analysis needs at least two forecast members");
-    if (M > ASSIM_MAX_MEMBERS)
-        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_network: at most 1024 forecast members");
+    CSIM_TRY(forecast_split(g.members, truth_member, &M, &t, 2, "the analysis needs at least two forecast members",
+                            ASSIM_MAX_MEMBERS, "csim_ensemble_assimilate_network: at most 1024 forecast members"));
     CSIM_REQUIRE(record == 0 || record == 1, "record must be 0 or 1");
     CSIM_REQUIRE(std::isfinite(tol) && tol >= 0, "tol must be finite and >= 0");
     if (!n->has_values)
@@ -326,21 +302,12 @@ int csim_ensemble_assimilate_screened(csim_ensemble* e, csim_obs_network* n, dou
         return fail(CSIM_ERR_STATE, n->log_cycles ? "csim_ensemble_assimilate_network: the log is full"
                                                   : "csim_ensemble_assimilate_network: the network has no log");
     if (n->batches_m != M) {
-        assim_batches(g, n->nlevels, n->off.data(), n->pi.data(), n->pj.data(), n->lx, n->ly, assim_batch_size(M),
-                      &n->batches);
+        assim_batches(g.nx, g.ny, *n, assim_batch_size(M), &n->batches);
         n->batches_m = M;
     }
     const ObsArgs oa = n->args();
-    AssimArgs a{};
-    a.forecast = M;
-    a.truth_member = t;
-    a.lx = n->lx, a.ly = n->ly;
-    a.rho = n->at<double>(n->l.rho);
-    a.obs.i = oa.i, a.obs.j = oa.j, a.obs.idx = oa.idx, a.obs.y = oa.y, a.obs.r = oa.r;
-    a.tstart = oa.tstart, a.toff = oa.toff, a.tw = oa.tw, a.tmax = n->tmax;  // null / 0: point observations
-    a.scal = n->at<double>(n->l.scal);
-    a.hp = n->at<double>(n->l.hp);
-    a.prior = nullptr;
+    AssimArgs a = assim_args(M, t, *n, n->at<double>(n->l.rho), {oa.i, oa.j, oa.idx, oa.y, oa.r}, n->at<double>(n->l.scal),
+                             n->at<double>(n->l.hp), nullptr, oa.tstart, oa.toff, oa.tw, n->tmax);
     const double* f = e->base(e->cur);
     // (hb, vb): of a recorded analysis where fetch reads them, of an unrecorded background check where it does not
     const bool check = tol > 0, screen = check || n->masked;
@@ -388,16 +355,7 @@ int csim_obs_network_fetch(csim_obs_network* n, double* y, double* truth, double
 }
 
 int csim_obs_network_log(csim_obs_network* n, int max, csim_obs_cycle* out, int* ncycles) {
-    CSIM_REQUIRE(n, "null network");
-    CSIM_REQUIRE(max >= 0 && (max == 0 || out), "max must be >= 0, with room for that many records");
-    CSIM_HIP(hipStreamSynchronize(n->e->st));
-    const int k = std::min(max, n->cycles);
-    if (k > 0) {
-        CSIM_HIP(hipMemcpyAsync(out, n->at<char>(n->l.log), sizeof(csim_obs_cycle) * k, hipMemcpyDeviceToHost, n->e->st));
-        CSIM_HIP(hipStreamSynchronize(n->e->st));
-    }
-    if (ncycles) *ncycles = n->cycles;
-    return CSIM_OK;
+    return fetch_log(n, &ObsLayout::log, sizeof(csim_obs_cycle), max, out, ncycles);
 }
 
 int csim_obs_network_log_reset(csim_obs_network* n) {
@@ -411,17 +369,7 @@ int csim_obs_network_log_reset(csim_obs_network* n) {
 }
 
 int csim_obs_network_screen_log(csim_obs_network* n, int max, csim_obs_screen_cycle* out, int* ncycles) {
-    CSIM_REQUIRE(n, "null network");
-    CSIM_REQUIRE(max >= 0 && (max == 0 || out), "max must be >= 0, with room for that many records");
-    CSIM_HIP(hipStreamSynchronize(n->e->st));
-    const int k = std::min(max, n->cycles);
-    if (k > 0) {
-        CSIM_HIP(hipMemcpyAsync(out, n->at<char>(n->l.slog), sizeof(csim_obs_screen_cycle) * k, hipMemcpyDeviceToHost,
-                                n->e->st));
-        CSIM_HIP(hipStreamSynchronize(n->e->st));
-    }
-    if (ncycles) *ncycles = n->cycles;
-    return CSIM_OK;
+    return fetch_log(n, &ObsLayout::slog, sizeof(csim_obs_screen_cycle), max, out, ncycles);
 }
 
 int csim_obs_network_status(csim_obs_network* n, unsigned char* status) {
@@ -433,11 +381,7 @@ int csim_obs_network_status(csim_obs_network* n, unsigned char* status) {
         std::fill(status, status + n->nobs, static_cast<unsigned char>(CSIM_OBS_USED));
         return CSIM_OK;
     }
-    std::vector<unsigned char> buf(n->nobs);
-    CSIM_HIP(hipMemcpyAsync(buf.data(), n->at<char>(n->l.status), buf.size(), hipMemcpyDeviceToHost, n->e->st));
-    CSIM_HIP(hipStreamSynchronize(n->e->st));
-    for (int q = 0; q < n->nobs; ++q) status[n->idx[q]] = buf[q];
-    return CSIM_OK;
+    return fetch_plan_order(n, n->l.status, status);
 }
 
 }  // extern "C"

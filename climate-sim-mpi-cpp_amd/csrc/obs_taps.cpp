@@ -8,11 +8,6 @@
 
 using namespace csim;
 
-#define OBS_REQUIRE(cond, msg)                                \
-    do {                                                      \
-        if (!(cond)) return ::csim::fail(CSIM_ERR_ARG, msg);  \
-    } while (0)
-
 extern "C" {
 
 int csim_obs_linear_check(int nx, int ny, int lx, int ly, int nobs, const int* i, const int* j, const int* start,

@@ -1,7 +1,7 @@
-// obs_taps.hpp — the host-only part of the observation networks that needs neither a device nor the HIP headers: the
-// byte layout of a network's device buffer (used by ensemble_obs.cpp) and, in obs_taps.cpp, the tap builders and the
-// check of linear observations (csim_obs_taps_bilinear, csim_obs_taps_box, csim_obs_linear_check of include/csim.h).
-// tools/obsop_host_check.cpp compiles both with plain g++ under AddressSanitizer.
+// obs_taps.hpp — the host-only part of the observations that needs neither a device nor the HIP headers (as
+// assim_plan.hpp on top of it): the byte layouts of the buffers of the analysis (ensemble_da.cpp) and of a network
+// (ensemble_obs.cpp) and, in obs_taps.cpp, the tap builders and the check of linear observations (csim_obs_taps_bilinear,
+// csim_obs_taps_box, csim_obs_linear_check).  tools/*_host_check.cpp compile them with plain g++ under AddressSanitizer.
 #pragma once
 #include <cstddef>
 #include <string>
@@ -11,6 +11,36 @@
 namespace csim {
 
 int fail(int code, const std::string& msg);  // api.cpp
+// the argument check of every host unit (stepper.hpp's CSIM_REQUIRE is this one)
+#define OBS_REQUIRE(cond, msg)                                \
+    do {                                                      \
+        if (!(cond)) return ::csim::fail(CSIM_ERR_ARG, msg);  \
+    } while (0)
+
+// every array of a device buffer starts at a multiple of 256 bytes
+inline size_t up(size_t b) { return (b + 255) & ~size_t(255); }
+
+// byte layout of csim_ensemble_assimilate's buffer: the staged inputs (y, r, table, i, j, input index), then the
+// device-only scalars (3 per observation), prior and posterior diagnostics (2 each) and one batch's h'_k
+struct AssimLayout {
+    size_t y, r, rho, i, j, idx, staged, scal, prior, post, hp, total;
+};
+inline AssimLayout assim_layout(size_t n, size_t tcells, size_t hp) {
+    AssimLayout l{};
+    l.y = 0;
+    l.r = up(l.y + 8 * n);
+    l.rho = up(l.r + 8 * n);
+    l.i = up(l.rho + 8 * tcells);
+    l.j = up(l.i + 4 * n);
+    l.idx = up(l.j + 4 * n);
+    l.staged = up(l.idx + 4 * n);
+    l.scal = l.staged;
+    l.prior = up(l.scal + 24 * n);
+    l.post = up(l.prior + 16 * n);
+    l.hp = up(l.post + 16 * n);
+    l.total = up(l.hp + 8 * hp);
+    return l;
+}
 
 // Written once at create: i, j, idx, r, sr (plan order), pos (by input index), the table, and of a linear network the
 // taps: tstart (plan order, n + 1 values), toff (the packed cell offset dj * pitch + di of each tap) and tw, both in
@@ -27,7 +57,6 @@ struct ObsLayout {
 // h'_k, part doubles of chunk sums, logd doubles of log, cnt ints of chunk counts, slogd doubles of screen log
 inline ObsLayout obs_layout(size_t n, size_t ntaps, size_t tcells, size_t hp, size_t part, size_t logd, size_t cnt = 0,
                             size_t slogd = 0) {
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
     ObsLayout l{};
     l.i = 0;
     l.j = up(l.i + 4 * n);

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "internal.hpp"
+#include "obs_taps.hpp"
 
 
 #define CSIM_NCCL(expr)                                                                        \
@@ -28,10 +29,7 @@
             return ::csim::fail(CSIM_ERR_RCCL, std::string(#expr) + ": " + ncclGetErrorString(r_)); \
     } while (0)
 
-#define CSIM_REQUIRE(cond, msg) \
-    do {                        \
-        if (!(cond)) return ::csim::fail(CSIM_ERR_ARG, msg); \
-    } while (0)
+#define CSIM_REQUIRE(cond, msg) OBS_REQUIRE(cond, msg)  // obs_taps.hpp
 
 
 struct csim_stepper {

@@ -1,12 +1,18 @@
 #!/bin/bash
 # tools/obsop_sanitize.sh — the host-only code of the linear observations (csrc/obs_taps.cpp, csrc/obs_taps.hpp: the
-# tap builders, csim_obs_linear_check, the layout of a network's buffer) as a stand-alone program under
-# AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.  The build goes to $TMP; nothing in the tree is replaced.
+# tap builders, csim_obs_linear_check, the layout of a network's buffer) and of the analysis plan (csrc/assim_plan.cpp,
+# csrc/assim_plan.hpp: levels, plan order, batches, the per-observation checks; the layout of the analysis buffer), each
+# as a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.  The build goes to $TMP;
+# nothing in the tree is replaced.
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 TMP=${TMPDIR:-/tmp}/csim_sanitize
 mkdir -p "$TMP"
-g++ -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g -O1 -Wall \
-    -ffp-contract=off -I"$R/include" -I"$R/climate-sim-mpi-cpp_amd/csrc" -o "$TMP/obsop_host_check" \
-    "$R/tools/obsop_host_check.cpp" "$R/climate-sim-mpi-cpp_amd/csrc/obs_taps.cpp"
-ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 "$TMP/obsop_host_check"
+S=$R/climate-sim-mpi-cpp_amd/csrc
+CXX=(g++ -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g -O1 -Wall
+     -ffp-contract=off -I"$R/include" -I"$S")
+"${CXX[@]}" -o "$TMP/obsop_host_check" "$R/tools/obsop_host_check.cpp" "$S/obs_taps.cpp"
+"${CXX[@]}" -o "$TMP/assim_plan_host_check" "$R/tools/assim_plan_host_check.cpp" "$S/assim_plan.cpp"
+export ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1
+"$TMP/obsop_host_check"
+"$TMP/assim_plan_host_check"
