@@ -854,7 +854,11 @@ class ObsNetwork:
 
     def close(self):
         if getattr(self, "_h", None):
-            lib().csim_obs_network_destroy(self._h)
+            # A closed ensemble has destroyed its networks.  It clears their handles, but only of those its weak set
+            # still holds: when the collector frees a network together with its ensemble (both kept by a failed
+            # test's traceback, say) it clears the weak references before it runs either __del__
+            if getattr(self._ens, "_h", None):
+                lib().csim_obs_network_destroy(self._h)
             self._h = None
             self._ens._nets.discard(self)
 

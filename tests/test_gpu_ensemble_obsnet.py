@@ -416,6 +416,39 @@ def test_errors_leave_everything_as_it_was(csim):
     other.close()
 
 
+def test_network_collected_together_with_its_ensemble(csim):
+    """An ensemble and its network, neither closed, freed by the cyclic collector in one go, as after a failed test
+    whose traceback keeps both.  The collector clears the ensemble's weak references to its networks before it runs
+    either __del__, so the ensemble cannot clear the network's handle: the network itself must see that its ensemble
+    is closed, and not hand the library a network that went with the ensemble"""
+    import gc
+    import weakref
+
+    e = csim.Ensemble(3, 8, 6, 1.0, 1.0, (0, 0, 0, 0))
+    net = e.obs_network([1, 8], [1, 6], 1.0, 2.0)
+    e.keeps = net                       # the ensemble reaches its network: one cycle, unreachable after the del
+    gone = weakref.ref(e)
+    del e, net
+    gc.collect()
+    assert gone() is None
+    # the other order, by hand: the ensemble first, then a network whose handle it could not clear
+    e = csim.Ensemble(3, 8, 6, 1.0, 1.0, (0, 0, 0, 0))
+    net = e.obs_network([1, 8], [1, 6], 1.0, 2.0)
+    e._nets.clear()
+    e.close()
+    assert net._h is not None
+    net.close()
+    assert net._h is None
+    # the library goes on working
+    e = csim.Ensemble(3, 8, 6, 1.0, 1.0, (0, 0, 0, 0))
+    e.upload_all(np.random.default_rng(0).standard_normal((3, 8, 10)))
+    net = e.obs_network([1, 8], [1, 6], 1.0, 2.0)
+    net.set_values([0.5, -0.5])
+    e.assimilate_network(net)
+    assert np.isfinite(e.download_all()).all()
+    e.close()
+
+
 # ---- an OSSE with observations on the left half of the domain --------------------------------------------------------
 
 def test_osse_with_half_the_domain_observed_by_a_network(csim):

@@ -120,6 +120,16 @@ def test_special_values(csim, B):
     assert np.isnan(got.min[4, 4]) and np.isnan(got.max[4, 4]) and got.min[8, 3] == a[-1, 8, 3]
 
 
+@pytest.mark.parametrize("B", [15, 16, 17, 31, 32, 33, 79, 80, 81, 127, 128, 129, 319, 320, 321])
+def test_member_count_seams(csim, B):
+    """either side of the kernel's member-count edges: a batch of 16 members and two of them, the switch to four
+    loading waves (80 / 81), four cooperative batches (128) and the LDS limit (320 / 321)"""
+    e = ensemble_with(csim, nasty_members(B, 37, 23, seed=1000 + B))
+    a = e.download_all()
+    for ddof in (0, 1):
+        assert_stats(e.stats(ddof), a, ddof, f"member-count seam, B = {B}")
+
+
 def test_null_outputs_are_skipped(csim):
     u0s = random_fields(3, 20, 10, seed=3)
     e = ensemble_with(csim, u0s)
