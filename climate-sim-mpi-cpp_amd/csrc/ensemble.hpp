@@ -167,7 +167,8 @@ struct PerturbArgs {
 hipError_t ens_launch_perturb(const EnsGeom& g, double* f, const PerturbArgs& a, bool centered, hipStream_t st);
 
 // the relaxation of csim_ensemble_prior_capture / csim_ensemble_relax (ensemble_relax.hip), one launch each; forecast
-// member k is member k + (k >= truth_member) (truth_member = B: none skipped), 2 <= forecast <= ASSIM_MAX_MEMBERS.
+// member k is forecast_member(k, truth_member) of ensemble_cell.hpp (truth_member = B: none skipped),
+// 2 <= forecast <= ASSIM_MAX_MEMBERS.
 // sb: nx * ny values, interior cell (i, j) at (j - 1) nx + (i - 1).
 // sb = sqrt(v) of mv(x) on every interior cell
 hipError_t ens_launch_relax_capture(const EnsGeom& g, const double* f, int forecast, int truth_member, double* sb,

@@ -17,13 +17,13 @@
 // Screening (a.status, csim_ensemble_assimilate_screened): a byte per plan position; the block of an observation whose
 // byte is not 0 leaves at once in assim_prior and skips it in assim_update, so it reads and writes nothing.  The
 // pointer is a kernel argument (null: as before), the test a scalar one: no instantiation of its own is needed.
-// Forecast member k is member k + (k >= t) of the ensemble (t = B: none skipped).  Every sum is a running sum from +0
-// in member order, without FMA contraction; / and sqrt are IEEE fp64 (no fast-math), so the numpy restatement of the
-// csim.h block gives the same bits.  Only interior cells of the forecast members are written; ghost rings, member t
-// and the other ping-pong buffer are never touched.
+// Forecast members, cell addressing, the register and memory forms of a cell's members and their running sums are
+// those of ensemble_cell.hpp; the covariance with h'_k and the update are summed and rounded the same way, / and sqrt
+// are IEEE fp64 (no fast-math), so the numpy restatement of the csim.h block gives the same bits.  Only interior cells
+// of the forecast members are written; ghost rings, member t and the other ping-pong buffer are never touched.
 #include <algorithm>
 
-#include "ensemble.hpp"
+#include "ensemble_cell.hpp"
 
 #pragma clang fp contract(off)
 
@@ -32,10 +32,6 @@ namespace csim {
 namespace {
 
 constexpr int ASSIM_GRID_Y = 65535;  // observations per launch row (larger batches loop)
-
-__device__ __forceinline__ double* cell(double* f, int i, int j, int pitch) {
-    return f + static_cast<ptrdiff_t>(j) * pitch + (LPAD - 1) + i;
-}
 
 // LDS of a wave that runs linear_h: M values of h, the tile of 64 members x (tmax | 1) values, 64 tap offsets
 size_t linear_lds(const AssimArgs& a) {
@@ -64,7 +60,7 @@ __device__ __forceinline__ void linear_h(const double* __restrict__ p, long slab
         int m = lane / nt, s = lane - m * nt;
         for (int e = lane; e < n; e += 64) {
             const int k = k0 + m;
-            tile[m * ld + s] = p[static_cast<ptrdiff_t>(k + (k >= t)) * slab + offs[s]];
+            tile[m * ld + s] = p[static_cast<ptrdiff_t>(forecast_member(k, t)) * slab + offs[s]];
             m += dm, s += ds;
             if (s >= nt) s -= nt, ++m;
         }
@@ -87,11 +83,11 @@ __global__ __launch_bounds__(64) void k_assim_prior(const double* __restrict__ f
     const int M = a.forecast, t = a.truth_member;
     const int q = first + blockIdx.x;
     if (a.status && a.status[q]) return;  // screened out: the whole block, before any barrier
-    const double* p = f + static_cast<ptrdiff_t>(a.obs.j[q]) * pitch + (LPAD - 1) + a.obs.i[q];
+    const double* p = cell_ptr(f, a.obs.i[q], a.obs.j[q], pitch);
     if constexpr (LIN) {
         linear_h(p, slab, a, q, sh, sh + M);
     } else {
-        for (int k = lane; k < M; k += 64) sh[k] = p[static_cast<ptrdiff_t>(k + (k >= t)) * slab];
+        for (int k = lane; k < M; k += 64) sh[k] = p[static_cast<ptrdiff_t>(forecast_member(k, t)) * slab];
         __syncthreads();
     }
     double s = 0.0;
@@ -125,15 +121,14 @@ __global__ __launch_bounds__(64) void k_assim_prior(const double* __restrict__ f
 // P > 0: the members in registers (P >= M); P = 0: re-read.  h'_k is staged in LDS (M values, dynamic) and read again
 // after a barrier for the update, so that the compiler does not keep all M of them live next to the members.  With
 // h'_k held in registers instead, P = 64 took 256 VGPRs plus AGPRs (one wave per SIMD); this form compiles to 177
-// VGPRs and no AGPRs (two waves per SIMD), DESIGN §7f.  P steps 4, 8, 16, 32, 48, 64: lanes load P values, those
-// past M being member M - 1 again
+// VGPRs and no AGPRs (two waves per SIMD), DESIGN §7f.  P from for_step
 template <int P>
 __global__ __launch_bounds__(64) void k_assim_update(double* __restrict__ f, int nx, int ny, int pitch, long slab,
                                                      AssimArgs a, int first, int count) {
     extern __shared__ double sh[];  // M values
     const int lane = threadIdx.x;
     const int M = a.forecast, t = a.truth_member, lx = a.lx, ly = a.ly, tw = 2 * lx + 1;
-    const double den = static_cast<double>(M), cden = static_cast<double>(M - 1);
+    const double cden = static_cast<double>(M - 1);
     for (int o = blockIdx.y; o < count; o += gridDim.y) {
         const int q = first + o;
         if (a.status && a.status[q]) continue;  // screened out: the same in every lane, nothing of it is read
@@ -152,22 +147,11 @@ __global__ __launch_bounds__(64) void k_assim_update(double* __restrict__ f, int
             const int ci = i0 + static_cast<int>(e - row * W), cj = j0 + row;
             const double rho = a.rho[static_cast<size_t>(cj - jo + ly) * tw + (ci - io + lx)];
             const bool act = e0 + lane < cells && rho > 0.0;
-            double* p = cell(f, ci, cj, pitch);
             if constexpr (P > 0) {
-                // member base pointers are wave-uniform, the cell's offset in a member is one 32-bit lane value
-                const unsigned off = static_cast<unsigned>(cj * pitch + (LPAD - 1) + ci);
-                // k >= M (P > M) loads member M - 1 again: no branch per member; the sums skip those
                 double x[P];
-#pragma unroll
-                for (int k = 0; k < P; ++k) {
-                    const int kk = min(k, M - 1);
-                    x[k] = f[static_cast<size_t>(kk + (kk >= t)) * slab + off];
-                }
-                double s = 0.0;
-#pragma unroll
-                for (int k = 0; k < P; ++k)
-                    if (k < M) s = s + x[k];
-                const double xbar = s / den;
+                const unsigned off = cell_off(ci, cj, pitch);
+                load_members<P>(f, slab, off, M, t, x);
+                const double xbar = mean_regs<P>(x, M);
                 double c = 0.0;
 #pragma unroll
                 for (int k = 0; k < P; ++k)
@@ -177,18 +161,19 @@ __global__ __launch_bounds__(64) void k_assim_update(double* __restrict__ f, int
                 __syncthreads();
 #pragma unroll
                 for (int k = 0; k < P; ++k)
-                    if (act && k < M) f[static_cast<size_t>(k + (k >= t)) * slab + off] = x[k] + (g * delta - beta * sh[k]);
+                    if (act && k < M)
+                        f[static_cast<size_t>(forecast_member(k, t)) * slab + off] = x[k] + (g * delta - beta * sh[k]);
             } else {
-                double s = 0.0;
-                for (int k = 0; k < M; ++k) s = s + p[static_cast<ptrdiff_t>(k + (k >= t)) * slab];
-                const double xbar = s / den;
+                double* p = cell_ptr(f, ci, cj, pitch);
+                const double xbar = mean_mem(p, slab, 0u, M, t);
                 double c = 0.0;
-                for (int k = 0; k < M; ++k) c = c + (p[static_cast<ptrdiff_t>(k + (k >= t)) * slab] - xbar) * sh[k];
+                for (int k = 0; k < M; ++k)
+                    c = c + (p[static_cast<ptrdiff_t>(forecast_member(k, t)) * slab] - xbar) * sh[k];
                 const double g = (rho * (c / cden)) / d;
                 const double beta = alpha * g;
                 if (act)
                     for (int k = 0; k < M; ++k) {
-                        double* pk = p + static_cast<ptrdiff_t>(k + (k >= t)) * slab;
+                        double* pk = p + static_cast<ptrdiff_t>(forecast_member(k, t)) * slab;
                         *pk = *pk + (g * delta - beta * sh[k]);
                     }
             }
@@ -200,16 +185,13 @@ __global__ __launch_bounds__(64) void k_assim_update(double* __restrict__ f, int
 __global__ __launch_bounds__(256) void k_assim_inflate(double* __restrict__ f, int nx, int ny, int pitch, long slab,
                                                        int M, int t, double lm1) {
     const long cells = static_cast<long>(nx) * ny;
-    const double den = static_cast<double>(M);
     for (long e = static_cast<long>(blockIdx.x) * 256 + threadIdx.x; e < cells;
          e += static_cast<long>(gridDim.x) * 256) {
-        const int j = static_cast<int>(e / nx);
-        double* p = cell(f, static_cast<int>(e - static_cast<long>(j) * nx) + 1, j + 1, pitch);
-        double s = 0.0;
-        for (int k = 0; k < M; ++k) s = s + p[static_cast<ptrdiff_t>(k + (k >= t)) * slab];
-        const double xbar = s / den;
+        const Cell c = cell_of(e, nx, pitch);
+        double* p = cell_ptr(f, c.i, c.j, pitch);
+        const double xbar = mean_mem(p, slab, 0u, M, t);
         for (int k = 0; k < M; ++k) {
-            double* pk = p + static_cast<ptrdiff_t>(k + (k >= t)) * slab;
+            double* pk = p + static_cast<ptrdiff_t>(forecast_member(k, t)) * slab;
             const double x = *pk;
             *pk = x + lm1 * (x - xbar);
         }
@@ -222,18 +204,11 @@ __global__ __launch_bounds__(256) void k_assim_post(const double* __restrict__ f
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= nobs) return;
     const int M = a.forecast, t = a.truth_member;
-    const double* p = f + static_cast<ptrdiff_t>(a.obs.j[q]) * pitch + (LPAD - 1) + a.obs.i[q];
-    double s = 0.0;
-    for (int k = 0; k < M; ++k) s = s + p[static_cast<ptrdiff_t>(k + (k >= t)) * slab];
-    const double m = s / static_cast<double>(M);
-    double v = 0.0;
-    for (int k = 0; k < M; ++k) {
-        const double dx = p[static_cast<ptrdiff_t>(k + (k >= t)) * slab] - m;
-        v = v + dx * dx;
-    }
+    const double* p = cell_ptr(f, a.obs.i[q], a.obs.j[q], pitch);
+    const double m = mean_mem(p, slab, 0u, M, t);
     const size_t o = 2 * static_cast<size_t>(a.obs.idx[q]);
     post[o] = m;
-    post[o + 1] = v / static_cast<double>(M - 1);
+    post[o + 1] = var_mem(p, slab, 0u, M, t, m);
 }
 
 // the same for linear observations, one wave per observation: mv of csim_ensemble_relax applied to h_k
@@ -242,28 +217,14 @@ __global__ __launch_bounds__(64) void k_assim_post_linear(const double* __restri
     extern __shared__ double sh[];  // linear_lds
     const int M = a.forecast;
     const int q = blockIdx.x;
-    linear_h(f + static_cast<ptrdiff_t>(a.obs.j[q]) * pitch + (LPAD - 1) + a.obs.i[q], slab, a, q, sh, sh + M);
-    double s = 0.0;
-    for (int k = 0; k < M; ++k) s = s + sh[k];
-    const double m = s / static_cast<double>(M);
-    double v = 0.0;
-    for (int k = 0; k < M; ++k) {
-        const double dx = sh[k] - m;
-        v = v + dx * dx;
-    }
+    linear_h(cell_ptr(f, a.obs.i[q], a.obs.j[q], pitch), slab, a, q, sh, sh + M);
+    double m, v;
+    mv(sh, M, m, v);
     if (threadIdx.x == 0) {
         const size_t o = 2 * static_cast<size_t>(a.obs.idx[q]);
         post[o] = m;
-        post[o + 1] = v / static_cast<double>(M - 1);
+        post[o + 1] = v;
     }
-}
-
-template <int P>
-hipError_t launch_update(const EnsGeom& g, double* f, const AssimArgs& a, int first, int count, long wcells,
-                         hipStream_t st) {
-    const dim3 grid(static_cast<unsigned>((wcells + 63) / 64), static_cast<unsigned>(std::min(count, ASSIM_GRID_Y)));
-    hipLaunchKernelGGL(k_assim_update<P>, grid, dim3(64), sizeof(double) * a.forecast, st, f, g.nx, g.ny, g.pitch, g.slab, a, first, count);
-    return hipGetLastError();
 }
 
 }  // namespace
@@ -287,13 +248,12 @@ hipError_t ens_launch_assim_update(const EnsGeom& g, double* f, const AssimArgs&
     if (count <= 0 || wcells <= 0) return hipSuccess;
     const int M = a.forecast;
     if (M < 2 || M > ASSIM_MAX_MEMBERS || wcells > 64L * 0x7fffffffL) return hipErrorInvalidValue;
-    if (M <= 4) return launch_update<4>(g, f, a, first, count, wcells, st);
-    if (M <= 8) return launch_update<8>(g, f, a, first, count, wcells, st);
-    if (M <= 16) return launch_update<16>(g, f, a, first, count, wcells, st);
-    if (M <= 32) return launch_update<32>(g, f, a, first, count, wcells, st);
-    if (M <= 48) return launch_update<48>(g, f, a, first, count, wcells, st);
-    if (M <= 64) return launch_update<64>(g, f, a, first, count, wcells, st);
-    return launch_update<0>(g, f, a, first, count, wcells, st);
+    const dim3 grid(static_cast<unsigned>((wcells + 63) / 64), static_cast<unsigned>(std::min(count, ASSIM_GRID_Y)));
+    return for_step(M, [&](auto s) {
+        hipLaunchKernelGGL(k_assim_update<decltype(s)::value>, grid, dim3(64), sizeof(double) * M, st, f, g.nx, g.ny,
+                           g.pitch, g.slab, a, first, count);
+        return hipGetLastError();
+    });
 }
 
 hipError_t ens_launch_assim_inflate(const EnsGeom& g, double* f, int forecast, int truth_member, double lm1,

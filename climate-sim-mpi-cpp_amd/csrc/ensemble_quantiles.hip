@@ -14,16 +14,11 @@
 // NaN, so a flag taken before the sort decides; the exceedance counts are taken before the sort too.  The members are
 // padded to P = 2^ceil(log2 B) with +inf, which sorts past every real member and leaves s[0 .. B) as it is.
 //
-// Form 1 (B <= 64): one cell per lane, as the statistics kernel: a one-wave workgroup owns 64 consecutive cells, each
-// member's 64 values one coalesced 512-B load, P values per lane in registers, a fully unrolled network with static
-// register indices (instantiated per P = 1 .. 64).  s[lo] is picked by a wave-uniform index.
-// Form 2 (64 < B <= QUANT_MAX_MEMBERS): one cell per wave.  Four waves load a tile of CT consecutive cells x B members
-// into LDS, CT cells per member load (coalesced), cell-major with an odd row stride so that both the tile's stores and a
-// wave's reads down one cell's members are free of bank conflicts.  A wave then holds its cell as E = P/64 values per
-// lane (element e*64 + lane), runs the strides >= 64 inside each lane and the others across lanes (ds_bpermute), writes
-// the sorted column back in place, and one lane per level reads s[lo], s[hi] from there (instantiated per E = 2 .. 64).
-// The networks' pieces are in ensemble_sort.hpp, shared with ensemble_verify.hip.
-#include "ensemble.hpp"
+// Lane form (B <= 64) and wave form (64 < B <= QUANT_MAX_MEMBERS) as ensemble_cell.hpp describes them; the lane form
+// runs one wave per workgroup and picks s[lo] by a wave-uniform index, the wave form writes the sorted column back to
+// its tile in place, and one lane per level reads s[lo], s[hi] from there.  The networks' pieces are in
+// ensemble_sort.hpp, shared with ensemble_verify.hip.
+#include "ensemble_cell.hpp"
 #include "ensemble_sort.hpp"
 
 #pragma clang fp contract(off)
@@ -31,9 +26,6 @@
 namespace csim {
 
 namespace {
-
-constexpr int QUANT_LDS_BUDGET = 64 * 1024;  // form 2 tile target: two workgroups (eight waves) per CU
-constexpr int QUANT_TILE_MAX = 16;           // form 2 cells per tile, at most
 
 __device__ __forceinline__ double lerp_numpy(double a, double b, double g, bool nan) {
     const double d = b - a;
@@ -48,9 +40,8 @@ __global__ __launch_bounds__(64) void k_quantiles_lane(const double* __restrict_
     const int lane = threadIdx.x;
     const int c = blockIdx.x * 64 + lane;
     const bool valid = c < ncells;
-    const int cc = valid ? c : ncells - 1;  // lanes past the end load a real cell and store nothing
-    const int j = cc / nx2, i = cc - j * nx2;
-    const double* __restrict__ p = f + static_cast<ptrdiff_t>(j) * pitch + (LPAD - 1) + i;
+    const DenseCell dc = dense_cell(c, nx2, ncells);
+    const double* __restrict__ p = cell_ptr(f, dc.i, dc.j, pitch);
 
     double s[P];
 #pragma unroll
@@ -94,23 +85,7 @@ __global__ __launch_bounds__(256) void k_quantiles_wave(const double* __restrict
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c0 = blockIdx.x * ct;
 
-    {  // the tile: thread tid loads cell tid % ct of members tid / ct, + 256 / ct, ...; ct consecutive cells per member
-        const int cl = tid & (ct - 1);
-        const int c = min(c0 + cl, ncells - 1);
-        const int j = c / nx2, i = c - j * nx2;
-        const double* __restrict__ p = f + static_cast<ptrdiff_t>(j) * pitch + (LPAD - 1) + i;
-        const int step = 256 / ct;
-        double* row = held + cl * stride;
-        int m = tid / ct;
-        for (; m + 7 * step < members; m += 8 * step) {
-            double x[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) x[u] = p[static_cast<ptrdiff_t>(m + u * step) * slab];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) row[m + u * step] = x[u];
-        }
-        for (; m < members; m += step) row[m] = p[static_cast<ptrdiff_t>(m) * slab];
-    }
+    CSIM_LOAD_TILE(f, nx2, ncells, pitch, slab, members, ct, stride, c0, tid, held);
     __syncthreads();
 
     // level `lane`'s plan in each lane (static indices only: a runtime index would copy the arguments to scratch)
@@ -164,49 +139,26 @@ __global__ __launch_bounds__(256) void k_quantiles_wave(const double* __restrict
     }
 }
 
-template <int P>
-hipError_t launch_lane(const EnsGeom& g, const double* f, const QuantArgs& qa, double* out, hipStream_t st) {
-    const int nx2 = g.nx + 2, ncells = nx2 * (g.ny + 2);
-    hipLaunchKernelGGL(k_quantiles_lane<P>, dim3((ncells + 63) / 64), dim3(64), 0, st, f, nx2, ncells, g.pitch, g.slab,
-                       g.members, qa, out);
-    return hipGetLastError();
-}
-
-template <int E>
-hipError_t launch_wave(const EnsGeom& g, const double* f, const QuantArgs& qa, double* out, hipStream_t st) {
-    const int nx2 = g.nx + 2, ncells = nx2 * (g.ny + 2);
-    const int stride = g.members | 1;
-    int ct = QUANT_TILE_MAX;
-    while (ct > 4 && static_cast<size_t>(ct) * stride * sizeof(double) > QUANT_LDS_BUDGET) ct >>= 1;
-    const size_t lds = static_cast<size_t>(ct) * stride * sizeof(double);
-    static const hipError_t attr =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_quantiles_wave<E>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(4 * sizeof(double) * (QUANT_MAX_MEMBERS | 1)));
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(k_quantiles_wave<E>, dim3((ncells + ct - 1) / ct), dim3(256), lds, st, f, nx2, ncells, g.pitch,
-                       g.slab, g.members, ct, stride, qa, out);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 hipError_t ens_launch_quantiles(const EnsGeom& g, const double* f, const QuantArgs& qa, double* out, hipStream_t st) {
-    const int B = g.members;
-    if (B <= 1) return launch_lane<1>(g, f, qa, out, st);
-    if (B <= 2) return launch_lane<2>(g, f, qa, out, st);
-    if (B <= 4) return launch_lane<4>(g, f, qa, out, st);
-    if (B <= 8) return launch_lane<8>(g, f, qa, out, st);
-    if (B <= 16) return launch_lane<16>(g, f, qa, out, st);
-    if (B <= 32) return launch_lane<32>(g, f, qa, out, st);
-    if (B <= 64) return launch_lane<64>(g, f, qa, out, st);
-    if (B <= 128) return launch_wave<2>(g, f, qa, out, st);
-    if (B <= 256) return launch_wave<4>(g, f, qa, out, st);
-    if (B <= 512) return launch_wave<8>(g, f, qa, out, st);
-    if (B <= 1024) return launch_wave<16>(g, f, qa, out, st);
-    if (B <= 2048) return launch_wave<32>(g, f, qa, out, st);
-    if (B <= QUANT_MAX_MEMBERS) return launch_wave<64>(g, f, qa, out, st);
-    return hipErrorInvalidValue;  // the host refuses these first
+    const int nx2 = g.nx + 2, ncells = nx2 * (g.ny + 2);
+    return for_sort_form(
+        g.members,
+        [&](auto s) {
+            hipLaunchKernelGGL(k_quantiles_lane<decltype(s)::value>, dim3((ncells + 63) / 64), dim3(64), 0, st, f, nx2,
+                               ncells, g.pitch, g.slab, g.members, qa, out);
+            return hipGetLastError();
+        },
+        [&](auto s) {
+            constexpr int E = decltype(s)::value;
+            const SortTile tile = sort_tile(g.members, 0);
+            const hipError_t attr = dynamic_lds_once<k_quantiles_wave<E>>(sort_tile(QUANT_MAX_MEMBERS, 0).lds);
+            if (attr != hipSuccess) return attr;
+            hipLaunchKernelGGL(k_quantiles_wave<E>, dim3((ncells + tile.ct - 1) / tile.ct), dim3(256), tile.lds, st, f,
+                               nx2, ncells, g.pitch, g.slab, g.members, tile.ct, tile.stride, qa, out);
+            return hipGetLastError();
+        });
 }
 
 }  // namespace csim

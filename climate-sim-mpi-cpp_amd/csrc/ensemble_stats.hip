@@ -13,7 +13,7 @@
 // (two where the cells wrap onto the next row), loaded a batch ahead of their use.  Above that, four waves load the
 // tile into LDS together and one of them runs both passes from there.  LDS holds at most STATS_LDS_MEMBERS members
 // (160 KiB, all of a CU's LDS): the members past that are read from memory in both passes.
-#include "ensemble.hpp"
+#include "ensemble_cell.hpp"
 
 #pragma clang fp contract(off)
 
@@ -37,9 +37,8 @@ __global__ __launch_bounds__(COOP ? 256 : 64) void k_ensemble_stats(const double
     const int lane = threadIdx.x & 63;
     const int c = blockIdx.x * 64 + lane;
     const bool valid = c < ncells;
-    const int cc = valid ? c : ncells - 1;  // lanes past the end load a real cell and store nothing
-    const int j = cc / nx2, i = cc - j * nx2;
-    const double* __restrict__ p = f + static_cast<ptrdiff_t>(j) * pitch + (LPAD - 1) + i;
+    const DenseCell dc = dense_cell(c, nx2, ncells);
+    const double* __restrict__ p = cell_ptr(f, dc.i, dc.j, pitch);
 
     double s = 0.0, lo = __builtin_nan(""), hi = __builtin_nan("");  // fmin(NaN, x) = x
     if (COOP) {
@@ -124,9 +123,7 @@ hipError_t launch_stats(const EnsGeom& g, const double* f, int ddof, double* out
     const int ncells = nx2 * (g.ny + 2);
     const int kl = g.members < STATS_LDS_MEMBERS ? g.members : STATS_LDS_MEMBERS;
     const size_t lds = sizeof(double) * 64 * static_cast<size_t>(kl);
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ensemble_stats<COOP>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       static_cast<int>(sizeof(double) * 64 * STATS_LDS_MEMBERS));
+    const hipError_t attr = dynamic_lds_once<k_ensemble_stats<COOP>>(sizeof(double) * 64 * STATS_LDS_MEMBERS);
     if (attr != hipSuccess) return attr;
     hipLaunchKernelGGL(k_ensemble_stats<COOP>, dim3((ncells + 63) / 64), dim3(COOP ? 256 : 64), lds, st, f, nx2,
                        ncells, g.pitch, g.slab, g.members, kl, static_cast<double>(g.members - ddof), out);

@@ -3,26 +3,27 @@
 // members.  Needs only the slab layout of ensemble.hpp and the sorting networks of ensemble_sort.hpp.
 //
 // M forecast members x_k and the truth y per cell (csim.h has the whole definition).  Forecast member k is member
-// k + (k >= t) of the ensemble, t the truth member (or B: none, the truth comes from a dense device field).  A cell is
-// NaN when y or any x_k is; its CRPS and Brier scores are NaN, and the histogram and the domain scores skip it.
+// forecast_member(k, t) of the ensemble, t the truth member (or B: none, the truth comes from a dense device field).
+// A cell is NaN when y or any x_k is; its CRPS and Brier scores are NaN, and the histogram and the domain scores skip
+// it.
 //   a = sum |x_k - y|, m = sum x_k / M, v = sum (x_k - m)^2 / (M - 1), lt = #(x_k < y), eq = #(x_k == y)
 //   c = sum_{i=1}^{M-1} i (M - i) (s_i - s_{i-1}), s sorted ascending;  CRPS = a / M - c / W, W = M^2 or M (M - 1)
 //   Brier_k = (#(x > thr_k) / M - (y > thr_k))^2;  rank = lt + mix(g) mod (eq + 1), g the interior index
 // Every sum starts from +0.  The order of the per-cell sums is fixed by M alone:
-// Form 1 (M <= 64): one cell per lane, the values in registers, as the quantile kernel's form 1 but with four waves
-// per workgroup.  a, the sum of x, v, the counts and the Brier scores are taken in member order before the sort, c in
-// sorted order after it (CSIM_SORT_LANE).
-// Form 2 (64 < M <= 4096): one cell per wave from an LDS tile, as the quantile kernel's form 2.  Element k is in lane
-// k % 64; each lane sums its elements in increasing k, and the 64 lane sums l are combined as l[i] += l[i ^ h] for
-// h = 32, 16, .., 1 (the same bits in every lane).  c is summed the same way over the sorted index i, whose
-// predecessor s_{i-1} is read from the sorted column written back to LDS.
+// Lane form (M <= 64, ensemble_cell.hpp): one cell per lane, the values in registers, four waves per workgroup.  a,
+// the sum of x, v, the counts and the Brier scores are taken in member order before the sort (five sums in one member
+// loop, so not the header's mean_regs / var_regs), c in sorted order after it (CSIM_SORT_LANE).
+// Wave form (64 < M <= 4096): one cell per wave from the LDS tile of ensemble_cell.hpp, the histogram behind the
+// tile.  Element k is in lane k % 64; each lane sums its elements in increasing k, and the 64 lane sums l are combined
+// as l[i] += l[i ^ h] for h = 32, 16, .., 1 (the same bits in every lane).  c is summed the same way over the sorted
+// index i, whose predecessor s_{i-1} is read from the sorted column written back to LDS.
 // Each workgroup loops over tiles (at most VERIFY_GRID_MAX workgroups), keeps its rank histogram in LDS and flushes it
 // once with one 64-bit atomic per non-empty bin.  Its partial sums of the domain scores are reduced in a fixed order
 // (per-lane sums in tile order, the same xor tree across a wave, then waves 0 .. 3) and stored, one record per
 // workgroup, for the host to add in workgroup order: the same state always gives the same bits.
 #include <algorithm>
 
-#include "ensemble.hpp"
+#include "ensemble_cell.hpp"
 #include "ensemble_sort.hpp"
 
 #pragma clang fp contract(off)
@@ -30,9 +31,6 @@
 namespace csim {
 
 namespace {
-
-constexpr int VERIFY_LDS_BUDGET = 64 * 1024;  // form 2 tile + histogram target: two workgroups per CU
-constexpr int VERIFY_TILE_MAX = 16;           // form 2 cells per tile, at most
 
 // l[lane] + l[lane ^ h] for h = 32 .. 1: the whole wave's sum, the same bits in every lane
 __device__ __forceinline__ double wave_tree(double x, int lane) {
@@ -96,14 +94,14 @@ __global__ __launch_bounds__(256) void k_verify_lane(const double* __restrict__ 
     for (int c0 = blockIdx.x * 256; c0 < ncells; c0 += gridDim.x * 256) {
         const int c = c0 + tid;
         const bool valid = c < ncells;
-        const int cc = valid ? c : ncells - 1;  // lanes past the end load a real cell and store nothing
-        const int j = cc / nx2, i = cc - j * nx2;
-        const double* __restrict__ p = f + static_cast<ptrdiff_t>(j) * pitch + (LPAD - 1) + i;
+        const DenseCell dc = dense_cell(c, nx2, ncells);
+        const int cc = dc.c, i = dc.i, j = dc.j;
+        const double* __restrict__ p = cell_ptr(f, i, j, pitch);
 
         double s[P];
 #pragma unroll
         for (int k = 0; k < P; ++k)
-            s[k] = k < M ? p[static_cast<ptrdiff_t>(k + (k >= t)) * slab] : __builtin_inf();
+            s[k] = k < M ? p[static_cast<ptrdiff_t>(forecast_member(k, t)) * slab] : __builtin_inf();
         const double y = va.truth ? va.truth[cc] : p[static_cast<ptrdiff_t>(t) * slab];
         bool nan = y != y;
 #pragma unroll
@@ -201,36 +199,20 @@ __global__ __launch_bounds__(256) void k_verify_wave(const double* __restrict__ 
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int c0 = tile * ct;
         __syncthreads();  // the previous tile's reads are done (and the zeroing above)
-        {  // the tile, as the quantile kernel loads it: ct consecutive cells per member load
-            const int cl = tid & (ct - 1);
-            const int c = min(c0 + cl, ncells - 1);
-            const int j = c / nx2, i = c - j * nx2;
-            const double* __restrict__ p = f + static_cast<ptrdiff_t>(j) * pitch + (LPAD - 1) + i;
-            const int step = 256 / ct;
-            double* row = held + cl * stride;
-            int m = tid / ct;
-            for (; m + 7 * step < members; m += 8 * step) {
-                double x[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) x[u] = p[static_cast<ptrdiff_t>(m + u * step) * slab];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) row[m + u * step] = x[u];
-            }
-            for (; m < members; m += step) row[m] = p[static_cast<ptrdiff_t>(m) * slab];
-        }
+        CSIM_LOAD_TILE(f, nx2, ncells, pitch, slab, members, ct, stride, c0, tid, held);
         __syncthreads();
 
         for (int cl = wave; cl < ct; cl += 4) {  // the same count in every wave: the barrier below is uniform
             const int c = c0 + cl;
-            const int cc = min(c, ncells - 1);
-            const int j = cc / nx2, i = cc - j * nx2;
+            const DenseCell dc = dense_cell(c, nx2, ncells);
+            const int cc = dc.c, i = dc.i, j = dc.j;
             double* col = held + cl * stride;
             const double y = va.truth ? va.truth[cc] : col[t];
             double v[E];
 #pragma unroll
             for (int e = 0; e < E; ++e) {
                 const int k = e * 64 + lane;
-                v[e] = k < M ? col[k + (k >= t)] : __builtin_inf();
+                v[e] = k < M ? col[forecast_member(k, t)] : __builtin_inf();
             }
             bool nan = y != y;
 #pragma unroll
@@ -310,43 +292,14 @@ __global__ __launch_bounds__(256) void k_verify_wave(const double* __restrict__ 
     finish_block(va, o, hist, wsum, cnt);
 }
 
-template <int P>
-hipError_t launch_lane(const EnsGeom& g, const double* f, const VerifyArgs& va, const VerifyOut& o, hipStream_t st) {
-    hipLaunchKernelGGL(k_verify_lane<P>, dim3(ens_verify_blocks(g, va.forecast)), dim3(256), 0, st, f, g.nx, g.ny,
-                       g.pitch, g.slab, va, o);
-    return hipGetLastError();
-}
-
-// form 2's tile: ct cells of stride B | 1 doubles, halved from VERIFY_TILE_MAX while tile and histogram exceed the
-// budget, down to 4
-int wave_tile(const EnsGeom& g, int forecast) {
-    const int stride = g.members | 1;
-    int ct = VERIFY_TILE_MAX;
-    while (ct > 4 && static_cast<size_t>(ct) * stride * sizeof(double) + sizeof(unsigned) * (forecast + 1) >
-                         VERIFY_LDS_BUDGET)
-        ct >>= 1;
-    return ct;
-}
-
-template <int E>
-hipError_t launch_wave(const EnsGeom& g, const double* f, const VerifyArgs& va, const VerifyOut& o, hipStream_t st) {
-    const int stride = g.members | 1, ct = wave_tile(g, va.forecast);
-    const size_t lds = static_cast<size_t>(ct) * stride * sizeof(double) + sizeof(unsigned) * (va.forecast + 1);
-    // the largest tile: 4 cells of B = VERIFY_MAX_MEMBERS + 1 members (a truth member and 4096 others)
-    static const hipError_t attr = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(k_verify_wave<E>), hipFuncAttributeMaxDynamicSharedMemorySize,
-        static_cast<int>(4 * sizeof(double) * ((VERIFY_MAX_MEMBERS + 1) | 1) + sizeof(unsigned) * (VERIFY_MAX_MEMBERS + 1)));
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(k_verify_wave<E>, dim3(ens_verify_blocks(g, va.forecast)), dim3(256), lds, st, f, g.nx, g.ny,
-                       g.pitch, g.slab, g.members, ct, stride, va, o);
-    return hipGetLastError();
-}
+// the wave form's tile of all B members with the M + 1 bins of the histogram behind it
+SortTile wave_tile(int members, int forecast) { return sort_tile(members, sizeof(unsigned) * (forecast + 1)); }
 
 }  // namespace
 
 int ens_verify_blocks(const EnsGeom& g, int forecast) {
     const int ncells = (g.nx + 2) * (g.ny + 2);
-    const int cells = forecast <= 64 ? 256 : wave_tile(g, forecast);
+    const int cells = forecast <= 64 ? 256 : wave_tile(g.members, forecast).ct;
     return std::min((ncells + cells - 1) / cells, VERIFY_GRID_MAX);
 }
 
@@ -354,20 +307,24 @@ hipError_t ens_launch_verify(const EnsGeom& g, const double* f, const VerifyArgs
                              hipStream_t st) {
     const int M = va.forecast;
     if (M < 1 || va.nt < 0 || va.nt > VERIFY_MAX_THRESHOLDS) return hipErrorInvalidValue;
-    if (M <= 1) return launch_lane<1>(g, f, va, o, st);
-    if (M <= 2) return launch_lane<2>(g, f, va, o, st);
-    if (M <= 4) return launch_lane<4>(g, f, va, o, st);
-    if (M <= 8) return launch_lane<8>(g, f, va, o, st);
-    if (M <= 16) return launch_lane<16>(g, f, va, o, st);
-    if (M <= 32) return launch_lane<32>(g, f, va, o, st);
-    if (M <= 64) return launch_lane<64>(g, f, va, o, st);
-    if (M <= 128) return launch_wave<2>(g, f, va, o, st);
-    if (M <= 256) return launch_wave<4>(g, f, va, o, st);
-    if (M <= 512) return launch_wave<8>(g, f, va, o, st);
-    if (M <= 1024) return launch_wave<16>(g, f, va, o, st);
-    if (M <= 2048) return launch_wave<32>(g, f, va, o, st);
-    if (M <= VERIFY_MAX_MEMBERS) return launch_wave<64>(g, f, va, o, st);
-    return hipErrorInvalidValue;  // the host refuses these first
+    return for_sort_form(
+        M,
+        [&](auto s) {
+            hipLaunchKernelGGL(k_verify_lane<decltype(s)::value>, dim3(ens_verify_blocks(g, M)), dim3(256), 0, st, f,
+                               g.nx, g.ny, g.pitch, g.slab, va, o);
+            return hipGetLastError();
+        },
+        [&](auto s) {
+            constexpr int E = decltype(s)::value;
+            const SortTile tile = wave_tile(g.members, M);
+            // the largest tile: 4 cells of B = VERIFY_MAX_MEMBERS + 1 members (a truth member and 4096 others)
+            const hipError_t attr =
+                dynamic_lds_once<k_verify_wave<E>>(wave_tile(VERIFY_MAX_MEMBERS + 1, VERIFY_MAX_MEMBERS).lds);
+            if (attr != hipSuccess) return attr;
+            hipLaunchKernelGGL(k_verify_wave<E>, dim3(ens_verify_blocks(g, M)), dim3(256), tile.lds, st, f, g.nx, g.ny,
+                               g.pitch, g.slab, g.members, tile.ct, tile.stride, va, o);
+            return hipGetLastError();
+        });
 }
 
 }  // namespace csim

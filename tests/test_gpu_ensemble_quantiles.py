@@ -49,7 +49,7 @@ def check(csim, e, qs=LEVELS, ts=(0.0, 0.5), what=""):
     return a
 
 
-@pytest.mark.parametrize("B", [1, 2, 3, 5, 12, 63, 64, 65, 100, 128, 129, 255, 256, 257, 1000])
+@pytest.mark.parametrize("B", [1, 2, 3, 4, 5, 8, 9, 12, 16, 17, 32, 33, 63, 64, 65, 100, 128, 129, 255, 256, 257, 1000])
 @pytest.mark.parametrize("shape", [(1, 1), (2, 5), (130, 67)])
 def test_members_and_shapes(csim, B, shape):
     nx, ny = shape

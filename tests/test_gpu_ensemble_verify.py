@@ -135,7 +135,7 @@ def pairwise_crps(x, y, fair):
 
 # ---- tests -------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("M", [1, 2, 3, 5, 63, 64, 65, 100, 128, 129, 256, 257, 1000])
+@pytest.mark.parametrize("M", [1, 2, 3, 4, 5, 8, 9, 16, 17, 32, 33, 63, 64, 65, 100, 128, 129, 256, 257, 1000])
 @pytest.mark.parametrize("shape", [(1, 1), (2, 5), (130, 67)])
 def test_members_and_shapes(csim, M, shape):
     nx, ny = shape
@@ -160,7 +160,7 @@ def test_512x512(csim, M):
     check_all(e.verify(y, thresholds=[0.25, 0.75, 0.5]), x, y, [0.25, 0.75, 0.5], False, f"{M} x 512^2")
 
 
-@pytest.mark.parametrize("M", [2048, 4095, 4096])
+@pytest.mark.parametrize("M", [2048, 2049, 4095, 4096])
 def test_largest_networks(csim, M):
     x = np.random.default_rng(M).standard_normal((M, 3, 3))
     x[: M // 3, 0, 1] = 0.5  # ties with the truth
