@@ -60,6 +60,46 @@ Phys make_phys(double dx, double dy, double D, double dt, double vx, double vy, 
         const double thr = std::ldexp(1.0, 1022) / std::pow(g, MAX_FUSE);
         p.fast_thr = (std::isfinite(g) && thr >= std::ldexp(1.0, 900)) ? thr : 0.0;
     }
+    // Power-of-two velocities (cell<.., P2>; derivation: DESIGN.md §4).  A = vx/dx and B = vy/dy are signed powers of
+    // two; the one factored out is vy unless only vx is positive.  Everything below is in exponents, so that no bound
+    // under- or overflows while it is being formed.
+    //   grid: every value a screened tile loads is 0 or >= L = 2^eL in magnitude, hence a multiple of G0 = 2^(eL - 52).
+    //   Sums, differences and the exact fmas of multiples of G are multiples of G.  A product with a power of two 2^e
+    //   is a multiple of 2^e G, a rounded product with any other constant k a multiple of ulp(k) G (ulp(k) =
+    //   2^(ilogb k - 52)).  One time level therefore refines the grid by at most 2^er, and within a level the finest
+    //   intermediate grid is 2^ew times the level's.  As long as every grid stays >= 2^-1074 no operation of either form
+    //   loses a bit to the subnormal range:  eL - 52 + MAX_FUSE er + ew >= -1074  (one level of margin: MAX_FUSE - 1
+    //   levels feed the last one).
+    //   overflow: below fast_thr no level reaches 2^1022; lowering the screen by 2^(eh + 2), 2^eh the largest factor a
+    //   difference is multiplied with in either form, keeps every product and F finite.
+    p.slow_thr = p.p2_hi = p.p2_q = p.p2_k = 0.0;
+    if (!contract && p.div_mode <= 1 && p.fast_thr > 0.0 && pow2(std::fabs(vx)) && pow2(std::fabs(vy)) && std::isfinite(p.kdiff) &&
+        std::isfinite(p.mdt)) {
+        const double A = p.div_mode == 1 ? vx * p.rdx : vx, B = p.div_mode == 1 ? vy * p.rdy : vy;
+        if (pow2(std::fabs(A)) && pow2(std::fabs(B))) {
+            const bool by_y = vy > 0.0 || vx < 0.0;  // the kernel's rule: SY == 1 || SX == 0
+            const double q = by_y ? A / B : B / A, K = p.mdt * (by_y ? B : A);
+            const int eA = std::ilogb(A), eB = std::ilogb(B), eq = std::ilogb(q);
+            int e2 = 0, ew = std::min({0, eA, eB, eq, -eq}), eh = std::max({0, eA, eB, eq, -eq});
+            if (p.div_mode == 1) {
+                e2 = std::min({0, std::ilogb(p.rdx2), std::ilogb(p.rdy2)});
+                ew = std::min({ew, e2, std::ilogb(p.rdx), std::ilogb(p.rdy)});
+                eh = std::max({eh, std::ilogb(p.rdx), std::ilogb(p.rdy)});
+            }
+            int er = 0;
+            if (p.kdiff != 0.0) er = std::min(er, std::ilogb(p.kdiff) - 52 + e2);
+            if (p.mdt != 0.0) er = std::min(er, std::ilogb(p.mdt) - 52 + std::min(eA, eB));
+            const int eL = -1074 + 52 - MAX_FUSE * er - ew;
+            // generous bounds: a screen above 2^-300 would send ordinary far fields to the plain body; a q beyond
+            // 2^+-100 is no velocity field anyone sweeps
+            if (eL <= -300 && eh <= 100 && pow2(std::fabs(q)) && (K == 0.0 || std::isnormal(K))) {  // K: exact unless it underflows
+                p.slow_thr = std::ldexp(1.0, eL);
+                p.p2_hi = std::ldexp(p.fast_thr, -(eh + 2));
+                p.p2_q = q;
+                p.p2_k = K;
+            }
+        }
+    }
     if (contract) p.div_mode = 3;
     return p;
 }
@@ -166,6 +206,14 @@ int csim_device_name(char* buf, size_t n) {
 }
 
 // reference include/stability.hpp:5-16
+// host arithmetic only: what make_phys derives for option "pow2_v" (0 in out[0]: the form is off for these parameters)
+int csim_pow2_velocity_screen(double dx, double dy, double D, double dt, double vx, double vy, double out[4]) {
+    CSIM_REQUIRE(out, "null argument");
+    const Phys p = make_phys(dx, dy, D, dt, vx, vy);
+    out[0] = p.slow_thr, out[1] = p.p2_hi, out[2] = p.p2_q, out[3] = p.p2_k;
+    return CSIM_OK;
+}
+
 double csim_safe_dt(double dx, double dy, double vx, double vy, double D) {
     const double inf = std::numeric_limits<double>::infinity();
     const double ax = std::fabs(vx), ay = std::fabs(vy);

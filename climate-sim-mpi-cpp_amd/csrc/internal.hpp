@@ -55,6 +55,12 @@ struct Phys {
     double a0, aW, aE, aS, aN;  // u' = a0 c + aW W + aE E + aS S + aN N, the same update as one 5-point stencil
     double fast_thr;    // > 0: k_sweepO_dpp may fuse E - 2c into one fma on tiles whose loaded values are all below
                         // this magnitude (no 2c of any level can overflow then); 0: always the plain form
+    // power-of-two velocities (option "pow2_v"; make_phys): the advection term as fma(q, g1, g2) and one
+    // product with K — 12 instead of 14 operations per cell — on tiles whose loaded values are all exactly zero or at
+    // least slow_thr in magnitude, and below p2_hi
+    double slow_thr;    // > 0: the form is enabled for these parameters (the screen's lower bound L); 0: off
+    double p2_hi;       // the screen's upper bound in that body: fast_thr lowered so that no product with q can overflow
+    double p2_q, p2_k;  // q = (vx/dx)/(vy/dy) or its reciprocal, K = (-dt) * the velocity factored out (see cell)
 };
 Phys make_phys(double dx, double dy, double D, double dt, double vx, double vy, bool contract = false);
 

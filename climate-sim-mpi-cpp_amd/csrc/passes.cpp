@@ -393,10 +393,21 @@ int tune_rows(csim_stepper* s, const Phys& p, int T, bool preferred_depth) {
 }  // namespace csim
 
 // Which arithmetic flavour of the multi-step sweep these parameters select (read-only options "fused_2c_active",
-// "diffusion_only_active").  v == 0: the screened interior body drops the advection term (sweep_core.hpp, cell) — another
+// "pow2_v_active", "diffusion_only_active").  v == 0: the screened interior body drops the advection term (sweep_core.hpp, cell) — another
 // balance of arithmetic against HBM traffic, so the chunk heights found for the other flavour are not carried over.
+// Option "pow2_v": 1 takes the 12-operation body wherever the parameters allow it, 2 (default) only on tiles where it was
+// measured to pay.  Launches of two or more rounds of wavefronts are bound by VALU throughput and gain what the body
+// saves (16384^2 +8.5 %, 8192^2 +6.4 %); a launch of one round or less runs as long as its slowest wavefront, and there
+// the body was measured SLOWER (4096 x 8192 -4 %, 4096^2 -17 %; profiles/pow2_velocity_ab.jsonl) — why is not established
+// (the listing differs in the screen: three compares per value instead of one, each handed to the scalar unit).
+constexpr long P2_MIN_CELLS = 60000000L;
+static bool pow2_v_wanted(const csim_stepper* s) {
+    return s->pow2_v == 1 || (s->pow2_v == 2 && static_cast<long>(s->nx) * s->ny >= P2_MIN_CELLS);
+}
+
 static void note_flavour(csim_stepper* s, const Phys& p) {
     s->fused_2c_active = p.fast_thr > 0.0 && p.div_mode != 3;
+    s->pow2_v_active = s->fused_2c_active && p.slow_thr > 0.0;
     const int still = s->fused_2c_active && p.div_mode <= 1 && p.vx == 0.0 && p.vy == 0.0;
     if (still != s->diffusion_only_active) s->forget_tuning();
     s->diffusion_only_active = still;
@@ -410,6 +421,7 @@ int csim_stepper_tune(csim_stepper* s, double D, double dt, double vx, double vy
     CSIM_SETTLE(s);
     Phys p = make_phys(s->dx, s->dy, D, dt, vx, vy, s->contract != 0);
     if (!s->fused_2c) p.fast_thr = 0.0;
+    if (!s->fused_2c || !pow2_v_wanted(s)) p.slow_thr = 0.0;
     note_flavour(s, p);
     const int depth = fused_depth(s);
     if (depth < 2 || s->cfg.rows_per_chunk != 0) return CSIM_OK;
@@ -439,6 +451,7 @@ int csim_stepper_keep_warm(csim_stepper* s, double D, double dt, double vx, doub
     auto elapsed = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
     Phys p = make_phys(s->dx, s->dy, D, dt, vx, vy, s->contract != 0);
     if (!s->fused_2c) p.fast_thr = 0.0;
+    if (!s->fused_2c || !pow2_v_wanted(s)) p.slow_thr = 0.0;
     note_flavour(s, p);
     const int depth = fused_depth(s);
     if (depth < 2) return CSIM_OK;
@@ -462,6 +475,7 @@ int csim_stepper_run(csim_stepper* s, double D, double dt, double vx, double vy,
     CSIM_REQUIRE(nsteps >= 0, "nsteps must be >= 0");
     Phys p = make_phys(s->dx, s->dy, D, dt, vx, vy, s->contract != 0);
     if (!s->fused_2c) p.fast_thr = 0.0;
+    if (!s->fused_2c || !pow2_v_wanted(s)) p.slow_thr = 0.0;
     note_flavour(s, p);  // before the depth: the diffusion-only flavour prefers 7 steps per pass at every size
     // Up to MAX_FUSE steps per HBM pass where possible (across ranks: a tile at least as large as
     // the face depth).

@@ -556,6 +556,11 @@ int csim_stepper_set_option(csim_stepper* s, const char* key, long value) {
         s->direct_faces = value != 0;
     } else if (k == "fused_2c") {
         s->fused_2c = value != 0;
+    } else if (k == "pow2_v") {
+        CSIM_REQUIRE(value >= 0 && value <= 2, "pow2_v must be 0 (off), 1 (on) or 2 (on where it pays: large tiles)");
+        s->pow2_v = static_cast<int>(value);
+    } else if (k == "pow2_v_active") {
+        return fail(CSIM_ERR_ARG, k + " is read-only");
     } else if (k == "external_halo") {
         s->external = value != 0;
         s->halo_fresh = false;
@@ -621,6 +626,8 @@ int csim_stepper_get_option(const csim_stepper* s, const char* key, long* value)
     else if (k == "relay_events") *value = s->relay_events;
     else if (k == "fused_2c") *value = s->fused_2c;
     else if (k == "fused_2c_active") *value = s->fused_2c_active;
+    else if (k == "pow2_v") *value = s->pow2_v;
+    else if (k == "pow2_v_active") *value = s->pow2_v_active;
     else if (k == "diffusion_only_active") *value = s->diffusion_only_active;
     else if (k == "frame_rows") *value = s->cfg.frame_rows;
     else if (k == "external_halo") *value = s->external;

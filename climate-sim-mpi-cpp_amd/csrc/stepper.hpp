@@ -82,6 +82,9 @@ struct csim_stepper {
     int frame_fence = 0, frame_prio = 1;  // experiment switches of mode 3, see FrameSync
     int fused_2c = 1;         // k_sweepO_dpp's interior body fuses E - 2c into one fma under the overflow guard (Phys::fast_thr)
     int fused_2c_active = 0;  // read-only: whether the last run's parameters allowed it
+    int pow2_v = 2;           // ... and the five-operation advection term of power-of-two velocities under its screen (Phys::slow_thr):
+                              // 0 off, 1 on, 2 on for tiles of at least P2_MIN_CELLS cells (passes.cpp)
+    int pow2_v_active = 0;    // read-only: whether the last run's parameters enabled it
     int diffusion_only_active = 0;  // read-only: the last run had v == 0 and swept with the advection term left out of the screened body
     int direct_faces = 1;                 // merged launch: the frame wavefronts fill send2[] themselves (no pack kernel)
     bool bulk_first_run = false;          // the current csim_stepper_run uses pass_fused_bulk_first

@@ -131,7 +131,18 @@ __global__ __launch_bounds__(256) void k_sweepO_dpp(const double* __restrict__ i
         }
     } else {
         bool redo = true;
-        if (DIV != 3 && a.p.fast_thr > 0.0) redo = CSIM_MARCH(M_FAST);
+        if (DIV != 3 && a.p.fast_thr > 0.0) {
+            if constexpr (P2_BODY<DIV, T, SX, SY>::value) {
+                if (a.p.slow_thr > 0.0) {
+                    keep_branch();
+                    redo = CSIM_MARCH(M_FAST_P2);
+                } else {
+                    redo = CSIM_MARCH(M_FAST);
+                }
+            } else {
+                redo = CSIM_MARCH(M_FAST);
+            }
+        }
         if (redo) {
             keep_branch();
             CSIM_MARCH(M_PLAIN);

@@ -3,8 +3,8 @@
 // the overlapped-strip sweep with its bodies (sweepO_march), the ghost-fill rule and the wavefront reductions.  No
 // kernel and no launcher is defined here; two host helpers of the launchers (cdiv, whole_groups) close the file.
 //
-// The path is HBM-bandwidth-bound by nature (16 algorithmic bytes and ~14 fp64 flops per cell
-// update), so there is no MFMA here.  What matters:
+// The path is HBM-bandwidth-bound by nature (16 algorithmic bytes and 12-15 fp64 operations per cell
+// update: 15 in the reference's sequence, 14 with E - 2c fused, 12 for power-of-two velocities), so there is no MFMA here.  What matters:
 //   * 16-byte-per-lane coalesced row accesses on 128-byte-aligned rows, each cell read once and
 //     written once per PASS: vertical reuse in registers while a wavefront marches up its column
 //     strip, horizontal reuse through cross-lane DPP moves (an LDS-staged variant is kept for
@@ -37,7 +37,7 @@ namespace csim {
 // the fused form rounds the same real number E - 2c once, exactly like the subtraction does — unless 2c
 // overflows (|c| >= 2^1023), where the reference gets +-inf and the fma a finite number.  Only k_sweepO_dpp's
 // interior body uses it, under a guard that re-runs the tile with the plain form if that could happen (see
-// sweepO_march); it removes one of the 15 fp64 operations per cell.
+// sweepO_march); it removes one of the 15 fp64 operations per cell (P2 below: two more of the remaining 14).
 template <int DIV, bool FAST = false>
 __device__ __forceinline__ double diffuse_term(double c, double W, double E, double S, double N,
                                                const Phys& p) {
@@ -95,7 +95,22 @@ __device__ __forceinline__ double advect_term(double c, double W, double E, doub
 // it is, a0 c + aW W + aE E + aS S + aN N with host-made coefficients (make_phys), evaluated as one
 // multiply and four FMAs instead of 15 non-FMA operations.  Differs from the reference's rounding by a
 // few ulp per step (tests: L_inf < 1e-10 after 1000 steps, the north-star tolerance).
-template <int DIV, int SX = -1, int SY = -1, bool FAST = false>
+//
+// P2 — both velocities non-zero powers of two (option "pow2_v"; DIV 0 / 1, SX, SY in {0, 1}, FAST): the seven
+// operations of the advection term as five.  With A = vx/dx and B = vy/dy (signed powers of two; rdx, rdy fold in on
+// the host) the reference computes  fl(fl(A gx) + fl(B gy))  and then (-dt) times that.  Both products are exact, and
+// scaling by a power of two commutes with rounding, so the sum is  B fl(q gx + gy)  with q = A/B, one fma, and the
+// product with -dt is the one rounding of  K F,  K = (-dt) B  formed exactly on the host.  All of this holds as long as
+// nothing lands in the subnormal range with bits to lose and nothing overflows: the tile's screen (sweepO_march) lets
+// only values through that are exactly zero or at least p.slow_thr in magnitude, and below p.p2_hi; DESIGN.md §4
+// derives the two bounds (make_phys).
+// Signs of zeros: factoring out a POSITIVE velocity leaves q gx and gy with the signs of A gx and B gy, so F is the
+// reference's sum down to the sign of a zero.  Hence vy is factored out where vy > 0 (SY == 1), vx where only vx is
+// (SX == 1, SY == 0: F = fma(q, gy, gx), q = B/A).  Both negative (SX == SY == 0): vy is factored out all the same and
+// an exactly cancelling sum or a pair of opposite zeros comes out as -0 where the reference has +0 — a zero m of the
+// other sign, which changes o + m only where o is -0, and that goes back to a LOADED -0 (see SX = 2 below): this
+// flavour's screen also sends tiles with a loaded -0 to the plain body, as the zero-velocity flavours' does.
+template <int DIV, int SX = -1, int SY = -1, bool FAST = false, bool P2 = false>
 __device__ __forceinline__ double cell(double c, double W, double E, double S, double N,
                                        const Phys& p) {
     if (DIV == 3) {
@@ -106,6 +121,13 @@ __device__ __forceinline__ double cell(double c, double W, double E, double S, d
         return __builtin_fma(p.aN, N, o);
     }
     const double o = diffuse_term<DIV, FAST>(c, W, E, S, N, p);
+    if (P2) {
+        static_assert(!P2 || (FAST && DIV <= 1 && (SX == 0 || SX == 1) && (SY == 0 || SY == 1)), "see P2 above");
+        const double gx = SX == 1 ? c - W : E - c;
+        const double gy = SY == 1 ? c - S : N - c;
+        const double F = (SY == 1 || SX == 0) ? __builtin_fma(p.p2_q, gx, gy) : __builtin_fma(p.p2_q, gy, gx);
+        return o + p.p2_k * F;
+    }
     // SX = 2 / SY = 2 — vx == 0 / vy == 0 (both: BASELINE configs[1], diffusion only; one: e.g. the reference's own
     // configs/dev.yaml, vy = 0).  The reference still evaluates o + (-dt) * (vx * dudx + vy * dudy).  With finite
     // differences a product with a zero velocity is +0 or -0; adding it to the other product changes nothing unless that
@@ -322,6 +344,8 @@ __device__ __forceinline__ void pin2(double2& v) { asm volatile("" : "+v"(v.x), 
 // interior body (several bodies chained in one function grew the kernel from 124 to 179-194 VGPRs, i.e. from 4 to 2
 // wavefronts per SIMD for EVERY tile):
 //   M_FAST / M_PLAIN  interior body with / without the fused E - 2c (see FAST above)
+//   M_FAST_P2         M_FAST with the five-operation advection term of power-of-two velocities (cell, P2) and its
+//                     wider screen; compiled where P2_BODY says so, tried first where the host enabled it (p.slow_thr > 0)
 //   M_GENERIC         edge body with every patch behind run-time tests: tiles that can produce ghost ROWS of a
 //                     physical edge (the launcher keeps them thin: bottom / top bands) and strips that hold BOTH ghost
 //                     columns; also every edge tile of the instantiations that are not specialised (SPECIALISE_EDGES)
@@ -329,7 +353,7 @@ __device__ __forceinline__ void pin2(double2& v) { asm volatile("" : "+v"(v.x), 
 //                     straight-line like the interior body: 0 none (a final pass's frame tile that only emits
 //                     FinLines), 1 / 2 left ghost kept / Neumann, 3 / 4 right ghost kept in .x / .y, 5 / 6 right
 //                     ghost Neumann in .x / .y
-constexpr int M_FAST = -3, M_PLAIN = -2, M_GENERIC = -1;
+constexpr int M_FAST_P2 = -4, M_FAST = -3, M_PLAIN = -2, M_GENERIC = -1;
 
 template <int DIV, int T, int MODE, int SX, int SY>
 __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, double* __restrict__ out,
@@ -338,7 +362,7 @@ __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, doub
                                              LateArgs late, bool fin_any, bool fin_l, bool fin_r, bool wt) {
     constexpr int TP = OverlapGeom<T>::TP;
     constexpr int STRIDE = OverlapGeom<T>::STRIDE;
-    constexpr bool EDGE = MODE >= M_GENERIC, FAST = MODE == M_FAST, GENERIC = MODE == M_GENERIC;
+    constexpr bool EDGE = MODE >= M_GENERIC, P2 = MODE == M_FAST_P2, FAST = MODE == M_FAST || P2, GENERIC = MODE == M_GENERIC;
     constexpr int CASE = MODE;
     // this lane's two columns, 0-based interior index (-1 = left ghost, nx = right ghost)
     const int gx = g0 + 2 * lane, gy = gx + 1;
@@ -373,9 +397,13 @@ __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, doub
     for (int q = 0; q < 6; ++q) L0[q] = load(min(r_first - 1 + q, last_row));
     bool big = false;  // FAST: some loaded value is not below the threshold
     auto screen = [&](const double2& v) {
-        big |= !(__builtin_fabs(v.x) < p.fast_thr);
-        big |= !(__builtin_fabs(v.y) < p.fast_thr);
-        if (SX == 2 || SY == 2) {  // flavours without (part of) the advection term (see cell): a loaded -0 sends the tile to the plain body too
+        big |= !(__builtin_fabs(v.x) < (P2 ? p.p2_hi : p.fast_thr));
+        big |= !(__builtin_fabs(v.y) < (P2 ? p.p2_hi : p.fast_thr));
+        if (P2) {  // exactly zero, or large enough that no level of the pass loses bits to the subnormal range (cell, P2)
+            big |= __builtin_fabs(v.x) < p.slow_thr && v.x != 0.0;
+            big |= __builtin_fabs(v.y) < p.slow_thr && v.y != 0.0;
+        }
+        if (SX == 2 || SY == 2 || (P2 && SX == 0 && SY == 0)) {  // flavours without (part of) the advection term (see cell): a loaded -0 sends the tile to the plain body too
             big |= __builtin_amdgcn_class(v.x, 0x20);
             big |= __builtin_amdgcn_class(v.y, 0x20);
         }
@@ -418,8 +446,8 @@ __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, doub
                     {
                         const double Wx = shift_from_prev(c.y);
                         const double Ey = shift_from_next(c.x);
-                        o.x = cell<DIV, SX, SY, FAST>(c.x, Wx, c.y, s.x, n.x, p);
-                        o.y = cell<DIV, SX, SY, FAST>(c.y, c.x, Ey, s.y, n.y, p);
+                        o.x = cell<DIV, SX, SY, FAST, P2>(c.x, Wx, c.y, s.x, n.x, p);
+                        o.y = cell<DIV, SX, SY, FAST, P2>(c.y, c.x, Ey, s.y, n.y, p);
                         if (FAST && l == 1) screen(n);
                     }
                     if (EDGE && !GENERIC && l < T) {  // the strip's one ghost column, unconditionally
@@ -540,6 +568,13 @@ __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, doub
 template <int DIV, int T>
 struct SPECIALISE_EDGES {
     static constexpr bool value = (DIV == 0 || DIV == 1) && T >= 4;
+};
+
+// Which instantiations of k_sweepO_dpp carry the M_FAST_P2 body: the same arithmetic modes and depths, with both
+// velocity components non-zero.  Elsewhere (and in the ensemble's kernel) p.slow_thr is ignored.
+template <int DIV, int T, int SX, int SY>
+struct P2_BODY {
+    static constexpr bool value = SPECIALISE_EDGES<DIV, T>::value && (SX == 0 || SX == 1) && (SY == 0 || SY == 1);
 };
 
 // -------------------------------------------------------------------------------------------

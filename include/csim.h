@@ -73,6 +73,10 @@ int csim_device_name(char* buf, size_t n); /* gcnArchName of the current device 
 /* ---- host-side scalars ------------------------------------------------------------------ */
 /* reference include/stability.hpp:5-16  double safe_dt(dx,dy,vx,vy,D) */
 double csim_safe_dt(double dx, double dy, double vx, double vy, double D);
+/* host arithmetic only: the screen and the constants of the stepper option "pow2_v" for these parameters —
+ * out[0] = L, the smallest non-zero magnitude a tile may load and still take the 12-operation body (0 = the form is off
+ * for these parameters), out[1] = its upper bound, out[2] = q, out[3] = K */
+int csim_pow2_velocity_screen(double dx, double dy, double D, double dt, double vx, double vy, double out[4]);
 /* reference src/decomp.cpp:5-34  Decomp2D::init(comm, nx_global, ny_global), MPI-free:
  * MPI_Dims_create(size,2) + MPI_Cart_create(periods 0,0, reorder 0) are re-derived. */
 int csim_decomp_init(int size, int rank, int nx_global, int ny_global, csim_decomp* out);
@@ -236,6 +240,18 @@ int csim_stepper_sum(csim_stepper* s, double* out);
  *                    sends the tile to the reference's sequence, because o + (+0) would turn an o of -0 into +0).
  *                    "diffusion_only_active" (read-only): whether the last run swept that way.  One zero component alone:
  *                    its three operations are left out under the same screen (11 per cell)
+ *   "pow2_v"         0/1/2 (default 2 = on for tiles of at least 6e7 cells, where it was measured to pay: 16384^2 +8.5 %,
+ *                    8192^2 +6.4 %, but 4096 x 8192 -4 % and 4096^2 -17 %; 1 = on wherever the parameters allow), bit-identical
+ *                    in every setting: where vx/dx and vy/dy are both non-zero powers of two
+ *                    (every shipped configuration: 0.5, 0.25) the same interior body forms the advection term as
+ *                    F = fma(q, gx, gy), m = K F with q = (vx/dx)/(vy/dy) and K = (-dt) vy/dy made on the host — products
+ *                    with powers of two are exact and commute with rounding — 12 instead of 14 operations per cell.  The
+ *                    identity fails only where such a product loses bits in the subnormal range, so the tile's screen
+ *                    also requires every loaded value to be exactly zero or at least L in magnitude (about 2^-600 for the
+ *                    bench physics, csim_pow2_velocity_screen; derivation: DESIGN.md section 4); other tiles are recomputed
+ *                    with the reference's sequence.  Needs "fused_2c"; passes of 2 or 3 steps, edge tiles, IEEE division,
+ *                    "contract" and the ensemble keep their bodies.  "pow2_v_active" (read-only): whether the last run's
+ *                    parameters and tile size enabled it.  0 restores the 14-operation body everywhere
  *   "fuse"           time steps per HBM pass: -1 auto (the cheapest split of a run into passes of 2..7 steps, e.g.
  *                    1000 = 166 x 6 + 4, 20 = 7 + 7 + 6), 0/1 off, 2..7 balanced passes of at most that depth
  *   "variant"        single-step kernel family: 0 auto, 1 dpp, 2 lds, 3 naive

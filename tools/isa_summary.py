@@ -8,7 +8,8 @@
 For every kernel whose mangled name contains SUBSTR: VGPRs / SGPR spills / occupancy from the resource remarks, and for
 every LOOP (a label that is the target of a backward branch, up to that branch) with at least --min-fp64 fp64
 instructions: counts of fp64 add/mul/fma, DPP moves, v_readlane/v_writelane (SGPR spill traffic), v_cndmask (per-lane
-selects), v_cmp, other VALU, scalar instructions, s_waitcnt, global loads / stores."""
+selects), v_cmp, other VALU, scalar instructions, s_waitcnt, global loads / stores.  --leaf lists the innermost such loops
+instead of the outermost (a backward branch that merely joins several march bodies otherwise hides them)."""
 import argparse
 import collections
 import re
@@ -16,7 +17,7 @@ import sys
 
 
 def classify(ins, line):
-    if ins.startswith(("v_add_f64", "v_mul_f64", "v_fma_f64")):
+    if ins.startswith(("v_add_f64", "v_mul_f64", "v_fma_f64", "v_fmac_f64")):  # v_fmac_f64: the two-address encoding of an fma
         return "fp64"
     if "dpp" in line or "row_" in line or "wave_sh" in line:
         return "dpp"
@@ -90,6 +91,7 @@ def main():
     ap.add_argument("res", nargs="?")
     ap.add_argument("--kernel", default="k_sweepO_dpp")
     ap.add_argument("--min-fp64", type=int, default=200)
+    ap.add_argument("--leaf", action="store_true", help="innermost loops of at least --min-fp64 instead of outermost")
     args = ap.parse_args()
     res = {}
     if args.res:
@@ -119,9 +121,14 @@ def main():
             if tgt not in widest or b > widest[tgt][2]:
                 widest[tgt] = (tgt, a, b)
         tops = []
-        for tgt, a, b in sorted(widest.values(), key=lambda t: (t[1], -t[2])):
-            if not any(a >= ta and b <= tb for _, ta, tb in tops):
-                tops.append((tgt, a, b))
+        if args.leaf:
+            fp = lambda a, b: sum(1 for mn, t in ins[a:b + 1] if classify(mn, t) == "fp64")
+            big = [w for w in sorted(widest.values(), key=lambda t: (t[1], -t[2])) if fp(w[1], w[2]) >= args.min_fp64]
+            tops = [w for w in big if not any(o is not w and o[1] >= w[1] and o[2] <= w[2] for o in big)]
+        else:
+            for tgt, a, b in sorted(widest.values(), key=lambda t: (t[1], -t[2])):
+                if not any(a >= ta and b <= tb for _, ta, tb in tops):
+                    tops.append((tgt, a, b))
         for tgt, a, b in tops:
             c = collections.Counter(classify(mn, t) for mn, t in ins[a:b + 1])
             if c["fp64"] < args.min_fp64:
