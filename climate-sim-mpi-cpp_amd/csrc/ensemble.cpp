@@ -29,7 +29,7 @@ int ensure_tables(csim_ensemble* e) {
     for (int m = 0; m < B; ++m) {
         Phys p = make_phys(e->dx, e->dy, e->D[m], e->dt[m], e->vx[m], e->vy[m]);
         if (!e->fused_2c) p.fast_thr = 0.0;
-        cls[m] = ens_sign_class(p);
+        cls[m] = sign_class(p);
         double* f = e->fin + static_cast<size_t>(m) * e->g.fin_stride;
         double* const lines[4] = {f, f + e->g.ly, f + 2 * e->g.ly, f + 2 * e->g.ly + e->g.lx};
         ens_entry_fill(host.data() + eb * m, p, lines);
@@ -71,7 +71,7 @@ int csim_ensemble_sign_class(double dx, double dy, double D, double dt, double v
     CSIM_REQUIRE(cls && dx > 0 && dy > 0, "bad argument");
     Phys p = make_phys(dx, dy, D, dt, vx, vy);
     if (!fused_2c) p.fast_thr = 0.0;
-    *cls = ens_sign_class(p);
+    *cls = sign_class(p);
     return CSIM_OK;
 }
 

@@ -232,15 +232,8 @@ hipError_t ens_sweepO_div(const EnsGeom& g, const double* in, double* out, const
     EnsArgs a;
     a.nx = g.nx, a.ny = g.ny, a.pitch = g.pitch, a.count = count, a.slab = g.slab;
     a.nstrips = cdivl(g.nx, STRIDE);
-    // Chunk height: as tall as keeps two rounds of wavefronts (8192 tiles) on the chip — every chunk marches
-    // 2 (T - 1) rows more than it stores — down to 6 rows, the single stepper's choice for small lone tiles.
-    int ry = 64;
-    while (ry > 6 && static_cast<long>(count) * a.nstrips * cdivl(g.ny, ry) < 8192) ry >>= 1;
-    if (ry < 6) ry = 6;
-    ry = whole_groups<T>(ry);  // whole groups of six march iterations
-    if (ry > g.ny) ry = g.ny;
-    a.ry = ry;
-    a.nchunks = cdivl(g.ny, ry);
+    a.ry = ens_chunk_rows(T, count, a.nstrips, g.ny);  // sweep_plan.cpp
+    a.nchunks = cdivl(g.ny, a.ry);
     a.members = members, a.table = table;
     for (int s = 0; s < 4; ++s) a.bc.kind[s] = g.bc[s];
     a.bc.value = g.value;

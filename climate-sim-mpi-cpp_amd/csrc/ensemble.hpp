@@ -19,16 +19,9 @@ namespace csim {
 constexpr int ENS_DEPTH = CSIM_ENS_T;
 static_assert(ENS_DEPTH >= 2 && ENS_DEPTH <= MAX_FUSE, "ensemble depth out of range");
 
-// upwind-sign flavour of a member (the launch it belongs to): 3 * cx + cy with per axis 0: v < 0, 1: v >= 0,
-// 2: v == 0 on a screened run (fast_thr > 0 and dx, dy without IEEE division) — exactly how the single stepper's
-// launcher picks k_sweepO_dpp<., ., SX, SY>
+// upwind-sign flavours of a member (the launch it belongs to): the values of sign_class (internal.hpp), which is also
+// how the single stepper's launcher picks k_sweepO_dpp<., ., SX, SY>
 constexpr int ENS_CLASSES = 9;
-inline int ens_sign_class(const Phys& p) {
-    const bool screened = p.div_mode <= 1 && p.fast_thr > 0.0;
-    const int cx = screened && p.vx == 0.0 ? 2 : (p.vx >= 0.0 ? 1 : 0);
-    const int cy = screened && p.vy == 0.0 ? 2 : (p.vy >= 0.0 ? 1 : 0);
-    return 3 * cx + cy;
-}
 
 struct EnsGeom {
     int members;

@@ -24,11 +24,11 @@
 #include <string>
 
 #include "csim.h"
+#include "sweep_plan.hpp"  // WAVE_COLS, MAX_FUSE, cdiv, the tile plan of the overlapped-strip sweep (host arithmetic)
 
 namespace csim {
 
-constexpr int LPAD = 16;        // doubles in front of the first interior column
-constexpr int WAVE_COLS = 128;  // columns one wavefront covers per row (64 lanes x 2 doubles)
+constexpr int LPAD = 16;  // doubles in front of the first interior column
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline int pitch_for(int nx) { return LPAD + round_up(nx + 1, WAVE_COLS) + WAVE_COLS; }
@@ -63,6 +63,15 @@ struct Phys {
     double p2_q, p2_k;  // q = (vx/dx)/(vy/dy) or its reciprocal, K = (-dt) * the velocity factored out (see cell)
 };
 Phys make_phys(double dx, double dy, double D, double dt, double vx, double vy, bool contract = false);
+// upwind-sign flavour of these parameters, 3 * cx + cy with per axis 0: v < 0, 1: v >= 0, 2: v == 0 on a screened run
+// (fast_thr > 0 and dx, dy without IEEE division): which k_sweepO_dpp<., ., SX, SY> / k_ensemble_sweepO<., ., SX, SY>
+// a launch runs, and the class an ensemble member is launched with (ENS_CLASSES of them)
+inline int sign_class(const Phys& p) {
+    const bool screened = p.div_mode <= 1 && p.fast_thr > 0.0;
+    const int cx = screened && p.vx == 0.0 ? 2 : (p.vx >= 0.0 ? 1 : 0);
+    const int cy = screened && p.vy == 0.0 ? 2 : (p.vy >= 0.0 ? 1 : 0);
+    return 3 * cx + cy;
+}
 
 // kernel variants of the fused sweep (option "variant")
 enum { VAR_AUTO = 0, VAR_DPP = 1, VAR_LDS = 2, VAR_NAIVE = 3 };
@@ -78,15 +87,23 @@ struct SweepCfg {
     int tail_split = 1;        // fused launches of two or more rounds of wavefronts end with a region of half-height
                                // chunks (see Tiling); 0 off, 2 experiment (half + quarter height)
     int frame_rows = 0;        // multi-rank pass: chunk height of the frame's side strips (0 = as thin as the bands)
-    int* rows_used = nullptr;  // out: chunk height of the last whole-field / bulk launch (option "last_rows")
 };
+// what the tile plan (sweep_plan.hpp) of one launch_sweepO with these settings is made from, and the plan
+inline SweepPlanIn plan_in_sweepO(int nx, int ny, int T, const Phys& p, const SweepCfg& cfg, const int kind[4], int part) {
+    return SweepPlanIn{nx, ny, T, p.div_mode, {kind[0], kind[1], kind[2], kind[3]}, part,
+                       cfg.rows_per_chunk, cfg.tuned_rows, cfg.tail_split, cfg.frame_rows};
+}
+inline SweepPlan plan_sweepO(int nx, int ny, int T, const Phys& p, const SweepCfg& cfg, const int kind[4], int part) {
+    return sweep_plan(plan_in_sweepO(nx, ny, T, p, cfg, kind, part));
+}
 
-// ---- kernel launchers (kernels.hip; launch_sweepO's templates: sweepO.hpp) -----------------
+// ---- kernel launchers (kernels.hip; launch_sweepO's templates: sweepO.hpp, its tile plan: sweep_plan.cpp) ----
 // All pointers are device pointers in the padded layout above.
 hipError_t launch_sweep(const double* in, double* out, int nx, int ny, int pitch, const Phys& p,
                         const SweepCfg& cfg, hipStream_t st);
-// T = 2..7 fused time steps per pass (overlapped strips).  kind[s] = CSIM_BC_* on physical sides, 3 on
-// neighbour sides; part: 0 = every tile, 1 = frame tiles only, 2 = all but the frame tiles.
+// T = 2..7 fused time steps per pass (overlapped strips) over the tiles of `plan` (plan_sweepO with the same p, cfg
+// and kind; nx, ny and T are the plan's).  kind[s] = CSIM_BC_* on physical sides, 3 on neighbour sides; the plan's
+// part: 0 = every tile, 1 = frame tiles only, 2 = all but the frame tiles.
 // fin_lines (last pass of a run, all four or nullptr): per side the level T-1 line the final ghost
 // fill needs — see FinLines in sweep_core.hpp
 // part 3 = frame and bulk in ONE grid (frame tiles dispatched first); with `sync` the frame wavefronts
@@ -96,7 +113,7 @@ struct FrameSync {
     unsigned* counter = nullptr;
     unsigned long long* flag = nullptr;
     unsigned long long pass = 0;
-    unsigned nframe = 0;  // filled in by the launcher
+    unsigned nframe = 0;  // filled in by the launcher, from the plan
     int fence = 0;        // 0 write-through result stores + drain (default), 1 plain stores + agent-scope fence per
                           // wavefront (slow: +40 us per pass)
     int prio = 1;         // frame wavefronts raise their issue priority
@@ -105,10 +122,9 @@ struct FrameSync {
     double* face[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int face_depth = 0;
 };
-hipError_t launch_sweepO(const double* in, double* out, int nx, int ny, int pitch, const Phys& p,
-                         const SweepCfg& cfg, const int kind[4], double value, int T, int part,
-                         hipStream_t st, double* const fin_lines[4] = nullptr, const FrameSync* sync = nullptr);
-constexpr int MAX_FUSE = 7;       // deepest temporal blocking (123 VGPRs: still 4 waves/SIMD; 8 would drop to 3)
+hipError_t launch_sweepO(const double* in, double* out, int pitch, const Phys& p, const SweepCfg& cfg,
+                         const int kind[4], double value, const SweepPlan& plan, hipStream_t st,
+                         double* const fin_lines[4] = nullptr, const FrameSync* sync = nullptr);
 // depth with the lowest measured cost per time step (tools/depth_ab.py, profiles/r02_depth_ab.jsonl): 7 on tiles
 // of >= 2e8 cells (+0.9 % over 6 at 16384^2 and 32768^2); 6 in between (7 loses 7 % on a 4096 x 8192 tile, which is
 // a single round of wavefronts: more overhead rows per chunk and nothing to amortise them); 4 on tiles below

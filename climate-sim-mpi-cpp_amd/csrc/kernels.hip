@@ -16,8 +16,8 @@ namespace csim {
 // compile time — are six translation units of their own (sweepO_inst.hip), built in parallel with this one, which
 // only declares the template: launch_sweepO below links against them.
 template <int T>
-hipError_t sweepO_T(const double* in, double* out, int nx, int ny, int pitch, const Phys& p, const SweepCfg& cfg,
-                    const Bc2& bc, const FinLines& fin, int part, hipStream_t st, const FrameSync& fs);
+hipError_t sweepO_T(const double* in, double* out, int pitch, const Phys& p, const SweepCfg& cfg, const Bc2& bc,
+                    const FinLines& fin, const SweepPlan& plan, hipStream_t st, const FrameSync& fs);
 
 // -------------------------------------------------------------------------------------------
 // VAR_DPP — the default fused sweep.
@@ -506,22 +506,22 @@ static hipError_t sweep_div(const double* in, double* out, int nx, int ny, int p
 }
 
 // overlapped-strip multi-step sweep, T = 2..7 (kind[] / part: see internal.hpp)
-hipError_t launch_sweepO(const double* in, double* out, int nx, int ny, int pitch, const Phys& p,
-                         const SweepCfg& cfg, const int kind[4], double value, int T, int part,
-                         hipStream_t st, double* const fin_lines[4], const FrameSync* sync) {
+hipError_t launch_sweepO(const double* in, double* out, int pitch, const Phys& p, const SweepCfg& cfg,
+                         const int kind[4], double value, const SweepPlan& plan, hipStream_t st,
+                         double* const fin_lines[4], const FrameSync* sync) {
     Bc2 bc;
     for (int s = 0; s < 4; ++s) bc.kind[s] = kind[s];
     bc.value = value;
     FinLines fin;
     for (int s = 0; s < 4; ++s) fin.line[s] = fin_lines ? fin_lines[s] : nullptr;
     const FrameSync fs = sync ? *sync : FrameSync{};
-    switch (T) {
-        case 2: return sweepO_T<2>(in, out, nx, ny, pitch, p, cfg, bc, fin, part, st, fs);
-        case 3: return sweepO_T<3>(in, out, nx, ny, pitch, p, cfg, bc, fin, part, st, fs);
-        case 4: return sweepO_T<4>(in, out, nx, ny, pitch, p, cfg, bc, fin, part, st, fs);
-        case 5: return sweepO_T<5>(in, out, nx, ny, pitch, p, cfg, bc, fin, part, st, fs);
-        case 6: return sweepO_T<6>(in, out, nx, ny, pitch, p, cfg, bc, fin, part, st, fs);
-        default: return sweepO_T<7>(in, out, nx, ny, pitch, p, cfg, bc, fin, part, st, fs);
+    switch (plan.T) {
+        case 2: return sweepO_T<2>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
+        case 3: return sweepO_T<3>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
+        case 4: return sweepO_T<4>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
+        case 5: return sweepO_T<5>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
+        case 6: return sweepO_T<6>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
+        default: return sweepO_T<7>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
     }
 }
 

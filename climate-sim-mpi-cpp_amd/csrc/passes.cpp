@@ -16,9 +16,15 @@ static hipError_t launch_fused(csim_stepper* s, const Phys& p, const int kind[4]
     SweepCfg cfg = s->cfg;
     if (lds_bytes > 0) cfg.lds_bytes = lds_bytes;
     if (T >= 2 && T <= MAX_FUSE && s->tuned_T[T] > 0) cfg.tuned_rows = s->tuned_T[T];  // this depth had its own trial
-    cfg.rows_used = &s->last_rows;
-    return launch_sweepO(s->cur, s->nxt, s->nx, s->ny, s->pitch, p, cfg, kind, s->bc_value, T, part, st,
-                         final_pass ? s->fin : nullptr, sync);
+    const SweepPlanIn in = plan_in_sweepO(s->nx, s->ny, T, p, cfg, kind, part);
+    csim_stepper::KeptPlan& kept = s->plans[T >= 2 && T <= MAX_FUSE ? T : MAX_FUSE][part & 3];  // launch_sweepO: any other T runs as 7
+    if (!kept.valid || std::memcmp(&kept.in, &in, sizeof(in)) != 0) {
+        kept.in = in;
+        kept.plan = sweep_plan(in);
+        kept.valid = true;
+    }
+    if (part != 1) s->last_rows = kept.plan.rows;  // the frame's heights are fixed
+    return launch_sweepO(s->cur, s->nxt, s->pitch, p, cfg, kind, s->bc_value, kept.plan, st, final_pass ? s->fin : nullptr, sync);
 }
 
 // final_pass (overlapped-strip kernels only): the last pass of a run.  The kernel also emits the
@@ -324,7 +330,7 @@ int tune_rows(csim_stepper* s, const Phys& p, int T, bool preferred_depth) {
     if (static_cast<long>(s->nx) * s->ny < (1L << 22)) return CSIM_OK;
     std::vector<int> cand;
     for (int ry = 6; ry <= 236 && ry <= s->ny; ry += (ry < 30 ? 4 : 6)) {
-        const int snapped = ry + (6 - (ry + 2 * (T - 1)) % 6) % 6;
+        const int snapped = whole_groups(T, ry);
         if (snapped <= s->ny && (cand.empty() || cand.back() != snapped)) cand.push_back(snapped);
     }
     if (cand.size() < 2) return CSIM_OK;
@@ -348,7 +354,8 @@ int tune_rows(csim_stepper* s, const Phys& p, int T, bool preferred_depth) {
     auto trial = [&](int ry, float* ms) -> int {
         cfg.tuned_rows = ry;
         CSIM_HIP(hipEventRecord(e0, s->s_comp));
-        CSIM_HIP(launch_sweepO(s->cur, s->nxt, s->nx, s->ny, s->pitch, p, cfg, kind, s->bc_value, T, part, s->s_comp));
+        CSIM_HIP(launch_sweepO(s->cur, s->nxt, s->pitch, p, cfg, kind, s->bc_value,
+                               plan_sweepO(s->nx, s->ny, T, p, cfg, kind, part), s->s_comp));
         CSIM_HIP(hipEventRecord(e1, s->s_comp));
         CSIM_HIP(hipEventSynchronize(e1));
         CSIM_HIP(hipEventElapsedTime(ms, e0, e1));
@@ -459,11 +466,12 @@ int csim_stepper_keep_warm(csim_stepper* s, double D, double dt, double vx, doub
     for (int k = 0; k < 4; ++k) kind[k] = s->phys[k] ? s->bc[k] : 3;
     CSIM_HIP(hipStreamSynchronize(s->s_comm));
     CSIM_HIP(hipStreamSynchronize(s->s_comp));
+    const SweepPlan plan = plan_sweepO(s->nx, s->ny, depth, p, s->cfg, kind, 0);
     double last = 0.0;
     for (int n = 0; n < 100000; ++n) {
         const double before = elapsed();
         if (before + 1.25 * last >= seconds) break;  // the next launch would run past the deadline
-        CSIM_HIP(launch_sweepO(s->cur, s->nxt, s->nx, s->ny, s->pitch, p, s->cfg, kind, s->bc_value, depth, 0, s->s_comp));
+        CSIM_HIP(launch_sweepO(s->cur, s->nxt, s->pitch, p, s->cfg, kind, s->bc_value, plan, s->s_comp));
         CSIM_HIP(hipStreamSynchronize(s->s_comp));
         last = elapsed() - before;
     }

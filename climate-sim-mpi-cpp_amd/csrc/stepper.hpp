@@ -95,6 +95,13 @@ struct csim_stepper {
     hipEvent_t ev_snap_src = nullptr, ev_snap_copied = nullptr;
     bool snap_pending = false;
     int last_rows = 0;    // chunk height the last fused whole-field / bulk launch used
+    // the tile plans of the fused passes, one per (depth, part): built at the first launch and again when an input
+    // (an option, a tuned height, the division mode) differs from what the kept plan was made from
+    struct KeptPlan {
+        csim::SweepPlanIn in{};
+        csim::SweepPlan plan{};
+        bool valid = false;
+    } plans[csim::MAX_FUSE + 1][4];
     long tile_cells = 0;  // cells of the decomposition's base tile (same on every rank): picks the preferred depth
     int fuse_cap = 1;     // deepest pass every rank of the decomposition can run (same on all ranks)
     int faces_depth = 0;  // recv2[] holds the neighbours' faces of `cur` of this depth (0 = none)

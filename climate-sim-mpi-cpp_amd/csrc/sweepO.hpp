@@ -1,7 +1,8 @@
 // sweepO.hpp — k_sweepO_dpp (2-7 steps/pass, overlapped strips, the DEFAULT sweep) around the march of
 // sweep_core.hpp, and its launcher templates sweepO_div / sweepO_T.  sweepO_inst.hip instantiates one depth per
 // translation unit; kernels.hip only declares sweepO_T.  In file order: what the kernel alone needs (face stores,
-// the CSIM_TRACE hook of tools/wavetrace.hip), the kernel, the launcher.
+// the CSIM_TRACE hook of tools/wavetrace.hip), the kernel, the launcher.  How a launch is cut into tiles is not
+// decided here: the launcher is handed a SweepPlan (sweep_plan.cpp, host arithmetic that a CPU program checks).
 #pragma once
 #include "sweep_core.hpp"
 
@@ -65,6 +66,8 @@ __global__ __launch_bounds__(256) void k_sweepO_dpp(const double* __restrict__ i
 #endif
     // blocks [0, frame_blocks): the frame tiles in plain order; the last tail_blocks blocks: the tail tiles in
     // plain order; the blocks in between own the main tiles, XCD-remapped among themselves
+    // (this decode — block -> tile -> region -> strip, jb, je — believes the plan's numbers blindly;
+    // tools/sweep_plan_host_check.cpp restates it and checks on the CPU that it reaches every tile of every plan once)
     int tile;
     bool frame_tile = false;
     {
@@ -222,131 +225,19 @@ __global__ __launch_bounds__(256) void k_sweepO_dpp(const double* __restrict__ i
 // launcher of the overlapped-strip sweep (templates: one depth per translation unit, see sweepO_inst.hip)
 // ============================================================================================
 
+// three steps: take the plan (sweep_plan.cpp: the launcher's caller built it), fill SweepArgs, dispatch on the sign class
 template <int DIV, int T>
-hipError_t sweepO_div(const double* in, double* out, int nx, int ny, int pitch, const Phys& p,
-                             const SweepCfg& cfg, const Bc2& bc, const FinLines& fin, int part, hipStream_t st,
-                             FrameSync fs) {
-    constexpr int STRIDE = OverlapGeom<T>::STRIDE;
-    const int nstrips = cdiv(nx, STRIDE);
-    int ry = cfg.rows_per_chunk;
-    if (ry <= 0) {
-        if (cfg.tuned_rows > 0) {
-            ry = cfg.tuned_rows;
-        } else {
-            ry = 64;
-            while (ry > 16 && static_cast<long>(nstrips) * cdiv(ny, ry) < 8192) ry >>= 1;
-            // tiles too small for the on-device trial (< 4 M cells): a launch is at most a round or two of
-            // wavefronts and the length of a wavefront's march decides — the shortest chunks win although
-            // they double the overhead rows (512^2: +52 %, 1024^2: +37 %, 2048^2: +25 % against 18 rows)
-            if (static_cast<long>(nx) * ny < (1L << 22)) ry = 6;
-        }
-        // the march runs whole groups of six iterations: make ry + 2 (T - 1) a multiple of six so
-        // that only a ragged last chunk computes surplus rows
-        ry = whole_groups<T>(ry);
-    }
-    if (ry > ny) ry = ny;
-    if (cfg.rows_used && part != 1) *cfg.rows_used = ry;
-    // part 0: the whole field.  part 1 / 2 (multi-rank pass): FRAME / BULK.  The frame is the
-    // bottom and top bands (hf rows, all strips) plus the first strip and the last one or two
-    // strips (>= MAX_FUSE columns) over the rows in between, in chunks of hf rows: thin tiles,
-    // one short round of wavefronts, so the faces are ready ~15 us into the pass.
-    const int hf = whole_groups<T>(12);  // >= the deepest face (8-row bands were measured slower: more, even thinner tiles)
-    const int nright = (nx - (nstrips - 1) * STRIDE >= MAX_FUSE) ? 1 : 2;
-    const bool split = ny >= 2 * hf + 1 && nstrips >= nright + 2;
-    // A band along a PHYSICAL bottom / top edge runs the generic edge body (ghost rows), about twice as slow per
-    // iteration as the other frame tiles, and the frame launch lasts as long as its slowest tile (47 us instead of 34 on
-    // a 4096 x 8192 tile with one physical side): such a band is only as high as the ghost rows require (T-1 rows,
-    // rounded so that its march is whole groups of six: 18 iterations at T = 7 instead of 24).  The tiles above it then
-    // start at row T and read the ghost row itself as level-0 input — in a bulk-first pass BEFORE this pass's ghost
-    // fill has run: fine for Dirichlet and Periodic sides, whose ghost ring never changes, not for Neumann ones, which
-    // keep the band of hf >= T rows.
-    const int hphys = whole_groups<T>(T - 1);
-    auto thin = [&](int side) {
-        return SPECIALISE_EDGES<DIV, T>::value && bc.kind[side] != 3 && bc.kind[side] != CSIM_BC_NEUMANN;
-    };
-    const int hfb = thin(CSIM_BOTTOM) ? std::min(hf, hphys) : hf;
-    const int hft = thin(CSIM_TOP) ? std::min(hf, hphys) : hf;
-    Tiling tl{};
-    auto add = [&](int strip0, int nstrip, int j0, int j1, int rows) {
-        if (nstrip <= 0 || j1 < j0) return;
-        TileRegion& r = tl.r[tl.nregions++];
-        r.strip0 = strip0, r.nstrip = nstrip, r.j0 = j0, r.j1 = j1, r.ry = rows;
-        tl.ntiles += nstrip * cdiv(j1 - j0 + 1, rows);
-        r.t_end = tl.ntiles;
-    };
-    // rows j0..j1 of `nstrip` strips: full-height chunks, or — on launches of two or more rounds of wavefronts —
-    // a main region of 7/8 of the chunks (a multiple of four, so that its tiles fill whole blocks whatever the
-    // number of strips) followed by a tail region at half the height; returns the tail tiles
-    auto add_rows = [&](int strip0, int nstrip, int j0, int j1, int rows) -> int {
-        const int nrows = j1 - j0 + 1;
-        if (nstrip <= 0 || nrows <= 0) return 0;
-        const int nchunks = cdiv(nrows, rows);
-        if (!cfg.tail_split || rows < 48 || nchunks < 16 || static_cast<long>(nstrip) * nchunks < 8192) {
-            add(strip0, nstrip, j0, j1, rows);
-            return 0;
-        }
-        const bool two_level = cfg.tail_split != 2;  // default: 7/8 of the chunks full height + the rest at half height;
-                                                     // 2 (experiment): 3/4 + half + quarter height — measured no better
-        const int main_chunks = (nchunks * (two_level ? 7 : 3) / (two_level ? 8 : 4)) / 4 * 4;
-        const int j_main = j0 + main_chunks * rows - 1;
-        const int half = whole_groups<T>(rows / 2), quarter = whole_groups<T>(rows / 4);
-        const int rest = j1 - j_main;                       // rows left for the tail regions
-        const int j_half = two_level ? j1 : j_main + (rest * 2 / 3) / half * half;  // about two thirds of them at half height
-        add(strip0, nstrip, j0, j_main, rows);
-        const int before = tl.ntiles;
-        add(strip0, nstrip, j_main + 1, j_half, half);
-        add(strip0, nstrip, j_half + 1, j1, quarter);
-        return tl.ntiles - before;
-    };
-    int tail_tiles = 0;
-    if (part == 0 || ((part == 1 || part == 3) && !split)) {
-        // Physical bottom / top edges: the rows whose chunks can produce ghost ROWS of the intermediate levels (the
-        // first and last T-1) go into thin bands of their own, so that only those few short tiles run the generic
-        // edge body and every other tile of the first / last strips a straight-line column flavour (sweepO_march).
-        // The bands come last in the tile order, with the tail region: they are the shortest tiles of the launch.
-        const int hb = whole_groups<T>(T - 1);
-        const bool bands = SPECIALISE_EDGES<DIV, T>::value && ny >= 2 * hb + 6;
-        const bool band_b = bands && bc.kind[CSIM_BOTTOM] != 3, band_t = bands && bc.kind[CSIM_TOP] != 3;
-        tail_tiles = add_rows(0, nstrips, band_b ? hb + 1 : 1, band_t ? ny - hb : ny, ry);
-        const int before = tl.ntiles;
-        if (band_b) add(0, nstrips, 1, hb, hb);
-        if (band_t) add(0, nstrips, ny - hb + 1, ny, hb);
-        tail_tiles += tl.ntiles - before;
-    } else if (part == 1 || part == 3) {
-        add(0, nstrips, 1, hfb, hfb);
-        add(0, nstrips, ny - hft + 1, ny, hft);
-        int hs = hf;  // side strips: taller chunks waste fewer warm-up rows (2 (T - 1) per chunk) but finish later
-        if (cfg.frame_rows >= MAX_FUSE) hs = whole_groups<T>(cfg.frame_rows);
-        add(0, 1, hfb + 1, ny - hft, hs);
-        add(nstrips - nright, nright, hfb + 1, ny - hft, hs);
-    }
-    int nblocks;
-    if (part == 3 && split) {  // merged launch: the frame tiles above, then the bulk in the same grid
-        tl.frame_tiles = tl.ntiles;
-        tl.frame_blocks = cdiv(tl.ntiles, 4);
-        fs.nframe = static_cast<unsigned>(tl.frame_tiles);
-        const int before = tl.ntiles;
-        tail_tiles = add_rows(1, nstrips - 1 - nright, hfb + 1, ny - hft, std::min(ry, ny - hfb - hft));
-        nblocks = tl.frame_blocks + cdiv(tl.ntiles - before, 4);
-    } else if (part == 3) {  // a tile that is all frame: every tile counts for the flag
-        tl.frame_tiles = tl.ntiles;
-        tl.frame_blocks = cdiv(tl.ntiles, 4);
-        tl.tail_blocks = 0;
-        tail_tiles = 0;
-        fs.nframe = static_cast<unsigned>(tl.frame_tiles);
-        nblocks = tl.frame_blocks;
-    } else {
-        if (part == 2 && split) tail_tiles = add_rows(1, nstrips - 1 - nright, hfb + 1, ny - hft, std::min(ry, ny - hfb - hft));
-        if (tl.ntiles == 0) return hipSuccess;  // part 2 of a field that is all frame
-        nblocks = cdiv(tl.ntiles, 4);
+hipError_t sweepO_div(const double* in, double* out, int pitch, const Phys& p, const SweepCfg& cfg, const Bc2& bc,
+                      const FinLines& fin, const SweepPlan& plan, hipStream_t st, FrameSync fs) {
+    if (plan.empty) return hipSuccess;
+    if (plan.signals)
+        fs.nframe = plan.nframe;
+    else
         fs = FrameSync{};
-    }
-    tl.tail_blocks = cdiv(tail_tiles, 4);
-    const dim3 grid(nblocks), block(256);
-    const int sw = cfg.xcd_swizzle;
+    const dim3 grid(plan.nblocks), block(256);
     SweepArgs ka;
-    ka.nx = nx, ka.ny = ny, ka.pitch = pitch, ka.nstrips = nstrips, ka.swz = sw;
-    ka.tl = tl, ka.p = p, ka.bc = bc, ka.fin = fin, ka.fs = fs;
+    ka.nx = plan.nx, ka.ny = plan.ny, ka.pitch = pitch, ka.nstrips = plan.nstrips, ka.swz = cfg.xcd_swizzle;
+    ka.tl = plan.tl, ka.p = p, ka.bc = bc, ka.fin = fin, ka.fs = fs;
 #define CSIM_LAUNCH_O(SXV, SYV) \
     hipLaunchKernelGGL((k_sweepO_dpp<DIV, T, SXV, SYV>), grid, block, cfg.lds_bytes, st, in, out, ka)
 #ifdef CSIM_ISA_PROBE
@@ -356,9 +247,7 @@ hipError_t sweepO_div(const double* in, double* out, int nx, int ny, int pitch, 
         CSIM_LAUNCH_O(1, 1);
     } else {
         // zero velocity components (DIV 0 / 1; the IEEE-division form keeps its four sign flavours): code 2 per axis
-        const bool screened = DIV <= 1 && p.fast_thr > 0.0;
-        const int cx = screened && p.vx == 0.0 ? 2 : (p.vx >= 0.0 ? 1 : 0), cy = screened && p.vy == 0.0 ? 2 : (p.vy >= 0.0 ? 1 : 0);
-        switch (3 * cx + cy) {
+        switch (sign_class(p)) {
             case 8: if constexpr (DIV <= 1) CSIM_LAUNCH_O(2, 2); break;
             case 7: if constexpr (DIV <= 1) CSIM_LAUNCH_O(2, 1); break;
             case 6: if constexpr (DIV <= 1) CSIM_LAUNCH_O(2, 0); break;
@@ -376,17 +265,19 @@ hipError_t sweepO_div(const double* in, double* out, int nx, int ny, int pitch, 
 }
 
 template <int T>
-hipError_t sweepO_T(const double* in, double* out, int nx, int ny, int pitch, const Phys& p,
-                           const SweepCfg& cfg, const Bc2& bc, const FinLines& fin, int part, hipStream_t st,
-                           const FrameSync& fs) {
+hipError_t sweepO_T(const double* in, double* out, int pitch, const Phys& p, const SweepCfg& cfg, const Bc2& bc,
+                    const FinLines& fin, const SweepPlan& plan, hipStream_t st, const FrameSync& fs) {
 #ifdef CSIM_ISA_PROBE  // tools: only the instantiation bench.py runs (dx = dy = 1, vx, vy >= 0), for a readable listing
-    return sweepO_div<0, T>(in, out, nx, ny, pitch, p, cfg, bc, fin, part, st, fs);
+    // the plan took its edge rule from p.div_mode (plan_sweepO): a probe build run with another mode would pair a plan
+    // without bands with a kernel that specialises its edges
+    if (p.div_mode != 0) return hipErrorInvalidValue;
+    return sweepO_div<0, T>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
 #else
     switch (p.div_mode) {
-        case 0: return sweepO_div<0, T>(in, out, nx, ny, pitch, p, cfg, bc, fin, part, st, fs);
-        case 1: return sweepO_div<1, T>(in, out, nx, ny, pitch, p, cfg, bc, fin, part, st, fs);
-        case 3: return sweepO_div<3, T>(in, out, nx, ny, pitch, p, cfg, bc, fin, part, st, fs);
-        default: return sweepO_div<2, T>(in, out, nx, ny, pitch, p, cfg, bc, fin, part, st, fs);
+        case 0: return sweepO_div<0, T>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
+        case 1: return sweepO_div<1, T>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
+        case 3: return sweepO_div<3, T>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
+        default: return sweepO_div<2, T>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
     }
 #endif
 }

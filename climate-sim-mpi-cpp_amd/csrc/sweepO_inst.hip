@@ -7,8 +7,8 @@
 
 namespace csim {
 
-template hipError_t sweepO_T<CSIM_INST_T>(const double* in, double* out, int nx, int ny, int pitch, const Phys& p,
-                                    const SweepCfg& cfg, const Bc2& bc, const FinLines& fin, int part, hipStream_t st,
-                                    const FrameSync& fs);
+template hipError_t sweepO_T<CSIM_INST_T>(const double* in, double* out, int pitch, const Phys& p, const SweepCfg& cfg,
+                                          const Bc2& bc, const FinLines& fin, const SweepPlan& plan, hipStream_t st,
+                                          const FrameSync& fs);
 
 }  // namespace csim

@@ -1,7 +1,9 @@
 // sweep_core.hpp — the device code that the single stepper (sweepO.hpp, kernels.hip) and the ensemble (ensemble.hip)
 // share: the per-cell update, the lane moves and pair stores, the argument blocks of the fused sweep, the march of
 // the overlapped-strip sweep with its bodies (sweepO_march), the ghost-fill rule and the wavefront reductions.  No
-// kernel and no launcher is defined here; two host helpers of the launchers (cdiv, whole_groups) close the file.
+// kernel and no launcher is defined here.  The geometry of a strip (OverlapGeom), the rule of SPECIALISE_EDGES and the
+// Tiling inside SweepArgs are sweep_plan.hpp's (host arithmetic, through internal.hpp): here they are compile-time
+// constants and an argument the kernel decodes.
 //
 // The path is HBM-bandwidth-bound by nature (16 algorithmic bytes and 12-15 fp64 operations per cell
 // update: 15 in the reference's sequence, 14 with E - 2c fused, 12 for power-of-two velocities), so there is no MFMA here.  What matters:
@@ -246,32 +248,6 @@ struct FinLines {
     double* line[4];  // left/right: ny entries; bottom/top: nx entries; all nullptr = off
 };
 
-// Tiles of one launch: up to four rectangular regions of (strip, chunk) tiles, numbered
-// consecutively; wavefront w of block b owns tile 4 b + w.  One region (all strips x all rows) is
-// the whole-field launch; a multi-rank pass splits the field into the FRAME (bottom band, top
-// band, left strip(s), right strip(s): thin tiles, finished early so that the faces can travel
-// while the rest computes) and the BULK (everything else).
-struct TileRegion {
-    int t_end;          // tiles [t_end of the previous region, t_end)
-    int strip0, nstrip; // strips strip0 .. strip0 + nstrip - 1
-    int j0, j1, ry;     // rows j0 .. j1 in chunks of ry
-};
-struct Tiling {
-    TileRegion r[8];
-    int nregions, ntiles;
-    // merged launch (frame + bulk in one grid): tiles [0, frame_tiles) are the frame, owned by blocks
-    // [0, frame_blocks) in plain order so that they are dispatched first and spread over all XCDs; the
-    // bulk tiles follow from tile 4 * frame_blocks on, XCD-remapped among themselves.  0 = not merged.
-    int frame_tiles, frame_blocks;
-    // TAIL region: the last tail_blocks blocks own, in plain order, the tiles of the last region(s) — the top
-    // eighth of the (bulk of the) field cut into chunks of half the height, dispatched last, so that the
-    // chip drains in half-height steps instead of idling behind the last full-height wavefronts
-    // (17 468 wavefronts are 4.26 rounds of 4096 slots on 16384^2: the partial last round was 7 % of the
-    // launch).  The main tiles before them fill their blocks exactly and are XCD-remapped.  0 = no tail.
-    int tail_blocks;
-};
-
-
 // The by-value argument block of k_sweepO_dpp (behind the two field pointers, which stay direct __restrict__
 // parameters).  Everything a wavefront needs BEFORE or DURING its march is read from the parameter as usual; what it
 // needs only rarely or only AFTER the march — the FinLines pointers, the whole FrameSync — is read from the
@@ -311,8 +287,8 @@ struct LateArgs {
 
 template <int T>
 struct OverlapGeom {
-    static constexpr int TP = 2 * ((T + 1) / 2);       // T rounded up to even
-    static constexpr int STRIDE = WAVE_COLS - 2 * TP;  // output columns per wavefront
+    static constexpr int TP = strip_overlap(T);     // T rounded up to even
+    static constexpr int STRIDE = strip_stride(T);  // output columns per wavefront
 };
 
 // FAST (interior body only): the cell update with E - 2c, N - 2c fused (diffuse_term<., true>), bit-identical to
@@ -562,12 +538,11 @@ __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, doub
     return FAST && __builtin_amdgcn_ballot_w64(big) != 0;
 }
 
-// Which instantiations get the straight-line edge flavours (seven more march bodies, ~13 KB of code each): the
-// arithmetic modes and depths that long runs are made of.  The others (IEEE division, contracted arithmetic, the
-// shallow depths of remainder passes) run every edge tile through the generic body, as round 2 did.
+// Which instantiations get the straight-line edge flavours: the rule is specialise_edges (sweep_plan.hpp), which the
+// tile plan reads too.
 template <int DIV, int T>
 struct SPECIALISE_EDGES {
-    static constexpr bool value = (DIV == 0 || DIV == 1) && T >= 4;
+    static constexpr bool value = specialise_edges(DIV, T);
 };
 
 // Which instantiations of k_sweepO_dpp carry the M_FAST_P2 body: the same arithmetic modes and depths, with both
@@ -695,15 +670,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
     return v;
-}
-
-// ---- host-side helpers of the launchers ------------------------------------------------------
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
-// the march runs whole groups of six iterations: `rows` rounded up so that rows + 2 (T - 1) is a multiple of six
-template <int T>
-constexpr int whole_groups(int rows) {
-    return rows + (6 - (rows + 2 * (T - 1)) % 6) % 6;
 }
 
 }  // namespace csim

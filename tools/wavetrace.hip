@@ -3,7 +3,8 @@
 // start/end wall clock and its XCC / SE / CU / SIMD) and prints the launch's timeline: how long
 // dispatch takes, how many wavefronts each SIMD received, spread of wave durations, idle tail.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DCSIM_TRACE \
-//              -I../include -I../climate-sim-mpi-cpp_amd/csrc -o wavetrace wavetrace.hip
+//              -I../include -I../climate-sim-mpi-cpp_amd/csrc -o wavetrace wavetrace.hip \
+//              ../climate-sim-mpi-cpp_amd/csrc/sweep_plan.cpp
 // Usage: ./wavetrace NX NY T RY [reps] [boundary kind: 0 dirichlet, 1 neumann, 2 periodic, 3 none]
 #include "../climate-sim-mpi-cpp_amd/csrc/sweepO.hpp"  // every depth of the fused sweep, in this one unit
 #include "../climate-sim-mpi-cpp_amd/csrc/kernels.hip"
@@ -61,12 +62,12 @@ int main(int argc, char** argv) {
     const int kd = argc > 6 ? std::atoi(argv[6]) : CSIM_BC_DIRICHLET;  // 3 = no physical edge (no edge-body waves)
     const int kind[4] = {kd, kd, kd, kd};
 
-    const int stride = 128 - 4 * ((T + 1) / 2);
-    const int nstrips = (nx + stride - 1) / stride;
+    const SweepPlan plan = plan_sweepO(nx, ny, T, p, cfg, kind, 0);
+    const int stride = strip_stride(T);
+    const int nstrips = plan.nstrips;
     const int nchunks = (ny + ry - 1) / ry;
-    const int nblocks = (nstrips * nchunks + 3) / 4;
-    // (trace slots: a launch with a tail region of half-height chunks has more tiles than strips x chunks)
-    const size_t nwaves = static_cast<size_t>(nblocks) * 4 * 2 + 64;
+    const int nblocks = plan.nblocks;  // with bands or a tail region more than strips x chunks / 4
+    const size_t nwaves = static_cast<size_t>(nblocks) * 4;
     unsigned long long* d_tr;
     CK(hipMalloc(&d_tr, nwaves * 3 * sizeof(unsigned long long)));
     CK(hipMemcpyToSymbol(HIP_SYMBOL(g_wave_trace), &d_tr, sizeof(d_tr)));
@@ -77,7 +78,7 @@ int main(int argc, char** argv) {
     CK(hipEventCreate(&e1));
     // leave the idle clocks first: ~0.4 s of back-to-back launches
     for (int r = 0; r < 4000; ++r) {
-        CK(launch_sweepO(va, vb, nx, ny, pitch, p, cfg, kind, 0.0, T, 0, st));
+        CK(launch_sweepO(va, vb, pitch, p, cfg, kind, 0.0, plan, st));
         std::swap(va, vb);
         if (r % 100 == 99) {
             CK(hipStreamSynchronize(st));
@@ -95,7 +96,7 @@ int main(int argc, char** argv) {
     for (int r = 0; r < reps; ++r) {
         CK(hipMemsetAsync(d_tr, 0, nwaves * 3 * sizeof(unsigned long long), st));
         CK(hipEventRecord(e0, st));
-        CK(launch_sweepO(va, vb, nx, ny, pitch, p, cfg, kind, 0.0, T, 0, st));
+        CK(launch_sweepO(va, vb, pitch, p, cfg, kind, 0.0, plan, st));
         CK(hipEventRecord(e1, st));
         CK(hipStreamSynchronize(st));
         float ms = 0;
@@ -151,7 +152,7 @@ int main(int argc, char** argv) {
         // edge-body wavefronts (first/last strip, chunks next to a physical bottom/top edge) vs the rest
         {
             std::vector<double> de, di, ee, ei;
-            const int TPv = 2 * ((T + 1) / 2);
+            const int TPv = strip_overlap(T);
             for (size_t w = 0; w < nwaves; ++w) {
                 const double d = (tr[3 * w + 1] - tr[3 * w]) * us;
                 if (!tr[3 * w] || d < 2.0) continue;
