@@ -80,6 +80,11 @@ class CsimObsScreenCycle(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("n_used", "n_inactive", "n_rejected")]
 
 
+class CsimObsImpactSummary(C.Structure):
+    """csim_obs_impact_summary of include/csim.h"""
+    _fields_ = [("used", C.c_longlong), ("beneficial", C.c_longlong), ("total", C.c_double)]
+
+
 class CsimVerifyScores(C.Structure):
     """csim_verify_scores of include/csim.h"""
     _fields_ = [("cells", C.c_longlong), ("nan_cells", C.c_longlong), ("crps", C.c_double), ("rmse", C.c_double),
@@ -229,6 +234,9 @@ def lib() -> C.CDLL:
         "csim_obs_network_screen_log": (i, [vp, i, C.POINTER(CsimObsScreenCycle), ip]),
         "csim_obs_network_status": (i, [vp, C.POINTER(C.c_ubyte)]),
         "csim_obs_screen_decide": (i, [d, d, d, d, d, i, ip]),
+        "csim_obs_network_impact_capture": (i, [vp, i]),
+        "csim_ensemble_obs_impact": (i, [vp, vp, dp, dp, C.POINTER(CsimObsImpactSummary)]),
+        "csim_obs_impact_fold": (i, [dp, C.c_long, dp]),
         "csim_ensemble_set_option": (i, [vp, C.c_char_p, C.c_long]),
         "csim_ensemble_get_option": (i, [vp, C.c_char_p, C.POINTER(C.c_long)]),
         "csim_ensemble_plan": (i, [i, i, i, i, ip]),
@@ -836,6 +844,38 @@ def obs_screen_decide(y, hb, vb, r, tol, active=True) -> int:
     return st.value
 
 
+IMPACT_MAX_DOUBLES = 1 << 27  # CSIM_IMPACT_MAX_DOUBLES
+ObsImpactSummary = collections.namedtuple("ObsImpactSummary", "used beneficial total")
+ObsImpactSummary.__doc__ = """of Ensemble.obs_impact(): the observations the captured analysis used, how many of them
+have a negative impact (they reduced the forecast error), and the sum of the impacts"""
+ObsImpact = collections.namedtuple("ObsImpact", "impact summary")
+ObsImpact.__doc__ = """what Ensemble.obs_impact() returns: J_o per observation in input order, and an ObsImpactSummary"""
+
+
+def obs_impact_fold(u) -> float:
+    """the lane-and-butterfly sum that Ensemble.obs_impact() makes of a window's terms (csim_obs_impact_fold) — host
+    only"""
+    uu = np.ascontiguousarray(np.atleast_1d(np.asarray(u, dtype=np.float64)))
+    if uu.ndim != 1:
+        raise ValueError("expected a one-dimensional sequence of terms")
+    out = C.c_double()
+    _ck(lib().csim_obs_impact_fold(_dp(uu), len(uu), C.byref(out)))
+    return out.value
+
+
+def impact_weight(mean_a, mean_b, truth) -> np.ndarray:
+    """the weight C (e_a + e_b) of Ensemble.obs_impact() for the mean squared error of the interior: from the mean
+    forecasts from the analysis and from the background and the truth at verification time, (ny+2, nx+2) each,
+    ((mean_a - truth) + (mean_b - truth)) / (nx ny) on the interior and 0 on the ghost ring — numpy only"""
+    a, b, t = (np.asarray(v, dtype=np.float64) for v in (mean_a, mean_b, truth))
+    if a.ndim != 2 or a.shape != b.shape or a.shape != t.shape or min(a.shape) < 3:
+        raise ValueError("mean_a, mean_b and truth must be fields of one shape (ny+2, nx+2)")
+    w = np.zeros(a.shape)
+    n = float((a.shape[0] - 2) * (a.shape[1] - 2))
+    w[1:-1, 1:-1] = ((a[1:-1, 1:-1] - t[1:-1, 1:-1]) + (b[1:-1, 1:-1] - t[1:-1, 1:-1])) / n
+    return w
+
+
 class ObsNetwork:
     """observations that live on the device (csim_obs_network_*): planned once, their values drawn on the GPU
     from a member or set from the host, read by Ensemble.assimilate_network without staging.  Point observations of
@@ -970,6 +1010,14 @@ class ObsNetwork:
 
     def log_reset(self):
         _ck(lib().csim_obs_network_log_reset(self._h))
+
+    def impact_capture(self, truth_member=None):
+        """keeps what Ensemble.obs_impact() needs of the last analysis, which must be a recorded one: the analysis
+        perturbations of the current members in observation space, the normalised innovations and which observations
+        were used.  Call it on the ensemble the forecast starts from (after relax / perturb if they are part of the
+        cycle); it stays valid across run() until the next capture; enqueued without waiting
+        (csim_obs_network_impact_capture)"""
+        _ck(lib().csim_obs_network_impact_capture(self._h, -1 if truth_member is None else int(truth_member)))
 
 
 def _scores(sc: CsimVerifyScores, nt: int) -> VerifyScores:
@@ -1175,6 +1223,17 @@ class Ensemble:
             _ck(lib().csim_ensemble_assimilate_network(self._h, net._h, float(inflation), tm, rec))
         else:
             _ck(lib().csim_ensemble_assimilate_screened(self._h, net._h, float(inflation), tm, rec, float(screen)))
+
+    def obs_impact(self, net: ObsNetwork, weight) -> ObsImpact:
+        """the forecast impact J_o of every observation of net's captured analysis on the error of the current
+        (verification-time) state, EFSOI: weight is C (e_a + e_b) as a (ny+2, nx+2) field, impact_weight() for the mean
+        squared error; J_o < 0: the observation reduced the forecast error.  Synchronous (csim_ensemble_obs_impact)"""
+        w = np.ascontiguousarray(weight, dtype=np.float64)
+        if w.shape != (self.ny + 2, self.nx + 2):
+            raise ValueError(f"weight must have shape {(self.ny + 2, self.nx + 2)}")
+        out, sm = np.empty(net.nobs), CsimObsImpactSummary()
+        _ck(lib().csim_ensemble_obs_impact(self._h, net._h, _dp(w), _dp(out), C.byref(sm)))
+        return ObsImpact(out, ObsImpactSummary(sm.used, sm.beneficial, sm.total))
 
     def perturb(self, sigma, corr_len, seed, draw=0, centered=False, truth_member=None):
         """adds sigma times a seeded Gaussian random field of correlation length corr_len to the interior of every

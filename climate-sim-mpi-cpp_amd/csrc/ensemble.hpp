@@ -144,6 +144,35 @@ hipError_t ens_launch_assim_inflate(const EnsGeom& g, double* f, int forecast, i
 hipError_t ens_launch_assim_post(const EnsGeom& g, const double* f, const AssimArgs& a, int nobs, double* post,
                                  hipStream_t st);
 
+// the per-observation forecast impact (ensemble_impact.hip): csim_obs_network_impact_capture and
+// csim_ensemble_obs_impact.  Everything is in plan order but `bg` and the result, which go by input index.
+struct ImpactCapture {
+    const double* bg;             // 2 per input index: hb, vb of the recorded analysis
+    const unsigned char* status;  // that analysis's status bytes; null: it was not screened, every observation was used
+    double* pert;                 // M per plan position: a_k = h_k - ha
+    double* dn;                   // (y - hb) / r
+    unsigned char* snap;          // the status bytes, kept
+};
+struct ImpactArgs {
+    int nobs;
+    int forecast;                 // M
+    int truth_member;             // t, or B (no member skipped)
+    int lx, ly;
+    const double* rho;            // (2 ly + 1) x (2 lx + 1)
+    const int* i;
+    const int* j;
+    const int* idx;
+    const unsigned char* snap;
+    const double* pert;
+    const double* dn;
+    const double* w;              // the weight, dense (ny+2) x (nx+2)
+};
+// a_k, dn and the status of every observation from the current members; the AssimArgs as for ens_launch_assim_post
+hipError_t ens_launch_impact_capture(const EnsGeom& g, const double* f, const AssimArgs& a, int nobs,
+                                     const ImpactCapture& c, hipStream_t st);
+// J_o of every observation, by input index, from the members at verification time
+hipError_t ens_launch_obs_impact(const EnsGeom& g, const double* f, const ImpactArgs& a, double* out, hipStream_t st);
+
 // the perturbation of csim_ensemble_perturb (ensemble_perturb.hip), one launch: x_k += sigma p_k on every interior
 // cell of the forecast members, p_k the white noise of ensemble_noise.hpp smoothed with the host's taps along x, then
 // along y (csim_ensemble_perturb_taps; tx[o + rx], ty[o + ry]), less its mean over the members when centered

@@ -1,5 +1,5 @@
 // ensemble_cell.hpp — one cell of an ensemble across its members: what the per-cell kernels of ensemble_stats,
-// _quantiles, _verify, _assim and _relax .hip share, said once.  Needs only the slab layout of ensemble.hpp.  Every
+// _quantiles, _verify, _assim, _relax and _impact .hip share, said once.  Needs only the slab layout of ensemble.hpp.  Every
 // device piece is force-inlined into its kernel (the tile's loader is a macro); the host pieces choose a kernel's
 // instantiation, size its tile and raise its dynamic LDS limit.
 //

@@ -4,6 +4,9 @@
 // then only points an AssimArgs into the network's buffer and enqueues the launches of ensemble_da.cpp's assim_enqueue.
 // Screening (csim_obs_network_set_active, csim_ensemble_assimilate_screened) adds a mask and a status byte per plan
 // position: one k_obs_screen launch ahead of the analysis, whose kernels then skip what is not used.
+// The forecast impact (csim_obs_network_impact_capture, csim_ensemble_obs_impact; kernels in ensemble_impact.hip) keeps
+// a capture in storage of the network's own, made at the first capture: a_k per observation, dn and the status bytes,
+// and a device copy of the caller's weight; nothing that an analysis, observe or set_values writes.
 #include <cmath>
 #include <memory>
 #include <new>
@@ -30,6 +33,19 @@ int screen_decide(double y, double hb, double vb, double r, double tol, bool act
     return lhs <= rhs ? CSIM_OBS_USED : CSIM_OBS_REJECTED;
 }
 
+// the lane-and-butterfly sum of csim_ensemble_obs_impact: what one wave of k_obs_impact does with its cells
+double impact_fold(const double* u, long n) {
+    double l[64];
+    for (int j = 0; j < 64; ++j) l[j] = 0.0;
+    for (long e = 0; e < n; ++e) l[e % 64] = l[e % 64] + u[e];
+    for (int h = 32; h >= 1; h >>= 1) {
+        double m[64];
+        for (int j = 0; j < 64; ++j) m[j] = l[j] + l[j ^ h];
+        for (int j = 0; j < 64; ++j) l[j] = m[j];
+    }
+    return l[0];
+}
+
 }  // namespace
 
 struct csim_obs_network : AssimPlan {   // the plan: nobs, nlevels, lx, ly, off, idx, pi, pj
@@ -45,6 +61,21 @@ struct csim_obs_network : AssimPlan {   // the plan: nobs, nlevels, lx, ly, off,
     bool masked = false;                // the mask on the device has an inactive observation (else it is not read)
     bool analysed = false, screened = false;  // there was an analysis; the last one launched the screening
     int cycles = 0;                     // records in both logs
+    bool last_recorded = false;         // the last analysis was a recorded one: bg and the status bytes are its own
+    // the capture of csim_obs_network_impact_capture, made at the first capture and kept until destroy
+    struct Impact {
+        DeviceBuf pert;                 // M doubles per plan position: a_k
+        DeviceBuf aux;                  // dn (plan order), J (input order), the status snapshot (plan order)
+        DeviceBuf w;                    // the weight of the last csim_ensemble_obs_impact, dense
+        Staging wstage;
+        bool valid = false;
+        int M = 0, t = 0;               // its forecast members: M of them, member t left out (t = B: none)
+        void release() { pert.release(), aux.release(), w.release(), wstage.release(); }
+    } imp;
+    size_t imp_dn() const { return 0; }
+    size_t imp_out() const { return up(sizeof(double) * nobs); }
+    size_t imp_snap() const { return 2 * up(sizeof(double) * nobs); }
+    size_t imp_bytes() const { return imp_snap() + up(nobs); }
     template <class T> T* at(size_t byte) const { return buf_at<T>(dev.p, byte); }
     ObsArgs args() const {
         ObsArgs a{};
@@ -56,7 +87,7 @@ struct csim_obs_network : AssimPlan {   // the plan: nobs, nlevels, lx, ly, off,
         if (ntaps) a.tstart = at<int>(l.tstart), a.toff = at<int>(l.toff), a.tw = at<double>(l.tw);
         return a;
     }
-    ~csim_obs_network() { dev.release(), stage.release(), mstage.release(); }
+    ~csim_obs_network() { dev.release(), stage.release(), mstage.release(), imp.release(); }
 };
 
 void csim_ensemble::Obs::release() {
@@ -322,7 +353,7 @@ int csim_ensemble_assimilate_screened(csim_ensemble* e, csim_obs_network* n, dou
         CSIM_HIP(ens_launch_obs_screen(oa, s, e->st));
         a.status = s.status;
     }
-    n->analysed = true, n->screened = screen;
+    n->analysed = true, n->screened = screen, n->last_recorded = record == 1;
     CSIM_TRY(assim_enqueue(e, a, inflation, n->batches));
     if (!record) return CSIM_OK;
     CSIM_HIP(ens_launch_assim_post(g, f, a, n->nobs, n->at<double>(n->l.post), e->st));
@@ -335,6 +366,103 @@ int csim_ensemble_assimilate_screened(csim_ensemble* e, csim_obs_network* n, dou
         CSIM_HIP(ens_launch_obs_cycle(oa, n->has_truth, slot, e->st));
     ++n->cycles;
     n->has_diag = true;
+    return CSIM_OK;
+}
+
+int csim_obs_network_impact_capture(csim_obs_network* n, int truth_member) {
+    CSIM_REQUIRE(n, "null network");
+    csim_ensemble* e = n->e;
+    const EnsGeom& g = e->g;
+    int M = 0, t = 0;
+    CSIM_TRY(forecast_split(g.members, truth_member, &M, &t, 2, "the impact needs at least two forecast members",
+                            ASSIM_MAX_MEMBERS, "csim_obs_network_impact_capture: at most 1024 forecast members"));
+    CSIM_REQUIRE(g.slab <= 0x7fffffffL, "grid too large for the impact");
+    const size_t doubles = static_cast<size_t>(n->nobs) * M;
+    if (doubles > static_cast<size_t>(CSIM_IMPACT_MAX_DOUBLES))
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_obs_network_impact_capture: nobs times the forecast members exceeds "
+                                          "CSIM_IMPACT_MAX_DOUBLES");
+    if (!n->has_diag || !n->last_recorded)
+        return fail(CSIM_ERR_STATE, "csim_obs_network_impact_capture: the network's last analysis was not recorded "
+                                    "(csim_ensemble_assimilate_network with record = 1)");
+    csim_obs_network::Impact& x = n->imp;
+    // a buffer that has to grow is replaced after the stream has drained, and the old capture goes with it
+    if (sizeof(double) * doubles > x.pert.cap || n->imp_bytes() > x.aux.cap) x.valid = false;
+    CSIM_TRY(x.pert.reserve(sizeof(double) * doubles, e->st));
+    CSIM_TRY(x.aux.reserve(n->imp_bytes(), e->st));
+    x.valid = false;  // from here on the last capture is being overwritten (in stream order, after its readers)
+    const ObsArgs oa = n->args();
+    const AssimArgs a = assim_args(M, t, *n, n->at<double>(n->l.rho), {oa.i, oa.j, oa.idx, oa.y, oa.r}, nullptr, nullptr,
+                                   nullptr, oa.tstart, oa.toff, oa.tw, n->tmax);
+    const ImpactCapture c{oa.bg, n->screened ? n->at<unsigned char>(n->l.status) : nullptr, x.pert.as(),
+                          buf_at<double>(x.aux.p, n->imp_dn()), buf_at<unsigned char>(x.aux.p, n->imp_snap())};
+    CSIM_HIP(ens_launch_impact_capture(g, e->base(e->cur), a, n->nobs, c, e->st));
+    x.valid = true, x.M = M, x.t = t;
+    return CSIM_OK;
+}
+
+int csim_ensemble_obs_impact(csim_ensemble* e, csim_obs_network* n, const double* weight, double* out_impact,
+                             csim_obs_impact_summary* summary) {
+    CSIM_REQUIRE(e, "null ensemble");
+    CSIM_REQUIRE(n, "null network");
+    CSIM_REQUIRE(n->e == e, "the network belongs to another ensemble");
+    CSIM_REQUIRE(weight, "null weight");
+    const EnsGeom& g = e->g;
+    csim_obs_network::Impact& x = n->imp;
+    if (!x.valid)
+        return fail(CSIM_ERR_STATE, "csim_ensemble_obs_impact: the network has no capture "
+                                    "(csim_obs_network_impact_capture)");
+    const size_t nx2 = static_cast<size_t>(g.nx) + 2, cells = stats_cells(e);
+    for (int j = 1; j <= g.ny; ++j)
+        for (int i = 1; i <= g.nx; ++i)
+            CSIM_REQUIRE(std::isfinite(weight[j * nx2 + i]), "every interior value of the weight must be finite");
+    try {
+        std::vector<double> J(n->nobs);
+        std::vector<unsigned char> snap(n->nobs);
+        // the interior of the weight, +0 on the ghost ring, copied before any kernel runs
+        void* staged = nullptr;
+        CSIM_TRY(x.wstage.acquire(sizeof(double) * cells, &staged));
+        auto* hw = static_cast<double*>(staged);
+        std::fill(hw, hw + cells, 0.0);
+        for (int j = 1; j <= g.ny; ++j) std::copy(weight + j * nx2 + 1, weight + j * nx2 + 1 + g.nx, hw + j * nx2 + 1);
+        CSIM_TRY(x.w.reserve(sizeof(double) * cells, e->st));
+        CSIM_TRY(x.wstage.send(x.w.p, sizeof(double) * cells, e->st));
+        const ObsArgs oa = n->args();
+        ImpactArgs a{};
+        a.nobs = n->nobs, a.forecast = x.M, a.truth_member = x.t, a.lx = n->lx, a.ly = n->ly;
+        a.rho = n->at<double>(n->l.rho), a.i = oa.i, a.j = oa.j, a.idx = oa.idx;
+        a.snap = buf_at<unsigned char>(x.aux.p, n->imp_snap());
+        a.pert = x.pert.as(), a.dn = buf_at<double>(x.aux.p, n->imp_dn()), a.w = x.w.as();
+        double* out = buf_at<double>(x.aux.p, n->imp_out());
+        CSIM_HIP(ens_launch_obs_impact(g, e->base(e->cur), a, out, e->st));
+        CSIM_HIP(hipMemcpyAsync(J.data(), out, sizeof(double) * J.size(), hipMemcpyDeviceToHost, e->st));
+        CSIM_HIP(hipMemcpyAsync(snap.data(), a.snap, snap.size(), hipMemcpyDeviceToHost, e->st));
+        CSIM_HIP(hipStreamSynchronize(e->st));
+        if (out_impact) std::copy(J.begin(), J.end(), out_impact);
+        if (summary) {
+            summary->used = summary->beneficial = 0;
+            for (unsigned char s : snap) summary->used += s == CSIM_OBS_USED;
+            // the chunks of csim_obs_cycle: T_c from +0 in input order, their running sum from +0 in chunk order
+            double total = 0.0;
+            for (int c0 = 0; c0 < n->nobs; c0 += OBS_CHUNK) {
+                double T = 0.0;
+                for (int o = c0; o < std::min(n->nobs, c0 + OBS_CHUNK); ++o) {
+                    T = T + J[o];
+                    summary->beneficial += J[o] < 0.0;
+                }
+                total = total + T;
+            }
+            summary->total = total;
+        }
+        return CSIM_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(CSIM_ERR_STATE, "csim_ensemble_obs_impact: out of host memory");
+    }
+}
+
+int csim_obs_impact_fold(const double* u, long n, double* S) {
+    CSIM_REQUIRE(S, "null argument");
+    CSIM_REQUIRE(n >= 0 && (n == 0 || u), "n must be >= 0, with that many values");
+    *S = impact_fold(u, n);
     return CSIM_OK;
 }
 

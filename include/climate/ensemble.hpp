@@ -53,6 +53,13 @@ struct ObsTaps {
     std::size_t size() const { return i.size(); }
 };
 
+// the forecast impact of a network's observations (see csim_ensemble_obs_impact): J_o per observation in input order,
+// J_o < 0: the observation reduced the forecast error, and the summary
+struct ObsImpact {
+    std::vector<double> impact;
+    csim_obs_impact_summary summary{};
+};
+
 class Ensemble;
 
 // observations that live on the device (csim_obs_network_*): planned once, their values drawn on the GPU from a
@@ -138,6 +145,9 @@ public:
         check(csim_obs_network_screen_log(handle(), k, out.data(), &k));
         return out;
     }
+    // keeps what Ensemble::obs_impact() needs of the last analysis, which must be a recorded one (see
+    // csim_obs_network_impact_capture); t as in Ensemble::assimilate.  Enqueued; valid across run() until the next capture
+    void impact_capture(int t = -1) { check(csim_obs_network_impact_capture(handle(), t)); }
 
 private:
     friend class Ensemble;
@@ -382,6 +392,14 @@ public:
     // (y - hb)^2 > screen_tol^2 (vb + r); the network's active mask acts either way
     void assimilate(ObsNetwork& net, double inflation = 1.0, int t = -1, bool record = false, double screen_tol = 0.0) {
         check(csim_ensemble_assimilate_screened(h_, net.handle(), inflation, t, record ? 1 : 0, screen_tol));
+    }
+    // the forecast impact of every observation of net's captured analysis on the error of the current state (EFSOI, see
+    // csim_ensemble_obs_impact); weight = C (e_a + e_b), member_size() values of which the interior is read.  Synchronous
+    ObsImpact obs_impact(ObsNetwork& net, const std::vector<double>& weight) {
+        ObsImpact r;
+        r.impact.resize(net.size());
+        check(csim_ensemble_obs_impact(h_, net.handle(), sized(weight, 1), r.impact.data(), &r.summary));
+        return r;
     }
     // adds sigma times a seeded Gaussian random field of correlation length corr_len to the interior of every forecast
     // member (t = -1: all members, else member t is left alone); enqueued on the ensemble's stream, so that run() follows

@@ -732,6 +732,71 @@ typedef struct csim_obs_screen_cycle {
 int csim_obs_network_screen_log(csim_obs_network* n, int max, csim_obs_screen_cycle* out, int* ncycles);
 int csim_obs_network_status(csim_obs_network* n, unsigned char* status);
 int csim_obs_screen_decide(double y, double hb, double vb, double r, double tol, int active, int* status);
+/* forecast impact: which observations of a network helped the forecast, and by how much: ensemble forecast sensitivity
+ * to observations (EFSOI; Kalnay et al. 2012, localised as in Hotta et al. 2017).  No adjoint, no data-denial runs.  With
+ * d = y - hb the innovations of a recorded analysis, Ya the analysis perturbations in observation space, Xf the forecast
+ * perturbations at verification time, M forecast members, e_a and e_b the errors of the mean forecasts from the analysis
+ * and from the background, and C a norm,
+ *
+ *     e_a' C e_a - e_b' C e_b  ~=  1/(M-1)  d' R^-1 Ya [rho o Xf' C (e_a + e_b)]  =  sum_o J_o
+ *
+ * J_o is the impact of observation o; J_o < 0: it reduced the forecast error.  rho is the network's own table around
+ * the observation's cell or anchor, where it was at analysis time (static localisation: rho is not advected with the
+ * flow), and a multiplicative inflation, a relaxation or a perturbation between the analysis and the capture enters only
+ * through the perturbations that are captured.  The cycle is
+ *     assimilate_network(record) [-> relax -> perturb] -> impact_capture -> run -> obs_impact(weight),
+ * the caller forming weight = C (e_a + e_b) on the host.  Point and linear networks alike.  All fp64 arithmetic IEEE,
+ * without FMA contraction, every product rounded, / correctly rounded.
+ * impact_capture: only enqueues.  The network's last analysis must be one recorded with record = 1; the M forecast
+ *   members are all B (truth_member = -1) or the B - 1 others in their order, as in csim_ensemble_assimilate.  For every
+ *   observation o, in the current buffer after everything enqueued so far:  h_k of forecast member k, the cell of a point
+ *   observation (its bits), sum_s w_s x_k(anchor + tap s) of a linear one as in csim_obs_network_create_linear;
+ *       ha = sum h_k / M  (a running sum from +0 in member order);   a_{o,k} = h_k - ha
+ *   kept as M doubles per observation in storage of the network's own, made at the first capture and kept until destroy.
+ *   Also kept:  dn_o = (y_o - hb_o) / r_o  from the network's values as they are now and the bg_mean of the recorded
+ *   analysis (one subtraction, one division), and that analysis's status byte; every observation counts as USED when it
+ *   was not screened.  Of an observation that is not USED only the byte is kept.  Later observe / set_values /
+ *   set_active calls, later analyses of either kind, runs and uploads leave a capture as it is: it ends at the next
+ *   capture or at destroy.
+ *   Errors, all before anything is enqueued, leaving an earlier capture as it was: CSIM_ERR_ARG for truth_member outside
+ *   -1 .. B-1 and M < 2; CSIM_ERR_UNSUPPORTED for M > CSIM_ASSIM_MAX_MEMBERS and for nobs M > CSIM_IMPACT_MAX_DOUBLES
+ *   (1 GiB of perturbations); CSIM_ERR_STATE when the network's last analysis was not a recorded one (there is none, or
+ *   an unrecorded one has replaced its status bytes since).
+ * obs_impact: synchronous, as csim_ensemble_verify.  e is the network's ensemble at verification time; its forecast
+ *   members are those of the capture (the same truth_member).  weight: a host field in the reference layout,
+ *   (ny+2) x (nx+2); only the interior is read, every interior value must be finite; it is copied before any kernel
+ *   runs.  Per USED observation o, with the table rho and half-widths lx, ly of the network, the window of the analysis
+ *   clipped to the interior, i0 = max(1, i_o - lx) .. i1 = min(nx, i_o + lx), j0 .. j1 likewise, and its cells numbered
+ *   row-major, e = (j - j0) (i1 - i0 + 1) + (i - i0), e = 0 .. cells-1:
+ *
+ *       cell e with rho = rho[j - j_o + ly][i - i_o + lx] > 0:
+ *           xbar = sum x_k / M;   c = sum (x_k - xbar) a_{o,k}      (running sums from +0 in member order k = 0 .. M-1)
+ *           u_e  = (rho (c / (M-1))) weight[j][i]
+ *       cell e with rho == 0:   u_e = +0, whatever the cell holds
+ *       S_o = fold(u_0 .. u_{cells-1});   J_o = dn_o S_o
+ *
+ *   fold is the lane rule of csim_ensemble_verify for M > 64, applied to cells (csim_obs_impact_fold): term e goes to
+ *   lane e % 64; lane l sums its terms in increasing e from +0 (a lane without terms holds +0); the 64 lane sums are
+ *   combined as l[j] = l[j] + l[j ^ h] for h = 32, 16, 8, 4, 2, 1, all j at once; the sum is l[0].  An observation that is
+ *   not USED gets J_o = +0.  No result depends on the launch geometry.
+ *   out_impact (may be NULL): nobs values in input order.  summary (may be NULL): used = the number of USED
+ *   observations, beneficial = the number with J_o < 0, total = sum J_o in input order by the chunk rule of
+ *   csim_obs_cycle: T_c over 256 consecutive input indices from +0, then the running sum of T_c from +0.
+ *   Errors, leaving the capture and everything else as it was: CSIM_ERR_ARG for a null ensemble, network or weight, a
+ *   network of another ensemble, a non-finite interior weight; CSIM_ERR_STATE without a capture.
+ * Neither call writes a member, a ghost ring or the other ping-pong buffer, nor the network's values, mask, logs or
+ * diagnostics.
+ * impact_fold (host-only, needs no device): *S = fold(u_0 .. u_{n-1}); n == 0 gives +0.  CSIM_ERR_ARG for n < 0, a null
+ *   S, a null u with n > 0. */
+#define CSIM_IMPACT_MAX_DOUBLES (1L << 27)
+typedef struct csim_obs_impact_summary {
+    long long used, beneficial;
+    double total;
+} csim_obs_impact_summary;
+int csim_obs_network_impact_capture(csim_obs_network* n, int truth_member);
+int csim_ensemble_obs_impact(csim_ensemble* e, csim_obs_network* n, const double* weight, double* out_impact,
+                             csim_obs_impact_summary* summary);
+int csim_obs_impact_fold(const double* u, long n, double* S);
 /* options (unknown keys: CSIM_ERR_ARG; "contract": CSIM_ERR_UNSUPPORTED), results never depend on them:
  *   "fuse"        -1 (default) passes of the ensemble depth where the grid allows; 0 / 1 single steps only
  *   "fused_2c"    0/1 (default 1), as for csim_stepper_set_option
