@@ -287,28 +287,40 @@ int csim_exchange_plan(const csim_decomp* dec, int depth, csim_msg sends[8], int
 }
 
 // ---- Field -------------------------------------------------------------------------------------
+// what csim_field_create hands out: the handle of internal.hpp (its pointers are views) and the owners of its memory
+struct FieldMem : csim_field {
+    DeviceBuf mem, partials;
+    void release() { mem.release(), partials.release(); }
+};
+static FieldMem* owner(csim_field* f) { return static_cast<FieldMem*>(f); }
+
+static int field_alloc(FieldMem* f) {
+    CSIM_TRY(f->mem.reserve(f->bytes()));
+    CSIM_HIP(hipMemset(f->mem.p, 0, f->bytes()));
+    CSIM_TRY(f->partials.reserve(sizeof(double) * 2 * REDUCE_BLOCKS));
+    f->alloc = f->mem.as();
+    f->d = f->alloc + static_cast<size_t>(GHOST_EXTRA) * f->pitch;
+    f->scratch = f->partials.as();
+    return CSIM_OK;
+}
+
 int csim_field_create(int nx, int ny, int halo, double dx, double dy, csim_field** out) {
     CSIM_REQUIRE(out, "out is null");
     *out = nullptr;
     CSIM_REQUIRE(nx > 0 && ny > 0, "nx/ny must be > 0");
     CSIM_REQUIRE(halo == 1, "only halo == 1 is supported (reference src/main.cpp:65)");
     CSIM_REQUIRE(dx > 0 && dy > 0, "dx/dy must be > 0");
-    csim_field* f = new csim_field;
+    FieldMem* f = new FieldMem;
     f->nx = nx;
     f->ny = ny;
     f->halo = halo;
     f->dx = dx;
     f->dy = dy;
     f->pitch = pitch_for(nx);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&f->alloc), f->bytes());
-    if (e == hipSuccess) e = hipMemset(f->alloc, 0, f->bytes());
-    if (e == hipSuccess) f->d = f->alloc + static_cast<size_t>(GHOST_EXTRA) * f->pitch;
-    if (e == hipSuccess)
-        e = hipMalloc(reinterpret_cast<void**>(&f->scratch), sizeof(double) * 2 * REDUCE_BLOCKS);
-    if (e != hipSuccess) {
-        if (f->alloc) (void)hipFree(f->alloc);
-        delete f;
-        return fail(CSIM_ERR_HIP, std::string("csim_field_create: ") + hipGetErrorString(e));
+    if (field_alloc(f) != CSIM_OK) {
+        const std::string why = g_err;
+        csim_field_destroy(f);
+        return fail(CSIM_ERR_HIP, "csim_field_create: " + why);
     }
     *out = f;
     return CSIM_OK;
@@ -316,9 +328,8 @@ int csim_field_create(int nx, int ny, int halo, double dx, double dy, csim_field
 
 int csim_field_destroy(csim_field* f) {
     if (!f) return CSIM_OK;
-    if (f->alloc) (void)hipFree(f->alloc);
-    if (f->scratch) (void)hipFree(f->scratch);
-    delete f;
+    owner(f)->release();
+    delete owner(f);
     return CSIM_OK;
 }
 
@@ -356,6 +367,7 @@ int csim_field_copy(csim_field* dst, const csim_field* src) {
 
 int csim_field_swap(csim_field* a, csim_field* b) {
     CSIM_REQUIRE(same_shape(a, b), "fields differ in shape");
+    std::swap(owner(a)->mem, owner(b)->mem);
     std::swap(a->alloc, b->alloc);
     std::swap(a->d, b->d);
     return CSIM_OK;

@@ -48,6 +48,19 @@ int ensure_tables(csim_ensemble* e) {
     return CSIM_OK;
 }
 
+// the stream and the device memory of a new ensemble
+int make_resources(csim_ensemble* e, size_t bytes, size_t nred) {
+    const int B = e->g.members;
+    CSIM_TRY(e->own.stream(&e->st));
+    // zero-filled: the pads and the device-only ghost layers the multi-step sweep reads as don't-care must be finite
+    CSIM_TRY(e->own.device(&e->alloc[0], bytes, true));
+    CSIM_TRY(e->own.device(&e->alloc[1], bytes, true));
+    CSIM_TRY(e->own.device(&e->fin, sizeof(double) * e->g.fin_stride * B, true));
+    CSIM_TRY(e->own.device(&e->table, ens_entry_bytes() * B));
+    CSIM_TRY(e->own.device(&e->order, sizeof(int) * B));
+    return e->own.device(&e->scratch, sizeof(double) * nred);
+}
+
 int ghost_fill(csim_ensemble* e, bool fin) {
     CSIM_HIP(ens_launch_ghost_fill(e->g, e->base(e->cur), e->base(1 - e->cur), e->table, fin, e->st));
     return CSIM_OK;
@@ -112,21 +125,10 @@ int csim_ensemble_create(int members, int nx, int ny, int halo, double dx, doubl
     e->D.assign(members, 0.0), e->dt.assign(members, 0.0), e->vx.assign(members, 0.0), e->vy.assign(members, 0.0);
     const size_t bytes = sizeof(double) * static_cast<size_t>(g.slab) * members;
     const size_t nred = static_cast<size_t>(members) * 2 * ENS_REDUCE_ROWS;
-    hipError_t err = hipSuccess;
-    auto ok = [&](hipError_t r) {
-        if (err == hipSuccess) err = r;
-        return err == hipSuccess;
-    };
-    // zero-filled: the pads and the device-only ghost layers the multi-step sweep reads as don't-care must be finite
-    ok(hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking)) && ok(hipMalloc(&e->alloc[0], bytes)) &&
-        ok(hipMalloc(&e->alloc[1], bytes)) && ok(hipMemset(e->alloc[0], 0, bytes)) && ok(hipMemset(e->alloc[1], 0, bytes)) &&
-        ok(hipMalloc(&e->fin, sizeof(double) * g.fin_stride * members)) &&
-        ok(hipMemset(e->fin, 0, sizeof(double) * g.fin_stride * members)) &&
-        ok(hipMalloc(&e->table, ens_entry_bytes() * members)) && ok(hipMalloc(&e->order, sizeof(int) * members)) &&
-        ok(hipMalloc(&e->scratch, sizeof(double) * nred));
-    if (err != hipSuccess) {
+    if (make_resources(e, bytes, nred) != CSIM_OK) {
+        const std::string why = csim_last_error();
         csim_ensemble_destroy(e);
-        return fail(CSIM_ERR_HIP, std::string("csim_ensemble_create: ") + hipGetErrorString(err));
+        return fail(CSIM_ERR_HIP, "csim_ensemble_create: " + why);
     }
     *out = e;
     return CSIM_OK;
@@ -134,20 +136,14 @@ int csim_ensemble_create(int members, int nx, int ny, int halo, double dx, doubl
 
 int csim_ensemble_destroy(csim_ensemble* e) {
     if (!e) return CSIM_OK;
-    if (e->st) (void)hipStreamSynchronize(e->st);
+    e->own.drain();
     e->obs.release();
     e->stats.release();
     e->quant.release();
     e->verify.release();
     e->assim.release();
     e->relax.release();
-    for (double* a : e->alloc)
-        if (a) (void)hipFree(a);
-    if (e->fin) (void)hipFree(e->fin);
-    if (e->table) (void)hipFree(e->table);
-    if (e->order) (void)hipFree(e->order);
-    if (e->scratch) (void)hipFree(e->scratch);
-    if (e->st) (void)hipStreamDestroy(e->st);
+    e->own.release();
     delete e;
     return CSIM_OK;
 }
@@ -168,8 +164,7 @@ int csim_ensemble_upload_all(csim_ensemble* e, const double* host) {
     CSIM_REQUIRE(e && host, "null argument");
     const size_t per = static_cast<size_t>(e->g.nx + 2) * (e->g.ny + 2);
     for (int m = 0; m < e->g.members; ++m) {
-        int rc = csim_ensemble_upload(e, m, host + per * m);
-        if (rc) return rc;
+        CSIM_TRY(csim_ensemble_upload(e, m, host + per * m));
     }
     return CSIM_OK;
 }
@@ -185,8 +180,7 @@ int csim_ensemble_download_all(csim_ensemble* e, double* host) {
     CSIM_REQUIRE(e && host, "null argument");
     const size_t per = static_cast<size_t>(e->g.nx + 2) * (e->g.ny + 2);
     for (int m = 0; m < e->g.members; ++m) {
-        int rc = csim_ensemble_download(e, m, host + per * m);
-        if (rc) return rc;
+        CSIM_TRY(csim_ensemble_download(e, m, host + per * m));
     }
     return CSIM_OK;
 }
@@ -227,10 +221,8 @@ int csim_ensemble_run(csim_ensemble* e, int nsteps) {
     CSIM_REQUIRE(nsteps >= 0, "nsteps must be >= 0");
     if (!e->physics) return fail(CSIM_ERR_STATE, "csim_ensemble_set_physics first");
     int plan[3];
-    int rc = csim_ensemble_plan(nsteps, e->g.nx, e->g.ny, e->fuse, plan);
-    if (rc) return rc;
-    rc = ensure_tables(e);
-    if (rc) return rc;
+    CSIM_TRY(csim_ensemble_plan(nsteps, e->g.nx, e->g.ny, e->fuse, plan));
+    CSIM_TRY(ensure_tables(e));
     const int q = plan[1], r = plan[2];
     const bool stat = e->static_ring();
     if (nsteps > 0) e->relax.mode = 0;  // the forecast a relaxation capture was taken of is gone
@@ -238,8 +230,7 @@ int csim_ensemble_run(csim_ensemble* e, int nsteps) {
     // (unless the ring is static) from which the closing ghost fill makes the reference's ring
     for (int k = 0; k < q; ++k) {
         if (!e->ring_ok) {
-            rc = ghost_fill(e, false);
-            if (rc) return rc;
+            CSIM_TRY(ghost_fill(e, false));
             e->ring_ok = stat;
         }
         const bool final_pass = k == q - 1 && r == 0 && !e->ring_ok;
@@ -251,14 +242,12 @@ int csim_ensemble_run(csim_ensemble* e, int nsteps) {
         }
         e->cur = 1 - e->cur;
         if (final_pass) {
-            rc = ghost_fill(e, true);
-            if (rc) return rc;
+            CSIM_TRY(ghost_fill(e, true));
         }
     }
     for (int k = 0; k < r; ++k) {
         if (!e->ring_ok) {
-            rc = ghost_fill(e, false);
-            if (rc) return rc;
+            CSIM_TRY(ghost_fill(e, false));
             e->ring_ok = stat;
         }
         CSIM_HIP(ens_launch_step(e->g, e->base(e->cur), e->base(1 - e->cur), e->table, e->st));

@@ -5,7 +5,34 @@
 
 using namespace csim;
 
-static int post_exchange2(csim_stepper* s, int H, hipStream_t st) { return post_plan(s, H, st); }
+// what launch_sweepO takes per side: the boundary type of a physical side, 3 for a neighbour side
+struct SideKinds {
+    int kind[4];
+    explicit SideKinds(const csim_stepper* s) {
+        for (int k = 0; k < 4; ++k) kind[k] = s->phys[k] ? s->bc[k] : 3;
+    }
+    operator const int*() const { return kind; }
+};
+
+// ghost fill of a deep pass: the neighbour sides come from the deep faces, not from recv[]
+static GhostArgs deep_ghost_args(const csim_stepper* s) {
+    GhostArgs g = ghost_args(s);
+    for (int k = 0; k < 4; ++k) g.recv[k] = nullptr;
+    return g;
+}
+
+// after the last pass of a run: the FinLines it left (per side the neighbour's edge line, or the own adjacent interior
+// line on a physical side, before the last step) become the ghost ring the reference leaves behind
+static int fill_from_fin_lines(csim_stepper* s, hipStream_t st) {
+    GhostArgs gf = ghost_args(s);
+    for (int k = 0; k < 4; ++k) {
+        gf.recv[k] = s->phys[k] ? nullptr : s->fin[k];
+        gf.adj[k] = s->phys[k] ? s->fin[k] : nullptr;
+    }
+    CSIM_HIP(launch_ghost_fill(s->cur, s->nxt, s->nx, s->ny, s->pitch, gf, st));
+    return CSIM_OK;
+}
+
 // T = 2..7 reference steps in one HBM pass.  Several ranks: faces of depth T (8 directions) are
 // staged in recv2[]; when the next pass is fused too (with `next_T` steps), the frame tiles are
 // computed first and the comm stream packs and exchanges their depth-next_T faces while the bulk
@@ -44,10 +71,8 @@ static hipError_t launch_fused(csim_stepper* s, const Phys& p, const int kind[4]
 // pass with the thin frame launch last (~7 us per pass against the merged launch), so it wins on runs
 // of fewer than ~16 passes, e.g. the three passes of a 20-step run.
 static int pass_fused_bulk_first(csim_stepper* s, const Phys& p, int T, bool final_pass) {
-    int kind[4];
-    for (int k = 0; k < 4; ++k) kind[k] = s->phys[k] ? s->bc[k] : 3;
-    GhostArgs g = ghost_args(s);
-    for (int k = 0; k < 4; ++k) g.recv[k] = nullptr;  // neighbour sides come from the deep faces
+    const SideKinds kind(s);
+    const GhostArgs g = deep_ghost_args(s);
     s->pre_unpacked = false;
     // Relay (option "relay", default on): X = the stream the field state is ordered on carries the bulk; Y, the other
     // one, carries the exchange chain and the frame launch — and, in the next pass, the bulk, which then follows the
@@ -76,21 +101,17 @@ static int pass_fused_bulk_first(csim_stepper* s, const Phys& p, int T, bool fin
     // everything enqueued so far on X produced `cur` (and the partner buffer's ring)
     CSIM_HIP(hipEventRecord(ev_state, X));
     CSIM_HIP(hipStreamWaitEvent(Y, ev_state, 0));
-    int rc = prof_begin(s, T, X);
-    if (rc) return rc;
+    CSIM_TRY(prof_begin(s, T, X));
     // the bulk goes out first: the GPU starts on it while the host is still enqueuing the exchange
     CSIM_HIP(launch_fused(s, p, kind, T, 2, X));  // nothing to launch on tiles that are all frame
     if (relay) CSIM_HIP(hipEventRecord(ev_bulk, X));  // the bulk's end, for whatever follows the frame on Y
     long comm_slot = -1;
-    rc = prof_start(s, csim_stepper::PROF_COMM, Y, &comm_slot);
-    if (rc) return rc;
+    CSIM_TRY(prof_start(s, csim_stepper::PROF_COMM, Y, &comm_slot));
     CSIM_HIP(launch_halo2_pack(s->cur, s->nx, s->ny, s->pitch, T, s->send2, Y));
-    rc = post_exchange2(s, T, Y);
-    if (rc) return rc;
+    CSIM_TRY(post_plan(s, T, Y));
     CSIM_HIP(launch_halo2_unpack(s->cur, s->nx, s->ny, s->pitch, T, s->recv2, Y));
     CSIM_HIP(launch_ghost_fill(s->cur, s->nxt, s->nx, s->ny, s->pitch, g, Y, T));
-    rc = prof_stop(s, comm_slot, Y);
-    if (rc) return rc;
+    CSIM_TRY(prof_stop(s, comm_slot, Y));
     hipStream_t F = Y;  // the frame launch follows the chain on its own stream
     if (!relay) {
         CSIM_HIP(hipEventRecord(s->ev_recv2, Y));
@@ -98,8 +119,7 @@ static int pass_fused_bulk_first(csim_stepper* s, const Phys& p, int T, bool fin
         F = X;
     }
     CSIM_HIP(launch_fused(s, p, kind, T, 1, F, final_pass));
-    rc = prof_end(s, F);
-    if (rc) return rc;
+    CSIM_TRY(prof_end(s, F));
     if (relay) {
         CSIM_HIP(hipStreamWaitEvent(Y, ev_bulk, 0));  // the field is complete on Y once the bulk is done too
         s->tail = Y;
@@ -107,15 +127,7 @@ static int pass_fused_bulk_first(csim_stepper* s, const Phys& p, int T, bool fin
     std::swap(s->cur, s->nxt);
     s->halo_fresh = false;
     s->faces_depth = 0;
-    if (final_pass) {
-        GhostArgs gf = ghost_args(s);
-        for (int k = 0; k < 4; ++k) {
-            gf.recv[k] = s->phys[k] ? nullptr : s->fin[k];
-            gf.adj[k] = s->phys[k] ? s->fin[k] : nullptr;
-        }
-        CSIM_HIP(launch_ghost_fill(s->cur, s->nxt, s->nx, s->ny, s->pitch, gf, s->tail));
-    }
-    return CSIM_OK;
+    return final_pass ? fill_from_fin_lines(s, s->tail) : CSIM_OK;
 }
 
 namespace csim {
@@ -127,8 +139,7 @@ int post_plan(csim_stepper* s, int depth, hipStream_t st) {
     if (!s->comm) return fail(CSIM_ERR_STATE, "halo exchange needs csim_stepper_comm_init first");
     csim_msg sends[8], recvs[8];
     int ns = 0, nr = 0;
-    int rc = csim_exchange_plan(&s->dec, depth, sends, &ns, recvs, &nr);
-    if (rc) return rc;
+    CSIM_TRY(csim_exchange_plan(&s->dec, depth, sends, &ns, recvs, &nr));
     double* const* sbuf = depth == 1 ? s->send : s->send2;
     double* const* rbuf = depth == 1 ? s->recv : s->recv2;
     CSIM_NCCL(ncclGroupStart());
@@ -154,8 +165,7 @@ int post_plan(csim_stepper* s, int depth, hipStream_t st) {
 // halos of the CURRENT field: pack its edge lines, exchange, leave them staged in recv[]
 int refresh_halos(csim_stepper* s) {
     CSIM_HIP(launch_pack(s->cur, s->nx, s->ny, s->pitch, s->send, s->s_comp));
-    int rc = post_plan(s, 1, s->s_comp);
-    if (rc) return rc;
+    CSIM_TRY(post_plan(s, 1, s->s_comp));
     s->halo_fresh = true;
     s->edge_async = false;
     return CSIM_OK;
@@ -187,8 +197,7 @@ int pass_single(csim_stepper* s, const Phys& p, const GhostArgs& g) {
     const bool rccl = s->multi && !s->external;
     if (rccl) {
         if (!s->halo_fresh) {
-            int rc = refresh_halos(s);  // on s_comp: ordered before the ghost fill
-            if (rc) return rc;
+            CSIM_TRY(refresh_halos(s));  // on s_comp: ordered before the ghost fill
         } else if (s->edge_async) {
             // whatever "overlap" says NOW: the exchange in flight was posted on the comm stream
             CSIM_HIP(hipStreamWaitEvent(s->s_comp, s->ev_recv, 0));
@@ -205,16 +214,13 @@ int pass_single(csim_stepper* s, const Phys& p, const GhostArgs& g) {
         CSIM_HIP(launch_edge_pack(s->cur, s->nx, s->ny, s->pitch, p, s->send, s->s_comp));
         CSIM_HIP(hipEventRecord(s->ev_edge, s->s_comp));
         CSIM_HIP(hipStreamWaitEvent(s->s_comm, s->ev_edge, 0));
-        int rc = post_plan(s, 1, s->s_comm);
-        if (rc) return rc;
+        CSIM_TRY(post_plan(s, 1, s->s_comm));
         CSIM_HIP(hipEventRecord(s->ev_recv, s->s_comm));
         s->edge_async = true;
     }
-    int rc = prof_begin(s, 1);
-    if (rc) return rc;
+    CSIM_TRY(prof_begin(s, 1));
     CSIM_HIP(launch_sweep(s->cur, s->nxt, s->nx, s->ny, s->pitch, p, s->cfg, s->s_comp));
-    rc = prof_end(s);
-    if (rc) return rc;
+    CSIM_TRY(prof_end(s));
     std::swap(s->cur, s->nxt);
     if (s->multi && (s->external || !s->overlap)) s->halo_fresh = false;  // exchange again next step
     s->faces_depth = 0;
@@ -226,10 +232,11 @@ int pass_fused(csim_stepper* s, const Phys& p, int T, int next_T, bool final_pas
     if (rccl && s->bulk_first_run && s->faces_depth == 0)
         return pass_fused_bulk_first(s, p, T, final_pass);
     CSIM_SETTLE(s);
-    int kind[4];
-    for (int k = 0; k < 4; ++k) kind[k] = s->phys[k] ? s->bc[k] : 3;
-    GhostArgs g = ghost_args(s);
-    for (int k = 0; k < 4; ++k) g.recv[k] = nullptr;  // neighbour sides come from the deep faces
+    const SideKinds kind(s);
+    const GhostArgs g = deep_ghost_args(s);
+    // the two option sets of the frame-first schedules
+    const bool merged_launch = (s->overlap == 3 || s->overlap == 5) && s->frame_flag;  // frame and bulk in ONE launch
+    const bool comm_prepares_next = s->overlap == 1 || s->overlap == 3 || s->overlap == 5;  // comm stream prepares the next pass
     const bool prepared = s->multi && s->faces_depth == T && s->pre_unpacked;
     s->pre_unpacked = false;
     if (s->multi) {
@@ -237,8 +244,7 @@ int pass_fused(csim_stepper* s, const Phys& p, int T, int next_T, bool final_pas
             if (s->external)
                 return fail(CSIM_ERR_STATE, "external halo transport: csim_stepper_faces_unpack (same depth) first");
             CSIM_HIP(launch_halo2_pack(s->cur, s->nx, s->ny, s->pitch, T, s->send2, s->s_comp));
-            int rc = post_plan(s, T, s->s_comp);
-            if (rc) return rc;
+            CSIM_TRY(post_plan(s, T, s->s_comp));
         } else if (rccl && s->overlap) {
             CSIM_HIP(hipStreamWaitEvent(s->s_comp, s->ev_recv2, 0));
         }
@@ -249,11 +255,10 @@ int pass_fused(csim_stepper* s, const Phys& p, int T, int next_T, bool final_pas
         s->ring_ok = ring_is_static(s);
     }
     if (s->ring_ok) final_pass = false;  // nothing to rebuild after the last step: the ring is constant
-    int rc = prof_begin(s, T);
-    if (rc) return rc;
+    CSIM_TRY(prof_begin(s, T));
     if (rccl && s->overlap && next_T >= 2) {
         bool direct = false;
-        if ((s->overlap == 3 || s->overlap == 5) && s->frame_flag) {
+        if (merged_launch) {
             // ONE launch: the frame tiles are the first blocks of the grid, the bulk tiles fill the rest of
             // the chip at once; the last frame wavefront publishes this pass's number and the comm stream,
             // parked on that value by the command processor, starts the exchange under the running kernel
@@ -279,12 +284,10 @@ int pass_fused(csim_stepper* s, const Phys& p, int T, int next_T, bool final_pas
             CSIM_HIP(hipStreamWaitEvent(s->s_comm, s->ev_edge2, 0));
         }
         long comm_slot = -1;
-        rc = prof_start(s, csim_stepper::PROF_COMM, s->s_comm, &comm_slot);
-        if (rc) return rc;
+        CSIM_TRY(prof_start(s, csim_stepper::PROF_COMM, s->s_comm, &comm_slot));
         if (!direct) CSIM_HIP(launch_halo2_pack(s->nxt, s->nx, s->ny, s->pitch, next_T, s->send2, s->s_comm));
-        rc = post_plan(s, next_T, s->s_comm);
-        if (rc) return rc;
-        if (s->overlap == 1 || s->overlap == 3 || s->overlap == 5) {
+        CSIM_TRY(post_plan(s, next_T, s->s_comm));
+        if (comm_prepares_next) {
             // the comm stream goes on to prepare the next pass — unpack of the faces into the new
             // field's halo cells, ghost fill of both buffers' rings — while the bulk is still
             // sweeping: those cells are disjoint from everything the bulk reads or writes, and
@@ -293,28 +296,18 @@ int pass_fused(csim_stepper* s, const Phys& p, int T, int next_T, bool final_pas
             CSIM_HIP(launch_ghost_fill(s->nxt, s->cur, s->nx, s->ny, s->pitch, g, s->s_comm, next_T));
             s->pre_unpacked = true;
         }
-        rc = prof_stop(s, comm_slot, s->s_comm);
-        if (rc) return rc;
+        CSIM_TRY(prof_stop(s, comm_slot, s->s_comm));
         CSIM_HIP(hipEventRecord(s->ev_recv2, s->s_comm));
-        if (!((s->overlap == 3 || s->overlap == 5) && s->frame_flag)) CSIM_HIP(launch_fused(s, p, kind, T, 2, s->s_comp));
+        if (!merged_launch) CSIM_HIP(launch_fused(s, p, kind, T, 2, s->s_comp));
         s->faces_depth = next_T;
     } else {
         CSIM_HIP(launch_fused(s, p, kind, T, 0, s->s_comp, final_pass));
         s->faces_depth = 0;
     }
-    rc = prof_end(s);
-    if (rc) return rc;
+    CSIM_TRY(prof_end(s));
     std::swap(s->cur, s->nxt);
     s->halo_fresh = false;
-    if (final_pass) {
-        GhostArgs gf = ghost_args(s);
-        for (int k = 0; k < 4; ++k) {
-            gf.recv[k] = s->phys[k] ? nullptr : s->fin[k];  // the neighbour's edge line before the last step
-            gf.adj[k] = s->phys[k] ? s->fin[k] : nullptr;   // own adjacent interior line before the last step
-        }
-        CSIM_HIP(launch_ghost_fill(s->cur, s->nxt, s->nx, s->ny, s->pitch, gf, s->s_comp));
-    }
-    return CSIM_OK;
+    return final_pass ? fill_from_fin_lines(s, s->s_comp) : CSIM_OK;
 }
 
 // Rows per chunk of the fused sweep by trial: how a launch's wavefronts tile the 256 CUs (rounds
@@ -334,18 +327,11 @@ int tune_rows(csim_stepper* s, const Phys& p, int T, bool preferred_depth) {
         if (snapped <= s->ny && (cand.empty() || cand.back() != snapped)) cand.push_back(snapped);
     }
     if (cand.size() < 2) return CSIM_OK;
-    int kind[4];
-    for (int k = 0; k < 4; ++k) kind[k] = s->phys[k] ? s->bc[k] : 3;
-    struct EventPair {  // destroyed on every return path
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EventPair() {
-            if (a) (void)hipEventDestroy(a);
-            if (b) (void)hipEventDestroy(b);
-        }
-    } ev;
-    CSIM_HIP(hipEventCreateWithFlags(&ev.a, hipEventDisableSystemFence));  // timing only
-    CSIM_HIP(hipEventCreateWithFlags(&ev.b, hipEventDisableSystemFence));
-    const hipEvent_t e0 = ev.a, e1 = ev.b;
+    const SideKinds kind(s);
+    Owned timing;  // given back on every return path
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    CSIM_TRY(timing.event(&e0, hipEventDisableSystemFence));  // timing only
+    CSIM_TRY(timing.event(&e1, hipEventDisableSystemFence));
     CSIM_HIP(hipStreamSynchronize(s->s_comp));
     SweepCfg cfg = s->cfg;
     // what a pass of this stepper launches with the chunk height under trial: the whole tile on one rank, the BULK of
@@ -364,16 +350,14 @@ int tune_rows(csim_stepper* s, const Phys& p, int T, bool preferred_depth) {
     // bring the clocks up first (a cold GPU runs its first ~20 ms well below the sustained rate)
     float ms = 0.f, spent = 0.f;
     for (int k = 0; k < 64 && spent < 30.f; ++k) {
-        int rc = trial(cand[cand.size() / 2], &ms);
-        if (rc) return rc;
+        CSIM_TRY(trial(cand[cand.size() / 2], &ms));
         spent += ms;
     }
     std::vector<float> best(cand.size(), 1e30f);
     for (int round = 0; round < 3; ++round)
         for (size_t c = 0; c < cand.size(); ++c) {
             const size_t idx = (round & 1) ? cand.size() - 1 - c : c;  // alternate the order: drift cancels
-            int rc = trial(cand[idx], &ms);
-            if (rc) return rc;
+            CSIM_TRY(trial(cand[idx], &ms));
             best[idx] = std::min(best[idx], ms);
         }
     // second stage: the candidates differ by a per cent or two, which is also the noise of three launches —
@@ -385,8 +369,7 @@ int tune_rows(csim_stepper* s, const Phys& p, int T, bool preferred_depth) {
     for (int round = 0; round < 5; ++round)
         for (size_t q = 0; q < finalists; ++q) {
             const size_t idx = order[(round & 1) ? finalists - 1 - q : q];
-            int rc = trial(cand[idx], &ms);
-            if (rc) return rc;
+            CSIM_TRY(trial(cand[idx], &ms));
             best[idx] = std::min(best[idx], ms);
         }
     size_t arg = order[0];
@@ -420,30 +403,31 @@ static void note_flavour(csim_stepper* s, const Phys& p) {
     s->diffusion_only_active = still;
 }
 
+// The Phys of a run, tune or keep_warm with these parameters under the stepper's options: the arithmetic flavours that
+// are switched off lose their thresholds, and the read-only options say what is left
+static Phys run_phys(csim_stepper* s, double D, double dt, double vx, double vy) {
+    Phys p = make_phys(s->dx, s->dy, D, dt, vx, vy, s->contract != 0);
+    if (!s->fused_2c) p.fast_thr = 0.0;
+    if (!s->fused_2c || !pow2_v_wanted(s)) p.slow_thr = 0.0;
+    note_flavour(s, p);
+    return p;
+}
+
 extern "C" {
 
 // the one-off trial of csim_stepper_run's first long call, on request (e.g. before a timed loop)
 int csim_stepper_tune(csim_stepper* s, double D, double dt, double vx, double vy) {
     CSIM_REQUIRE(s, "null stepper");
     CSIM_SETTLE(s);
-    Phys p = make_phys(s->dx, s->dy, D, dt, vx, vy, s->contract != 0);
-    if (!s->fused_2c) p.fast_thr = 0.0;
-    if (!s->fused_2c || !pow2_v_wanted(s)) p.slow_thr = 0.0;
-    note_flavour(s, p);
+    const Phys p = run_phys(s, D, dt, vx, vy);
     const int depth = fused_depth(s);
     if (depth < 2 || s->cfg.rows_per_chunk != 0) return CSIM_OK;
-    if (!s->tuned) {
-        int rc = tune_rows(s, p, depth);
-        if (rc) return rc;
-    }
+    if (!s->tuned) CSIM_TRY(tune_rows(s, p, depth));
     // the other depths an automatic pass plan mixes in (20 steps = 7 + 7 + 6, remainders of 4 and 5): each has its own
     // balance of overhead rows per chunk against rounds of wavefronts, so each gets its own trial
     if (s->fuse < 0)
         for (int T = std::min(MAX_FUSE, s->fuse_cap); T >= 4; --T)
-            if (T != depth && s->tuned_T[T] == 0) {
-                int rc = tune_rows(s, p, T, false);
-                if (rc) return rc;
-            }
+            if (T != depth && s->tuned_T[T] == 0) CSIM_TRY(tune_rows(s, p, T, false));
     return CSIM_OK;
 }
 
@@ -456,14 +440,10 @@ int csim_stepper_keep_warm(csim_stepper* s, double D, double dt, double vx, doub
     CSIM_SETTLE(s);
     const auto t0 = std::chrono::steady_clock::now();
     auto elapsed = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
-    Phys p = make_phys(s->dx, s->dy, D, dt, vx, vy, s->contract != 0);
-    if (!s->fused_2c) p.fast_thr = 0.0;
-    if (!s->fused_2c || !pow2_v_wanted(s)) p.slow_thr = 0.0;
-    note_flavour(s, p);
+    const Phys p = run_phys(s, D, dt, vx, vy);
     const int depth = fused_depth(s);
     if (depth < 2) return CSIM_OK;
-    int kind[4];
-    for (int k = 0; k < 4; ++k) kind[k] = s->phys[k] ? s->bc[k] : 3;
+    const SideKinds kind(s);
     CSIM_HIP(hipStreamSynchronize(s->s_comm));
     CSIM_HIP(hipStreamSynchronize(s->s_comp));
     const SweepPlan plan = plan_sweepO(s->nx, s->ny, depth, p, s->cfg, kind, 0);
@@ -481,10 +461,7 @@ int csim_stepper_keep_warm(csim_stepper* s, double D, double dt, double vx, doub
 int csim_stepper_run(csim_stepper* s, double D, double dt, double vx, double vy, int nsteps) {
     CSIM_REQUIRE(s, "null stepper");
     CSIM_REQUIRE(nsteps >= 0, "nsteps must be >= 0");
-    Phys p = make_phys(s->dx, s->dy, D, dt, vx, vy, s->contract != 0);
-    if (!s->fused_2c) p.fast_thr = 0.0;
-    if (!s->fused_2c || !pow2_v_wanted(s)) p.slow_thr = 0.0;
-    note_flavour(s, p);  // before the depth: the diffusion-only flavour prefers 7 steps per pass at every size
+    const Phys p = run_phys(s, D, dt, vx, vy);  // before the depth: the diffusion-only flavour prefers 7 steps per pass at every size
     // Up to MAX_FUSE steps per HBM pass where possible (across ranks: a tile at least as large as
     // the face depth).
     const int depth = fused_depth(s);
@@ -513,8 +490,7 @@ int csim_stepper_run(csim_stepper* s, double D, double dt, double vx, double vy,
     // steps never contains a single-step pass.
     if (can_fuse && s->autotune && !s->tuned && s->cfg.rows_per_chunk == 0 && nsteps >= 4 * depth) {
         CSIM_SETTLE(s);
-        int rc = tune_rows(s, p, depth);
-        if (rc) return rc;
+        CSIM_TRY(tune_rows(s, p, depth));
     }
     PassPlan plan;
     plan_passes(nsteps, cap, !auto_depth, s->tile_cells, plan, s->diffusion_only_active != 0);
@@ -529,22 +505,14 @@ int csim_stepper_run(csim_stepper* s, double D, double dt, double vx, double vy,
         // physical Dirichlet / Periodic side (sweepO_div) read that side's ghost line as level-0 input, which never changes
         // — once it has been written: after an upload or an initialisation that is now (physical sides only, both
         // buffers; the halo-dependent corners and every later refresh are the passes' own ghost fills).
-        GhostArgs gp = ghost_args(s);
-        for (int k = 0; k < 4; ++k) gp.recv[k] = nullptr;
-        CSIM_HIP(launch_ghost_fill(s->cur, s->nxt, s->nx, s->ny, s->pitch, gp, s->tail ? s->tail : s->s_comp));
+        CSIM_HIP(launch_ghost_fill(s->cur, s->nxt, s->nx, s->ny, s->pitch, deep_ghost_args(s), s->tail ? s->tail : s->s_comp));
         s->phys_ring_filled = true;
     }
     for (long k = 0; k < plan.size(); ++k) {
         const int t = plan.at(k);
-        int rc;
-        if (t >= 2) {
-            const bool last = k + 1 == plan.size();
-            const int nt = last ? 0 : plan.at(k + 1);
-            rc = pass_fused(s, p, t, nt >= 2 ? nt : 0, last);
-        } else {
-            rc = pass_single(s, p, g);
-        }
-        if (rc) return rc;
+        const bool last = k + 1 == plan.size();
+        const int nt = last ? 0 : plan.at(k + 1);
+        CSIM_TRY(t >= 2 ? pass_fused(s, p, t, nt >= 2 ? nt : 0, last) : pass_single(s, p, g));
     }
     return prof_close(s);
 }

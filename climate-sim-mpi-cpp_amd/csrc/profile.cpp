@@ -16,10 +16,8 @@ namespace csim {
 // pool, nothing of this fold is added to the totals, and the error is returned once: later timer calls start clean.
 int prof_fold(csim_stepper* s) {
     if (s->ev_used == 0) return CSIM_OK;
-    int rc0 = prof_close(s);
-    if (rc0) return rc0;
-    rc0 = wait_streams(s);
-    if (rc0) return rc0;
+    CSIM_TRY(prof_close(s));
+    CSIM_TRY(wait_streams(s));
     double ms_sum[csim::MAX_FUSE + 2]{};
     long launches[csim::MAX_FUSE + 2]{};
     const size_t used = s->ev_used;
@@ -86,14 +84,10 @@ int prof_begin(csim_stepper* s, int steps, hipStream_t st) {
             s->ev_count[static_cast<size_t>(s->prof_open_slot) / 2] += 1;
             return CSIM_OK;
         }
-        int rc = prof_close(s);
-        if (rc) return rc;
-        if (s->ev_used + 4 > POOL) {
-            rc = prof_fold(s);
-            if (rc) return rc;
-        }
+        CSIM_TRY(prof_close(s));
+        if (s->ev_used + 4 > POOL) CSIM_TRY(prof_fold(s));
         s->prof_active = true;  // prof_start looks at it
-        rc = prof_start(s, steps, s->s_comp, &s->prof_open_slot);
+        const int rc = prof_start(s, steps, s->s_comp, &s->prof_open_slot);
         s->prof_active = false;
         if (rc == CSIM_OK) s->prof_open_kind = steps;
         return rc;
@@ -102,18 +96,20 @@ int prof_begin(csim_stepper* s, int steps, hipStream_t st) {
     // of stream time each, which shows on the ~170 us passes of a small multi-rank tile)
     s->prof_active = s->profile > 0 && (s->prof_counter++ % s->profile) == 0;
     if (!s->prof_active) return CSIM_OK;
-    if (s->ev_used + 4 > POOL) {
-        int rc = prof_fold(s);
-        if (rc) return rc;
-    }
+    if (s->ev_used + 4 > POOL) CSIM_TRY(prof_fold(s));
     return prof_start(s, steps, st, &s->prof_slot);
 }
 
 int prof_end(csim_stepper* s, hipStream_t st) {
     if (!s->prof_active) return CSIM_OK;
-    int rc = prof_stop(s, s->prof_slot, st ? st : s->s_comp);
     s->prof_active = false;
-    return rc;
+    return prof_stop(s, s->prof_slot, st ? st : s->s_comp);
+}
+
+void prof_release(csim_stepper* s) {
+    for (hipEvent_t ev : s->ev_pool) (void)hipEventDestroy(ev);
+    s->ev_pool.clear();
+    s->ev_used = 0;
 }
 
 }  // namespace csim

@@ -71,14 +71,110 @@ static int wait_stream(csim_stepper* s, hipStream_t st, const std::chrono::stead
 // prof_fold before it reads its events)
 int wait_streams(csim_stepper* s) {
     const auto t0 = std::chrono::steady_clock::now();
-    int rc = wait_stream(s, s->s_comp, t0);
-    if (rc) return rc;
+    CSIM_TRY(wait_stream(s, s->s_comp, t0));
     for (hipStream_t r : s->s_relay)
-        if (r) {
-            rc = wait_stream(s, r, t0);
-            if (rc) return rc;
-        }
+        if (r) CSIM_TRY(wait_stream(s, r, t0));
     return wait_stream(s, s->s_comm, t0);
+}
+
+// The field was replaced (upload, initialisation): both ping-pong buffers start with the same ghost ring (reference
+// main.cpp:104 copies u->tmp), and nothing staged or filled for the old field is valid any more.  Waits for the copy.
+static int field_replaced(csim_stepper* s) {
+    CSIM_HIP(hipMemcpyAsync(s->base(s->nxt), s->base(s->cur), s->bytes(), hipMemcpyDeviceToDevice, s->s_comp));
+    CSIM_HIP(hipStreamSynchronize(s->s_comp));
+    s->halo_fresh = false;
+    s->faces_depth = 0;
+    s->ring_ok = false;
+    s->phys_ring_filled = false;
+    return CSIM_OK;
+}
+
+// External transport: the lines of the neighbour sides (n = 4, lengths by line_bytes) or the faces of the neighbour
+// directions at `depth` (n = 8) between the staging buffers and the caller's host buffers, on the compute stream,
+// and the wait for them.  `missing`: what a null host buffer of a direction that has a peer is reported as.
+static size_t staged_bytes(const csim_stepper* s, int n, int d, int depth) {
+    return n == 4 ? s->line_bytes(d) : sizeof(double) * s->face_len(d, depth);
+}
+static int staged_to_host(csim_stepper* s, int n, int depth, double* const dev[], double* const host[], const char* missing) {
+    for (int d = 0; d < n; ++d) {
+        if (s->nbr8[d] < 0) continue;
+        CSIM_REQUIRE(host[d], missing);
+        CSIM_HIP(hipMemcpyAsync(host[d], dev[d], staged_bytes(s, n, d, depth), hipMemcpyDeviceToHost, s->s_comp));
+    }
+    CSIM_HIP(hipStreamSynchronize(s->s_comp));
+    return CSIM_OK;
+}
+static int host_to_staged(csim_stepper* s, int n, int depth, double* const dev[], const double* const host[], const char* missing) {
+    for (int d = 0; d < n; ++d) {
+        if (s->nbr8[d] < 0) continue;
+        CSIM_REQUIRE(host[d], missing);
+        CSIM_HIP(hipMemcpyAsync(dev[d], host[d], staged_bytes(s, n, d, depth), hipMemcpyHostToDevice, s->s_comp));
+    }
+    CSIM_HIP(hipStreamSynchronize(s->s_comp));
+    return CSIM_OK;
+}
+constexpr const char* NO_SIDE_BUFFER = "missing host buffer for a neighbour side";
+constexpr const char* NO_FACE_BUFFER = "missing host buffer for a neighbour direction";
+
+// Everything csim_stepper_create allocates, in the order the allocator and RCCL have always seen: one allocation per
+// buffer, line and face.
+static int make_resources(csim_stepper* s) {
+    Owned& o = s->own;
+    CSIM_TRY(o.device(&s->buf[0], s->bytes(), true));
+    CSIM_TRY(o.device(&s->buf[1], s->bytes(), true));
+    CSIM_TRY(o.device(&s->scratch, sizeof(double) * 2 * REDUCE_BLOCKS));
+    CSIM_TRY(o.event(&s->ev_tail));
+    CSIM_TRY(o.event(&s->ev_relay_ready, hipEventDisableTiming | hipEventDisableSystemFence));
+    CSIM_TRY(o.event(&s->ev_relay_bulk, hipEventDisableTiming | hipEventDisableSystemFence));
+    CSIM_TRY(o.event(&s->ev_ready));
+    CSIM_TRY(o.event(&s->ev_edge));
+    CSIM_TRY(o.event(&s->ev_recv));
+    for (int k = 0; k < 4; ++k) CSIM_TRY(o.device(&s->fin[k], s->line_bytes(k), true));
+    for (int k = 0; k < 4; ++k) {
+        if (s->phys[k]) continue;
+        CSIM_TRY(o.device(&s->send[k], s->line_bytes(k), true));
+        CSIM_TRY(o.device(&s->recv[k], s->line_bytes(k), true));
+    }
+    for (int d = 0; d < 8; ++d) {
+        if (s->nbr8[d] < 0) continue;
+        s->cap2[d] = s->face_len(d, MAX_FUSE);
+        CSIM_TRY(o.device(&s->send2[d], sizeof(double) * s->cap2[d], true));
+        CSIM_TRY(o.device(&s->recv2[d], sizeof(double) * s->cap2[d], true));
+    }
+    // the exchange goes on a high-priority stream, so its small kernels are dispatched ahead of the
+    // bulk sweep that is hiding them
+    CSIM_TRY(o.stream(&s->s_comm, true));
+    CSIM_TRY(o.stream(&s->s_comp));
+    // the relay pair of the bulk-first passes: two streams of EQUAL (high) priority — they carry the same kinds of
+    // work in turn —, apart from the compute stream, which keeps its normal priority below the comm stream for
+    // the frame-first schedules (their exchange kernels must be dispatched ahead of the sweep that hides them)
+    if (s->multi) {
+        CSIM_TRY(o.stream(&s->s_relay[0], true));
+        CSIM_TRY(o.stream(&s->s_relay[1], true));
+    }
+    s->tail = s->s_comp;
+    CSIM_TRY(o.event(&s->ev_edge2));
+    CSIM_TRY(o.event(&s->ev_recv2));
+    if (s->multi) {
+        CSIM_TRY(o.device(&s->frame_counter, sizeof(unsigned), true));
+        // signal memory: absent or refused -> mode 3 is simply not offered (set_option reports it)
+        int can = 0, dev = 0;
+        if (hipGetDevice(&dev) == hipSuccess &&
+            hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, dev) == hipSuccess && can) {
+            void* p = nullptr;
+            if (hipExtMallocWithFlags(&p, 8, hipMallocSignalMemory) == hipSuccess) {
+                o.adopt(p, 8);
+                s->frame_flag = static_cast<unsigned long long*>(p);
+                *s->frame_flag = 0;  // host-visible
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+    }
+    CSIM_HIP(hipDeviceSynchronize());
+    s->cur = s->buf[0] + static_cast<size_t>(GHOST_EXTRA) * s->pitch;
+    s->nxt = s->buf[1] + static_cast<size_t>(GHOST_EXTRA) * s->pitch;
+    return CSIM_OK;
 }
 
 }  // namespace csim
@@ -107,32 +203,6 @@ int csim_stepper_create(const csim_decomp* dec, double dx, double dy, const int 
         s->phys[k] = dec->nbr[k] < 0;
         if (!s->phys[k]) s->multi = true;
     }
-    hipError_t e = hipSuccess;
-    auto ok = [&](hipError_t r) {
-        if (e == hipSuccess) e = r;
-        return e == hipSuccess;
-    };
-    ok(hipMalloc(reinterpret_cast<void**>(&s->buf[0]), s->bytes())) &&
-        ok(hipMalloc(reinterpret_cast<void**>(&s->buf[1]), s->bytes())) &&
-        ok(hipMemset(s->buf[0], 0, s->bytes())) && ok(hipMemset(s->buf[1], 0, s->bytes())) &&
-        ok(hipMalloc(reinterpret_cast<void**>(&s->scratch), sizeof(double) * 2 * REDUCE_BLOCKS)) &&
-        ok(hipEventCreateWithFlags(&s->ev_tail, hipEventDisableTiming)) &&
-        ok(hipEventCreateWithFlags(&s->ev_relay_ready, hipEventDisableTiming | hipEventDisableSystemFence)) &&
-        ok(hipEventCreateWithFlags(&s->ev_relay_bulk, hipEventDisableTiming | hipEventDisableSystemFence)) &&
-        ok(hipEventCreateWithFlags(&s->ev_ready, hipEventDisableTiming)) &&
-        ok(hipEventCreateWithFlags(&s->ev_edge, hipEventDisableTiming)) &&
-        ok(hipEventCreateWithFlags(&s->ev_recv, hipEventDisableTiming));
-    for (int k = 0; k < 4 && e == hipSuccess; ++k) {
-        const size_t nf = sizeof(double) * static_cast<size_t>(k < 2 ? s->ny : s->nx);
-        ok(hipMalloc(reinterpret_cast<void**>(&s->fin[k]), nf)) && ok(hipMemset(s->fin[k], 0, nf));
-    }
-    for (int k = 0; k < 4 && e == hipSuccess; ++k) {
-        if (s->phys[k]) continue;
-        const size_t n = sizeof(double) * static_cast<size_t>(k < 2 ? s->ny : s->nx);
-        ok(hipMalloc(reinterpret_cast<void**>(&s->send[k]), n)) &&
-            ok(hipMalloc(reinterpret_cast<void**>(&s->recv[k]), n)) &&
-            ok(hipMemset(s->send[k], 0, n)) && ok(hipMemset(s->recv[k], 0, n));
-    }
     // The fused-pass depth must be decided identically on every rank (the face exchange is
     // collective in effect): depth <= the smallest tile of the decomposition.
     {
@@ -148,105 +218,24 @@ int csim_stepper_create(const csim_decomp* dec, double dx, double dy, const int 
         s->fuse_cap = std::max(1, std::min(MAX_FUSE, min_tile));
     }
     neighbours8(*dec, s->nbr8);  // diagonal peers only where both adjacent sides have neighbours
-    for (int d = 0; d < 8 && e == hipSuccess; ++d) {
-        if (s->nbr8[d] < 0) continue;
-        s->cap2[d] = s->face_len(d, MAX_FUSE);
-        const size_t n = sizeof(double) * s->cap2[d];
-        ok(hipMalloc(reinterpret_cast<void**>(&s->send2[d]), n)) &&
-            ok(hipMalloc(reinterpret_cast<void**>(&s->recv2[d]), n)) &&
-            ok(hipMemset(s->send2[d], 0, n)) && ok(hipMemset(s->recv2[d], 0, n));
-    }
-    if (e == hipSuccess) {
-        // the exchange goes on a high-priority stream, so its small kernels are dispatched ahead of the
-        // bulk sweep that is hiding them
-        int lo = 0, hi = 0;  // numerically lower = higher priority
-        ok(hipDeviceGetStreamPriorityRange(&lo, &hi)) &&
-            ok(hipStreamCreateWithPriority(&s->s_comm, hipStreamNonBlocking, hi)) &&
-            ok(hipStreamCreateWithFlags(&s->s_comp, hipStreamNonBlocking));
-        // the relay pair of the bulk-first passes: two streams of EQUAL (high) priority — they carry the same kinds of
-        // work in turn —, apart from the compute stream, which keeps its normal priority below the comm stream for
-        // the frame-first schedules (their exchange kernels must be dispatched ahead of the sweep that hides them)
-        if (s->multi)
-            ok(hipStreamCreateWithPriority(&s->s_relay[0], hipStreamNonBlocking, hi)) &&
-                ok(hipStreamCreateWithPriority(&s->s_relay[1], hipStreamNonBlocking, hi));
-        s->tail = s->s_comp;
-    }
-    if (e == hipSuccess) {
-        ok(hipEventCreateWithFlags(&s->ev_edge2, hipEventDisableTiming)) &&
-            ok(hipEventCreateWithFlags(&s->ev_recv2, hipEventDisableTiming));
-    }
-    if (e == hipSuccess && s->multi) {
-        ok(hipMalloc(reinterpret_cast<void**>(&s->frame_counter), sizeof(unsigned))) &&
-            ok(hipMemset(s->frame_counter, 0, sizeof(unsigned)));
-        // signal memory: absent or refused -> mode 3 is simply not offered (set_option reports it)
-        if (e == hipSuccess) {
-            int can = 0;
-            int dev = 0;
-            if (hipGetDevice(&dev) == hipSuccess &&
-                hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, dev) == hipSuccess && can) {
-                void* p = nullptr;
-                if (hipExtMallocWithFlags(&p, 8, hipMallocSignalMemory) == hipSuccess) {
-                    s->frame_flag = static_cast<unsigned long long*>(p);
-                    *s->frame_flag = 0;  // host-visible
-                } else {
-                    (void)hipGetLastError();
-                }
-            }
-        }
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) {
-        s->cur = s->buf[0] + static_cast<size_t>(GHOST_EXTRA) * s->pitch;
-        s->nxt = s->buf[1] + static_cast<size_t>(GHOST_EXTRA) * s->pitch;
-    }
-    if (e != hipSuccess) {
+    if (make_resources(s) != CSIM_OK) {
+        const std::string why = csim_last_error();
         csim_stepper_destroy(s);
-        return fail(CSIM_ERR_HIP, std::string("csim_stepper_create: ") + hipGetErrorString(e));
+        return fail(CSIM_ERR_HIP, "csim_stepper_create: " + why);
     }
     *out = s;
     return CSIM_OK;
 }
 
+// drain every stream the handle has, then the communicator (unless borrowed), then memory, events and streams
 int csim_stepper_destroy(csim_stepper* s) {
     if (!s) return CSIM_OK;
-    if (s->s_comp) (void)hipStreamSynchronize(s->s_comp);
-    if (s->s_comm) (void)hipStreamSynchronize(s->s_comm);
-    for (hipStream_t r : s->s_relay)
-        if (r) (void)hipStreamSynchronize(r);
-    if (s->s_io) (void)hipStreamSynchronize(s->s_io);
-    if (s->snap_d) (void)hipFree(s->snap_d);
-    if (s->snap_h) (void)hipHostFree(s->snap_h);
-    if (s->ev_snap_src) (void)hipEventDestroy(s->ev_snap_src);
-    if (s->ev_snap_copied) (void)hipEventDestroy(s->ev_snap_copied);
-    if (s->s_io) (void)hipStreamDestroy(s->s_io);
+    s->own.drain();
+    if (s->snap.io) (void)hipStreamSynchronize(s->snap.io);
     if (s->comm && !s->comm_borrowed) (void)ncclCommDestroy(s->comm);
-    for (hipEvent_t ev : s->ev_pool) (void)hipEventDestroy(ev);
-    for (int k = 0; k < 4; ++k) {
-        if (s->send[k]) (void)hipFree(s->send[k]);
-        if (s->recv[k]) (void)hipFree(s->recv[k]);
-        if (s->fin[k]) (void)hipFree(s->fin[k]);
-    }
-    for (int d = 0; d < 8; ++d) {
-        if (s->send2[d]) (void)hipFree(s->send2[d]);
-        if (s->recv2[d]) (void)hipFree(s->recv2[d]);
-    }
-    if (s->frame_counter) (void)hipFree(s->frame_counter);
-    if (s->frame_flag) (void)hipFree(s->frame_flag);
-    if (s->ev_edge2) (void)hipEventDestroy(s->ev_edge2);
-    if (s->ev_recv2) (void)hipEventDestroy(s->ev_recv2);
-    if (s->ev_edge) (void)hipEventDestroy(s->ev_edge);
-    if (s->ev_recv) (void)hipEventDestroy(s->ev_recv);
-    if (s->s_comp) (void)hipStreamDestroy(s->s_comp);
-    for (hipStream_t r : s->s_relay)
-        if (r) (void)hipStreamDestroy(r);
-    if (s->s_comm) (void)hipStreamDestroy(s->s_comm);
-    if (s->ev_ready) (void)hipEventDestroy(s->ev_ready);
-    if (s->ev_tail) (void)hipEventDestroy(s->ev_tail);
-    if (s->ev_relay_ready) (void)hipEventDestroy(s->ev_relay_ready);
-    if (s->ev_relay_bulk) (void)hipEventDestroy(s->ev_relay_bulk);
-    if (s->buf[0]) (void)hipFree(s->buf[0]);
-    if (s->buf[1]) (void)hipFree(s->buf[1]);
-    if (s->scratch) (void)hipFree(s->scratch);
+    s->snap.release();
+    prof_release(s);
+    s->own.release();
     delete s;
     return CSIM_OK;
 }
@@ -288,20 +277,11 @@ int csim_stepper_upload(csim_stepper* s, const double* host) {
     CSIM_SETTLE(s);
     CSIM_HIP(hipStreamSynchronize(s->s_comp));
     CSIM_HIP(hipStreamSynchronize(s->s_comm));
-    int rc = upload_2d(s->cur, s->nx, s->ny, s->pitch, host);
-    if (rc) return rc;
-    // both ping-pong buffers start with the same ghost ring (reference main.cpp:104 copies u->tmp)
+    CSIM_TRY(upload_2d(s->cur, s->nx, s->ny, s->pitch, host));
     // (a device-to-device hipMemcpy may return before it has run, and the stepper's streams do
-    // not synchronise with the null stream: order the copy on the compute stream and wait)
+    // not synchronise with the null stream: the mirror copy is ordered on the compute stream)
     CSIM_HIP(hipDeviceSynchronize());
-    CSIM_HIP(hipMemcpyAsync(s->base(s->nxt), s->base(s->cur), s->bytes(), hipMemcpyDeviceToDevice,
-                            s->s_comp));
-    CSIM_HIP(hipStreamSynchronize(s->s_comp));
-    s->halo_fresh = false;
-    s->faces_depth = 0;
-    s->ring_ok = false;
-    s->phys_ring_filled = false;
-    return CSIM_OK;
+    return field_replaced(s);
 }
 
 int csim_stepper_download(csim_stepper* s, double* host) {
@@ -320,40 +300,27 @@ int csim_stepper_download_interior(csim_stepper* s, double* host) {
 
 // Snapshot without stalling the time loop (the reference packs and writes the interior inside the
 // step loop, src/io.cpp:402-424 called from src/main.cpp:96-99).  _begin enqueues a device-side
-// copy of the current interior (the ping-pong buffers are free to move on after ~1 ms) followed
-// by an asynchronous D2H into a pinned buffer on a third stream, and returns at once; the caller
+// copy of the current interior on the compute stream (the ping-pong buffers are free to move on after ~1 ms)
+// followed by an asynchronous D2H into a pinned buffer on a stream of its own (Capture), and returns at once; the caller
 // keeps enqueuing steps and calls _wait when it wants the data (pointer valid until the next
 // _begin).  Layout: ny_local x nx_local, row-major — what write_field_netcdf packs.
 int csim_stepper_snapshot_begin(csim_stepper* s) {
     CSIM_REQUIRE(s, "null stepper");
     CSIM_SETTLE(s);
     const size_t bytes = sizeof(double) * static_cast<size_t>(s->nx) * s->ny;
-    // each piece is created once; a failed allocation is reported and retried by the next call
-    if (!s->s_io) CSIM_HIP(hipStreamCreateWithFlags(&s->s_io, hipStreamNonBlocking));
-    if (!s->ev_snap_src) CSIM_HIP(hipEventCreateWithFlags(&s->ev_snap_src, hipEventDisableTiming));
-    if (!s->ev_snap_copied) CSIM_HIP(hipEventCreateWithFlags(&s->ev_snap_copied, hipEventDisableTiming));
-    if (!s->snap_d) CSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s->snap_d), bytes));
-    if (!s->snap_h) CSIM_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->snap_h), bytes, hipHostMallocDefault));
-    if (s->snap_pending) CSIM_HIP(hipStreamSynchronize(s->s_io));  // previous snapshot still in flight
-    CSIM_HIP(hipEventRecord(s->ev_snap_src, s->s_comp));
-    CSIM_HIP(hipStreamWaitEvent(s->s_io, s->ev_snap_src, 0));
-    CSIM_HIP(hipMemcpy2DAsync(s->snap_d, sizeof(double) * s->nx, s->cur + s->pitch + LPAD,
+    CSIM_TRY(s->snap.prepare(bytes, true, nullptr));  // a previous snapshot still in flight finishes first
+    // the staging copy is in stream order in front of the sweeps that overwrite its source; only the copy to the
+    // host leaves the compute stream
+    CSIM_HIP(hipMemcpy2DAsync(s->snap.dev.p, sizeof(double) * s->nx, s->cur + s->pitch + LPAD,
                               sizeof(double) * s->pitch, sizeof(double) * s->nx, s->ny,
-                              hipMemcpyDeviceToDevice, s->s_io));
-    CSIM_HIP(hipEventRecord(s->ev_snap_copied, s->s_io));
-    // the sweeps may overwrite the source buffer only after the staging copy has read it
-    CSIM_HIP(hipStreamWaitEvent(s->s_comp, s->ev_snap_copied, 0));
-    CSIM_HIP(hipMemcpyAsync(s->snap_h, s->snap_d, bytes, hipMemcpyDeviceToHost, s->s_io));
-    s->snap_pending = true;
-    return CSIM_OK;
+                              hipMemcpyDeviceToDevice, s->s_comp));
+    return s->snap.begin(bytes, s->s_comp);
 }
 
 int csim_stepper_snapshot_wait(csim_stepper* s, const double** host_interior) {
     CSIM_REQUIRE(s && host_interior, "null argument");
-    if (!s->snap_pending) return fail(CSIM_ERR_STATE, "no snapshot in flight: csim_stepper_snapshot_begin first");
-    CSIM_HIP(hipStreamSynchronize(s->s_io));
-    s->snap_pending = false;
-    *host_interior = s->snap_h;
+    CSIM_TRY(s->snap.wait("no snapshot in flight: csim_stepper_snapshot_begin first"));
+    *host_interior = s->snap.host.as<double>();
     return CSIM_OK;
 }
 
@@ -366,14 +333,7 @@ int csim_stepper_init_gaussian(csim_stepper* s, double A, double sigma_frac, dou
     CSIM_HIP(launch_gaussian(s->cur, s->nx, s->ny, s->pitch, s->dec.x_offset, s->dec.y_offset,
                              s->dec.nx_global, s->dec.ny_global, s->dx, s->dy, A, sigma_frac,
                              xc_frac, yc_frac, s->s_comp));
-    CSIM_HIP(hipMemcpyAsync(s->base(s->nxt), s->base(s->cur), s->bytes(), hipMemcpyDeviceToDevice,
-                            s->s_comp));
-    CSIM_HIP(hipStreamSynchronize(s->s_comp));
-    s->halo_fresh = false;
-    s->faces_depth = 0;
-    s->ring_ok = false;
-    s->phys_ring_filled = false;
-    return CSIM_OK;
+    return field_replaced(s);
 }
 
 // External transport (e.g. the reference's own MPI): the caller moves the edge lines between
@@ -385,26 +345,13 @@ int csim_stepper_halo_pack(csim_stepper* s, double* const host_send[4]) {
     CSIM_SETTLE(s);
     if (!s->multi) return CSIM_OK;
     CSIM_HIP(launch_pack(s->cur, s->nx, s->ny, s->pitch, s->send, s->s_comp));
-    for (int k = 0; k < 4; ++k) {
-        if (s->phys[k]) continue;
-        CSIM_REQUIRE(host_send[k], "missing host buffer for a neighbour side");
-        const size_t n = sizeof(double) * static_cast<size_t>(k < 2 ? s->ny : s->nx);
-        CSIM_HIP(hipMemcpyAsync(host_send[k], s->send[k], n, hipMemcpyDeviceToHost, s->s_comp));
-    }
-    CSIM_HIP(hipStreamSynchronize(s->s_comp));
-    return CSIM_OK;
+    return staged_to_host(s, 4, 1, s->send, host_send, NO_SIDE_BUFFER);
 }
 
 int csim_stepper_halo_unpack(csim_stepper* s, const double* const host_recv[4]) {
     CSIM_REQUIRE(s && host_recv, "null argument");
     if (!s->multi) return CSIM_OK;
-    for (int k = 0; k < 4; ++k) {
-        if (s->phys[k]) continue;
-        CSIM_REQUIRE(host_recv[k], "missing host buffer for a neighbour side");
-        const size_t n = sizeof(double) * static_cast<size_t>(k < 2 ? s->ny : s->nx);
-        CSIM_HIP(hipMemcpyAsync(s->recv[k], host_recv[k], n, hipMemcpyHostToDevice, s->s_comp));
-    }
-    CSIM_HIP(hipStreamSynchronize(s->s_comp));
+    CSIM_TRY(host_to_staged(s, 4, 1, s->recv, host_recv, NO_SIDE_BUFFER));
     s->halo_fresh = true;
     return CSIM_OK;
 }
@@ -433,27 +380,14 @@ int csim_stepper_faces_pack(csim_stepper* s, int depth, double* const host_send[
     CSIM_REQUIRE(depth_ok(s, depth), "face depth must be 2..7 and fit the tile");
     if (!s->multi) return CSIM_OK;
     CSIM_HIP(launch_halo2_pack(s->cur, s->nx, s->ny, s->pitch, depth, s->send2, s->s_comp));
-    for (int d = 0; d < 8; ++d) {
-        if (s->nbr8[d] < 0) continue;
-        CSIM_REQUIRE(host_send[d], "missing host buffer for a neighbour direction");
-        CSIM_HIP(hipMemcpyAsync(host_send[d], s->send2[d], sizeof(double) * s->face_len(d, depth),
-                                hipMemcpyDeviceToHost, s->s_comp));
-    }
-    CSIM_HIP(hipStreamSynchronize(s->s_comp));
-    return CSIM_OK;
+    return staged_to_host(s, 8, depth, s->send2, host_send, NO_FACE_BUFFER);
 }
 
 int csim_stepper_faces_unpack(csim_stepper* s, int depth, const double* const host_recv[8]) {
     CSIM_REQUIRE(s && host_recv, "null argument");
     CSIM_REQUIRE(depth_ok(s, depth), "face depth must be 2..7 and fit the tile");
     if (!s->multi) return CSIM_OK;
-    for (int d = 0; d < 8; ++d) {
-        if (s->nbr8[d] < 0) continue;
-        CSIM_REQUIRE(host_recv[d], "missing host buffer for a neighbour direction");
-        CSIM_HIP(hipMemcpyAsync(s->recv2[d], host_recv[d], sizeof(double) * s->face_len(d, depth),
-                                hipMemcpyHostToDevice, s->s_comp));
-    }
-    CSIM_HIP(hipStreamSynchronize(s->s_comp));
+    CSIM_TRY(host_to_staged(s, 8, depth, s->recv2, host_recv, NO_FACE_BUFFER));
     s->faces_depth = depth;
     return CSIM_OK;
 }
@@ -462,8 +396,7 @@ int csim_stepper_exchange_halos(csim_stepper* s) {
     CSIM_REQUIRE(s, "null stepper");
     CSIM_SETTLE(s);
     if (!s->multi) return CSIM_OK;
-    int rc = refresh_halos(s);
-    if (rc) return rc;
+    CSIM_TRY(refresh_halos(s));
     // unpack only (no boundary rule): physical sides are left alone, like reference halo.cpp
     GhostArgs g = ghost_args(s);
     for (int k = 0; k < 4; ++k)
@@ -646,8 +579,7 @@ int csim_stepper_kernel_time(csim_stepper* s, int steps_per_launch, double* tota
                              long* launches) {
     CSIM_REQUIRE(s && total_ms && launches, "null argument");
     CSIM_REQUIRE(steps_per_launch >= 1 && steps_per_launch <= MAX_FUSE, "steps_per_launch must be 1..7");
-    int rc = prof_fold(s);
-    if (rc) return rc;
+    CSIM_TRY(prof_fold(s));
     *total_ms = s->prof_ms[steps_per_launch];
     *launches = s->prof_launches[steps_per_launch];
     return CSIM_OK;
@@ -655,8 +587,7 @@ int csim_stepper_kernel_time(csim_stepper* s, int steps_per_launch, double* tota
 
 int csim_stepper_reset_timers(csim_stepper* s) {
     CSIM_REQUIRE(s, "null stepper");
-    int rc = prof_fold(s);
-    if (rc) return rc;
+    CSIM_TRY(prof_fold(s));
     for (int t = 0; t <= csim_stepper::PROF_COMM; ++t) {
         s->prof_ms[t] = 0.0;
         s->prof_launches[t] = 0;
@@ -666,8 +597,7 @@ int csim_stepper_reset_timers(csim_stepper* s) {
 
 int csim_stepper_comm_time(csim_stepper* s, double* total_ms, long* passes) {
     CSIM_REQUIRE(s && total_ms && passes, "null argument");
-    int rc = prof_fold(s);
-    if (rc) return rc;
+    CSIM_TRY(prof_fold(s));
     *total_ms = s->prof_ms[csim_stepper::PROF_COMM];
     *passes = s->prof_launches[csim_stepper::PROF_COMM];
     return CSIM_OK;

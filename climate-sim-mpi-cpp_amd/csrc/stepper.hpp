@@ -1,5 +1,6 @@
 // stepper.hpp — what the translation units behind include/csim.h share: the stepper handle and the helpers
 // that cross file boundaries.  Layout of the host side of the engine (kernels live in kernels.hip and sweepO.hpp, over sweep_core.hpp):
+//   owned.hpp    the owning helpers every handle is built from: DeviceBuf, PinnedBuf, Capture, Staging, Owned; CSIM_TRY
 //   api.cpp      library / device, safe_dt, decomposition, exchange plan, Field mirror, reference-granularity operators
 //   stepper.cpp  the stepper handle: create / destroy, communicator, upload / download / snapshots, external halo
 //                transport, reductions, options, timers
@@ -20,6 +21,7 @@
 
 #include "internal.hpp"
 #include "obs_taps.hpp"
+#include "owned.hpp"
 
 
 #define CSIM_NCCL(expr)                                                                        \
@@ -39,6 +41,10 @@ struct csim_stepper {
     int phys[4]{1, 1, 1, 1};
     double bc_value = 0.0;
     int nx = 0, ny = 0, pitch = 0;
+    // Every device buffer, stream and event made by csim_stepper_create; the pointers, streams and events named below
+    // are views of it (the launches and RCCL read them as before).  The snapshot's pieces belong to `snap`, the
+    // profiling events to ev_pool (profile.cpp).
+    csim::Owned own;
     double* buf[2]{nullptr, nullptr};  // allocations incl. the device-only ghost layers, see internal.hpp
     double* cur = nullptr;             // views (row j = 0) into buf[], ping-pong
     double* nxt = nullptr;
@@ -88,12 +94,7 @@ struct csim_stepper {
     int diffusion_only_active = 0;  // read-only: the last run had v == 0 and swept with the advection term left out of the screened body
     int direct_faces = 1;                 // merged launch: the frame wavefronts fill send2[] themselves (no pack kernel)
     bool bulk_first_run = false;          // the current csim_stepper_run uses pass_fused_bulk_first
-    // asynchronous snapshot of the interior (device staging copy + pinned host buffer + I/O stream)
-    double* snap_d = nullptr;
-    double* snap_h = nullptr;
-    hipStream_t s_io = nullptr;
-    hipEvent_t ev_snap_src = nullptr, ev_snap_copied = nullptr;
-    bool snap_pending = false;
+    csim::Capture snap;   // asynchronous snapshot of the interior (device staging copy + pinned host buffer + I/O stream)
     int last_rows = 0;    // chunk height the last fused whole-field / bulk launch used
     // the tile plans of the fused passes, one per (depth, part): built at the first launch and again when an input
     // (an option, a tuned height, the division mode) differs from what the kept plan was made from
@@ -143,6 +144,8 @@ struct csim_stepper {
     size_t bytes() const { return sizeof(double) * static_cast<size_t>(ny + 2 + 2 * csim::GHOST_EXTRA) * pitch; }
     // whole-allocation pointer of a view
     double* base(double* view) const { return view - static_cast<size_t>(csim::GHOST_EXTRA) * pitch; }
+    // bytes of the edge line of side k (left, right: ny doubles; bottom, top: nx)
+    size_t line_bytes(int k) const { return sizeof(double) * static_cast<size_t>(k < 2 ? ny : nx); }
 };
 
 namespace csim {
@@ -191,11 +194,8 @@ int prof_stop(csim_stepper* s, long slot, hipStream_t st);
 int prof_close(csim_stepper* s);
 int prof_begin(csim_stepper* s, int steps, hipStream_t st = nullptr);
 int prof_end(csim_stepper* s, hipStream_t st = nullptr);
+void prof_release(csim_stepper* s);  // the event pool, at destruction
 
 }  // namespace csim
 
-#define CSIM_SETTLE(s_)            \
-    do {                           \
-        int rc_ = ::csim::settle(s_);      \
-        if (rc_) return rc_;       \
-    } while (0)
+#define CSIM_SETTLE(s_) CSIM_TRY(::csim::settle(s_))
