@@ -104,29 +104,47 @@ Phys make_phys(double dx, double dy, double D, double dt, double vx, double vy, 
     return p;
 }
 
-int finish_partials(const double* scratch_dev, int nblocks, int kind, double out[2],
-                           hipStream_t st) {
-    std::vector<double> h(2 * REDUCE_BLOCKS);
-    CSIM_HIP(hipMemcpyAsync(h.data(), scratch_dev, sizeof(double) * 2 * REDUCE_BLOCKS,
-                            hipMemcpyDeviceToHost, st));
+// copies the partials the launch wrote and folds each member's in block order, starting from its first
+int fold_partials(const double* scratch_dev, int rows, int kind, double* out, hipStream_t st, const Members& mb) {
+    const size_t G = static_cast<size_t>(reduce_blocks(rows, mb.cap)), hi = G * mb.count;
+    std::vector<double> h(kind == 0 ? 2 * hi : hi);
+    CSIM_HIP(hipMemcpyAsync(h.data(), scratch_dev, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
     CSIM_HIP(hipStreamSynchronize(st));
-    double r0 = h[0], r1 = h[REDUCE_BLOCKS];
-    for (int k = 1; k < nblocks; ++k) {
+    for (int m = 0; m < mb.count; ++m) {
+        const double* p = h.data() + m * G;
+        double r0 = p[0], r1 = kind == 0 ? p[hi] : 0.0;
+        for (size_t k = 1; k < G; ++k) {
+            if (kind == 0) {
+                r0 = std::fmin(r0, p[k]);
+                r1 = std::fmax(r1, p[hi + k]);
+            } else if (kind == 1) {
+                r0 += p[k];
+            } else {
+                r0 = max_nan(r0, p[k]);  // fmax would drop the NaN the kernel kept
+            }
+        }
         if (kind == 0) {
-            r0 = std::fmin(r0, h[k]);
-            r1 = std::fmax(r1, h[REDUCE_BLOCKS + k]);
-        } else if (kind == 1) {
-            r0 += h[k];
+            out[2 * m] = r0;
+            out[2 * m + 1] = r1;
         } else {
-            r0 = max_nan(r0, h[k]);  // fmax would drop the NaN the kernel kept
+            out[m] = r0;
         }
     }
-    out[0] = r0;
-    out[1] = r1;
     return CSIM_OK;
 }
 
-int reduce_blocks(int nrows) { return nrows < REDUCE_BLOCKS ? nrows : REDUCE_BLOCKS; }
+int fold_checksum(const double* scratch_dev, int rows, unsigned long long* out, hipStream_t st, const Members& mb) {
+    const size_t G = static_cast<size_t>(reduce_blocks(rows, mb.cap));
+    std::vector<unsigned long long> h(G * mb.count);
+    CSIM_HIP(hipMemcpyAsync(h.data(), scratch_dev, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, st));
+    CSIM_HIP(hipStreamSynchronize(st));
+    for (int m = 0; m < mb.count; ++m) {
+        unsigned long long acc = 0;
+        for (size_t k = 0; k < G; ++k) acc += h[m * G + k];
+        out[m] = acc;
+    }
+    return CSIM_OK;
+}
 
 int upload_2d(double* d, int nx, int ny, int pitch, const double* host) {
     CSIM_HIP(hipMemcpy2D(d + (LPAD - 1), sizeof(double) * pitch, host, sizeof(double) * (nx + 2),
@@ -376,25 +394,19 @@ int csim_field_swap(csim_field* a, csim_field* b) {
 int csim_field_minmax(const csim_field* f, double out[2]) {
     CSIM_REQUIRE(f && out, "null argument");
     CSIM_HIP(launch_minmax(f->d, f->nx, f->ny, f->pitch, f->scratch, nullptr));
-    return finish_partials(f->scratch, reduce_blocks(f->ny + 2), 0, out, nullptr);
+    return fold_partials(f->scratch, f->ny + 2, 0, out, nullptr);
 }
 
 int csim_field_sum(const csim_field* f, double* out) {
     CSIM_REQUIRE(f && out, "null argument");
-    double r[2];
     CSIM_HIP(launch_sum(f->d, f->nx, f->ny, f->pitch, f->scratch, nullptr));
-    int rc = finish_partials(f->scratch, reduce_blocks(f->ny), 1, r, nullptr);
-    *out = r[0];
-    return rc;
+    return fold_partials(f->scratch, f->ny, 1, out, nullptr);
 }
 
 int csim_field_linf_diff(const csim_field* a, const csim_field* b, double* out) {
     CSIM_REQUIRE(same_shape(a, b) && out, "fields differ in shape");
-    double r[2];
     CSIM_HIP(launch_linf(a->d, b->d, a->nx, a->ny, a->pitch, a->scratch, nullptr));
-    int rc = finish_partials(a->scratch, reduce_blocks(a->ny), 2, r, nullptr);
-    *out = r[0];
-    return rc;
+    return fold_partials(a->scratch, a->ny, 2, out, nullptr);
 }
 
 // ---- operators ----------------------------------------------------------------------------------

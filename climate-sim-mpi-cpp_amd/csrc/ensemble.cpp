@@ -263,56 +263,28 @@ int csim_ensemble_sync(csim_ensemble* e) {
     return CSIM_OK;
 }
 
+// the ensemble's members for the reductions of internal.hpp
+static Members members_of(const csim_ensemble* e) { return {e->g.members, e->g.slab, ENS_REDUCE_ROWS}; }
+
 int csim_ensemble_checksum(csim_ensemble* e, unsigned long long* out) {
     CSIM_REQUIRE(e && out, "null argument");
-    const int R = ens_reduce_rows(e->g.ny), B = e->g.members;
-    auto* part = reinterpret_cast<unsigned long long*>(e->scratch);
-    CSIM_HIP(ens_launch_checksum(e->g, e->base(e->cur), part, e->st));
-    std::vector<unsigned long long> h(static_cast<size_t>(R) * B);
-    CSIM_HIP(hipMemcpyAsync(h.data(), part, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, e->st));
-    CSIM_HIP(hipStreamSynchronize(e->st));
-    for (int m = 0; m < B; ++m) {
-        unsigned long long acc = 0;
-        for (int k = 0; k < R; ++k) acc += h[static_cast<size_t>(m) * R + k];
-        out[m] = acc;
-    }
-    return CSIM_OK;
+    const Members mb = members_of(e);
+    CSIM_HIP(launch_checksum(e->base(e->cur), e->g.nx, e->g.ny, e->g.pitch, 0, 0, e->g.nx, e->scratch, e->st, mb));
+    return fold_checksum(e->scratch, e->g.ny, out, e->st, mb);
 }
 
 int csim_ensemble_minmax(csim_ensemble* e, double* out) {
     CSIM_REQUIRE(e && out, "null argument");
-    const int R = ens_reduce_rows(e->g.ny + 2), B = e->g.members;
-    CSIM_HIP(ens_launch_minmax(e->g, e->base(e->cur), e->scratch, e->st));
-    std::vector<double> h(2 * static_cast<size_t>(R) * B);
-    CSIM_HIP(hipMemcpyAsync(h.data(), e->scratch, sizeof(double) * h.size(), hipMemcpyDeviceToHost, e->st));
-    CSIM_HIP(hipStreamSynchronize(e->st));
-    const size_t hi = static_cast<size_t>(R) * B;
-    for (int m = 0; m < B; ++m) {
-        const size_t k0 = static_cast<size_t>(m) * R;
-        double lo = h[k0], up = h[hi + k0];
-        for (int k = 1; k < R; ++k) {
-            lo = std::fmin(lo, h[k0 + k]);
-            up = std::fmax(up, h[hi + k0 + k]);
-        }
-        out[2 * m] = lo;
-        out[2 * m + 1] = up;
-    }
-    return CSIM_OK;
+    const Members mb = members_of(e);
+    CSIM_HIP(launch_minmax(e->base(e->cur), e->g.nx, e->g.ny, e->g.pitch, e->scratch, e->st, mb));
+    return fold_partials(e->scratch, e->g.ny + 2, 0, out, e->st, mb);
 }
 
 int csim_ensemble_sum(csim_ensemble* e, double* out) {
     CSIM_REQUIRE(e && out, "null argument");
-    const int R = ens_reduce_rows(e->g.ny), B = e->g.members;
-    CSIM_HIP(ens_launch_sum(e->g, e->base(e->cur), e->scratch, e->st));
-    std::vector<double> h(static_cast<size_t>(R) * B);
-    CSIM_HIP(hipMemcpyAsync(h.data(), e->scratch, sizeof(double) * h.size(), hipMemcpyDeviceToHost, e->st));
-    CSIM_HIP(hipStreamSynchronize(e->st));
-    for (int m = 0; m < B; ++m) {
-        double acc = h[static_cast<size_t>(m) * R];
-        for (int k = 1; k < R; ++k) acc += h[static_cast<size_t>(m) * R + k];
-        out[m] = acc;
-    }
-    return CSIM_OK;
+    const Members mb = members_of(e);
+    CSIM_HIP(launch_sum(e->base(e->cur), e->g.nx, e->g.ny, e->g.pitch, e->scratch, e->st, mb));
+    return fold_partials(e->scratch, e->g.ny, 1, out, e->st, mb);
 }
 
 int csim_ensemble_set_option(csim_ensemble* e, const char* key, long value) {

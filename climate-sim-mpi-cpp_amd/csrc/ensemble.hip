@@ -153,76 +153,6 @@ __global__ __launch_bounds__(256) void k_ensemble_ghost(double* __restrict__ a, 
     ghost_fill_cell(a + off, b + off, nx, ny, pitch, g, blockIdx.x * 256 + threadIdx.x);
 }
 
-// per-member reductions: block (x, m) reduces rows x, x + gridDim.x, ... of member m into partial[m * gridDim.x + x]
-__global__ __launch_bounds__(256) void k_ensemble_checksum(const double* __restrict__ f, int nx, int ny, int pitch,
-                                                           long slab, unsigned long long* __restrict__ partial) {
-    __shared__ unsigned long long sh[4];
-    const int m = blockIdx.y;
-    f += static_cast<ptrdiff_t>(m) * slab;
-    unsigned long long acc = 0;
-    for (int j = 1 + blockIdx.x; j <= ny; j += gridDim.x) {
-        const unsigned long long row = static_cast<unsigned long long>(j - 1) * static_cast<unsigned long long>(nx);
-        for (int i = 1 + threadIdx.x; i <= nx; i += 256) {
-            const unsigned long long bits = static_cast<unsigned long long>(__double_as_longlong(f[at(i, j, pitch)]));
-            acc += bits * (0x9E3779B97F4A7C15ull + 2ull * (row + static_cast<unsigned long long>(i - 1)));
-        }
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) sh[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[static_cast<size_t>(m) * gridDim.x + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// KIND 0: min / max over the whole array, ghosts included (partial: min, then max at + members * gridDim.x);
-// KIND 1: sum over the interior
-template <int KIND>
-__global__ __launch_bounds__(256) void k_ensemble_reduce(const double* __restrict__ f, int nx, int ny, int pitch,
-                                                         long slab, double* __restrict__ partial) {
-    __shared__ double sh[2][4];
-    const int m = blockIdx.y;
-    f += static_cast<ptrdiff_t>(m) * slab;
-    const int i0 = KIND == 0 ? 0 : 1, i1 = KIND == 0 ? nx + 1 : nx, j0 = i0, j1 = KIND == 0 ? ny + 1 : ny;
-    double r0 = KIND == 0 ? INFINITY : 0.0, r1 = -INFINITY;
-    for (int j = j0 + blockIdx.x; j <= j1; j += gridDim.x)
-        for (int i = i0 + threadIdx.x; i <= i1; i += 256) {
-            const double v = f[at(i, j, pitch)];
-            if (KIND == 0) {
-                r0 = fmin(r0, v);
-                r1 = fmax(r1, v);
-            } else {
-                r0 = r0 + v;
-            }
-        }
-    if (KIND == 0) {
-        r0 = wave_min(r0);
-        r1 = wave_max(r1);
-    } else {
-        r0 = wave_sum(r0);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        sh[0][wave] = r0;
-        sh[1][wave] = r1;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double x0 = sh[0][0], x1 = sh[1][0];
-        for (int w = 1; w < 4; ++w) {
-            if (KIND == 0) {
-                x0 = fmin(x0, sh[0][w]);
-                x1 = fmax(x1, sh[1][w]);
-            } else {
-                x0 = x0 + sh[0][w];
-            }
-        }
-        const size_t k = static_cast<size_t>(m) * gridDim.x + blockIdx.x;
-        partial[k] = x0;
-        if (KIND == 0) partial[static_cast<size_t>(gridDim.y) * gridDim.x + k] = x1;
-    }
-}
-
 inline int cdivl(long a, long b) { return static_cast<int>((a + b - 1) / b); }
 
 template <int DIV, int T>
@@ -293,24 +223,6 @@ hipError_t ens_launch_ghost_fill(const EnsGeom& g, double* a, double* b, const v
     bc.value = g.value;
     const dim3 grid(cdivl(std::max(g.nx, g.ny) + 1, 256), g.members), block(256);
     hipLaunchKernelGGL(k_ensemble_ghost, grid, block, 0, st, a, b, g.nx, g.ny, g.pitch, g.slab, bc, table, fin ? 1 : 0);
-    return hipGetLastError();
-}
-
-int ens_reduce_rows(int nrows) { return nrows < ENS_REDUCE_ROWS ? nrows : ENS_REDUCE_ROWS; }
-
-hipError_t ens_launch_checksum(const EnsGeom& g, const double* f, unsigned long long* partial, hipStream_t st) {
-    hipLaunchKernelGGL(k_ensemble_checksum, dim3(ens_reduce_rows(g.ny), g.members), dim3(256), 0, st, f, g.nx, g.ny,
-                       g.pitch, g.slab, partial);
-    return hipGetLastError();
-}
-hipError_t ens_launch_minmax(const EnsGeom& g, const double* f, double* partial, hipStream_t st) {
-    hipLaunchKernelGGL(k_ensemble_reduce<0>, dim3(ens_reduce_rows(g.ny + 2), g.members), dim3(256), 0, st, f, g.nx,
-                       g.ny, g.pitch, g.slab, partial);
-    return hipGetLastError();
-}
-hipError_t ens_launch_sum(const EnsGeom& g, const double* f, double* partial, hipStream_t st) {
-    hipLaunchKernelGGL(k_ensemble_reduce<1>, dim3(ens_reduce_rows(g.ny), g.members), dim3(256), 0, st, f, g.nx, g.ny,
-                       g.pitch, g.slab, partial);
     return hipGetLastError();
 }
 

@@ -46,12 +46,8 @@ hipError_t ens_launch_sweepO(const EnsGeom& g, const double* in, double* out, co
 hipError_t ens_launch_step(const EnsGeom& g, const double* in, double* out, const void* table, hipStream_t st);
 // apply_boundary of every member into a and b; fin: Neumann ghosts from the members' FinLines
 hipError_t ens_launch_ghost_fill(const EnsGeom& g, double* a, double* b, const void* table, bool fin, hipStream_t st);
-// per-member reductions: `rows` partials per member in `partial` (member-major), finished on the host
+// per-member reductions: the launchers and folds of internal.hpp with this cap (scratch: members * 2 * 64 doubles)
 constexpr int ENS_REDUCE_ROWS = 64;
-int ens_reduce_rows(int nrows);
-hipError_t ens_launch_checksum(const EnsGeom& g, const double* f, unsigned long long* partial, hipStream_t st);
-hipError_t ens_launch_minmax(const EnsGeom& g, const double* f, double* partial, hipStream_t st);
-hipError_t ens_launch_sum(const EnsGeom& g, const double* f, double* partial, hipStream_t st);
 
 // per-cell statistics over all members (ensemble_stats.hip), one launch: out = mean, var (divided by members - ddof),
 // min, max, each dense (ny+2) x (nx+2); members beyond STATS_LDS_MEMBERS are read twice

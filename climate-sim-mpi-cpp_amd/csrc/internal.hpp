@@ -177,18 +177,28 @@ hipError_t launch_gaussian(double* f, int nx, int ny, int pitch, int x_off, int 
                            int nyg, double dx, double dy, double A, double sigma_frac,
                            double xc_frac, double yc_frac, hipStream_t st);
 
-// reductions: partial results per block in `scratch` (>= 2 * REDUCE_BLOCKS doubles), finished on host
-constexpr int REDUCE_BLOCKS = 1024;
-hipError_t launch_minmax(const double* f, int nx, int ny, int pitch, double* scratch, hipStream_t st);
-hipError_t launch_sum(const double* f, int nx, int ny, int pitch, double* scratch, hipStream_t st);
+// reductions (k_reduce<KIND>, k_checksum of kernels.hip): partial results per block in `scratch`, finished on the host
+// (fold_partials, fold_checksum of api.cpp).  A window of `rows` rows takes G = reduce_blocks(rows, cap) blocks per
+// member; the partial of member m's block b is scratch[m * G + b], the maxima of minmax follow all the minima.
+constexpr int REDUCE_BLOCKS = 1024;  // cap of a Field or Stepper: scratch >= 2 * REDUCE_BLOCKS doubles
+inline int reduce_blocks(int rows, int cap) { return rows < cap ? rows : cap; }
+struct Members {  // the fields one launch reduces: one Field or Stepper, or an ensemble's members
+    int count = 1;
+    long slab = 0;  // doubles from one member to the next
+    int cap = REDUCE_BLOCKS;
+};
+hipError_t launch_minmax(const double* f, int nx, int ny, int pitch, double* scratch, hipStream_t st,
+                         const Members& mb = {});
+hipError_t launch_sum(const double* f, int nx, int ny, int pitch, double* scratch, hipStream_t st,
+                      const Members& mb = {});
 hipError_t launch_linf(const double* a, const double* b, int nx, int ny, int pitch, double* scratch,
                        hipStream_t st);
 // max that keeps a NaN (fmax drops one): every stage of the L-inf reduction — lane, wave, block (k_reduce<2>) and the
-// host merge (finish_partials) — goes through it, so max |a-b| is NaN as soon as one |a-b| is
+// host merge (fold_partials) — goes through it, so max |a-b| is NaN as soon as one |a-b| is
 __host__ __device__ __forceinline__ double max_nan(double r, double d) { return (d > r || d != d) ? d : r; }
-// position-weighted 64-bit checksum of the interior (k_checksum): min(ny, REDUCE_BLOCKS) u64 partials in `scratch`
+// position-weighted 64-bit checksum of the interior (k_checksum): reduce_blocks(ny, cap) u64 partials per member
 hipError_t launch_checksum(const double* f, int nx, int ny, int pitch, long x_off, long y_off, long nx_global,
-                           double* scratch, hipStream_t st);
+                           double* scratch, hipStream_t st, const Members& mb = {});
 
 }  // namespace csim
 

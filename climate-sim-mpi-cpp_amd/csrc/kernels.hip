@@ -378,12 +378,29 @@ __global__ __launch_bounds__(256) void k_gaussian(double* __restrict__ f, int nx
     f[at(i + 1, j + 1, pitch)] = A * exp(-r2 / (2.0 * sig * sig));
 }
 
-// ---- reductions (wave_min / wave_max / wave_sum: sweep_core.hpp) ---------------------------
+// ---- reductions: Field, Stepper (gridDim.y == 1, slab == 0) and ensemble (blockIdx.y = member, slab = its stride) ----
 // KIND 0: min/max over i0..i1, j0..j1 ; KIND 1: sum ; KIND 2: max |a-b|
+// Block b of a member takes rows j0 + b, j0 + b + G, ... (G = gridDim.x); its result goes to partial[m * G + b], the
+// maximum of KIND 0 to partial[gridDim.y * G + m * G + b]; fold_partials (api.cpp) merges a member's blocks in order.
 // NaN: min/max skip it (fmin / fmax; all NaN gives +inf, -inf), the sum carries it, and max |a-b| is NaN as soon as
-// one |a-b| is — max_nan (internal.hpp) at all of its stages, and again on the host (finish_partials), where fmax would lose it.
+// one |a-b| is — max_nan (internal.hpp) at all of its stages, and again on the host (fold_partials), where fmax would lose it.
 // The sum's order is fixed (tests/reduce_restatement.py restates it): a lane adds its columns of its rows serially,
 // then the xor butterfly of wave_sum, the four waves in order, the blocks in order on the host.
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fmin(v, __shfl_xor(v, m, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
+    return v;
+}
 __device__ __forceinline__ double wave_max_nan(double v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v = max_nan(v, __shfl_xor(v, m, 64));
@@ -392,9 +409,11 @@ __device__ __forceinline__ double wave_max_nan(double v) {
 template <int KIND>
 __global__ __launch_bounds__(256) void k_reduce(const double* __restrict__ a,
                                                 const double* __restrict__ b, int i0, int i1,
-                                                int j0, int j1, int pitch,
+                                                int j0, int j1, int pitch, long slab,
                                                 double* __restrict__ partial) {
     __shared__ double sh[2][4];
+    a += static_cast<ptrdiff_t>(blockIdx.y) * slab;
+    if (KIND == 2) b += static_cast<ptrdiff_t>(blockIdx.y) * slab;
     double r0 = KIND == 0 ? INFINITY : 0.0;  // min | sum | linf
     double r1 = -INFINITY;                   // max
     for (int j = j0 + blockIdx.x; j <= j1; j += gridDim.x) {
@@ -437,8 +456,9 @@ __global__ __launch_bounds__(256) void k_reduce(const double* __restrict__ a,
                 x0 = max_nan(x0, sh[0][w]);
             }
         }
-        partial[blockIdx.x] = x0;
-        partial[REDUCE_BLOCKS + blockIdx.x] = x1;
+        const size_t k = static_cast<size_t>(blockIdx.y) * gridDim.x + blockIdx.x;
+        partial[k] = x0;
+        if (KIND == 0) partial[static_cast<size_t>(gridDim.y) * gridDim.x + k] = x1;
     }
 }
 
@@ -446,10 +466,12 @@ __global__ __launch_bounds__(256) void k_reduce(const double* __restrict__ a,
 // GLOBAL linear index.  Every multiplier is odd, so any change of any cell changes the sum, and because the
 // weights follow the global position the per-rank sums of a decomposed field add up (mod 2^64) to the checksum
 // of the same field held by one rank — the bit-identity check a multi-GPU run can carry in one number.
-__global__ __launch_bounds__(256) void k_checksum(const double* __restrict__ f, int nx, int ny, int pitch,
+// Members as in k_reduce; an ensemble's members are whole fields: x_off = y_off = 0, nx_global = nx.
+__global__ __launch_bounds__(256) void k_checksum(const double* __restrict__ f, int nx, int ny, int pitch, long slab,
                                                   long x_off, long y_off, long nx_global,
                                                   unsigned long long* __restrict__ partial) {
     __shared__ unsigned long long sh[4];
+    f += static_cast<ptrdiff_t>(blockIdx.y) * slab;
     unsigned long long acc = 0;
     for (int j = 1 + blockIdx.x; j <= ny; j += gridDim.x) {
         const unsigned long long row = static_cast<unsigned long long>(y_off + j - 1) * static_cast<unsigned long long>(nx_global) +
@@ -464,7 +486,7 @@ __global__ __launch_bounds__(256) void k_checksum(const double* __restrict__ f, 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) sh[wave] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+    if (threadIdx.x == 0) partial[static_cast<size_t>(blockIdx.y) * gridDim.x + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
 }
 
 // ============================================================================================
@@ -633,29 +655,27 @@ hipError_t launch_gaussian(double* f, int nx, int ny, int pitch, int x_off, int 
     return hipGetLastError();
 }
 
-static int reduce_grid(int nrows) { return nrows < REDUCE_BLOCKS ? nrows : REDUCE_BLOCKS; }
-
-hipError_t launch_minmax(const double* f, int nx, int ny, int pitch, double* scratch, hipStream_t st) {
-    hipLaunchKernelGGL(k_reduce<0>, dim3(reduce_grid(ny + 2)), dim3(256), 0, st, f, nullptr, 0, nx + 1,
-                       0, ny + 1, pitch, scratch);
+hipError_t launch_minmax(const double* f, int nx, int ny, int pitch, double* scratch, hipStream_t st, const Members& mb) {
+    hipLaunchKernelGGL(k_reduce<0>, dim3(reduce_blocks(ny + 2, mb.cap), mb.count), dim3(256), 0, st, f, nullptr, 0,
+                       nx + 1, 0, ny + 1, pitch, mb.slab, scratch);
     return hipGetLastError();
 }
-hipError_t launch_sum(const double* f, int nx, int ny, int pitch, double* scratch, hipStream_t st) {
-    hipLaunchKernelGGL(k_reduce<1>, dim3(reduce_grid(ny)), dim3(256), 0, st, f, nullptr, 1, nx, 1, ny,
-                       pitch, scratch);
+hipError_t launch_sum(const double* f, int nx, int ny, int pitch, double* scratch, hipStream_t st, const Members& mb) {
+    hipLaunchKernelGGL(k_reduce<1>, dim3(reduce_blocks(ny, mb.cap), mb.count), dim3(256), 0, st, f, nullptr, 1, nx, 1,
+                       ny, pitch, mb.slab, scratch);
     return hipGetLastError();
 }
 hipError_t launch_linf(const double* a, const double* b, int nx, int ny, int pitch, double* scratch,
                        hipStream_t st) {
-    hipLaunchKernelGGL(k_reduce<2>, dim3(reduce_grid(ny)), dim3(256), 0, st, a, b, 1, nx, 1, ny, pitch,
-                       scratch);
+    hipLaunchKernelGGL(k_reduce<2>, dim3(reduce_blocks(ny, REDUCE_BLOCKS)), dim3(256), 0, st, a, b, 1, nx, 1, ny, pitch,
+                       0L, scratch);
     return hipGetLastError();
 }
 
 hipError_t launch_checksum(const double* f, int nx, int ny, int pitch, long x_off, long y_off, long nx_global,
-                           double* scratch, hipStream_t st) {
-    hipLaunchKernelGGL(k_checksum, dim3(reduce_grid(ny)), dim3(256), 0, st, f, nx, ny, pitch, x_off, y_off, nx_global,
-                       reinterpret_cast<unsigned long long*>(scratch));
+                           double* scratch, hipStream_t st, const Members& mb) {
+    hipLaunchKernelGGL(k_checksum, dim3(reduce_blocks(ny, mb.cap), mb.count), dim3(256), 0, st, f, nx, ny, pitch, mb.slab,
+                       x_off, y_off, nx_global, reinterpret_cast<unsigned long long*>(scratch));
     return hipGetLastError();
 }
 

@@ -418,31 +418,21 @@ int csim_stepper_checksum(csim_stepper* s, unsigned long long* out) {
     CSIM_SETTLE(s);
     const long nxg = s->dec.nx_global > 0 ? s->dec.nx_global : s->nx;
     CSIM_HIP(launch_checksum(s->cur, s->nx, s->ny, s->pitch, s->dec.x_offset, s->dec.y_offset, nxg, s->scratch, s->s_comp));
-    const int nb = reduce_blocks(s->ny);
-    std::vector<unsigned long long> h(static_cast<size_t>(nb));
-    CSIM_HIP(hipMemcpyAsync(h.data(), s->scratch, sizeof(unsigned long long) * nb, hipMemcpyDeviceToHost, s->s_comp));
-    CSIM_HIP(hipStreamSynchronize(s->s_comp));
-    unsigned long long acc = 0;
-    for (int k = 0; k < nb; ++k) acc += h[static_cast<size_t>(k)];
-    *out = acc;
-    return CSIM_OK;
+    return fold_checksum(s->scratch, s->ny, out, s->s_comp);
 }
 
 int csim_stepper_minmax(csim_stepper* s, double out[2]) {
     CSIM_REQUIRE(s && out, "null argument");
     CSIM_SETTLE(s);
     CSIM_HIP(launch_minmax(s->cur, s->nx, s->ny, s->pitch, s->scratch, s->s_comp));
-    return finish_partials(s->scratch, reduce_blocks(s->ny + 2), 0, out, s->s_comp);
+    return fold_partials(s->scratch, s->ny + 2, 0, out, s->s_comp);
 }
 
 int csim_stepper_sum(csim_stepper* s, double* out) {
     CSIM_REQUIRE(s && out, "null argument");
     CSIM_SETTLE(s);
-    double r[2];
     CSIM_HIP(launch_sum(s->cur, s->nx, s->ny, s->pitch, s->scratch, s->s_comp));
-    int rc = finish_partials(s->scratch, reduce_blocks(s->ny), 1, r, s->s_comp);
-    *out = r[0];
-    return rc;
+    return fold_partials(s->scratch, s->ny, 1, out, s->s_comp);
 }
 
 int csim_stepper_set_option(csim_stepper* s, const char* key, long value) {

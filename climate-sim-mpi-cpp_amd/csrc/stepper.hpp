@@ -151,8 +151,10 @@ struct csim_stepper {
 namespace csim {
 
 // api.cpp
-int finish_partials(const double* scratch_dev, int nblocks, int kind, double out[2], hipStream_t st);
-int reduce_blocks(int nrows);
+// the host's finish of a reduction over a window of `rows` rows: kind 0 gives out[2 m], out[2 m + 1] = min, max of
+// member m; kind 1 (sum) and 2 (max |a-b|) give out[m]
+int fold_partials(const double* scratch_dev, int rows, int kind, double* out, hipStream_t st, const Members& mb = {});
+int fold_checksum(const double* scratch_dev, int rows, unsigned long long* out, hipStream_t st, const Members& mb = {});
 int upload_2d(double* d, int nx, int ny, int pitch, const double* host);
 int download_2d(const double* d, int nx, int ny, int pitch, double* host);
 int download_interior_2d(const double* d, int nx, int ny, int pitch, double* host);

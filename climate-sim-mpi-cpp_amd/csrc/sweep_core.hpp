@@ -1,6 +1,6 @@
 // sweep_core.hpp — the device code that the single stepper (sweepO.hpp, kernels.hip) and the ensemble (ensemble.hip)
 // share: the per-cell update, the lane moves and pair stores, the argument blocks of the fused sweep, the march of
-// the overlapped-strip sweep with its bodies (sweepO_march), the ghost-fill rule and the wavefront reductions.  No
+// the overlapped-strip sweep with its bodies (sweepO_march), the ghost-fill rule.  No
 // kernel and no launcher is defined here.  The geometry of a strip (OverlapGeom), the rule of SPECIALISE_EDGES and the
 // Tiling inside SweepArgs are sweep_plan.hpp's (host arithmetic, through internal.hpp): here they are compile-time
 // constants and an argument the kernel decodes.
@@ -653,23 +653,6 @@ __device__ __forceinline__ void ghost_fill_cell(double* __restrict__ a, double* 
             }
         }
     }
-}
-
-// ---- wavefront-level reductions --------------------------------------------------------------
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmin(v, __shfl_xor(v, m, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
 }
 
 }  // namespace csim

@@ -1,7 +1,8 @@
 """The reductions of include/csim.h (csim_field_minmax / _sum / _linf_diff, csim_stepper_minmax / _sum,
 csim_ensemble_minmax / _sum) restated in numpy, their references, and the cases the host and the GPU tests share.
 
-The sum's order (k_reduce<1> of kernels.hip, k_ensemble_reduce<1> of ensemble.hip), every + one IEEE fp64 addition:
+The sum's order (k_reduce<1> of kernels.hip, for one field or one member per blockIdx.y, and fold_partials of api.cpp),
+every + one IEEE fp64 addition:
   * the window has `rows` rows; G = min(rows, cap) blocks, cap = 1024 (REDUCE_BLOCKS: Field, Stepper) or 64
     (ENS_REDUCE_ROWS: ensemble); block b takes rows b, b + G, b + 2 G, ... in that order;
   * lane t of the block's 256 adds columns t, t + 256, ... of each of its rows, serially from +0.0;

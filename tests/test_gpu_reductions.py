@@ -1,5 +1,5 @@
-"""The reductions of include/csim.h on the GPU (k_reduce<0|1|2>, k_checksum, k_ensemble_reduce, k_ensemble_checksum
-and their host finishes) at the seams of their loops: widths around one trip of the column loop (255 / 256 / 257),
+"""The reductions of include/csim.h on the GPU (k_reduce<0|1|2> and k_checksum, for one field or one member per
+blockIdx.y, and their host folds) at the seams of their loops: widths around one trip of the column loop (255 / 256 / 257),
 one row, one column, row counts around one trip of the row loop (1024 blocks; 64 per member in the ensemble), extrema
 and differences in the ghost ring, and NaN / Inf as data.
 
@@ -18,6 +18,7 @@ import pytest
 
 import reduce_restatement as rr
 from __graft_entry__ import load_package
+from virtual_ranks import VirtualRanks
 
 pytestmark = pytest.mark.gpu
 
@@ -333,3 +334,59 @@ def test_ensemble_sums_and_checksums_per_member(csim, B, nx, ny):
         assert e.checksums() == [csim.checksum_host(x[1:-1, 1:-1]) for x in X]
     finally:
         e.close()
+
+
+# ---- one kernel, two kinds of offsets: a rank's global position and a member's slab ------------------------------
+
+def test_checksum_follows_the_global_offsets_of_a_decomposition(csim):
+    """Four ranks of a 61 x 29 field: every rank's checksum is checksum_host of its tile at its global offsets, and the
+    four add up (mod 2^64) to the checksum of the whole interior; again with a -0.0 in the tile of rank 3."""
+    nxg, nyg, world = 61, 29, 4
+    u = rr.field(nxg, nyg)
+    vr = VirtualRanks(csim, world, nxg, nyg)
+    try:
+        assert any(d.x_offset > 0 for d in vr.decs) and any(d.y_offset > 0 for d in vr.decs)
+        d3 = vr.decs[3]
+        spot = (1 + d3.y_offset + d3.ny_local // 2, 1 + d3.x_offset + d3.nx_local // 2)  # array position in u
+        seen = []
+        for planted in (None, -0.0):
+            v = u.copy()
+            if planted is not None:
+                v[spot] = planted
+            # tiles cut with their ring of neighbouring values: the ghosts are not zero and not in the checksum
+            vr.upload_tiles(lambda r, d: v[d.y_offset:d.y_offset + d.ny_local + 2,
+                                           d.x_offset:d.x_offset + d.nx_local + 2].copy())
+            per_rank = [st.checksum() for st in vr.st]
+            for r, d in enumerate(vr.decs):
+                tile = v[1 + d.y_offset:1 + d.y_offset + d.ny_local, 1 + d.x_offset:1 + d.x_offset + d.nx_local]
+                assert per_rank[r] == csim.checksum_host(tile, d.x_offset, d.y_offset, nxg), (r, planted)
+            whole = csim.checksum_host(v[1:-1, 1:-1])
+            assert sum(per_rank) % (1 << 64) == whole == vr.checksum(), planted
+            seen.append((whole, per_rank))
+        assert seen[0][0] != seen[1][0] and seen[0][1][:3] == seen[1][1][:3] and seen[0][1][3] != seen[1][1][3]
+    finally:
+        vr.close()
+
+
+def test_a_member_reduces_as_the_stepper_that_holds_the_same_field(csim):
+    """Member 1 of three 257 x 65 members against a Stepper of the same array: the same checksum and min / max; each
+    sum is its own cap's restated order bit for bit (65 rows: 64 blocks in the ensemble, 65 in the Stepper), so the two
+    sums differ by no more than the two orders' bounds against the exact sum together."""
+    B, nx, ny = 3, 257, 65
+    X = ens_fields(B, nx, ny)
+    u = X[1]
+    e, st = csim.Ensemble(B, nx, ny), csim.Stepper.single(nx, ny)
+    try:
+        e.upload_all(X)
+        st.upload(u)
+        assert e.checksums()[1] == st.checksum() == csim.checksum_host(u[1:-1, 1:-1])
+        got, want = e.minmax()[1], st.minmax()
+        assert (bits(got[0]), bits(got[1])) == (bits(want[0]), bits(want[1])) and want == rr.ref_minmax(u)
+        se, ss = e.sums()[1], st.sum()
+        print(f"sum 257x65: member {se!r} stepper {ss!r}")
+        assert bits(se) == bits(rr.restated_sum(u, rr.CAP_ENSEMBLE))
+        assert bits(ss) == bits(rr.restated_sum(u, rr.CAP_FIELD))
+        assert abs(se - ss) <= rr.sum_bound(u, rr.CAP_ENSEMBLE) + rr.sum_bound(u, rr.CAP_FIELD)
+    finally:
+        e.close()
+        st.close()
