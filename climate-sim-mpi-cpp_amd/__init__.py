@@ -91,6 +91,17 @@ class CsimVerifyScores(C.Structure):
                 ("spread", C.c_double), ("brier", C.c_double * VERIFY_MAX_THRESHOLDS)]
 
 
+SPATIAL_MAX_HALF, SPATIAL_MAX_SCALES, SPATIAL_MAX_MEMBERS = 32, 8, 4096
+
+
+class CsimSpatialScores(C.Structure):
+    """csim_spatial_scores of include/csim.h"""
+    _fields_ = [("cells", C.c_longlong), ("nan_cells", C.c_longlong)] + [
+        (k, C.c_double * VERIFY_MAX_THRESHOLDS) for k in ("brier", "reliability", "resolution", "uncertainty",
+                                                          "roc_area")] + [
+        ("fss", (C.c_double * SPATIAL_MAX_SCALES) * VERIFY_MAX_THRESHOLDS)]
+
+
 def build(force: bool = False) -> str:
     """Compile csrc/ for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force or not os.path.exists(LIB_PATH):
@@ -122,6 +133,7 @@ def lib() -> C.CDLL:
     L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     dp, ip, vp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p
     d, i = C.c_double, C.c_int
+    u8p = C.POINTER(C.c_ulonglong)
     sig = {
         "csim_last_error": (C.c_char_p, []),
         "csim_abi_version": (i, []),
@@ -205,6 +217,15 @@ def lib() -> C.CDLL:
         "csim_ensemble_verify_wait": (i, [vp, C.POINTER(dp), C.POINTER(dp), C.POINTER(C.POINTER(C.c_ulonglong)),
                                           C.POINTER(CsimVerifyScores)]),
         "csim_ensemble_rank_slot": (i, [C.c_longlong, i, ip]),
+        "csim_ensemble_verify_spatial": (i, [vp, dp, i, i, dp, i, ip, u8p, u8p, C.POINTER(C.c_ushort),
+                                             C.POINTER(C.c_uint), u8p, u8p]),
+        "csim_ensemble_verify_spatial_begin": (i, [vp, dp, i, i, dp, i, ip, i]),
+        "csim_ensemble_verify_spatial_wait": (i, [vp, C.POINTER(u8p), C.POINTER(u8p),
+                                                  C.POINTER(C.POINTER(C.c_ushort)), C.POINTER(C.POINTER(C.c_uint)),
+                                                  u8p, u8p]),
+        "csim_verify_spatial_limit": (i, [i, i, i, i]),
+        "csim_verify_spatial_finish": (i, [i, i, i, u8p, u8p, C.c_ulonglong, C.c_ulonglong,
+                                           C.POINTER(CsimSpatialScores), dp, dp]),
         "csim_ensemble_assimilate": (i, [vp, i, ip, ip, dp, dp, d, d, i, i, dp, dp, dp, dp, ip]),
         "csim_ensemble_gc_table": (i, [d, d, d, i, i, ip, ip, dp]),
         "csim_ensemble_assim_plan": (i, [i, ip, ip, i, i, i, ip, ip]),
@@ -648,6 +669,49 @@ def ensemble_rank_slot(g: int, ties: int) -> int:
     return v.value
 
 
+SpatialScores = collections.namedtuple(
+    "SpatialScores", "cells nan_cells brier reliability resolution uncertainty roc_area fss hit_rate false_alarm")
+SpatialScores.__doc__ = """scores finished from the integer tables of a spatial verification (csim_verify_spatial_finish):
+per threshold (nt,) the Brier score and its reliability, resolution and uncertainty, the ROC area, fss (nt, ns), and
+the ROC points hit_rate / false_alarm (nt, M+1) of the decisions "at least k members exceed", k = 0 .. M"""
+
+SpatialVerification = collections.namedtuple("SpatialVerification", "table nbh cells nan_cells scores counts flags")
+SpatialVerification.__doc__ = """Ensemble.verify_spatial: table (nt, M+1, 2) and nbh (nt, ns, 3) uint64, the non-NaN and NaN
+interior cells, SpatialScores, and with counts=True the count planes (nt, ny, nx) uint16 and flags (ny, nx) uint32"""
+
+
+def _u8p(a):
+    assert a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"]
+    return a.ctypes.data_as(C.POINTER(C.c_ulonglong))
+
+
+def verify_spatial_limit(M: int, nx: int, ny: int, half_max: int) -> bool:
+    """whether M forecast members on nx x ny cells with half-widths up to half_max stay inside the overflow bound
+    M^2 w^4 nx ny <= 2^62, M <= 4096 (csim_verify_spatial_limit) — host only"""
+    rc = lib().csim_verify_spatial_limit(int(M), int(nx), int(ny), int(half_max))
+    if rc not in (0, 5):  # CSIM_ERR_UNSUPPORTED: outside the bound
+        _ck(rc)
+    return rc == 0
+
+
+def verify_spatial_finish(M: int, table, nbh, cells: int, nan_cells: int = 0) -> SpatialScores:
+    """the scores of the integer tables: table (nt, M+1, 2), nbh (nt, ns, 3) (csim_verify_spatial_finish) — host only"""
+    table = np.ascontiguousarray(table, dtype=np.uint64)
+    nt = table.shape[0]
+    if table.shape != (nt, int(M) + 1, 2):
+        raise ValueError("table must have shape (nt, M + 1, 2)")
+    nbh = np.ascontiguousarray(nbh, dtype=np.uint64).reshape(nt, -1, 3)
+    ns = nbh.shape[1]
+    sc = CsimSpatialScores()
+    hit, fa = np.empty((nt, int(M) + 1)), np.empty((nt, int(M) + 1))
+    _ck(lib().csim_verify_spatial_finish(int(M), nt, ns, _u8p(table), _u8p(nbh) if ns else None, int(cells),
+                                         int(nan_cells), C.byref(sc), _dp(hit), _dp(fa)))
+    per = [np.array(getattr(sc, k)[:nt], dtype=np.float64)
+           for k in ("brier", "reliability", "resolution", "uncertainty", "roc_area")]
+    fss = np.array([[sc.fss[q][s] for s in range(ns)] for q in range(nt)], dtype=np.float64).reshape(nt, ns)
+    return SpatialScores(sc.cells, sc.nan_cells, *per, fss, hit, fa)
+
+
 EnsembleAnalysis = collections.namedtuple("EnsembleAnalysis", "nlevels prior_mean prior_var post_mean post_var")
 EnsembleAnalysis.__doc__ = """an analysis (Ensemble.assimilate): the plan's level count and, per observation in input
 order, the forecast mean and variance at its cell when its turn came and the analysis mean and variance there after
@@ -1036,6 +1100,7 @@ class Ensemble:
         self.members, self.nx, self.ny = members, nx, ny
         self._q_counts = (0, 0)  # levels and thresholds of the last quantiles_begin()
         self._v_counts = (0, 0)  # forecast members and thresholds of the last verify_begin()
+        self._s_counts = (0, 0, 0, False)  # members, thresholds, scales, fields of the last verify_spatial_begin()
         # observation networks that are alive (the library destroys them with the ensemble); weak, so that a network,
         # which keeps its ensemble alive, makes no reference cycle with it
         self._nets = weakref.WeakSet()
@@ -1182,6 +1247,57 @@ class Ensemble:
         brier = np.ctypeslib.as_array(pb, shape=(nt,) + shape).copy() if nt else np.empty((0,) + shape)
         hist = np.ctypeslib.as_array(ph, shape=(M + 1,)).copy()
         return EnsembleVerification(crps, brier, hist, _scores(sc, nt))
+
+    def _spatial_args(self, truth, truth_member, thresholds, half_widths):
+        truth, tp, tm, M = self._truth_args(truth, truth_member)
+        ts = _levels(thresholds)
+        hs = _ints(half_widths) if len(half_widths) else np.zeros(0, dtype=np.int32)
+        return truth, tp, tm, M, ts, hs
+
+    def _spatial_result(self, M, nt, ns, table, nbh, cells, nan_cells, counts, flags) -> SpatialVerification:
+        scores = verify_spatial_finish(M, table, nbh, cells, nan_cells)
+        return SpatialVerification(table, nbh.reshape(nt, ns, 3), cells, nan_cells, scores, counts, flags)
+
+    def verify_spatial(self, truth=None, *, truth_member=None, thresholds, half_widths=(),
+                       counts=False) -> SpatialVerification:
+        """neighbourhood and probability verification against a truth (as verify()): per threshold the contingency
+        table of (members exceeding, truth exceeding) over the interior and, per half-width, the window sums behind the
+        Fractions Skill Score, all exact integers from the device, and the scores finished from them: Brier score with
+        reliability / resolution / uncertainty, ROC and FSS (csim_ensemble_verify_spatial).  counts=True also returns
+        the per-cell member counts and the flags word"""
+        truth, tp, tm, M, ts, hs = self._spatial_args(truth, truth_member, thresholds, half_widths)
+        nt, ns = len(ts), len(hs)
+        table = np.zeros((nt, max(M, 0) + 1, 2), dtype=np.uint64)
+        nbh = np.zeros((nt, ns, 3), dtype=np.uint64)
+        cnt = np.zeros((nt, self.ny, self.nx), dtype=np.uint16) if counts else None
+        fl = np.zeros((self.ny, self.nx), dtype=np.uint32) if counts else None
+        n, nan = C.c_ulonglong(), C.c_ulonglong()
+        _ck(lib().csim_ensemble_verify_spatial(
+            self._h, tp, tm, nt, _dp(ts), ns, _ip(hs), _u8p(table), _u8p(nbh),
+            cnt.ctypes.data_as(C.POINTER(C.c_ushort)) if counts else None,
+            fl.ctypes.data_as(C.POINTER(C.c_uint)) if counts else None, C.byref(n), C.byref(nan)))
+        return self._spatial_result(M, nt, ns, table, nbh, n.value, nan.value, cnt, fl)
+
+    def verify_spatial_begin(self, truth=None, *, truth_member=None, thresholds, half_widths=(), counts=False):
+        """start verify_spatial() of the current state without waiting; run() may follow before verify_spatial_wait()"""
+        truth, tp, tm, M, ts, hs = self._spatial_args(truth, truth_member, thresholds, half_widths)
+        _ck(lib().csim_ensemble_verify_spatial_begin(self._h, tp, tm, len(ts), _dp(ts), len(hs), _ip(hs),
+                                                     int(bool(counts))))
+        self._s_counts = (M, len(ts), len(hs), bool(counts))
+
+    def verify_spatial_wait(self) -> SpatialVerification:
+        """the verification verify_spatial_begin() captured (copies)"""
+        u8p = C.POINTER(C.c_ulonglong)
+        pt, pn, pc, pf = u8p(), u8p(), C.POINTER(C.c_ushort)(), C.POINTER(C.c_uint)()
+        n, nan = C.c_ulonglong(), C.c_ulonglong()
+        _ck(lib().csim_ensemble_verify_spatial_wait(self._h, C.byref(pt), C.byref(pn), C.byref(pc), C.byref(pf),
+                                                    C.byref(n), C.byref(nan)))
+        M, nt, ns, fields = self._s_counts
+        table = np.ctypeslib.as_array(pt, shape=(nt, M + 1, 2)).copy()
+        nbh = np.ctypeslib.as_array(pn, shape=(nt, ns, 3)).copy() if ns else np.zeros((nt, 0, 3), dtype=np.uint64)
+        cnt = np.ctypeslib.as_array(pc, shape=(nt, self.ny, self.nx)).copy() if fields else None
+        fl = np.ctypeslib.as_array(pf, shape=(self.ny, self.nx)).copy() if fields else None
+        return self._spatial_result(M, nt, ns, table, nbh, n.value, nan.value, cnt, fl)
 
     def assimilate(self, i, j, y, r, loc, inflation=1.0, truth_member=None, ordered=False, diagnostics=True):
         """serial EnSRF analysis of the forecast members with point observations at interior cells (i, j), values y

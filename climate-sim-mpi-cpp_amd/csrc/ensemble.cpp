@@ -6,6 +6,8 @@
 //                      the pass plan and sign classes, run / sync, per-member reductions, options
 //   ensemble_diag.cpp  diagnostics, synchronous and as _begin / _wait captures: statistics, quantiles (and their
 //                      plan), verification (and its rank slot)
+//   ensemble_spatial.cpp  neighbourhood and probability verification (tables, window sums), its overflow bound and the
+//                      host-only finishing of the tables into scores
 //   ensemble_da.cpp    data assimilation: the analysis of a plan, Philox / normal numbers, perturbations, relaxation
 //                      (prior capture, relax); the plan, the Gaspari-Cohn table and the taps: assim_plan.cpp, without HIP
 //   ensemble_obs.cpp   observation networks: create / destroy, values from the host or from a member, the analysis that
@@ -141,6 +143,7 @@ int csim_ensemble_destroy(csim_ensemble* e) {
     e->stats.release();
     e->quant.release();
     e->verify.release();
+    e->spatial.release();
     e->assim.release();
     e->relax.release();
     e->own.release();
@@ -297,6 +300,12 @@ int csim_ensemble_set_option(csim_ensemble* e, const char* key, long value) {
         CSIM_REQUIRE(value == 0 || value == 1, "fused_2c must be 0 or 1");
         e->fused_2c = static_cast<int>(value);
         e->dirty = true;
+    } else if (k == "spatial_grid_max") {
+        CSIM_REQUIRE(value >= 0 && value <= 65535, "spatial_grid_max must be 0 (automatic) or 1 .. 65535");
+        e->spatial.grid_max = static_cast<int>(value);
+    } else if (k == "spatial_member_split") {
+        CSIM_REQUIRE(value >= 0 && value <= 4096, "spatial_member_split must be 0 (automatic) or 1 .. 4096");
+        e->spatial.member_split = static_cast<int>(value);
     } else if (k == "depth_used") {
         return fail(CSIM_ERR_ARG, "option depth_used is read-only");
     } else if (k == "contract") {
@@ -316,6 +325,10 @@ int csim_ensemble_get_option(const csim_ensemble* e, const char* key, long* valu
         *value = e->fused_2c;
     else if (k == "depth_used")
         *value = e->depth_used;
+    else if (k == "spatial_grid_max")
+        *value = e->spatial.grid_max;
+    else if (k == "spatial_member_split")
+        *value = e->spatial.member_split;
     else if (k == "contract")
         return fail(CSIM_ERR_UNSUPPORTED, "an ensemble is always bit-identical: no contract mode");
     else

@@ -94,6 +94,43 @@ int ens_verify_blocks(const EnsGeom& g, int forecast);  // workgroups of the lau
 hipError_t ens_launch_verify(const EnsGeom& g, const double* f, const VerifyArgs& va, const VerifyOut& o,
                              hipStream_t st);
 
+// neighbourhood and probability verification (ensemble_spatial.hip, csim_ensemble_verify_spatial): integers only.
+// Pass 1, ens_launch_spatial_counts: one read of the members -> the count planes n_q (uint16, nt planes of ny x nx, no
+// ghost ring) and the flags word per interior cell (bit q = o_q, bit 31 = NaN cell).  With split > 1 the members of a
+// cell are divided over blockIdx.y, the parts add into `acc` (32-bit atomics; nt + 1 planes, the last one the NaN
+// marks, zeroed by the launcher) and a merge kernel writes counts and flags.
+// Pass 2, ens_launch_spatial_scores: reads only counts and flags; per threshold the contingency table and, per scale,
+// the sums A, Bo, C over square windows, from a summed-area table in LDS.  Both loop under a cap on gridDim.x.
+constexpr int SPATIAL_MAX_HALF = 32;
+constexpr int SPATIAL_MAX_SCALES = 8;
+constexpr int SPATIAL_TILE = 32;               // centres per tile side of pass 2
+constexpr int SPATIAL_COUNTS_GRID_MAX = 2048;  // default caps on gridDim.x
+constexpr int SPATIAL_SCORES_GRID_MAX = 1024;
+struct SpatialArgs {
+    int forecast;          // M
+    int truth_member;      // t, or B with `truth`
+    int nt, ns;
+    int hmax;              // the call's largest half-width (0 without scales)
+    int split;             // parts of the members in pass 1, >= 1
+    int grid_max;          // cap on gridDim.x of both passes; 0: the defaults above
+    const double* truth;   // device, dense (ny+2) x (nx+2); null with a truth member
+    int half[SPATIAL_MAX_SCALES];
+    double thr[VERIFY_MAX_THRESHOLDS];
+};
+struct SpatialOut {
+    unsigned long long* table;   // nt x (M + 1) x 2, zeroed by the caller
+    unsigned long long* nbh;     // nt x ns x 3, zeroed by the caller
+    unsigned long long* cells;   // 2: non-NaN and NaN interior cells, zeroed by the caller
+    unsigned* flags;             // nx ny
+    unsigned short* counts;      // nt x nx ny
+    unsigned* acc;               // (nt + 1) x nx ny, used with split > 1
+};
+int ens_spatial_split(int cells, int forecast);  // the default split of pass 1
+size_t ens_spatial_lds(int forecast, int hmax);  // dynamic LDS of a workgroup of pass 2, bytes
+hipError_t ens_launch_spatial_counts(const EnsGeom& g, const double* f, const SpatialArgs& a, const SpatialOut& o,
+                                     hipStream_t st);
+hipError_t ens_launch_spatial_scores(const EnsGeom& g, const SpatialArgs& a, const SpatialOut& o, hipStream_t st);
+
 // the analysis (ensemble_assim.hip): the serial EnSRF of csim.h, one level of mutually non-conflicting observations
 // after the other, two launches per batch of a level: assim_prior (one wave per observation: h'_k and its scalars)
 // and assim_update (one wave per 64 cells of one observation's window).  Observations are in plan order; `first` is

@@ -66,6 +66,16 @@ struct csim_ensemble {
         int forecast = 0, nt = 0, blocks = 0;  // of the capture in flight
         void release() { cap.release(), truth.release(), stage.release(); }
     } verify;
+    // neighbourhood and probability verification (csim_ensemble_verify_spatial*, ensemble_spatial.cpp): one buffer
+    // (SpatialLayout), the device copy of a host truth, and its two options
+    struct Spatial {
+        csim::Capture cap;
+        csim::DeviceBuf truth;
+        csim::Staging stage;
+        int forecast = 0, nt = 0, ns = 0, fields = 0;  // of the capture in flight
+        int grid_max = 0, member_split = 0;            // options spatial_grid_max, spatial_member_split; 0: automatic
+        void release() { cap.release(), truth.release(), stage.release(); }
+    } spatial;
     // analysis (csim_ensemble_assimilate): one device buffer (AssimLayout) and the staging of its inputs
     struct Assim {
         csim::DeviceBuf dev;

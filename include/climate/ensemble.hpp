@@ -32,6 +32,25 @@ struct EnsembleVerification {
     csim_verify_scores scores;
 };
 
+// neighbourhood and probability verification (see csim_ensemble_verify_spatial): the integer tables of the device
+// (table: thresholds x (forecast + 1) x 2, nbh: thresholds x scales x 3), the non-NaN and NaN interior cells, and
+// what csim_verify_spatial_finish makes of them: the scores and the ROC points (thresholds x (forecast + 1) each)
+struct SpatialVerification {
+    std::vector<unsigned long long> table, nbh;
+    unsigned long long cells = 0, nan_cells = 0;
+    std::size_t thresholds = 0, scales = 0, forecast = 0;
+    csim_spatial_scores scores{};
+    std::vector<double> hit_rate, false_alarm;
+};
+
+// host-only: whether M forecast members on nx x ny cells with half-widths up to half_max are inside the overflow bound
+// of csim_verify_spatial_limit; other errors throw
+inline bool verify_spatial_limit(int M, int nx, int ny, int half_max) {
+    const int rc = csim_verify_spatial_limit(M, nx, ny, half_max);
+    if (rc != CSIM_OK && rc != CSIM_ERR_UNSUPPORTED) throw std::runtime_error(std::string("csim: ") + csim_last_error());
+    return rc == CSIM_OK;
+}
+
 // an analysis (see csim_ensemble_assimilate): the plan's level count and, per observation in input order, the forecast
 // mean and variance at its cell at its turn and the analysis mean and variance there after all observations
 struct EnsembleAnalysis {
@@ -304,6 +323,42 @@ public:
         check(csim_ensemble_verify_wait(h_, &v.crps, &v.brier, &v.rank_hist, &v.scores));
         return v;
     }
+    // neighbourhood and probability verification of the members against a host truth field (member_size() values) or
+    // of the other members against member t: contingency tables and window sums as exact integers from the device,
+    // finished into Brier decomposition, ROC and Fractions Skill Score on the host (see csim_ensemble_verify_spatial)
+    SpatialVerification verify_spatial(const std::vector<double>& truth, const std::vector<double>& thresholds,
+                                       const std::vector<int>& half_widths = {}) {
+        return spatial_any(sized(truth, 1), -1, members_, thresholds, half_widths);
+    }
+    SpatialVerification verify_spatial_member(int t, const std::vector<double>& thresholds,
+                                              const std::vector<int>& half_widths = {}) {
+        return spatial_any(nullptr, t, members_ - 1, thresholds, half_widths);
+    }
+    // captured after everything enqueued so far, with a capture of its own: run(), verify_begin(), stats_begin() and
+    // quantiles_begin() may follow before verify_spatial_wait(), which copies the tables and finishes the scores
+    void verify_spatial_begin(const std::vector<double>& truth, const std::vector<double>& thresholds,
+                              const std::vector<int>& half_widths = {}) {
+        check(csim_ensemble_verify_spatial_begin(h_, sized(truth, 1), -1, static_cast<int>(thresholds.size()),
+                                                 thresholds.data(), static_cast<int>(half_widths.size()),
+                                                 half_widths.data(), 0));
+        s_forecast_ = members_, s_thresholds_ = thresholds.size(), s_scales_ = half_widths.size();
+    }
+    void verify_spatial_member_begin(int t, const std::vector<double>& thresholds,
+                                     const std::vector<int>& half_widths = {}) {
+        check(csim_ensemble_verify_spatial_begin(h_, nullptr, t, static_cast<int>(thresholds.size()), thresholds.data(),
+                                                 static_cast<int>(half_widths.size()), half_widths.data(), 0));
+        s_forecast_ = members_ - 1, s_thresholds_ = thresholds.size(), s_scales_ = half_widths.size();
+    }
+    SpatialVerification verify_spatial_wait() {
+        const unsigned long long *table = nullptr, *nbh = nullptr;
+        SpatialVerification r;
+        check(csim_ensemble_verify_spatial_wait(h_, &table, &nbh, nullptr, nullptr, &r.cells, &r.nan_cells));
+        shape(r, s_forecast_, s_thresholds_, s_scales_);
+        std::copy(table, table + r.table.size(), r.table.begin());
+        std::copy(nbh, nbh + r.nbh.size(), r.nbh.begin());
+        finish(r);
+        return r;
+    }
     // serial EnSRF analysis with point observations (i[o], j[o], y[o], r[o]), Gaspari-Cohn length loc; t = -1: all
     // members are the forecast, else member t is left alone.  Synchronous, with the diagnostics
     EnsembleAnalysis assimilate(const std::vector<int>& i, const std::vector<int>& j, const std::vector<double>& y,
@@ -445,6 +500,29 @@ private:
                                    r.crps.data(), r.brier.data(), r.rank_hist.data(), &r.scores));
         return r;
     }
+    static void shape(SpatialVerification& r, int forecast, std::size_t nt, std::size_t ns) {
+        r.forecast = static_cast<std::size_t>(forecast > 0 ? forecast : 0);
+        r.thresholds = nt, r.scales = ns;
+        r.table.assign(nt * (r.forecast + 1) * 2, 0);
+        r.nbh.assign(nt * ns * 3, 0);
+        r.hit_rate.assign(nt * (r.forecast + 1), 0.0);
+        r.false_alarm.assign(nt * (r.forecast + 1), 0.0);
+    }
+    static void finish(SpatialVerification& r) {
+        check(csim_verify_spatial_finish(static_cast<int>(r.forecast), static_cast<int>(r.thresholds),
+                                         static_cast<int>(r.scales), r.table.data(), r.nbh.data(), r.cells, r.nan_cells,
+                                         &r.scores, r.hit_rate.data(), r.false_alarm.data()));
+    }
+    SpatialVerification spatial_any(const double* truth, int t, int forecast, const std::vector<double>& thresholds,
+                                    const std::vector<int>& half_widths) {
+        SpatialVerification r;
+        shape(r, forecast, thresholds.size(), half_widths.size());
+        check(csim_ensemble_verify_spatial(h_, truth, t, static_cast<int>(thresholds.size()), thresholds.data(),
+                                           static_cast<int>(half_widths.size()), half_widths.data(), r.table.data(),
+                                           r.nbh.data(), nullptr, nullptr, &r.cells, &r.nan_cells));
+        finish(r);
+        return r;
+    }
     static std::size_t obs_size(const std::vector<int>& i, const std::vector<int>& j, const std::vector<double>& y,
                                 const std::vector<double>& r) {
         if (j.size() != i.size() || y.size() != i.size() || r.size() != i.size())
@@ -456,6 +534,8 @@ private:
     int members_, nx_, ny_;
     std::size_t q_levels_ = 0, q_thresholds_ = 0;  // of the last quantiles_begin()
     std::size_t v_forecast_ = 0, v_thresholds_ = 0;  // of the last verify_begin()
+    int s_forecast_ = 0;                             // of the last verify_spatial_begin()
+    std::size_t s_thresholds_ = 0, s_scales_ = 0;
 };
 
 }  // namespace climate

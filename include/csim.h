@@ -405,6 +405,81 @@ int csim_ensemble_verify_wait(csim_ensemble* e, const double** out_crps, const d
                               const unsigned long long** rank_hist, csim_verify_scores* scores);
 /* host-only: the rank histogram's tie-break, mix(g) mod (ties + 1) for g >= 0, ties >= 0 */
 int csim_ensemble_rank_slot(long long g, int ties, int* slot);
+/* neighbourhood and probability verification: the contingency table of the ensemble probability against the truth, and
+ * the sums behind the Fractions Skill Score (Roberts & Lean 2008) over square neighbourhoods.  Forecast members and
+ * truth as in csim_ensemble_verify: a host field (truth, truth_member = -1, M = B) or member t = truth_member
+ * (truth = NULL, the M = B - 1 others, in their order, are the forecast).  Only interior cells take part (1 <= i <= nx,
+ * 1 <= j <= ny); the ghost ring is never read as data.  A cell is NaN when its truth or any forecast member is NaN.
+ * Per threshold thr[q] (1 <= nt <= CSIM_VERIFY_MAX_THRESHOLDS) and interior cell:
+ *   n_q = #(x_k > thr[q]) over the forecast members (0 .. M);  o_q = y > thr[q] ? 1 : 0;  both 0 on a NaN cell.
+ *   The comparisons are strict and IEEE: -0.0 > 0.0 is false, +Inf > thr unless thr is +Inf, nothing exceeds +Inf.
+ * Everything the device computes is an integer, so the results do not depend on launch geometry or summation order:
+ *   table[q][k][b]  (nt x (M + 1) x 2): the non-NaN interior cells with n_q == k and o_q == b;  cells / nan_cells: the
+ *                   non-NaN / NaN interior cells.
+ *   nbh[q][s][3]    (nt x ns x 3), scale s with half-width half[s], 0 <= ns <= CSIM_SPATIAL_MAX_SCALES,
+ *                   0 <= half[s] <= CSIM_SPATIAL_MAX_HALF, any order, repeats allowed.  With w = 2 half[s] + 1, F(i, j)
+ *                   is the sum of n_q over the w x w window centred on the cell and O(i, j) that of o_q; cells outside
+ *                   the interior count as zero (zero padding, the usual convention of the score), and so do NaN cells.
+ *                   Over the non-NaN interior centres: A = sum F F, Bo = sum O O, C = sum F O, in that order.
+ *   counts          nt planes of ny x nx uint16_t holding n_q (no ghost ring);  flags: one uint32_t per interior cell,
+ *                   bit q = o_q, bit 31 = NaN cell.
+ * Any output may be NULL (not copied).  Synchronous.  No set_physics needed; no member's field is written.
+ * Overflow: csim_verify_spatial_limit (host only) returns CSIM_ERR_UNSUPPORTED unless M <= CSIM_SPATIAL_MAX_MEMBERS and
+ * M M w^4 nx ny <= 2^62, w = 2 half_max + 1.  Under that bound A <= 2^62, M M Bo <= 2^62 and 2 M C <= 2^63, so every
+ * 64-bit unsigned sum below is exact, and a single F is below 2^32.  The compute entry points make the same check, with
+ * the call's largest half-width (0 without scales), before anything is enqueued.  At M = 64 and half = 32 the bound
+ * allows nx ny <= 63 073 416 (7941 x 7941; 8192 x 8192 up to half = 31); at M = 4096 and half = 32 only 15 398 cells
+ * (124 x 124).
+ * Errors: CSIM_ERR_ARG unless exactly one truth is given, for truth_member outside -1 .. B-1, nt outside 1 .. 16, ns
+ * outside 0 .. 8, a half-width outside 0 .. 32, no forecast member; CSIM_ERR_UNSUPPORTED for M > 4096, the bound, or more than 2^27 interior cells. */
+#define CSIM_SPATIAL_MAX_HALF 32
+#define CSIM_SPATIAL_MAX_SCALES 8
+#define CSIM_SPATIAL_MAX_MEMBERS 4096
+int csim_ensemble_verify_spatial(csim_ensemble* e, const double* truth, int truth_member, int nt, const double* thr,
+                                 int ns, const int* half, unsigned long long* table, unsigned long long* nbh,
+                                 unsigned short* counts, unsigned int* flags, unsigned long long* cells,
+                                 unsigned long long* nan_cells);
+/* the same, captured as csim_ensemble_verify_begin captures (the kernels in stream order, the copy to pinned host
+ * buffers on a stream of its own; a host truth is copied before the call returns), with a capture and a truth staging
+ * of their own: statistics, quantiles, a plain verification and this one may all be in flight together, and
+ * csim_ensemble_run may follow.  fields = 1: counts and flags are copied too; 0: only the tables.  A _begin while one
+ * is in flight first waits for it. */
+int csim_ensemble_verify_spatial_begin(csim_ensemble* e, const double* truth, int truth_member, int nt,
+                                       const double* thr, int ns, const int* half, int fields);
+/* the capture's outputs (pointers valid until the next _begin or destroy; any may be NULL; counts and flags are NULL
+ * after a _begin with fields = 0); CSIM_ERR_STATE when nothing is in flight */
+int csim_ensemble_verify_spatial_wait(csim_ensemble* e, const unsigned long long** table,
+                                      const unsigned long long** nbh, const unsigned short** counts,
+                                      const unsigned int** flags, unsigned long long* cells,
+                                      unsigned long long* nan_cells);
+/* host-only: the overflow bound above; CSIM_ERR_ARG for M, nx or ny < 1 or half_max outside 0 .. 32 */
+int csim_verify_spatial_limit(int M, int nx, int ny, int half_max);
+/* host-only: the scores of the tables, so that C, C++ and Python derive the same bits.  Per threshold, with T = table[q],
+ * n = cells, p_k = (double)k / (double)M, every sum from +0 in increasing k, one rounding per operation, no contraction;
+ * integer sums are exact and converted to double once:
+ *   N_k = T[k][0] + T[k][1], O_k = T[k][1], SO = sum O_k, obar = (double)SO / (double)n
+ *   brier       = (sum_k (p_k p_k (double)T[k][0] + (p_k - 1)(p_k - 1) (double)T[k][1])) / n
+ *   reliability = (sum_{N_k > 0} (double)N_k (d d)) / n, d = p_k - f_k, f_k = (double)O_k / (double)N_k
+ *   resolution  = (sum_{N_k > 0} (double)N_k (d d)) / n, d = f_k - obar
+ *   uncertainty = obar (1 - obar);  brier = reliability - resolution + uncertainty up to rounding
+ *   ROC: for the decision "at least k members exceed", hit_rate[q][k] = (double)(sum_{k' >= k} O_k') / (double)SO and
+ *   false_alarm[q][k] = (double)(sum_{k' >= k} T[k'][0]) / (double)(n - SO), k = 0 .. M (both are 0 at k = M + 1);
+ *   roc_area = sum over k = M down to 0 of ((F_k - F_{k+1}) (H_k + H_{k+1})) 0.5.  With SO = 0 the hit rates, with
+ *   SO = n the false-alarm rates, and in both cases roc_area, are NaN.  With n = 0 every score of the threshold is NaN.
+ *   fss[q][s]: in 64-bit unsigned integers S = A + M M Bo and D = S - 2 M C, which is sum (F - M O)^2 exactly;
+ *   fss = 1 - (double)D / (double)S, NaN when S = 0.
+ * hit_rate and false_alarm are the caller's: nt (M + 1) doubles each, or NULL.  Entries of `out` past nt / ns are 0.
+ * CSIM_ERR_ARG for M < 1, nt outside 1 .. 16, ns outside 0 .. 8 or a null table / out (nbh may be NULL with ns = 0). */
+typedef struct csim_spatial_scores {
+    long long cells, nan_cells;
+    double brier[CSIM_VERIFY_MAX_THRESHOLDS], reliability[CSIM_VERIFY_MAX_THRESHOLDS];
+    double resolution[CSIM_VERIFY_MAX_THRESHOLDS], uncertainty[CSIM_VERIFY_MAX_THRESHOLDS];
+    double roc_area[CSIM_VERIFY_MAX_THRESHOLDS];
+    double fss[CSIM_VERIFY_MAX_THRESHOLDS][CSIM_SPATIAL_MAX_SCALES];
+} csim_spatial_scores;
+int csim_verify_spatial_finish(int M, int nt, int ns, const unsigned long long* table, const unsigned long long* nbh,
+                               unsigned long long cells, unsigned long long nan_cells, csim_spatial_scores* out,
+                               double* hit_rate, double* false_alarm);
 /* analysis: pulls the forecast members towards point observations with the serial ensemble square-root filter
  * (Whitaker & Hamill 2002), localised with Gaspari & Cohn (1999).  Deterministic: no perturbed observations, no
  * random numbers, no matrix solves (every observation is a rank-1 update).
@@ -800,7 +875,11 @@ int csim_obs_impact_fold(const double* u, long n, double* S);
 /* options (unknown keys: CSIM_ERR_ARG; "contract": CSIM_ERR_UNSUPPORTED), results never depend on them:
  *   "fuse"        -1 (default) passes of the ensemble depth where the grid allows; 0 / 1 single steps only
  *   "fused_2c"    0/1 (default 1), as for csim_stepper_set_option
- *   "depth_used"  read-only: time steps per pass of the last run (1 = single steps only) */
+ *   "depth_used"  read-only: time steps per pass of the last run (1 = single steps only)
+ *   "spatial_grid_max"      0 (default: the kernels' own caps) or 1 .. 65535: workgroups along x of both kernels of
+ *                           csim_ensemble_verify_spatial, each of which loops over its cells or tiles
+ *   "spatial_member_split"  0 (default: chosen from cells and M) or 1 .. 4096: parts the forecast members of a cell
+ *                           are split into in that call's count pass (1: no split; more than M: M) */
 int csim_ensemble_set_option(csim_ensemble* e, const char* key, long value);
 int csim_ensemble_get_option(const csim_ensemble* e, const char* key, long* value);
 /* host-only pass planner of csim_ensemble_run: out[0] = steps per fused pass (1: none; members with nx or ny below

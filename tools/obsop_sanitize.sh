@@ -3,7 +3,8 @@
 # tap builders, csim_obs_linear_check, the layout of a network's buffer) and of the analysis plan (csrc/assim_plan.cpp,
 # csrc/assim_plan.hpp: levels, plan order, batches, the per-observation checks; the layout of the analysis buffer) and of
 # the sweep's tile plan (csrc/sweep_plan.cpp, csrc/sweep_plan.hpp: every plan of the check's enumeration through the
-# kernel's restated tile decode), each as a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.  The build goes to $TMP;
+# kernel's restated tile decode) and of the spatial verification (csrc/spatial_scores.cpp, csrc/spatial_scores.hpp: the
+# overflow bound at its edge, the finishing of the integer tables), each as a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.  The build goes to $TMP;
 # nothing in the tree is replaced.
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -15,7 +16,9 @@ CXX=(g++ -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined
 "${CXX[@]}" -o "$TMP/obsop_host_check" "$R/tools/obsop_host_check.cpp" "$S/obs_taps.cpp"
 "${CXX[@]}" -o "$TMP/assim_plan_host_check" "$R/tools/assim_plan_host_check.cpp" "$S/assim_plan.cpp"
 "${CXX[@]}" -o "$TMP/sweep_plan_host_check" "$R/tools/sweep_plan_host_check.cpp" "$S/sweep_plan.cpp"
+"${CXX[@]}" -o "$TMP/spatial_host_check" "$R/tools/spatial_host_check.cpp" "$S/spatial_scores.cpp"
 export ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1
 "$TMP/obsop_host_check"
 "$TMP/assim_plan_host_check"
 "$TMP/sweep_plan_host_check"
+"$TMP/spatial_host_check"
