@@ -306,6 +306,12 @@ int csim_ensemble_set_option(csim_ensemble* e, const char* key, long value) {
     } else if (k == "spatial_member_split") {
         CSIM_REQUIRE(value >= 0 && value <= 4096, "spatial_member_split must be 0 (automatic) or 1 .. 4096");
         e->spatial.member_split = static_cast<int>(value);
+    } else if (k == "perturb_tile_rows") {
+        CSIM_REQUIRE(value == 0 || value == 8 || value == 32, "perturb_tile_rows must be 0 (automatic), 8 or 32");
+        e->perturb.tile_rows = static_cast<int>(value);
+    } else if (k == "perturb_member_shares") {
+        CSIM_REQUIRE(value >= 0 && value <= 65535, "perturb_member_shares must be 0 (automatic) or 1 .. 65535");
+        e->perturb.member_shares = static_cast<int>(value);
     } else if (k == "depth_used") {
         return fail(CSIM_ERR_ARG, "option depth_used is read-only");
     } else if (k == "contract") {
@@ -329,6 +335,10 @@ int csim_ensemble_get_option(const csim_ensemble* e, const char* key, long* valu
         *value = e->spatial.grid_max;
     else if (k == "spatial_member_split")
         *value = e->spatial.member_split;
+    else if (k == "perturb_tile_rows")
+        *value = e->perturb.tile_rows;
+    else if (k == "perturb_member_shares")
+        *value = e->perturb.member_shares;
     else if (k == "contract")
         return fail(CSIM_ERR_UNSUPPORTED, "an ensemble is always bit-identical: no contract mode");
     else

@@ -219,7 +219,10 @@ struct PerturbArgs {
     double sigma;
     double tx[PERTURB_TAPS], ty[PERTURB_TAPS];
 };
-hipError_t ens_launch_perturb(const EnsGeom& g, double* f, const PerturbArgs& a, bool centered, hipStream_t st);
+// tile_rows: 0 (the launcher's choice), 8 or 32 rows per tile; member_shares: 0 (the launcher's choice) or
+// 1 .. 65535 workgroups per tile, clipped to the forecast members.  The result depends on neither.
+hipError_t ens_launch_perturb(const EnsGeom& g, double* f, const PerturbArgs& a, bool centered, hipStream_t st,
+                              int tile_rows = 0, int member_shares = 0);
 
 // the relaxation of csim_ensemble_prior_capture / csim_ensemble_relax (ensemble_relax.hip), one launch each; forecast
 // member k is forecast_member(k, truth_member) of ensemble_cell.hpp (truth_member = B: none skipped),

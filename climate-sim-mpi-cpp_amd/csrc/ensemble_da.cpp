@@ -139,7 +139,8 @@ int csim_ensemble_perturb(csim_ensemble* e, unsigned long long seed, unsigned dr
     a.forecast = M;
     a.truth_member = t;
     a.sigma = sigma;
-    CSIM_HIP(ens_launch_perturb(g, e->base(e->cur), a, centered == 1, e->st));
+    CSIM_HIP(ens_launch_perturb(g, e->base(e->cur), a, centered == 1, e->st, e->perturb.tile_rows,
+                                e->perturb.member_shares));
     return CSIM_OK;
 }
 

@@ -82,6 +82,10 @@ struct csim_ensemble {
         csim::Staging stage;
         void release() { dev.release(), stage.release(); }
     } assim;
+    // perturbations (csim_ensemble_perturb): no storage, its two launch options
+    struct Perturb {
+        int tile_rows = 0, member_shares = 0;  // options perturb_tile_rows, perturb_member_shares; 0: automatic
+    } perturb;
     // relaxation (csim_ensemble_prior_capture / csim_ensemble_relax).  A capture lives in the handle's own storage, so
     // that no call that writes the ping-pong buffers touches it: sqrt(v_b) per interior cell (RTPS), a copy of the
     // current buffer (RTPP, allocated at the first such capture), and the factor field of a call that asks for it

@@ -168,19 +168,25 @@ hipError_t launch_perturb(const EnsGeom& g, double* f, const PerturbArgs& a, int
 
 }  // namespace
 
-hipError_t ens_launch_perturb(const EnsGeom& g, double* f, const PerturbArgs& a, bool centered, hipStream_t st) {
+hipError_t ens_launch_perturb(const EnsGeom& g, double* f, const PerturbArgs& a, bool centered, hipStream_t st,
+                              int tile_rows, int member_shares) {
     if (a.rx < 0 || a.ry < 0 || a.rx > PERTURB_MAX_RADIUS || a.ry > PERTURB_MAX_RADIUS || a.forecast < 1)
+        return hipErrorInvalidValue;
+    if ((tile_rows != 0 && tile_rows != 8 && tile_rows != 32) || member_shares < 0 || member_shares > 65535)
         return hipErrorInvalidValue;
     if (static_cast<long long>((g.nx + PERTURB_TX - 1) / PERTURB_TX) * ((g.ny + 7) / 8) > 0x7fffffffLL)
         return hipErrorInvalidValue;
     // Tiles of 32 rows regenerate the least apron; tiles of 8 rows give a small grid four times the workgroups.  The
     // member shares then fill the machine: about 2048 workgroups, or, centered, 512, as every share repeats the sum
-    // over all members (M + M / shares fields per workgroup).
+    // over all members (M + M / shares fields per workgroup).  The options perturb_tile_rows and
+    // perturb_member_shares (tests) replace either choice; 0 keeps it.
     const long tiles32 = static_cast<long>((g.nx + PERTURB_TX - 1) / PERTURB_TX) * ((g.ny + 31) / 32);
     const long want = centered ? 512 : 2048;
-    const bool tall = tiles32 * (centered ? 1 : a.forecast) >= want / 2;
+    const bool tall = tile_rows ? tile_rows == 32 : tiles32 * (centered ? 1 : a.forecast) >= want / 2;
     const long tiles = tall ? tiles32 : static_cast<long>((g.nx + PERTURB_TX - 1) / PERTURB_TX) * ((g.ny + 7) / 8);
-    const int shares = static_cast<int>(std::max(1L, std::min<long>({(want + tiles - 1) / tiles, a.forecast, 65535L})));
+    const int shares =
+        member_shares ? std::min(member_shares, a.forecast)
+                      : static_cast<int>(std::max(1L, std::min<long>({(want + tiles - 1) / tiles, a.forecast, 65535L})));
     if (tall)
         return centered ? launch_perturb<32, true>(g, f, a, shares, st) : launch_perturb<32, false>(g, f, a, shares, st);
     return centered ? launch_perturb<8, true>(g, f, a, shares, st) : launch_perturb<8, false>(g, f, a, shares, st);

@@ -879,7 +879,11 @@ int csim_obs_impact_fold(const double* u, long n, double* S);
  *   "spatial_grid_max"      0 (default: the kernels' own caps) or 1 .. 65535: workgroups along x of both kernels of
  *                           csim_ensemble_verify_spatial, each of which loops over its cells or tiles
  *   "spatial_member_split"  0 (default: chosen from cells and M) or 1 .. 4096: parts the forecast members of a cell
- *                           are split into in that call's count pass (1: no split; more than M: M) */
+ *                           are split into in that call's count pass (1: no split; more than M: M)
+ *   "perturb_tile_rows"     0 (default: chosen from the grid and M), 8 or 32: interior rows per workgroup tile of
+ *                           csim_ensemble_perturb; any other value is CSIM_ERR_ARG
+ *   "perturb_member_shares" 0 (default: chosen from the tiles and M) or 1 .. 65535: workgroups that share the forecast
+ *                           members of one tile in that call (more than M: M) */
 int csim_ensemble_set_option(csim_ensemble* e, const char* key, long value);
 int csim_ensemble_get_option(const csim_ensemble* e, const char* key, long* value);
 /* host-only pass planner of csim_ensemble_run: out[0] = steps per fused pass (1: none; members with nx or ny below
