@@ -16,7 +16,8 @@ def opposite8(d):
 
 
 class VirtualRanks:
-    def __init__(self, csim, world, nx, ny, dx=1.0, dy=1.0, bc=(0, 0, 0, 0), bc_value=0.0, fuse=None):
+    def __init__(self, csim, world, nx, ny, dx=1.0, dy=1.0, bc=(0, 0, 0, 0), bc_value=0.0, fuse=None, opts=None):
+        """opts: stepper options (name -> value) set on every rank"""
         self.csim, self.world = csim, world
         self.decs = [csim.decomp_init(world, r, nx, ny) for r in range(world)]
         self.st = []
@@ -25,6 +26,8 @@ class VirtualRanks:
             st.set_option("external_halo", 1)
             if fuse is not None:
                 st.set_option("fuse", fuse)
+            for k, v in (opts or {}).items():
+                st.set_option(k, v)
             self.st.append(st)
         limits = {st.fuse_limit() for st in self.st}
         assert len(limits) == 1, f"ranks disagree on the deepest pass: {limits}"
