@@ -258,6 +258,9 @@ def lib() -> C.CDLL:
         "csim_obs_network_impact_capture": (i, [vp, i]),
         "csim_ensemble_obs_impact": (i, [vp, vp, dp, dp, C.POINTER(CsimObsImpactSummary)]),
         "csim_obs_impact_fold": (i, [dp, C.c_long, dp]),
+        "csim_ensemble_assimilate_local": (i, [vp, vp, d, i, i, d]),
+        "csim_obs_network_local_info": (i, [vp, ip]),
+        "csim_obs_local_count": (i, [i, i, i, ip, ip, i, i, ip, ip]),
         "csim_ensemble_set_option": (i, [vp, C.c_char_p, C.c_long]),
         "csim_ensemble_get_option": (i, [vp, C.c_char_p, C.POINTER(C.c_long)]),
         "csim_ensemble_plan": (i, [i, i, i, i, ip]),
@@ -940,6 +943,22 @@ def impact_weight(mean_a, mean_b, truth) -> np.ndarray:
     return w
 
 
+LOCAL_MAX_OBS, LOCAL_MAX_DOUBLES, LOCAL_MAX_PRIOR_DOUBLES = 64, 4096, 1 << 26  # CSIM_LOCAL_MAX_*
+
+
+def obs_local_count(nx, ny, i, j, lx, ly):
+    """(count, max_local): per interior cell, (ny, nx), the observations at the cells (i, j) whose window rectangle of
+    half-widths lx, ly, clipped to the interior, contains it, and the largest of them: the bound that
+    Ensemble.assimilate_local() holds against LOCAL_MAX_OBS (csim_obs_local_count) — host only"""
+    ii = _ints(i)
+    jj = _ints(j, len(ii))
+    count = np.zeros((int(ny), int(nx)), dtype=np.int32)
+    most = C.c_int()
+    _ck(lib().csim_obs_local_count(int(nx), int(ny), len(ii), _ip(ii), _ip(jj), int(lx), int(ly),
+                                   count.ctypes.data_as(C.POINTER(C.c_int)), C.byref(most)))
+    return count, most.value
+
+
 class ObsNetwork:
     """observations that live on the device (csim_obs_network_*): planned once, their values drawn on the GPU
     from a member or set from the host, read by Ensemble.assimilate_network without staging.  Point observations of
@@ -987,6 +1006,13 @@ class ObsNetwork:
         """taps of all observations of a linear network, 0 for point observations (csim_obs_network_taps)"""
         v = C.c_int()
         _ck(lib().csim_obs_network_taps(self._h, C.byref(v)))
+        return v.value
+
+    def local_info(self) -> int:
+        """max_local: the most window rectangles of the network over one cell, which Ensemble.assimilate_local() holds
+        against LOCAL_MAX_OBS and, times the forecast members, LOCAL_MAX_DOUBLES (csim_obs_network_local_info)"""
+        v = C.c_int()
+        _ck(lib().csim_obs_network_local_info(self._h, C.byref(v)))
         return v.value
 
     def set_values(self, y):
@@ -1339,6 +1365,16 @@ class Ensemble:
             _ck(lib().csim_ensemble_assimilate_network(self._h, net._h, float(inflation), tm, rec))
         else:
             _ck(lib().csim_ensemble_assimilate_screened(self._h, net._h, float(inflation), tm, rec, float(screen)))
+
+    def assimilate_local(self, net: ObsNetwork, inflation=1.0, truth_member=None, record=False, screen=None):
+        """the local analysis with the network's observations, always enqueued: every cell from all used observations
+        near it, R-localised, in input order, in one pass whatever the network (csim_ensemble_assimilate_local).
+        inflation, truth_member, record and screen as in assimilate_network; CsimError (unsupported) beyond
+        LOCAL_MAX_OBS windows over one cell, see net.local_info()"""
+        tm = -1 if truth_member is None else int(truth_member)
+        rec = record if isinstance(record, int) else int(bool(record))
+        _ck(lib().csim_ensemble_assimilate_local(self._h, net._h, float(inflation), tm, rec,
+                                                 0.0 if screen is None else float(screen)))
 
     def obs_impact(self, net: ObsNetwork, weight) -> ObsImpact:
         """the forecast impact J_o of every observation of net's captured analysis on the error of the current

@@ -153,6 +153,43 @@ void assim_batches(int nx, int ny, const AssimPlan& p, int batch, std::vector<As
         }
 }
 
+bool local_tiles_build(int nx, int ny, const AssimPlan& p, int tile, LocalTiles* out) {
+    const int ntx = (nx + tile - 1) / tile, nty = (ny + tile - 1) / tile;
+    const size_t nt = static_cast<size_t>(ntx) * nty;
+    // the tiles that the clipped rectangle of the observation at (i, j) meets
+    struct Span {
+        int x0, x1, y0, y1;
+    };
+    auto span = [&](int i, int j) {
+        const long long i0 = std::max(1LL, static_cast<long long>(i) - p.lx), i1 = std::min<long long>(nx, static_cast<long long>(i) + p.lx);
+        const long long j0 = std::max(1LL, static_cast<long long>(j) - p.ly), j1 = std::min<long long>(ny, static_cast<long long>(j) + p.ly);
+        return Span{static_cast<int>((i0 - 1) / tile), static_cast<int>((i1 - 1) / tile), static_cast<int>((j0 - 1) / tile),
+                    static_cast<int>((j1 - 1) / tile)};
+    };
+    std::vector<long long> cnt(nt + 1, 0);
+    for (int q = 0; q < p.nobs; ++q) {
+        const Span s = span(p.pi[q], p.pj[q]);
+        for (int ty = s.y0; ty <= s.y1; ++ty)
+            for (int tx = s.x0; tx <= s.x1; ++tx) ++cnt[static_cast<size_t>(ty) * ntx + tx + 1];
+    }
+    for (size_t t = 0; t < nt; ++t) cnt[t + 1] += cnt[t];
+    if (cnt[nt] > 0x7fffffffLL) return false;
+    out->tile = tile, out->ntx = ntx, out->nty = nty;
+    out->start.assign(cnt.begin(), cnt.end());
+    out->pos.resize(static_cast<size_t>(cnt[nt]));
+    // in input order, so that every tile's list comes out sorted by input index
+    std::vector<int> at(p.nobs);
+    for (int q = 0; q < p.nobs; ++q) at[p.idx[q]] = q;
+    std::vector<int> fill(out->start.begin(), out->start.end() - 1);
+    for (int o = 0; o < p.nobs; ++o) {
+        const int q = at[o];
+        const Span s = span(p.pi[q], p.pj[q]);
+        for (int ty = s.y0; ty <= s.y1; ++ty)
+            for (int tx = s.x0; tx <= s.x1; ++tx) out->pos[fill[static_cast<size_t>(ty) * ntx + tx]++] = q;
+    }
+    return true;
+}
+
 }  // namespace csim
 
 extern "C" {
@@ -178,6 +215,39 @@ int csim_ensemble_assim_plan(int nobs, const int* i, const int* j, int lx, int l
     if (nobs > CSIM_ASSIM_MAX_OBS)
         return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assim_plan: at most 2^20 observations");
     *nlevels = assim_levels(nobs, i, j, lx, ly, ordered == 1, level);
+    return CSIM_OK;
+}
+
+int csim_obs_local_count(int nx, int ny, int nobs, const int* i, const int* j, int lx, int ly, int* count,
+                         int* max_local) {
+    OBS_REQUIRE(nx >= 1 && ny >= 1, "empty grid");
+    OBS_REQUIRE(nobs >= 0, "nobs must be >= 0");
+    OBS_REQUIRE(nobs == 0 || (i && j), "null array");
+    OBS_REQUIRE(lx >= 0 && ly >= 0, "lx and ly must be >= 0");
+    for (int o = 0; o < nobs; ++o)
+        OBS_REQUIRE(i[o] >= 1 && i[o] <= nx && j[o] >= 1 && j[o] <= ny, "observation outside the interior");
+    // a 2-D difference array with one spare row and column: +1 at the rectangle's first corner, -1 past its ends
+    const size_t w = static_cast<size_t>(nx) + 1;
+    std::vector<int> d(w * (static_cast<size_t>(ny) + 1), 0);
+    for (int o = 0; o < nobs; ++o) {
+        const size_t i0 = static_cast<size_t>(std::max(1LL, static_cast<long long>(i[o]) - lx)) - 1;
+        const size_t i1 = static_cast<size_t>(std::min<long long>(nx, static_cast<long long>(i[o]) + lx));
+        const size_t j0 = static_cast<size_t>(std::max(1LL, static_cast<long long>(j[o]) - ly)) - 1;
+        const size_t j1 = static_cast<size_t>(std::min<long long>(ny, static_cast<long long>(j[o]) + ly));
+        ++d[j0 * w + i0], --d[j0 * w + i1], --d[j1 * w + i0], ++d[j1 * w + i1];
+    }
+    int most = 0;
+    for (size_t b = 0; b < static_cast<size_t>(ny); ++b)
+        for (size_t a = 0; a < static_cast<size_t>(nx); ++a) {
+            long long v = d[b * w + a];  // at most nobs, its parts up to twice that
+            if (a) v += d[b * w + a - 1];
+            if (b) v += d[(b - 1) * w + a];
+            if (a && b) v -= d[(b - 1) * w + a - 1];
+            d[b * w + a] = static_cast<int>(v);
+            most = std::max(most, static_cast<int>(v));
+            if (count) count[b * static_cast<size_t>(nx) + a] = static_cast<int>(v);
+        }
+    if (max_local) *max_local = most;
     return CSIM_OK;
 }
 

@@ -31,4 +31,15 @@ struct AssimBatch {
 // the launches of a plan on an nx x ny grid: no batch crosses a level or holds more than `batch` observations
 void assim_batches(int nx, int ny, const AssimPlan& p, int batch, std::vector<AssimBatch>* out);
 
+// The lookup of the local analysis (csim_ensemble_assimilate_local): the interior cut into tiles of tile x tile cells
+// (the last ones of a row or column clipped by the domain), ntx x nty of them, row-major.  Tile T holds
+// pos[start[T] .. start[T + 1]): the plan positions of the observations whose window rectangle, clipped to the
+// interior, meets the tile, sorted by input index.
+struct LocalTiles {
+    int tile = 0, ntx = 0, nty = 0;
+    std::vector<int> start, pos;
+};
+// false: more than 2^31 - 1 entries (nothing is built)
+bool local_tiles_build(int nx, int ny, const AssimPlan& p, int tile, LocalTiles* out);
+
 }  // namespace csim

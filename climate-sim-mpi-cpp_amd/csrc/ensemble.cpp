@@ -312,6 +312,12 @@ int csim_ensemble_set_option(csim_ensemble* e, const char* key, long value) {
     } else if (k == "perturb_member_shares") {
         CSIM_REQUIRE(value >= 0 && value <= 65535, "perturb_member_shares must be 0 (automatic) or 1 .. 65535");
         e->perturb.member_shares = static_cast<int>(value);
+    } else if (k == "local_tile") {
+        CSIM_REQUIRE(value == 0 || value == 4 || value == 8 || value == 16, "local_tile must be 0 (automatic), 4, 8 or 16");
+        e->local.tile = static_cast<int>(value);
+    } else if (k == "local_pack") {
+        CSIM_REQUIRE(value >= 0 && value <= 64, "local_pack must be 0 (automatic) or 1 .. 64");
+        e->local.pack = static_cast<int>(value);
     } else if (k == "depth_used") {
         return fail(CSIM_ERR_ARG, "option depth_used is read-only");
     } else if (k == "contract") {
@@ -339,6 +345,10 @@ int csim_ensemble_get_option(const csim_ensemble* e, const char* key, long* valu
         *value = e->perturb.tile_rows;
     else if (k == "perturb_member_shares")
         *value = e->perturb.member_shares;
+    else if (k == "local_tile")
+        *value = e->local.tile;
+    else if (k == "local_pack")
+        *value = e->local.pack;
     else if (k == "contract")
         return fail(CSIM_ERR_UNSUPPORTED, "an ensemble is always bit-identical: no contract mode");
     else

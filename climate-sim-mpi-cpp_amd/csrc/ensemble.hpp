@@ -206,6 +206,27 @@ hipError_t ens_launch_impact_capture(const EnsGeom& g, const double* f, const As
 // J_o of every observation, by input index, from the members at verification time
 hipError_t ens_launch_obs_impact(const EnsGeom& g, const double* f, const ImpactArgs& a, double* out, hipStream_t st);
 
+// the local analysis of csim_ensemble_assimilate_local (ensemble_local.hip): the observation priors h_{o,k} of the used
+// observations (one wave per observation, `prior`: M doubles per plan position), then the cell pass, one wave per
+// `pack` cells of one tile of the host's lookup (LocalTiles of assim_plan.hpp, on the device).  The AssimArgs as for
+// ens_launch_assim_post, with `status` where the analysis is screened.
+constexpr int LOCAL_MAX_OBS = 64;        // CSIM_LOCAL_MAX_OBS
+constexpr int LOCAL_MAX_DOUBLES = 4096;  // CSIM_LOCAL_MAX_DOUBLES
+struct LocalArgs {
+    int tile, ntx, nty;           // tiles of tile x tile cells, ntx x nty of them
+    int lmax;                     // the network's max_local: a cell's lanes are lmax + 1
+    int pack;                     // cells per wave, from ens_local_pack
+    const int* cstart;            // per tile, one more than tiles: its entries are cpos[cstart[T]] .. cpos[cstart[T + 1] - 1]
+    const int* cpos;              // plan positions, sorted by input index within a tile
+    const double* prior;          // M per plan position: h_{o,k}
+};
+// cells per wave for M forecast members and max_local = lmax: `want` (0: as many as fit) cut to what the lanes of a
+// wave and its LDS hold, at least 1
+int ens_local_pack(int M, int lmax, int want);
+hipError_t ens_launch_local_prior(const EnsGeom& g, const double* f, const AssimArgs& a, int nobs, double* prior,
+                                  hipStream_t st);
+hipError_t ens_launch_local_update(const EnsGeom& g, double* f, const AssimArgs& a, const LocalArgs& l, hipStream_t st);
+
 // the perturbation of csim_ensemble_perturb (ensemble_perturb.hip), one launch: x_k += sigma p_k on every interior
 // cell of the forecast members, p_k the white noise of ensemble_noise.hpp smoothed with the host's taps along x, then
 // along y (csim_ensemble_perturb_taps; tx[o + rx], ty[o + ry]), less its mean over the members when centered

@@ -86,6 +86,10 @@ struct csim_ensemble {
     struct Perturb {
         int tile_rows = 0, member_shares = 0;  // options perturb_tile_rows, perturb_member_shares; 0: automatic
     } perturb;
+    // the local analysis (csim_ensemble_assimilate_local): no storage of the ensemble's, its two launch options
+    struct Local {
+        int tile = 0, pack = 0;  // options local_tile, local_pack; 0: automatic
+    } local;
     // relaxation (csim_ensemble_prior_capture / csim_ensemble_relax).  A capture lives in the handle's own storage, so
     // that no call that writes the ping-pong buffers touches it: sqrt(v_b) per interior cell (RTPS), a copy of the
     // current buffer (RTPP, allocated at the first such capture), and the factor field of a call that asks for it

@@ -7,6 +7,9 @@
 // The forecast impact (csim_obs_network_impact_capture, csim_ensemble_obs_impact; kernels in ensemble_impact.hip) keeps
 // a capture in storage of the network's own, made at the first capture: a_k per observation, dn and the status bytes,
 // and a device copy of the caller's weight; nothing that an analysis, observe or set_values writes.
+// The local analysis (csim_ensemble_assimilate_local; kernels in ensemble_local.hip) shares the checks, the screening
+// and the recording of the serial one (analysis_check, analysis_begin, analysis_record) and differs in what runs between
+// them; its lookup and the observation priors are storage of the network's own, made at the first local analysis.
 #include <cmath>
 #include <memory>
 #include <new>
@@ -72,6 +75,16 @@ struct csim_obs_network : AssimPlan {   // the plan: nobs, nlevels, lx, ly, off,
         int M = 0, t = 0;               // its forecast members: M of them, member t left out (t = B: none)
         void release() { pert.release(), aux.release(), w.release(), wstage.release(); }
     } imp;
+    // the local analysis (csim_ensemble_assimilate_local), made at the first one and kept until destroy
+    struct Local {
+        int max_local = -1;             // the most window rectangles over one cell (-1: not counted yet)
+        DeviceBuf prior;                // M doubles per plan position: h_{o,k}
+        DeviceBuf tiles;                // the lookup (LocalTiles): its starts, then its plan positions
+        Staging stage;
+        int tile = 0, ntx = 0, nty = 0; // of the lookup on the device (tile 0: none)
+        size_t pos_at = 0;              // where the plan positions start, bytes
+        void release() { prior.release(), tiles.release(), stage.release(); }
+    } loc;
     size_t imp_dn() const { return 0; }
     size_t imp_out() const { return up(sizeof(double) * nobs); }
     size_t imp_snap() const { return 2 * up(sizeof(double) * nobs); }
@@ -87,7 +100,7 @@ struct csim_obs_network : AssimPlan {   // the plan: nobs, nlevels, lx, ly, off,
         if (ntaps) a.tstart = at<int>(l.tstart), a.toff = at<int>(l.toff), a.tw = at<double>(l.tw);
         return a;
     }
-    ~csim_obs_network() { dev.release(), stage.release(), mstage.release(), imp.release(); }
+    ~csim_obs_network() { dev.release(), stage.release(), mstage.release(), imp.release(), loc.release(); }
 };
 
 void csim_ensemble::Obs::release() {
@@ -204,6 +217,95 @@ int network_create(csim_ensemble* e, int nobs, const int* i, const int* j, const
     }
 }
 
+// What csim_ensemble_assimilate_screened and csim_ensemble_assimilate_local share.  The argument and state checks, in
+// the order they fire; M forecast members without member t
+int analysis_check(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member, int record, double tol,
+                   int* M, int* t) {
+    CSIM_REQUIRE(e, "null ensemble");
+    CSIM_REQUIRE(n, "null network");
+    CSIM_REQUIRE(n->e == e, "the network belongs to another ensemble");
+    CSIM_REQUIRE(std::isfinite(inflation) && inflation >= 1.0, "inflation must be finite and >= 1");
+    CSIM_TRY(forecast_split(e->g.members, truth_member, M, t, 2, "the analysis needs at least two forecast members",
+                            ASSIM_MAX_MEMBERS, "csim_ensemble_assimilate_network: at most 1024 forecast members"));
+    CSIM_REQUIRE(record == 0 || record == 1, "record must be 0 or 1");
+    CSIM_REQUIRE(std::isfinite(tol) && tol >= 0, "tol must be finite and >= 0");
+    if (!n->has_values)
+        return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_network: the network has no values yet "
+                                    "(csim_obs_network_set_values or csim_obs_network_observe)");
+    if (record && n->cycles >= n->log_cycles)
+        return fail(CSIM_ERR_STATE, n->log_cycles ? "csim_ensemble_assimilate_network: the log is full"
+                                                  : "csim_ensemble_assimilate_network: the network has no log");
+    return CSIM_OK;
+}
+
+// an analysis between its screening and its record
+struct Analysis {
+    ObsArgs oa;
+    AssimArgs a;       // `status` set where the analysis is screened
+    ObsScreen s;
+    bool screen;
+    const double* f;   // the current buffer
+};
+
+// the first launches of an analysis: (hb, vb) where they are wanted and the status bytes where something is screened;
+// sets the network's flags
+int analysis_begin(csim_ensemble* e, csim_obs_network* n, int M, int t, int record, double tol, Analysis* x) {
+    x->oa = n->args();
+    const ObsArgs& oa = x->oa;
+    x->a = assim_args(M, t, *n, n->at<double>(n->l.rho), {oa.i, oa.j, oa.idx, oa.y, oa.r}, n->at<double>(n->l.scal),
+                      n->at<double>(n->l.hp), nullptr, oa.tstart, oa.toff, oa.tw, n->tmax);
+    x->f = e->base(e->cur);
+    // (hb, vb): of a recorded analysis where fetch reads them, of an unrecorded background check where it does not
+    const bool check = tol > 0;
+    x->screen = check || n->masked;
+    double* bg = n->at<double>(record ? n->l.bg : n->l.sbg);
+    if (record || check) CSIM_HIP(ens_launch_assim_post(e->g, x->f, x->a, n->nobs, bg, e->st));
+    x->s = ObsScreen{};
+    if (x->screen) {
+        ObsScreen& s = x->s;
+        s.mask = n->masked ? n->at<unsigned char>(n->l.mask) : nullptr;
+        s.status = n->at<unsigned char>(n->l.status);
+        s.bg = bg, s.check = check ? 1 : 0, s.k2 = tol * tol;
+        s.cnt = n->at<int>(n->l.cnt);
+        CSIM_HIP(ens_launch_obs_screen(oa, s, e->st));
+        x->a.status = s.status;
+    }
+    n->analysed = true, n->screened = x->screen, n->last_recorded = record == 1;
+    return CSIM_OK;
+}
+
+// the last launches of a recorded analysis: (ha, va) and the cycle's records
+int analysis_record(csim_ensemble* e, csim_obs_network* n, const Analysis& x) {
+    CSIM_HIP(ens_launch_assim_post(e->g, x.f, x.a, n->nobs, n->at<double>(n->l.post), e->st));
+    double* slot = n->at<double>(n->l.log) + static_cast<size_t>(OBS_CYCLE_FIELDS) * n->cycles;
+    // the screen record of a cycle that is not screened is the (nobs, 0, 0) that create and log_reset put there
+    if (x.screen)
+        CSIM_HIP(ens_launch_obs_cycle_screened(x.oa, x.s, n->has_truth, slot, n->at<double>(n->l.slog) +
+                                               static_cast<size_t>(OBS_SCREEN_FIELDS) * n->cycles, e->st));
+    else
+        CSIM_HIP(ens_launch_obs_cycle(x.oa, n->has_truth, slot, e->st));
+    ++n->cycles;
+    n->has_diag = true;
+    return CSIM_OK;
+}
+
+// max_local of the network, counted once
+int local_max(csim_obs_network* n, int* max_local) {
+    if (n->loc.max_local < 0)
+        CSIM_TRY(csim_obs_local_count(n->e->g.nx, n->e->g.ny, n->nobs, n->pi.data(), n->pj.data(), n->lx, n->ly, nullptr,
+                                      &n->loc.max_local));
+    *max_local = n->loc.max_local;
+    return CSIM_OK;
+}
+
+// the tile of the lookup: the option, or 8 (64 cells fill the last wave of a tile better than 16 do, and a tile's
+// entries stay few), 4 on grids too small to give every SIMD a wave that way, 16 on very large ones
+int local_tile(const csim_ensemble* e) {
+    if (e->local.tile) return e->local.tile;
+    const long cells = static_cast<long>(e->g.nx) * e->g.ny;
+    return cells >= 2048L * 2048 ? 16 : cells >= 128L * 128 ? 8 : 4;
+}
+
 }  // namespace
 
 extern "C" {
@@ -316,57 +418,74 @@ int csim_ensemble_assimilate_network(csim_ensemble* e, csim_obs_network* n, doub
 
 int csim_ensemble_assimilate_screened(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
                                       int record, double tol) {
-    CSIM_REQUIRE(e, "null ensemble");
-    CSIM_REQUIRE(n, "null network");
-    CSIM_REQUIRE(n->e == e, "the network belongs to another ensemble");
-    const EnsGeom& g = e->g;
-    CSIM_REQUIRE(std::isfinite(inflation) && inflation >= 1.0, "inflation must be finite and >= 1");
     int M = 0, t = 0;
-    CSIM_TRY(forecast_split(g.members, truth_member, &M, &t, 2, "the analysis needs at least two forecast members",
-                            ASSIM_MAX_MEMBERS, "csim_ensemble_assimilate_network: at most 1024 forecast members"));
-    CSIM_REQUIRE(record == 0 || record == 1, "record must be 0 or 1");
-    CSIM_REQUIRE(std::isfinite(tol) && tol >= 0, "tol must be finite and >= 0");
-    if (!n->has_values)
-        return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_network: the network has no values yet "
-                                    "(csim_obs_network_set_values or csim_obs_network_observe)");
-    if (record && n->cycles >= n->log_cycles)
-        return fail(CSIM_ERR_STATE, n->log_cycles ? "csim_ensemble_assimilate_network: the log is full"
-                                                  : "csim_ensemble_assimilate_network: the network has no log");
+    CSIM_TRY(analysis_check(e, n, inflation, truth_member, record, tol, &M, &t));
     if (n->batches_m != M) {
-        assim_batches(g.nx, g.ny, *n, assim_batch_size(M), &n->batches);
+        assim_batches(e->g.nx, e->g.ny, *n, assim_batch_size(M), &n->batches);
         n->batches_m = M;
     }
-    const ObsArgs oa = n->args();
-    AssimArgs a = assim_args(M, t, *n, n->at<double>(n->l.rho), {oa.i, oa.j, oa.idx, oa.y, oa.r}, n->at<double>(n->l.scal),
-                             n->at<double>(n->l.hp), nullptr, oa.tstart, oa.toff, oa.tw, n->tmax);
-    const double* f = e->base(e->cur);
-    // (hb, vb): of a recorded analysis where fetch reads them, of an unrecorded background check where it does not
-    const bool check = tol > 0, screen = check || n->masked;
-    double* bg = n->at<double>(record ? n->l.bg : n->l.sbg);
-    if (record || check) CSIM_HIP(ens_launch_assim_post(g, f, a, n->nobs, bg, e->st));
-    ObsScreen s{};
-    if (screen) {
-        s.mask = n->masked ? n->at<unsigned char>(n->l.mask) : nullptr;
-        s.status = n->at<unsigned char>(n->l.status);
-        s.bg = bg, s.check = check ? 1 : 0, s.k2 = tol * tol;
-        s.cnt = n->at<int>(n->l.cnt);
-        CSIM_HIP(ens_launch_obs_screen(oa, s, e->st));
-        a.status = s.status;
+    Analysis x;
+    CSIM_TRY(analysis_begin(e, n, M, t, record, tol, &x));
+    CSIM_TRY(assim_enqueue(e, x.a, inflation, n->batches));
+    return record ? analysis_record(e, n, x) : CSIM_OK;
+}
+
+int csim_ensemble_assimilate_local(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
+                                   int record, double tol) {
+    int M = 0, t = 0, lmax = 0;
+    CSIM_TRY(analysis_check(e, n, inflation, truth_member, record, tol, &M, &t));
+    const EnsGeom& g = e->g;
+    CSIM_TRY(local_max(n, &lmax));
+    if (lmax > CSIM_LOCAL_MAX_OBS)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_local: more than CSIM_LOCAL_MAX_OBS observation "
+                                          "windows over one cell");
+    if (static_cast<long>(lmax) * M > CSIM_LOCAL_MAX_DOUBLES)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_local: the windows over one cell times the forecast "
+                                          "members exceed CSIM_LOCAL_MAX_DOUBLES");
+    const size_t doubles = static_cast<size_t>(n->nobs) * M;
+    if (doubles > static_cast<size_t>(CSIM_LOCAL_MAX_PRIOR_DOUBLES))
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_local: nobs times the forecast members exceeds "
+                                          "CSIM_LOCAL_MAX_PRIOR_DOUBLES");
+    csim_obs_network::Local& x = n->loc;
+    const int tile = local_tile(e);
+    try {
+        // the lookup for this tile, made and uploaded when the tile is another one than the last
+        if (x.tile != tile) {
+            LocalTiles lt;
+            if (!local_tiles_build(g.nx, g.ny, *n, tile, &lt))
+                return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_local: the lookup exceeds 2^31 entries");
+            const size_t pos_at = up(sizeof(int) * lt.start.size()), bytes = up(pos_at + sizeof(int) * lt.pos.size());
+            void* staged = nullptr;
+            CSIM_TRY(x.stage.acquire(bytes, &staged));
+            std::copy(lt.start.begin(), lt.start.end(), buf_at<int>(staged, 0));
+            std::copy(lt.pos.begin(), lt.pos.end(), buf_at<int>(staged, pos_at));
+            x.tile = 0;  // from here on the last lookup is being replaced (after its readers)
+            CSIM_TRY(x.tiles.reserve(bytes, e->st));
+            CSIM_TRY(x.stage.send(x.tiles.p, bytes, e->st));
+            x.tile = tile, x.ntx = lt.ntx, x.nty = lt.nty, x.pos_at = pos_at;
+        }
+    } catch (const std::bad_alloc&) {
+        return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_local: out of host memory");
     }
-    n->analysed = true, n->screened = screen, n->last_recorded = record == 1;
-    CSIM_TRY(assim_enqueue(e, a, inflation, n->batches));
-    if (!record) return CSIM_OK;
-    CSIM_HIP(ens_launch_assim_post(g, f, a, n->nobs, n->at<double>(n->l.post), e->st));
-    double* slot = n->at<double>(n->l.log) + static_cast<size_t>(OBS_CYCLE_FIELDS) * n->cycles;
-    // the screen record of a cycle that is not screened is the (nobs, 0, 0) that create and log_reset put there
-    if (screen)
-        CSIM_HIP(ens_launch_obs_cycle_screened(oa, s, n->has_truth, slot, n->at<double>(n->l.slog) +
-                                               static_cast<size_t>(OBS_SCREEN_FIELDS) * n->cycles, e->st));
-    else
-        CSIM_HIP(ens_launch_obs_cycle(oa, n->has_truth, slot, e->st));
-    ++n->cycles;
-    n->has_diag = true;
-    return CSIM_OK;
+    CSIM_TRY(x.prior.reserve(sizeof(double) * doubles, e->st));
+    Analysis an;
+    CSIM_TRY(analysis_begin(e, n, M, t, record, tol, &an));
+    double* f = e->base(e->cur);
+    if (inflation != 1.0) CSIM_HIP(ens_launch_assim_inflate(g, f, M, t, inflation - 1.0, e->st));
+    LocalArgs l{};
+    l.tile = x.tile, l.ntx = x.ntx, l.nty = x.nty, l.lmax = lmax;
+    l.pack = ens_local_pack(M, lmax, e->local.pack);
+    l.cstart = buf_at<int>(x.tiles.p, 0), l.cpos = buf_at<int>(x.tiles.p, x.pos_at);
+    l.prior = x.prior.as();
+    CSIM_HIP(ens_launch_local_prior(g, f, an.a, n->nobs, x.prior.as(), e->st));
+    CSIM_HIP(ens_launch_local_update(g, f, an.a, l, e->st));
+    return record ? analysis_record(e, n, an) : CSIM_OK;
+}
+
+int csim_obs_network_local_info(csim_obs_network* n, int* max_local) {
+    CSIM_REQUIRE(n, "null network");
+    CSIM_REQUIRE(max_local, "null argument");
+    return local_max(n, max_local);
 }
 
 int csim_obs_network_impact_capture(csim_obs_network* n, int truth_member) {

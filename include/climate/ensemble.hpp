@@ -167,6 +167,13 @@ public:
     // keeps what Ensemble::obs_impact() needs of the last analysis, which must be a recorded one (see
     // csim_obs_network_impact_capture); t as in Ensemble::assimilate.  Enqueued; valid across run() until the next capture
     void impact_capture(int t = -1) { check(csim_obs_network_impact_capture(handle(), t)); }
+    // the most window rectangles of the network over one cell, which Ensemble::assimilate_local() holds against
+    // CSIM_LOCAL_MAX_OBS (see csim_obs_network_local_info)
+    int local_info() {
+        int most = 0;
+        check(csim_obs_network_local_info(handle(), &most));
+        return most;
+    }
 
 private:
     friend class Ensemble;
@@ -447,6 +454,13 @@ public:
     // (y - hb)^2 > screen_tol^2 (vb + r); the network's active mask acts either way
     void assimilate(ObsNetwork& net, double inflation = 1.0, int t = -1, bool record = false, double screen_tol = 0.0) {
         check(csim_ensemble_assimilate_screened(h_, net.handle(), inflation, t, record ? 1 : 0, screen_tol));
+    }
+    // the local analysis with the network's observations, always enqueued: every cell from all used observations near
+    // it, R-localised, in input order, one pass whatever the network (see csim_ensemble_assimilate_local); the
+    // arguments as for assimilate(ObsNetwork&, ...)
+    void assimilate_local(ObsNetwork& net, double inflation = 1.0, int t = -1, bool record = false,
+                          double screen_tol = 0.0) {
+        check(csim_ensemble_assimilate_local(h_, net.handle(), inflation, t, record ? 1 : 0, screen_tol));
     }
     // the forecast impact of every observation of net's captured analysis on the error of the current state (EFSOI, see
     // csim_ensemble_obs_impact); weight = C (e_a + e_b), member_size() values of which the interior is read.  Synchronous

@@ -872,6 +872,60 @@ int csim_obs_network_impact_capture(csim_obs_network* n, int truth_member);
 int csim_ensemble_obs_impact(csim_ensemble* e, csim_obs_network* n, const double* weight, double* out_impact,
                              csim_obs_impact_summary* summary);
 int csim_obs_impact_fold(const double* u, long n, double* S);
+/* local analysis: every interior cell is analysed on its own from all observations of a network near it, with the
+ * localisation applied to the observation error (R-localisation; Hunt et al. 2007, the LETKF).  Cells are independent,
+ * so a call is one pass over the observations and one over the cells whatever the network: the levels of the plan play
+ * no part, and the result does not depend on them.  With the diagonal observation errors of this library, taking a
+ * cell's local observations one at a time and carrying the local observation priors that are still to come along is the
+ * Kalman update with R_loc = diag(r_o / rho_o(c)): the analysis mean and variance at the cell are the LETKF's in exact
+ * arithmetic, and independent of the order of the observations.  Only + - * / sqrt: fp64 IEEE, no FMA contraction,
+ * every product rounded, every sum a running sum from +0 in member order k = 0 .. M-1.
+ * assimilate_local: forecast members, truth_member, inflation, record and tol (0: no background check) as in
+ *   csim_ensemble_assimilate_screened; the call only enqueues on the ensemble's stream.  Point and linear networks.
+ *   1. Screening: the status bytes exactly as in csim_ensemble_assimilate_screened, (hb, vb) from the state before the
+ *      inflation.  The used observations are those with status CSIM_OBS_USED (all, when nothing is screened).
+ *   2. Inflation: lambda != 1 as in csim_ensemble_assimilate, on every interior cell.
+ *   3. Observation priors: for every used observation o and forecast member k, h_{o,k} = the operator value from the
+ *      inflated state: the observed cell of a point observation (its bits), sum_s w_s x_k(anchor + tap s) of a linear
+ *      one as in csim_obs_network_create_linear.
+ *   4. Cell pass: for every interior cell c = (i_c, j_c), L(c) = the used observations o with |i_c - i_o| <= lx,
+ *      |j_c - j_o| <= ly, rho_o(c) = rho[j_c - j_o + ly][i_c - i_o + lx] > 0 and r_o / rho_o(c) finite, taken in
+ *      increasing input index.  With z_k = x_k(c) and private copies w_{o,k} = h_{o,k}:
+ *
+ *          for o in L(c), in order:
+ *              re = r_o / rho_o(c)
+ *              hbar = (sum_k w_{o,k}) / M;   h'_k = w_{o,k} - hbar;   p = (sum_k h'_k h'_k) / (M-1)
+ *              d = p + re;   alpha = 1 / (1 + sqrt(re / d));   delta = y_o - hbar
+ *              for the target v = z, and then v = w_q for every q in L(c) after o:
+ *                  vbar = (sum_k v_k) / M;   v'_k = v_k - vbar;   cov = (sum_k v'_k h'_k) / (M-1)
+ *                  g = cov / d;   beta = alpha g;   v_k <- v_k + (g delta - beta h'_k)
+ *          x_k(c) <- z_k
+ *
+ *      A cell with empty L(c) is not written and keeps its bits.  Ghost rings, the other ping-pong buffer and member t
+ *      are never touched.  At the cell of a lone point observation rho = 1 and the members are those of
+ *      csim_ensemble_assimilate bit for bit.
+ *   5. record = 1 appends the two log records of csim_ensemble_assimilate_screened, with
+ *      (ha, va) taken after the cell pass, and leaves the network in the same "last analysis was recorded" state:
+ *      fetch, log, screen_log, status and impact_capture behave as after a recorded serial analysis.
+ *   Limits (resource bounds of the cell pass): with max_local = the largest number of observations whose window
+ *   rectangle, clipped to the interior, contains one cell (masks and rho ignored), max_local <= CSIM_LOCAL_MAX_OBS,
+ *   max_local M <= CSIM_LOCAL_MAX_DOUBLES (32 KiB of private priors per cell) and nobs M <=
+ *   CSIM_LOCAL_MAX_PRIOR_DOUBLES; beyond them CSIM_ERR_UNSUPPORTED (also where the lookup of step 4 would exceed 2^31
+ *   entries).  The other errors are those of csim_ensemble_assimilate_screened, in its order and first.  Every error is
+ *   raised before anything is enqueued and leaves members, values, mask, logs and diagnostics as they were.
+ * local_info: *max_local of the network, computed at the first call and kept.
+ * local_count (host-only, needs no device): the rectangle count above for nobs >= 0 observations at interior cells
+ *   (i, j) with half-widths lx, ly >= 0 (either may exceed the grid): count (may be NULL) gets ny x nx values,
+ *   row-major, cell (i, j) at (j - 1) nx + (i - 1); *max_local (may be NULL) their maximum, 0 without observations.
+ *   CSIM_ERR_ARG for nx or ny < 1, nobs < 0, lx or ly < 0, a null array with nobs > 0, a cell outside the interior. */
+#define CSIM_LOCAL_MAX_OBS 64
+#define CSIM_LOCAL_MAX_DOUBLES 4096
+#define CSIM_LOCAL_MAX_PRIOR_DOUBLES (1L << 26)
+int csim_ensemble_assimilate_local(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
+                                   int record, double tol);
+int csim_obs_network_local_info(csim_obs_network* n, int* max_local);
+int csim_obs_local_count(int nx, int ny, int nobs, const int* i, const int* j, int lx, int ly, int* count,
+                         int* max_local);
 /* options (unknown keys: CSIM_ERR_ARG; "contract": CSIM_ERR_UNSUPPORTED), results never depend on them:
  *   "fuse"        -1 (default) passes of the ensemble depth where the grid allows; 0 / 1 single steps only
  *   "fused_2c"    0/1 (default 1), as for csim_stepper_set_option
@@ -883,7 +937,11 @@ int csim_obs_impact_fold(const double* u, long n, double* S);
  *   "perturb_tile_rows"     0 (default: chosen from the grid and M), 8 or 32: interior rows per workgroup tile of
  *                           csim_ensemble_perturb; any other value is CSIM_ERR_ARG
  *   "perturb_member_shares" 0 (default: chosen from the tiles and M) or 1 .. 65535: workgroups that share the forecast
- *                           members of one tile in that call (more than M: M) */
+ *                           members of one tile in that call (more than M: M)
+ *   "local_tile"            0 (default: chosen from the grid), 4, 8 or 16: cells per side of a tile of the lookup of
+ *                           csim_ensemble_assimilate_local; any other value is CSIM_ERR_ARG
+ *   "local_pack"            0 (default: as many as fit) or 1 .. 64: cells that one wave of that call's cell pass takes
+ *                           together (more than fit beside max_local observations each: as many as fit) */
 int csim_ensemble_set_option(csim_ensemble* e, const char* key, long value);
 int csim_ensemble_get_option(const csim_ensemble* e, const char* key, long* value);
 /* host-only pass planner of csim_ensemble_run: out[0] = steps per fused pass (1: none; members with nx or ny below
