@@ -261,6 +261,13 @@ def lib() -> C.CDLL:
         "csim_ensemble_assimilate_local": (i, [vp, vp, d, i, i, d]),
         "csim_obs_network_local_info": (i, [vp, ip]),
         "csim_obs_local_count": (i, [i, i, i, ip, ip, i, i, ip, ip]),
+        "csim_ensemble_gram": (i, [vp, i, i, dp]),
+        "csim_ensemble_gram_plan": (i, [i, i, i, C.POINTER(C.c_long), ip]),
+        "csim_ensemble_project": (i, [vp, i, i, i, dp, dp]),
+        "csim_ensemble_transform": (i, [vp, i, i, dp, dp]),
+        "csim_sym_eigen": (i, [i, dp, dp, dp, ip]),
+        "csim_ensemble_eofs": (i, [vp, i, i, dp, dp, dp, ip]),
+        "csim_ensemble_space_check": (i, [i] * 6),
         "csim_ensemble_set_option": (i, [vp, C.c_char_p, C.c_long]),
         "csim_ensemble_get_option": (i, [vp, C.c_char_p, C.POINTER(C.c_long)]),
         "csim_ensemble_plan": (i, [i, i, i, i, ip]),
@@ -959,6 +966,36 @@ def obs_local_count(nx, ny, i, j, lx, ly):
     return count, most.value
 
 
+ESPACE_MAX_MEMBERS, SYM_EIGEN_MAX_N, SYM_EIGEN_MAX_SWEEPS = 256, 256, 64  # CSIM_ESPACE_MAX_MEMBERS, CSIM_SYM_EIGEN_*
+
+SymEigen = collections.namedtuple("SymEigen", "lambda_ V sweeps")
+SymEigen.__doc__ = """eigenvalues (descending), eigenvectors (column r belongs to lambda_[r]) and the sweeps made"""
+EnsembleEOFs = collections.namedtuple("EnsembleEOFs", "lambda_ variance pcs patterns n_valid")
+EnsembleEOFs.__doc__ = """leading modes of an ensemble's spread: eigenvalues of the Gram matrix, variance = lambda_ /
+(M - 1), principal components (M, n_modes), patterns (n_modes, ny+2, nx+2) or None, and the number of modes that are
+not null"""
+
+
+def sym_eigen(A) -> SymEigen:
+    """eigenvalues and eigenvectors of a symmetric matrix by the cyclic Jacobi method, bit for bit the same for every
+    caller (csim_sym_eigen) — host only"""
+    a = np.ascontiguousarray(A, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] != a.shape[1]:
+        raise ValueError("A must be a square matrix")
+    n = a.shape[0]
+    lam, V, sweeps = np.empty(n), np.empty((n, n)), C.c_int()
+    _ck(lib().csim_sym_eigen(n, _dp(a), _dp(lam), _dp(V), C.byref(sweeps)))
+    return SymEigen(lam, V, sweeps.value)
+
+
+def ensemble_gram_plan(M: int, nx: int, ny: int):
+    """(nseg, Gc): the 64-cell segments of the interior and the classes whose partial sums Ensemble.gram() adds in
+    order (csim_ensemble_gram_plan) — host only"""
+    nseg, gc = C.c_long(), C.c_int()
+    _ck(lib().csim_ensemble_gram_plan(int(M), int(nx), int(ny), C.byref(nseg), C.byref(gc)))
+    return nseg.value, gc.value
+
+
 class ObsNetwork:
     """observations that live on the device (csim_obs_network_*): planned once, their values drawn on the GPU
     from a member or set from the host, read by Ensemble.assimilate_network without staging.  Point observations of
@@ -1414,6 +1451,57 @@ class Ensemble:
         out = np.empty((self.ny + 2, self.nx + 2)) if factor else None
         _ck(lib().csim_ensemble_relax(self._h, mode, float(alpha), tm, None if out is None else _dp(out)))
         return out
+
+    def _forecast(self, truth_member):
+        return -1 if truth_member is None else int(truth_member), self.members - (truth_member is not None)
+
+    def gram(self, truth_member=None, centered=True) -> np.ndarray:
+        """(M, M) Gram matrix of the forecast members over the interior, G[a, b] = sum over cells of p_a p_b, p the
+        perturbations from the per-cell mean (centered) or the members themselves; the same bits whatever the launch
+        geometry, symmetric bit for bit (csim_ensemble_gram)"""
+        tm, M = self._forecast(truth_member)
+        G = np.empty((max(M, 0), max(M, 0)))
+        _ck(lib().csim_ensemble_gram(self._h, tm, int(bool(centered)), _dp(G)))
+        return G
+
+    def project(self, W, truth_member=None, centered=True) -> np.ndarray:
+        """(K, ny+2, nx+2): out[r] = sum_k p_k W[k, r] on every cell, ghost ring included; W is (M, K) or (M,)
+        (csim_ensemble_project)"""
+        tm, M = self._forecast(truth_member)
+        w = np.ascontiguousarray(W, dtype=np.float64)
+        if w.ndim == 1:
+            w = np.ascontiguousarray(w[:, None])
+        if w.ndim != 2 or w.shape[0] != M:
+            raise ValueError(f"W must have {M} rows")
+        out = np.empty((w.shape[1], self.ny + 2, self.nx + 2))
+        _ck(lib().csim_ensemble_project(self._h, tm, int(bool(centered)), w.shape[1], _dp(w), _dp(out)))
+        return out
+
+    def transform(self, W, wbar=None, truth_member=None, centered=True):
+        """replaces the forecast members on the interior by x'_r = m' + sum_k p_k W[k, r], m' = m + sum_k p_k wbar[k]
+        (centered; without wbar m' = m), or by x'_r = sum_k x_k W[k, r] (not centered: a 0/1 selection matrix copies
+        or resamples members exactly); W is (M, M).  Enqueued without waiting, W and wbar may be reused at once
+        (csim_ensemble_transform)"""
+        tm, M = self._forecast(truth_member)
+        w = np.ascontiguousarray(W, dtype=np.float64)
+        if w.shape != (M, M):
+            raise ValueError(f"W must have shape {(M, M)}")
+        wb = None if wbar is None else np.ascontiguousarray(wbar, dtype=np.float64)
+        if wb is not None and wb.shape != (M,):
+            raise ValueError(f"wbar must have shape {(M,)}")
+        _ck(lib().csim_ensemble_transform(self._h, tm, int(bool(centered)), _dp(w), None if wb is None else _dp(wb)))
+
+    def eofs(self, n_modes, truth_member=None, patterns=True) -> EnsembleEOFs:
+        """the n_modes leading EOFs of the forecast members' spread: centered gram(), sym_eigen() and project()
+        composed in the library (csim_ensemble_eofs)"""
+        tm, M = self._forecast(truth_member)
+        K = int(n_modes)
+        lam, pcs = np.empty(max(K, 0)), np.empty((max(M, 0), max(K, 0)))
+        pat = np.empty((max(K, 0), self.ny + 2, self.nx + 2)) if patterns else None
+        nv = C.c_int()
+        _ck(lib().csim_ensemble_eofs(self._h, tm, K, _dp(lam), _dp(pcs), None if pat is None else _dp(pat),
+                                     C.byref(nv)))
+        return EnsembleEOFs(lam, lam / (M - 1), pcs, pat, nv.value)
 
     def set_option(self, key: str, value: int):
         _ck(lib().csim_ensemble_set_option(self._h, key.encode(), int(value)))

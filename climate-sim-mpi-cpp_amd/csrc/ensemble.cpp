@@ -12,6 +12,8 @@
 //                      (prior capture, relax); the plan, the Gaspari-Cohn table and the taps: assim_plan.cpp, without HIP
 //   ensemble_obs.cpp   observation networks: create / destroy, values from the host or from a member, the analysis that
 //                      reads a network, its diagnostics and log
+//   ensemble_space.cpp ensemble space: Gram matrix, projection, transform and EOFs; the eigensolver: sym_eigen.cpp,
+//                      without HIP
 #include <cmath>
 #include <string>
 #include <vector>
@@ -146,6 +148,7 @@ int csim_ensemble_destroy(csim_ensemble* e) {
     e->spatial.release();
     e->assim.release();
     e->relax.release();
+    e->espace.release();
     e->own.release();
     delete e;
     return CSIM_OK;
@@ -318,6 +321,12 @@ int csim_ensemble_set_option(csim_ensemble* e, const char* key, long value) {
     } else if (k == "local_pack") {
         CSIM_REQUIRE(value >= 0 && value <= 64, "local_pack must be 0 (automatic) or 1 .. 64");
         e->local.pack = static_cast<int>(value);
+    } else if (k == "gram_form") {
+        CSIM_REQUIRE(value >= 0 && value <= GRAM_FORMS, "gram_form must be 0 (automatic) or 1 .. 3");
+        e->espace.gram_form = static_cast<int>(value);
+    } else if (k == "project_form") {
+        CSIM_REQUIRE(value >= 0 && value <= PROJECT_FORMS, "project_form must be 0 (automatic) or 1");
+        e->espace.project_form = static_cast<int>(value);
     } else if (k == "depth_used") {
         return fail(CSIM_ERR_ARG, "option depth_used is read-only");
     } else if (k == "contract") {
@@ -349,6 +358,10 @@ int csim_ensemble_get_option(const csim_ensemble* e, const char* key, long* valu
         *value = e->local.tile;
     else if (k == "local_pack")
         *value = e->local.pack;
+    else if (k == "gram_form")
+        *value = e->espace.gram_form;
+    else if (k == "project_form")
+        *value = e->espace.project_form;
     else if (k == "contract")
         return fail(CSIM_ERR_UNSUPPORTED, "an ensemble is always bit-identical: no contract mode");
     else

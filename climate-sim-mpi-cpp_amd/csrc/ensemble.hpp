@@ -307,6 +307,33 @@ hipError_t ens_launch_obs_cycle_screened(const ObsArgs& a, const ObsScreen& s, b
 // (nobs, 0, 0) into each of `cycles` records of a screen log: what a cycle that is not screened leaves there
 hipError_t ens_launch_obs_screen_log_fill(double* slog, int cycles, int nobs, hipStream_t st);
 
+// ensemble space (ensemble_space.hip; csim_ensemble_gram, _project, _transform): the M x M space spanned by the forecast
+// members' perturbations p_k (x_k less the cell's mean when centered, x_k itself otherwise).
+constexpr int ESPACE_MAX_MEMBERS = 256;  // CSIM_ESPACE_MAX_MEMBERS
+constexpr int GRAM_SEG = 64;             // interior cells per segment
+constexpr int GRAM_FORMS = 3;            // gram_form 1 .. 3: 1, 2, 4 blocks of 4 x 4 pairs per lane
+constexpr int PROJECT_FORMS = 1;         // project_form 1: the members of a cell in LDS whatever M
+// classes of the Gram sum for M forecast members (0: M out of range), and the plan of csim_ensemble_gram_plan
+inline int gram_cap(int M) { return M < 1 ? 0 : M <= 64 ? 1024 : M <= 128 ? 256 : M <= ESPACE_MAX_MEMBERS ? 64 : 0; }
+inline long gram_segments(int nx, int ny) { return (static_cast<long>(nx) * ny + GRAM_SEG - 1) / GRAM_SEG; }
+inline int gram_classes(int M, int nx, int ny) {
+    const long nseg = gram_segments(nx, ny);
+    return static_cast<int>(nseg < gram_cap(M) ? nseg : gram_cap(M));
+}
+inline size_t gram_pairs(int M) { return static_cast<size_t>(M) * (M + 1) / 2; }  // packed upper triangle
+// G (M x M, device) from the members; partial: gram_classes x gram_pairs doubles.  form: 0 (the launcher's choice)
+// or 1 .. GRAM_FORMS; the result does not depend on it
+hipError_t ens_launch_gram(const EnsGeom& g, const double* f, int forecast, int truth_member, bool centered,
+                           double* partial, double* G, int form, hipStream_t st);
+// out_r = sum_k p_k W[k K + r] on every cell of the dense layout (ny+2) x (nx+2): K dense fields.  W on the device.
+// form: 0 or 1 .. PROJECT_FORMS
+hipError_t ens_launch_project(const EnsGeom& g, const double* f, int forecast, int truth_member, bool centered, int K,
+                              const double* W, double* out, int form, hipStream_t st);
+// x_r <- (m + sum_k p_k wbar[k]) + sum_k p_k W[k M + r] (centered; wbar null: m) or sum_k p_k W[k M + r] on every
+// interior cell of the forecast members, in place
+hipError_t ens_launch_transform(const EnsGeom& g, double* f, int forecast, int truth_member, bool centered,
+                                const double* W, const double* wbar, int form, hipStream_t st);
+
 // the rank histogram's tie-break: splitmix64's finaliser of the interior index g; a cell with `eq` members equal to the
 // truth goes to bin lt + mix(g) mod (eq + 1)
 __host__ __device__ inline unsigned long long verify_mix(unsigned long long z) {

@@ -99,6 +99,15 @@ struct csim_ensemble {
         int truth = -1;  // its truth_member
         void release() { sb.release(), prior.release(), factor.release(); }
     } relax;
+    // ensemble space (csim_ensemble_gram, _project, _transform, _eofs; ensemble_space.cpp): the class partials and G
+    // of the Gram matrix, the output fields of a projection, W (and wbar) on the device with their staging, and its
+    // two launch options
+    struct Espace {
+        csim::DeviceBuf partial, gram, out, w;
+        csim::Staging stage;
+        int gram_form = 0, project_form = 0;  // options gram_form, project_form; 0: automatic
+        void release() { partial.release(), gram.release(), out.release(), w.release(), stage.release(); }
+    } espace;
     // observation networks (csim_obs_network_*, ensemble_obs.cpp): the ones that are alive; each owns its device buffer
     struct Obs {
         std::vector<csim_obs_network*> nets;

@@ -1,0 +1,323 @@
+// ensemble_space.hip — the ensemble-space primitives of csim_ensemble_gram, _project and _transform (host side in
+// ensemble_space.cpp; the definitions are the block in csim.h).  Needs only the slab layout of ensemble.hpp.
+//
+// p_k of a cell: x_k less the cell's mean m = (running sum of x_k from +0 in member order) / M when centered, x_k
+// otherwise.  Every product and every sum is one rounded fp64 operation, no FMA contraction.
+//
+// Gram, two kernels:
+//   k_gram_partial  Workgroup (g, y) of 256 lanes serves class g: the segments g, g + Gc, ... of 64 interior cells.  It
+//                   stages a segment's perturbations in LDS as [cell][member] (row stride even, so a lane's four
+//                   members are one or two 16-byte reads; the lanes of a wave mostly share the a-side address, which
+//                   broadcasts, and read neighbouring 32-byte pieces on the b-side), then every lane walks the
+//                   segment's cells in order for its NB blocks of 4 x 4 pairs (a, b) of the upper triangle, block
+//                   (blockIdx.y NB + u) 256 + lane, and carries the 16 NB running sums on to the class's next segment.
+//                   Which lane owns which pair is geometry: the order of each pair's sum is that of the cells.
+//                   Each class writes the packed upper triangle of its partial.
+//   k_gram_fold     entry (a, b), a <= b: partial 0, then + partial 1, ... + partial Gc - 1; written to G[a][b] and
+//                   G[b][a].
+// Project / transform, one kernel template k_espace_apply<P, XFORM>: one cell per lane, p_k in registers (P > 0, the
+// steps of for_step) or in LDS as [member][lane] (P = 0: M > 64, or project_form 1).  W is read with wave-uniform
+// indices, so its loads are scalar; four outputs r share one pass over k, four independent chains.  In the LDS form
+// four waves share a tile of 64 cells and divide the outputs among them, so that the tile's LDS (512 B per member)
+// keeps four waves busy instead of one.  All M values of a cell are held before any is stored, so the transform may
+// write the members it read.
+#include <algorithm>
+
+#include "ensemble_cell.hpp"
+
+#pragma clang fp contract(off)
+
+namespace csim {
+
+namespace {
+
+constexpr int GRAM_THREADS = 256;
+constexpr int GRAM_TB = 4;                   // pairs per block side
+constexpr long ESPACE_MAX_BLOCKS = 1L << 20;  // larger fields loop
+
+__host__ __device__ inline int gram_stride(int M) { return (M + GRAM_TB - 1) / GRAM_TB * GRAM_TB + 2; }
+
+template <int NB>
+__global__ __launch_bounds__(GRAM_THREADS) void k_gram_partial(const double* __restrict__ f, int nx, long cells,
+                                                               long nseg, int pitch, long slab, int M, int t,
+                                                               int centered, double* __restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) double held[];  // [64][stride], then the 64 means
+    const int stride = gram_stride(M);
+    double* __restrict__ mean = held + GRAM_SEG * stride;
+    const int tid = threadIdx.x;
+    const int nblk = (M + GRAM_TB - 1) / GRAM_TB;
+    const int nblocks = nblk * (nblk + 1) / 2;
+    const int mpad = nblk * GRAM_TB;
+
+    // this lane's blocks (ia <= ib), row by row of the block triangle; past the end: the last one, computed and dropped
+    int ia[NB], ib[NB];
+    bool mine[NB];
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+        const int bidx = (blockIdx.y * NB + u) * GRAM_THREADS + tid;
+        mine[u] = bidx < nblocks;
+        int r = min(bidx, nblocks - 1), a = 0;
+        while (r >= nblk - a) r -= nblk - a, ++a;
+        ia[u] = a, ib[u] = a + r;
+    }
+    // a wave none of whose lanes owns a block only helps staging
+    const bool wave_on = blockIdx.y * NB * GRAM_THREADS + (tid & ~63) < nblocks;
+
+    double acc[NB][GRAM_TB * GRAM_TB];
+#pragma unroll
+    for (int u = 0; u < NB; ++u)
+#pragma unroll
+        for (int v = 0; v < GRAM_TB * GRAM_TB; ++v) acc[u][v] = 0.0;
+
+    const int c = tid & 63, kq = tid >> 6;
+    double* __restrict__ row = held + c * stride;
+    for (long q = blockIdx.x; q < nseg; q += gridDim.x) {
+        const long e0 = q * GRAM_SEG;
+        const int nc = static_cast<int>(min(static_cast<long>(GRAM_SEG), cells - e0));
+        if (c < nc) {
+            const Cell cc = cell_of(e0 + c, nx, pitch);
+            const double* __restrict__ p = f + static_cast<size_t>(cc.off);
+#pragma unroll 8
+            for (int k = kq; k < M; k += 4) row[k] = p[static_cast<size_t>(forecast_member(k, t)) * slab];
+            for (int k = M + kq; k < mpad; k += 4) row[k] = 0.0;
+        }
+        __syncthreads();
+        if (centered) {
+            if (tid < nc) {
+                const double* __restrict__ x = held + tid * stride;
+                double s = 0.0;
+#pragma unroll 8
+                for (int k = 0; k < M; ++k) s = s + x[k];
+                mean[tid] = s / static_cast<double>(M);
+            }
+            __syncthreads();
+            if (c < nc) {
+                const double m = mean[c];
+#pragma unroll 8
+                for (int k = kq; k < M; k += 4) row[k] = row[k] - m;
+            }
+            __syncthreads();
+        }
+        if (wave_on) {
+#pragma unroll 2
+            for (int cc = 0; cc < nc; ++cc) {
+                const double* __restrict__ x = held + cc * stride;
+#pragma unroll
+                for (int u = 0; u < NB; ++u) {
+                    const double2* __restrict__ pa = reinterpret_cast<const double2*>(x + GRAM_TB * ia[u]);
+                    const double2* __restrict__ pb = reinterpret_cast<const double2*>(x + GRAM_TB * ib[u]);
+                    const double2 a0 = pa[0], a1 = pa[1], b0 = pb[0], b1 = pb[1];
+                    const double a[GRAM_TB] = {a0.x, a0.y, a1.x, a1.y};
+                    const double b[GRAM_TB] = {b0.x, b0.y, b1.x, b1.y};
+#pragma unroll
+                    for (int i = 0; i < GRAM_TB; ++i)
+#pragma unroll
+                        for (int j = 0; j < GRAM_TB; ++j)
+                            acc[u][i * GRAM_TB + j] = acc[u][i * GRAM_TB + j] + a[i] * b[j];
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    double* __restrict__ mine_out = partial + static_cast<size_t>(blockIdx.x) * (static_cast<size_t>(M) * (M + 1) / 2);
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+        if (!mine[u]) continue;
+#pragma unroll
+        for (int i = 0; i < GRAM_TB; ++i)
+#pragma unroll
+            for (int j = 0; j < GRAM_TB; ++j) {
+                const int a = GRAM_TB * ia[u] + i, b = GRAM_TB * ib[u] + j;
+                if (a <= b && b < M)
+                    mine_out[static_cast<size_t>(a) * M - static_cast<size_t>(a) * (a - 1) / 2 + (b - a)] =
+                        acc[u][i * GRAM_TB + j];
+            }
+    }
+}
+
+// grid (ceil(M / 64), M): row a = blockIdx.y, column b
+__global__ __launch_bounds__(64) void k_gram_fold(const double* __restrict__ partial, int classes, int M,
+                                                  double* __restrict__ G) {
+    const int a = blockIdx.y, b = blockIdx.x * 64 + threadIdx.x;
+    if (b < a || b >= M) return;
+    const size_t pairs = static_cast<size_t>(M) * (M + 1) / 2;
+    const double* __restrict__ p = partial + (static_cast<size_t>(a) * M - static_cast<size_t>(a) * (a - 1) / 2 + (b - a));
+    double s = p[0];
+#pragma unroll 16
+    for (int g = 1; g < classes; ++g) s = s + p[static_cast<size_t>(g) * pairs];
+    G[static_cast<size_t>(a) * M + b] = s;
+    G[static_cast<size_t>(b) * M + a] = s;
+}
+
+constexpr int APPLY_RB = 4;     // outputs r that share one pass over k
+constexpr int APPLY_WAVES = 4;  // LDS form: waves that share one tile of 64 cells, each taking every fourth group of outputs
+
+// XFORM = false: project; cells are the dense cells of (ny+2) x (nx+2), out gets K fields.
+// XFORM = true: transform; cells are the interior cells, K = M, the members are written in place.
+// P > 0: one wave per workgroup.  P = 0: APPLY_WAVES waves load the tile's members together, every wave sums the mean
+// of its lane's cell (the same bits in each), the waves subtract it from a quarter of the members each, and wave w
+// computes the outputs r of groups w, w + APPLY_WAVES, ...
+template <int P, bool XFORM>
+__global__ __launch_bounds__(P > 0 ? 64 : 64 * APPLY_WAVES) void k_espace_apply(double* __restrict__ f, int nx, int ny, int pitch, long slab,
+                                                     int M, int t, int centered, int K, const double* __restrict__ W,
+                                                     const double* __restrict__ wbar, double* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) double held[];  // P = 0: [M][64]
+    constexpr int NW = P > 0 ? 1 : APPLY_WAVES;
+    // the register form is one wave: `wave` is a constant 0 there, so the loop over the outputs keeps no state for it
+    const int lane = threadIdx.x & 63, wave = P > 0 ? 0 : threadIdx.x >> 6;
+    const int nx2 = nx + 2;
+    const long cells = XFORM ? static_cast<long>(nx) * ny : static_cast<long>(nx2) * (ny + 2);
+    const long rounded = (cells + 63) / 64 * 64;  // whole waves: a lane past the end works on the last cell, stores nothing
+    for (long e = static_cast<long>(blockIdx.x) * 64 + lane; e < rounded; e += static_cast<long>(gridDim.x) * 64) {
+        const bool valid = e < cells;
+        const long ec = valid ? e : cells - 1;
+        double* __restrict__ p;
+        if (XFORM) {
+            p = f + static_cast<size_t>(cell_of(ec, nx, pitch).off);
+        } else {
+            const int j = static_cast<int>(ec / nx2);
+            p = cell_ptr(f, static_cast<int>(ec - static_cast<long>(j) * nx2), j, pitch);
+        }
+        double x[P > 0 ? P : 1];
+        double m = 0.0;
+        if constexpr (P > 0) {
+#pragma unroll
+            for (int k = 0; k < P; ++k) x[k] = p[static_cast<size_t>(forecast_member(min(k, M - 1), t)) * slab];
+            if (centered) {
+                m = mean_regs<P>(x, M);
+#pragma unroll
+                for (int k = 0; k < P; ++k) x[k] = x[k] - m;
+            }
+        } else {
+#pragma unroll 8
+            for (int k = wave; k < M; k += NW)
+                held[k * 64 + lane] = p[static_cast<size_t>(forecast_member(k, t)) * slab];
+            __syncthreads();
+            if (centered) {
+                double s = 0.0;
+#pragma unroll 8
+                for (int k = 0; k < M; ++k) s = s + held[k * 64 + lane];
+                m = s / static_cast<double>(M);
+                __syncthreads();  // every wave has read the members it did not load before any is replaced
+#pragma unroll 8
+                for (int k = wave; k < M; k += NW) held[k * 64 + lane] = held[k * 64 + lane] - m;
+                __syncthreads();
+            }
+        }
+        double mp = m;
+        if (XFORM && wbar) {
+            double d = 0.0;
+            if constexpr (P > 0) {
+#pragma unroll
+                for (int k = 0; k < P; ++k)
+                    if (k < M) d = d + x[k] * wbar[k];
+            } else {
+#pragma unroll 4
+                for (int k = 0; k < M; ++k) d = d + held[k * 64 + lane] * wbar[k];
+            }
+            mp = m + d;
+        }
+        for (int r0 = APPLY_RB * wave; r0 < K; r0 += APPLY_RB * NW) {
+            int rr[APPLY_RB];
+            double s[APPLY_RB];
+#pragma unroll
+            for (int u = 0; u < APPLY_RB; ++u) rr[u] = min(r0 + u, K - 1), s[u] = 0.0;
+            if constexpr (P > 0) {
+#pragma unroll
+                for (int k = 0; k < P; ++k)
+                    if (k < M) {
+#pragma unroll
+                        for (int u = 0; u < APPLY_RB; ++u) s[u] = s[u] + x[k] * W[static_cast<size_t>(k) * K + rr[u]];
+                    }
+            } else {
+#pragma unroll 4
+                for (int k = 0; k < M; ++k) {
+                    const double pk = held[k * 64 + lane];
+#pragma unroll
+                    for (int u = 0; u < APPLY_RB; ++u) s[u] = s[u] + pk * W[static_cast<size_t>(k) * K + rr[u]];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < APPLY_RB; ++u) {
+                if (r0 + u >= K || !valid) continue;
+                if (XFORM)
+                    p[static_cast<size_t>(forecast_member(r0 + u, t)) * slab] = centered ? mp + s[u] : s[u];
+                else
+                    out[static_cast<size_t>(r0 + u) * cells + e] = s[u];
+            }
+        }
+        if constexpr (P == 0) __syncthreads();  // the tile is free for the next cells
+    }
+}
+
+template <int NB>
+hipError_t launch_gram(const EnsGeom& g, const double* f, int M, int t, bool centered, double* partial, double* G,
+                       hipStream_t st) {
+    const long cells = static_cast<long>(g.nx) * g.ny;
+    const long nseg = gram_segments(g.nx, g.ny);
+    const int classes = gram_classes(M, g.nx, g.ny);
+    const int nblk = (M + GRAM_TB - 1) / GRAM_TB;
+    const int nblocks = nblk * (nblk + 1) / 2;
+    const int shares = (nblocks + NB * GRAM_THREADS - 1) / (NB * GRAM_THREADS);
+    const size_t lds = sizeof(double) * (static_cast<size_t>(GRAM_SEG) * gram_stride(M) + GRAM_SEG);
+    const hipError_t attr = dynamic_lds_once<k_gram_partial<NB>>(
+        sizeof(double) * (static_cast<size_t>(GRAM_SEG) * gram_stride(ESPACE_MAX_MEMBERS) + GRAM_SEG));
+    if (attr != hipSuccess) return attr;
+    hipLaunchKernelGGL(k_gram_partial<NB>, dim3(classes, shares), dim3(GRAM_THREADS), lds, st, f, g.nx, cells, nseg,
+                       g.pitch, g.slab, M, t, centered ? 1 : 0, partial);
+    hipError_t rc = hipGetLastError();
+    if (rc != hipSuccess) return rc;
+    hipLaunchKernelGGL(k_gram_fold, dim3((M + 63) / 64, M), dim3(64), 0, st, partial, classes, M, G);
+    return hipGetLastError();
+}
+
+unsigned apply_blocks(long cells) { return static_cast<unsigned>(std::min((cells + 63) / 64, ESPACE_MAX_BLOCKS)); }
+
+template <bool XFORM>
+hipError_t launch_apply(const EnsGeom& g, double* f, int M, int t, bool centered, int K, const double* W,
+                        const double* wbar, double* out, int form, hipStream_t st) {
+    const long cells = XFORM ? static_cast<long>(g.nx) * g.ny : static_cast<long>(g.nx + 2) * (g.ny + 2);
+    auto launch = [&](auto s) {
+        constexpr int P = decltype(s)::value;
+        const size_t lds = P > 0 ? 0 : sizeof(double) * 64 * static_cast<size_t>(M);
+        if (P == 0) {
+            const hipError_t attr =
+                dynamic_lds_once<k_espace_apply<P, XFORM>>(sizeof(double) * 64 * ESPACE_MAX_MEMBERS);
+            if (attr != hipSuccess) return attr;
+        }
+        hipLaunchKernelGGL((k_espace_apply<P, XFORM>), dim3(apply_blocks(cells)), dim3(P > 0 ? 64 : 64 * APPLY_WAVES), lds, st, f, g.nx, g.ny,
+                           g.pitch, g.slab, M, t, centered ? 1 : 0, K, W, wbar, out);
+        return hipGetLastError();
+    };
+    if (form == 1) return launch(Step<0>{});
+    return for_step(M, launch);
+}
+
+bool espace_ok(int M, int form, int forms) { return M >= 1 && M <= ESPACE_MAX_MEMBERS && form >= 0 && form <= forms; }
+
+}  // namespace
+
+hipError_t ens_launch_gram(const EnsGeom& g, const double* f, int forecast, int truth_member, bool centered,
+                           double* partial, double* G, int form, hipStream_t st) {
+    if (!espace_ok(forecast, form, GRAM_FORMS)) return hipErrorInvalidValue;
+    if (form == 0) form = forecast <= 64 ? 1 : forecast <= 128 ? 2 : 3;
+    if (form == 1) return launch_gram<1>(g, f, forecast, truth_member, centered, partial, G, st);
+    if (form == 2) return launch_gram<2>(g, f, forecast, truth_member, centered, partial, G, st);
+    return launch_gram<4>(g, f, forecast, truth_member, centered, partial, G, st);
+}
+
+hipError_t ens_launch_project(const EnsGeom& g, const double* f, int forecast, int truth_member, bool centered, int K,
+                              const double* W, double* out, int form, hipStream_t st) {
+    if (!espace_ok(forecast, form, PROJECT_FORMS) || K < 1 || K > forecast) return hipErrorInvalidValue;
+    return launch_apply<false>(g, const_cast<double*>(f), forecast, truth_member, centered, K, W, nullptr, out, form,
+                               st);
+}
+
+hipError_t ens_launch_transform(const EnsGeom& g, double* f, int forecast, int truth_member, bool centered,
+                                const double* W, const double* wbar, int form, hipStream_t st) {
+    if (!espace_ok(forecast, form, PROJECT_FORMS) || (wbar && !centered)) return hipErrorInvalidValue;
+    return launch_apply<true>(g, f, forecast, truth_member, centered, forecast, W, wbar, nullptr, form, st);
+}
+
+}  // namespace csim

@@ -79,6 +79,30 @@ struct ObsImpact {
     csim_obs_impact_summary summary{};
 };
 
+// eigenvalues (descending) and vectors (n x n row-major, column r belongs to lambda[r]) of a symmetric matrix
+struct SymEigen {
+    std::vector<double> lambda, V;
+    int sweeps = 0;
+};
+// cyclic Jacobi on the n x n row-major symmetric matrix A, host only (see csim_sym_eigen)
+inline SymEigen sym_eigen(const std::vector<double>& A, int n) {
+    if (n < 0 || A.size() != static_cast<std::size_t>(n) * static_cast<std::size_t>(n))
+        throw std::invalid_argument("sym_eigen: array size");
+    SymEigen e;
+    e.lambda.resize(static_cast<std::size_t>(n));
+    e.V.resize(A.size());
+    if (csim_sym_eigen(n, A.data(), e.lambda.data(), e.V.data(), &e.sweeps) != CSIM_OK)
+        throw std::runtime_error(std::string("csim: ") + csim_last_error());
+    return e;
+}
+
+// the leading modes of an ensemble's spread (see csim_ensemble_eofs): lambda and variance = lambda / (M - 1) per mode,
+// pcs M x n_modes row-major, patterns n_modes dense fields (empty when not asked for)
+struct EnsembleEOFs {
+    std::vector<double> lambda, variance, pcs, patterns;
+    int n_valid = 0;
+};
+
 class Ensemble;
 
 // observations that live on the device (csim_obs_network_*): planned once, their values drawn on the GPU from a
@@ -489,6 +513,41 @@ public:
         check(csim_ensemble_relax(h_, CSIM_RELAX_SPREAD, alpha, t, f.data()));
         return f;
     }
+    // ensemble space (see csim_ensemble_gram): M forecast members, all of them or, with t >= 0, all but member t.
+    // The M x M Gram matrix of the perturbations from the per-cell mean (centered) or of the members, row-major
+    std::vector<double> gram(int t = -1, bool centered = true) {
+        const std::size_t M = forecast(t);
+        std::vector<double> G(M * M);
+        check(csim_ensemble_gram(h_, t, centered ? 1 : 0, G.data()));
+        return G;
+    }
+    // K dense fields out_r = sum_k p_k W[k K + r], W is M x K row-major
+    std::vector<double> project(const std::vector<double>& W, int K, int t = -1, bool centered = true) {
+        if (K < 0 || W.size() != forecast(t) * static_cast<std::size_t>(K))
+            throw std::invalid_argument("ensemble: W must be M x K");
+        std::vector<double> out(member_size() * static_cast<std::size_t>(K));
+        check(csim_ensemble_project(h_, t, centered ? 1 : 0, K, W.data(), out.data()));
+        return out;
+    }
+    // the forecast members replaced on the interior by a linear combination of them, W is M x M row-major and wbar
+    // (centered only) M values or empty; enqueued without waiting, W and wbar may be reused at once
+    void transform(const std::vector<double>& W, const std::vector<double>& wbar = {}, int t = -1,
+                   bool centered = true) {
+        const std::size_t M = forecast(t);
+        if (W.size() != M * M || (!wbar.empty() && wbar.size() != M))
+            throw std::invalid_argument("ensemble: W must be M x M and wbar M values");
+        check(csim_ensemble_transform(h_, t, centered ? 1 : 0, W.data(), wbar.empty() ? nullptr : wbar.data()));
+    }
+    EnsembleEOFs eofs(int n_modes, int t = -1, bool patterns = true) {
+        const std::size_t M = forecast(t), K = static_cast<std::size_t>(n_modes > 0 ? n_modes : 0);
+        EnsembleEOFs r;
+        r.lambda.resize(K), r.pcs.resize(M * K);
+        if (patterns) r.patterns.resize(K * member_size());
+        check(csim_ensemble_eofs(h_, t, n_modes, r.lambda.data(), r.pcs.data(), patterns ? r.patterns.data() : nullptr,
+                                 &r.n_valid));
+        for (double l : r.lambda) r.variance.push_back(l / static_cast<double>(M - 1));
+        return r;
+    }
     void set_option(const char* key, long value) { check(csim_ensemble_set_option(h_, key, value)); }
     long get_option(const char* key) const {
         long v = 0;
@@ -500,6 +559,7 @@ private:
     static void check(int rc) {
         if (rc != CSIM_OK) throw std::runtime_error(std::string("csim: ") + csim_last_error());
     }
+    std::size_t forecast(int t) const { return static_cast<std::size_t>(members_ - (t >= 0 ? 1 : 0)); }
     const double* sized(const std::vector<double>& a, int n) const {
         if (a.size() != member_size() * static_cast<std::size_t>(n)) throw std::invalid_argument("ensemble: array size");
         return a.data();

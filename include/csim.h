@@ -926,6 +926,60 @@ int csim_ensemble_assimilate_local(csim_ensemble* e, csim_obs_network* n, double
 int csim_obs_network_local_info(csim_obs_network* n, int* max_local);
 int csim_obs_local_count(int nx, int ny, int nobs, const int* i, const int* j, int lx, int ly, int* count,
                          int* max_local);
+/* ensemble space: the M x M space spanned by the forecast members' perturbations.  Two primitives, both one pass over
+ * the members, and two composites on the host.  M forecast members in forecast order, truth member t stepped over
+ * (truth_member = -1: none), 1 <= M <= CSIM_ESPACE_MAX_MEMBERS (more: CSIM_ERR_UNSUPPORTED).  Every * + - / below is
+ * one IEEE fp64 operation, no FMA contraction; running sums start from +0 and take their terms in the stated order.
+ * Perturbations of a cell:  centered = 1:  s = +0; s = s + x_k (k = 0 .. M-1); m = s / M; p_k = x_k - m.
+ *                           centered = 0:  p_k = x_k.
+ * gram: G[a][b] = sum over the interior cells of p_a p_b, M x M row-major; synchronous, writes no member.  The order:
+ *   interior cells are numbered e = (j-1) nx + (i-1); segment q holds cells 64 q .. 64 q + 63 (the last may be short),
+ *   nseg = ceil(nx ny / 64); Gc = min(nseg, cap), cap = 1024 for M <= 64, 256 for M <= 128, 64 above.  Class g owns
+ *   segments g, g + Gc, g + 2 Gc, ...; for each (a, b) the class partial is one running sum over the class's cells in
+ *   increasing e, carried across its segments: acc = acc + (p_a * p_b).  G[a][b] = partial_0 + partial_1 + ... +
+ *   partial_{Gc-1}, starting from partial 0.  Nothing in this order depends on the launch geometry; G is symmetric
+ *   bit for bit.  gram_plan (host-only, needs no device): *nseg and *classes = Gc (either may be NULL).
+ * project: out_r = s_r on every cell of the reference layout (ny+2) x (nx+2), ghost ring included, K dense fields,
+ *   1 <= K <= M, W is M x K row-major:  s_r = +0; s_r = s_r + p_k * W[k K + r]  (k = 0 .. M-1).  Synchronous.
+ * transform: replaces the forecast members by a linear combination of them, on every interior cell (ghost ring and
+ *   member t keep their bits); W is M x M row-major, s_r as above with K = M:
+ *     centered = 1:  d = +0; d = d + p_k * wbar[k] (k in order); m' = m + d (wbar NULL: m' = m);  x'_r = m' + s_r
+ *     centered = 0:  x'_r = s_r;  a non-NULL wbar is CSIM_ERR_ARG
+ *   All M values of a cell are read before any is written.  With centered = 0 and W a 0/1 selection matrix the result
+ *   is an exact copy or resampling of members (up to the sign of a zero).  The call only enqueues on the ensemble's
+ *   stream: W and wbar are copied to staging before it returns, so run -> gram -> transform -> run needs no
+ *   synchronisation beyond the one gram makes.
+ * sym_eigen (host-only): the eigenvalues and vectors of the symmetric n x n matrix A (row-major; the upper triangle is
+ *   read), 1 <= n <= CSIM_SYM_EIGEN_MAX_N, by the cyclic Jacobi method.  a = A (kept symmetric entry by entry),
+ *   v = I.  A sweep takes the pairs p < q in row-cyclic order (p = 0 .. n-2, q = p+1 .. n-1); with g = |a_pq|:
+ *     a_pq == 0: nothing;  |a_pp| + g == |a_pp| and |a_qq| + g == |a_qq|: a_pq <- 0, no rotation;  otherwise
+ *     h = a_qq - a_pp;  |h| + g == |h|: t = a_pq / h;  else theta = (0.5 h) / a_pq,
+ *     t = 1 / (|theta| + sqrt(theta theta + 1)), negated for theta < 0;
+ *     c = 1 / sqrt(t t + 1);  s = t c;  tau = s / (1 + c);  h = t a_pq;  a_pp <- a_pp - h;  a_qq <- a_qq + h;  a_pq <- 0;
+ *     for j != p, q (j ascending), x = a_jp, y = a_jq:  a_jp <- x - s (y + x tau);  a_jq <- y + s (x - y tau);
+ *     for every j, the same with x = v_jp, y = v_jq.
+ *   It stops before a sweep that finds every off-diagonal element exactly zero, or after CSIM_SYM_EIGEN_MAX_SWEEPS
+ *   sweeps; *sweeps (may be NULL) = sweeps made.  lambda: the diagonal, sorted descending, ties to the lower original
+ *   index; V (n x n row-major): column r is the vector of lambda[r], negated if its first component of largest
+ *   magnitude is negative.  CSIM_ERR_ARG: n < 1, a non-finite entry; CSIM_ERR_UNSUPPORTED: n above the limit.
+ * eofs: the leading patterns of the ensemble's spread, 1 <= n_modes <= M - 1:  G = gram(centered = 1);
+ *   (lam, V) = sym_eigen(G);  lambda[r] = lam_r;  mode r is null when lam_r <= (M 2^-52) lam_0 or lam_r <= 0, else
+ *   W[k][r] = V[k][r] / sqrt(lam_r) and pcs[k n_modes + r] = V[k][r] * sqrt(lam_r);  patterns (NULL: not wanted) =
+ *   project(centered = 1, K = n_modes, W): n_modes dense fields, so that p_k = sum_r pcs[k][r] pattern_r on every cell
+ *   up to rounding.  A null mode has zero pcs and a zero pattern; *n_valid (may be NULL) counts the others.
+ * space_check (host-only): the argument checks of the four calls for an ensemble of `members` members, in the order
+ *   truth_member, M, centered, K (0: not a projection), wbar, n_modes (0: not eofs). */
+#define CSIM_ESPACE_MAX_MEMBERS 256
+#define CSIM_SYM_EIGEN_MAX_N 256
+#define CSIM_SYM_EIGEN_MAX_SWEEPS 64
+int csim_ensemble_gram(csim_ensemble* e, int truth_member, int centered, double* G);
+int csim_ensemble_gram_plan(int M, int nx, int ny, long* nseg, int* classes);
+int csim_ensemble_project(csim_ensemble* e, int truth_member, int centered, int K, const double* W, double* out);
+int csim_ensemble_transform(csim_ensemble* e, int truth_member, int centered, const double* W, const double* wbar);
+int csim_sym_eigen(int n, const double* A, double* lambda, double* V, int* sweeps);
+int csim_ensemble_eofs(csim_ensemble* e, int truth_member, int n_modes, double* lambda, double* pcs, double* patterns,
+                       int* n_valid);
+int csim_ensemble_space_check(int members, int truth_member, int centered, int K, int has_wbar, int n_modes);
 /* options (unknown keys: CSIM_ERR_ARG; "contract": CSIM_ERR_UNSUPPORTED), results never depend on them:
  *   "fuse"        -1 (default) passes of the ensemble depth where the grid allows; 0 / 1 single steps only
  *   "fused_2c"    0/1 (default 1), as for csim_stepper_set_option
@@ -941,7 +995,11 @@ int csim_obs_local_count(int nx, int ny, int nobs, const int* i, const int* j, i
  *   "local_tile"            0 (default: chosen from the grid), 4, 8 or 16: cells per side of a tile of the lookup of
  *                           csim_ensemble_assimilate_local; any other value is CSIM_ERR_ARG
  *   "local_pack"            0 (default: as many as fit) or 1 .. 64: cells that one wave of that call's cell pass takes
- *                           together (more than fit beside max_local observations each: as many as fit) */
+ *                           together (more than fit beside max_local observations each: as many as fit)
+ *   "gram_form"             0 (default: chosen from M) or 1, 2, 3: 1, 2 or 4 blocks of 4 x 4 pairs per lane in the
+ *                           class-partial kernel of csim_ensemble_gram; any other value is CSIM_ERR_ARG
+ *   "project_form"          0 (default: a cell's members in registers up to M = 64, in LDS above) or 1 (in LDS whatever
+ *                           M) in csim_ensemble_project and csim_ensemble_transform; any other value is CSIM_ERR_ARG */
 int csim_ensemble_set_option(csim_ensemble* e, const char* key, long value);
 int csim_ensemble_get_option(const csim_ensemble* e, const char* key, long* value);
 /* host-only pass planner of csim_ensemble_run: out[0] = steps per fused pass (1: none; members with nx or ny below

@@ -5,7 +5,8 @@
 # the sweep's tile plan (csrc/sweep_plan.cpp, csrc/sweep_plan.hpp: every plan of the check's enumeration through the
 # kernel's restated tile decode) and of the spatial verification (csrc/spatial_scores.cpp, csrc/spatial_scores.hpp: the
 # overflow bound at its edge, the finishing of the integer tables) and of the local analysis (csrc/assim_plan.cpp again:
-# csim_obs_local_count and the per-tile lookup against brute force), each as a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.  The build goes to $TMP;
+# csim_obs_local_count and the per-tile lookup against brute force) and of the ensemble-space eigensolver (csrc/sym_eigen.cpp,
+# csrc/sym_eigen.hpp: residual, orthogonality, ordering and sign rule up to the largest n), each as a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.  The build goes to $TMP;
 # nothing in the tree is replaced.
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -19,9 +20,11 @@ CXX=(g++ -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined
 "${CXX[@]}" -o "$TMP/sweep_plan_host_check" "$R/tools/sweep_plan_host_check.cpp" "$S/sweep_plan.cpp"
 "${CXX[@]}" -o "$TMP/spatial_host_check" "$R/tools/spatial_host_check.cpp" "$S/spatial_scores.cpp"
 "${CXX[@]}" -o "$TMP/local_plan_host_check" "$R/tools/local_plan_host_check.cpp" "$S/assim_plan.cpp"
+"${CXX[@]}" -o "$TMP/sym_eigen_host_check" "$R/tools/sym_eigen_host_check.cpp" "$S/sym_eigen.cpp"
 export ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1
 "$TMP/obsop_host_check"
 "$TMP/assim_plan_host_check"
 "$TMP/sweep_plan_host_check"
 "$TMP/spatial_host_check"
 "$TMP/local_plan_host_check"
+"$TMP/sym_eigen_host_check"
