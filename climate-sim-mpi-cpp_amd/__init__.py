@@ -268,6 +268,11 @@ def lib() -> C.CDLL:
         "csim_sym_eigen": (i, [i, dp, dp, dp, ip]),
         "csim_ensemble_eofs": (i, [vp, i, i, dp, dp, dp, ip]),
         "csim_ensemble_space_check": (i, [i] * 6),
+        "csim_ensemble_obs_gram": (i, [vp, vp, i, dp, dp, C.POINTER(C.c_longlong)]),
+        "csim_obs_gram_plan": (i, [i, i, C.POINTER(C.c_long), ip]),
+        "csim_etkf_weights": (i, [i, dp, d, dp, dp, dp, dp, ip]),
+        "csim_ensemble_assimilate_etkf": (i, [vp, vp, d, i, i, d]),
+        "csim_ensemble_etkf_info": (i, [vp, C.POINTER(C.c_longlong), dp, dp, dp, ip]),
         "csim_ensemble_set_option": (i, [vp, C.c_char_p, C.c_long]),
         "csim_ensemble_get_option": (i, [vp, C.c_char_p, C.POINTER(C.c_long)]),
         "csim_ensemble_plan": (i, [i, i, i, i, ip]),
@@ -996,6 +1001,40 @@ def ensemble_gram_plan(M: int, nx: int, ny: int):
     return nseg.value, gc.value
 
 
+ObsGram = collections.namedtuple("ObsGram", "A loglik n_used")
+ObsGram.__doc__ = """what Ensemble.obs_gram() returns: A (M+1, M+1) = Z^T Z of the normalised observation-space
+perturbations with the normalised innovation as column M (A[:M, :M] = Y^T R^-1 Y, A[:M, M] = Y^T R^-1 (y - hb), A[M, M]
+the innovation chi^2), loglik (M,) or None, and the number of observations used"""
+EtkfWeights = collections.namedtuple("EtkfWeights", "W wbar gamma dfs sweeps")
+EtkfWeights.__doc__ = """what etkf_weights() returns: Ensemble.transform(W, wbar) is the ETKF analysis; gamma are the
+eigenvalues of Y^T R^-1 Y clamped at 0, dfs the degrees of freedom for signal, sweeps those of sym_eigen"""
+EtkfAnalysis = collections.namedtuple("EtkfAnalysis", "n_used chi2 gamma dfs")
+EtkfAnalysis.__doc__ = """what Ensemble.assimilate_etkf() returns: the observations used, the innovation chi^2, and gamma
+and dfs of its weights"""
+
+
+def obs_gram_plan(M: int, nobs: int):
+    """(nseg, Gc): the 64-observation segments of a network's plan order and the classes whose partial sums
+    Ensemble.obs_gram() adds in order (csim_obs_gram_plan) — host only"""
+    nseg, gc = C.c_long(), C.c_int()
+    _ck(lib().csim_obs_gram_plan(int(M), int(nobs), C.byref(nseg), C.byref(gc)))
+    return nseg.value, gc.value
+
+
+def etkf_weights(A, inflation=1.0) -> EtkfWeights:
+    """the symmetric square-root ETKF in ensemble space from the (M+1, M+1) matrix of Ensemble.obs_gram(), inflation
+    taken in ensemble space (csim_etkf_weights) — host only"""
+    a = np.ascontiguousarray(A, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 1:
+        raise ValueError("A must be a square matrix, (M+1, M+1)")
+    M = a.shape[0] - 1
+    W, wbar, gamma = np.empty((M, M)), np.empty(M), np.empty(M)
+    dfs, sweeps = C.c_double(), C.c_int()
+    _ck(lib().csim_etkf_weights(M, _dp(a), float(inflation), _dp(W), _dp(wbar), _dp(gamma), C.byref(dfs),
+                                C.byref(sweeps)))
+    return EtkfWeights(W, wbar, gamma, dfs.value, sweeps.value)
+
+
 class ObsNetwork:
     """observations that live on the device (csim_obs_network_*): planned once, their values drawn on the GPU
     from a member or set from the host, read by Ensemble.assimilate_network without staging.  Point observations of
@@ -1412,6 +1451,34 @@ class Ensemble:
         rec = record if isinstance(record, int) else int(bool(record))
         _ck(lib().csim_ensemble_assimilate_local(self._h, net._h, float(inflation), tm, rec,
                                                  0.0 if screen is None else float(screen)))
+
+    def obs_gram(self, net: ObsNetwork, truth_member=None, loglik=False) -> ObsGram:
+        """the observation-space Gram matrix of the forecast members over the network's active observations, and with
+        loglik=True each member's sum of squared normalised departures (a particle weight is exp(-loglik / 2));
+        synchronous, writes nothing of the network (csim_ensemble_obs_gram)"""
+        tm, M = self._forecast(truth_member)
+        A = np.empty((max(M, 0) + 1, max(M, 0) + 1))
+        ll = np.empty(max(M, 0)) if loglik else None
+        used = C.c_longlong()
+        _ck(lib().csim_ensemble_obs_gram(self._h, net._h, tm, _dp(A), None if ll is None else _dp(ll),
+                                         C.byref(used)))
+        return ObsGram(A, ll, used.value)
+
+    def assimilate_etkf(self, net: ObsNetwork, inflation=1.0, truth_member=None, record=False,
+                        screen=None) -> EtkfAnalysis:
+        """the global ETKF analysis with the network's observations: obs_gram() over the used ones, etkf_weights() and
+        transform() composed in the library; waits for the Gram matrix, the transform is enqueued.  inflation (taken in
+        ensemble space), truth_member, record and screen as in assimilate_network; the network's loc plays no part
+        (csim_ensemble_assimilate_etkf)"""
+        tm, M = self._forecast(truth_member)
+        rec = record if isinstance(record, int) else int(bool(record))
+        _ck(lib().csim_ensemble_assimilate_etkf(self._h, net._h, float(inflation), tm, rec,
+                                                0.0 if screen is None else float(screen)))
+        used, chi2, dfs, ng = C.c_longlong(), C.c_double(), C.c_double(), C.c_int()
+        gamma = np.empty(M)
+        _ck(lib().csim_ensemble_etkf_info(self._h, C.byref(used), C.byref(chi2), C.byref(dfs), _dp(gamma),
+                                          C.byref(ng)))
+        return EtkfAnalysis(used.value, chi2.value, gamma, dfs.value)
 
     def obs_impact(self, net: ObsNetwork, weight) -> ObsImpact:
         """the forecast impact J_o of every observation of net's captured analysis on the error of the current

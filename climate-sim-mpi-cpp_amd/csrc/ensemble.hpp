@@ -334,6 +334,32 @@ hipError_t ens_launch_project(const EnsGeom& g, const double* f, int forecast, i
 hipError_t ens_launch_transform(const EnsGeom& g, double* f, int forecast, int truth_member, bool centered,
                                 const double* W, const double* wbar, int form, hipStream_t st);
 
+// the observation-space Gram matrix of csim_ensemble_obs_gram (ensemble_obsgram.hip): A = Z^T Z, (M + 1) x (M + 1), of
+// the normalised observation-space perturbations of a network, and the members' sums of squared normalised departures.
+// Device arrays in plan order.  An observation is used iff flag is null or flag[q] == used: the mask (1: active) of
+// the stand-alone call, the status bytes (0: CSIM_OBS_USED) of an analysis.
+constexpr int OBS_GRAM_FORMS = GRAM_FORMS;  // obs_gram_form 1 .. 3: 1, 2, 4 blocks of 4 x 4 pairs per lane
+struct ObsGramArgs {
+    int nobs;
+    int forecast;                 // M
+    int truth_member;             // t, or B (no member skipped)
+    const int* i;
+    const int* j;
+    const double* y;
+    const double* sr;             // sqrt(r)
+    const unsigned char* flag;
+    int used;
+    const int* tstart;            // the taps, as in AssimArgs; null: point observations
+    const int* toff;
+    const double* tw;
+};
+// doubles of `partial` for a call: per class the packed upper triangle of A, M sums of loglik and one count
+size_t ens_obs_gram_partial_doubles(int forecast, int nobs);
+// out (device): A, then M values of loglik (written only with want_loglik), then the number of used observations as
+// one long long.  form: 0 (the launcher's choice) or 1 .. OBS_GRAM_FORMS; the result does not depend on it
+hipError_t ens_launch_obs_gram(const EnsGeom& g, const double* f, const ObsGramArgs& a, bool want_loglik,
+                               double* partial, double* out, int form, hipStream_t st);
+
 // the rank histogram's tie-break: splitmix64's finaliser of the interior index g; a cell with `eq` members equal to the
 // truth goes to bin lt + mix(g) mod (eq + 1)
 __host__ __device__ inline unsigned long long verify_mix(unsigned long long z) {

@@ -106,6 +106,13 @@ struct csim_ensemble {
         csim::DeviceBuf partial, gram, out, w;
         csim::Staging stage;
         int gram_form = 0, project_form = 0;  // options gram_form, project_form; 0: automatic
+        // the observation-space Gram matrix (csim_ensemble_obs_gram, ensemble_obs.cpp) shares `partial` and `gram`;
+        // what the last completed csim_ensemble_assimilate_etkf found, for csim_ensemble_etkf_info
+        int obs_gram_form = 0;                // option obs_gram_form; 0: automatic
+        bool etkf_valid = false;
+        long long etkf_used = 0;
+        double etkf_chi2 = 0.0, etkf_dfs = 0.0;
+        std::vector<double> etkf_gamma;
         void release() { partial.release(), gram.release(), out.release(), w.release(), stage.release(); }
     } espace;
     // observation networks (csim_obs_network_*, ensemble_obs.cpp): the ones that are alive; each owns its device buffer

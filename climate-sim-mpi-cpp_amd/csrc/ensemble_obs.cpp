@@ -10,7 +10,11 @@
 // The local analysis (csim_ensemble_assimilate_local; kernels in ensemble_local.hip) shares the checks, the screening
 // and the recording of the serial one (analysis_check, analysis_begin, analysis_record) and differs in what runs between
 // them; its lookup and the observation priors are storage of the network's own, made at the first local analysis.
+// The observation-space Gram matrix (csim_ensemble_obs_gram; kernels in ensemble_obsgram.hip) reads a network and writes
+// nothing of it; the ETKF (csim_ensemble_assimilate_etkf) is the third analysis between the shared pieces: that matrix of
+// the used observations, csim_etkf_weights (etkf_weights.cpp) on the host, and csim_ensemble_transform.
 #include <cmath>
+#include <cstring>
 #include <memory>
 #include <new>
 #include <vector>
@@ -289,6 +293,30 @@ int analysis_record(csim_ensemble* e, csim_obs_network* n, const Analysis& x) {
     return CSIM_OK;
 }
 
+// csim_ensemble_obs_gram and step 3 of csim_ensemble_assimilate_etkf: A, loglik (with want_ll) and the count of the
+// observations whose flag byte is `used` (flag null: all), synchronous.  *out: (M + 1)^2 + M doubles, A first.  The
+// class partials and the result use the buffers of csim_ensemble_gram, which is synchronous as well
+int obs_gram(csim_ensemble* e, csim_obs_network* n, int M, int t, const unsigned char* flag, int used, bool want_ll,
+             std::vector<double>* out, long long* n_used) {
+    csim_ensemble::Espace& x = e->espace;
+    const ObsArgs oa = n->args();
+    ObsGramArgs a{};
+    a.nobs = n->nobs, a.forecast = M, a.truth_member = t;
+    a.i = oa.i, a.j = oa.j, a.y = oa.y, a.sr = oa.sr;
+    a.flag = flag, a.used = used;
+    a.tstart = oa.tstart, a.toff = oa.toff, a.tw = oa.tw;
+    const size_t ma = static_cast<size_t>(M) + 1, doubles = ma * ma + M + 1;
+    CSIM_TRY(x.partial.reserve(sizeof(double) * ens_obs_gram_partial_doubles(M, n->nobs), e->st));
+    CSIM_TRY(x.gram.reserve(sizeof(double) * doubles, e->st));
+    CSIM_HIP(ens_launch_obs_gram(e->g, e->base(e->cur), a, want_ll, x.partial.as(), x.gram.as(), x.obs_gram_form, e->st));
+    out->resize(doubles);
+    CSIM_HIP(hipMemcpyAsync(out->data(), x.gram.p, sizeof(double) * doubles, hipMemcpyDeviceToHost, e->st));
+    CSIM_HIP(hipStreamSynchronize(e->st));
+    static_assert(sizeof(long long) == sizeof(double), "the count travels behind loglik");
+    std::memcpy(n_used, out->data() + ma * ma + M, sizeof(long long));
+    return CSIM_OK;
+}
+
 // max_local of the network, counted once
 int local_max(csim_obs_network* n, int* max_local) {
     if (n->loc.max_local < 0)
@@ -480,6 +508,80 @@ int csim_ensemble_assimilate_local(csim_ensemble* e, csim_obs_network* n, double
     CSIM_HIP(ens_launch_local_prior(g, f, an.a, n->nobs, x.prior.as(), e->st));
     CSIM_HIP(ens_launch_local_update(g, f, an.a, l, e->st));
     return record ? analysis_record(e, n, an) : CSIM_OK;
+}
+
+int csim_ensemble_obs_gram(csim_ensemble* e, csim_obs_network* n, int truth_member, double* A, double* loglik,
+                           long long* n_used) {
+    CSIM_REQUIRE(e, "null ensemble");
+    CSIM_REQUIRE(n, "null network");
+    CSIM_REQUIRE(n->e == e, "the network belongs to another ensemble");
+    int M = 0, t = 0;
+    CSIM_TRY(forecast_split(e->g.members, truth_member, &M, &t, 2, "the observation-space Gram matrix needs at least "
+                            "two forecast members", ESPACE_MAX_MEMBERS,
+                            "csim_ensemble_obs_gram: at most CSIM_ESPACE_MAX_MEMBERS forecast members"));
+    if (!n->has_values)
+        return fail(CSIM_ERR_STATE, "csim_ensemble_obs_gram: the network has no values yet "
+                                    "(csim_obs_network_set_values or csim_obs_network_observe)");
+    try {
+        std::vector<double> out;
+        long long used = 0;
+        CSIM_TRY(obs_gram(e, n, M, t, n->masked ? n->at<unsigned char>(n->l.mask) : nullptr, 1, loglik != nullptr, &out,
+                          &used));
+        const size_t ma = static_cast<size_t>(M) + 1;
+        if (A) std::copy(out.begin(), out.begin() + ma * ma, A);
+        if (loglik) std::copy(out.begin() + ma * ma, out.begin() + ma * ma + M, loglik);
+        if (n_used) *n_used = used;
+        return CSIM_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(CSIM_ERR_STATE, "csim_ensemble_obs_gram: out of host memory");
+    }
+}
+
+int csim_ensemble_assimilate_etkf(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
+                                  int record, double tol) {
+    int M = 0, t = 0;
+    CSIM_TRY(analysis_check(e, n, inflation, truth_member, record, tol, &M, &t));
+    if (M > ESPACE_MAX_MEMBERS)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_etkf: at most CSIM_ESPACE_MAX_MEMBERS forecast "
+                                          "members");
+    try {
+        const size_t m = static_cast<size_t>(M), ma = m + 1;
+        std::vector<double> out, W(m * m), wbar(m), gamma(m);
+        long long used = 0;
+        double dfs = 0.0;
+        Analysis x;
+        e->espace.etkf_valid = false;
+        CSIM_TRY(analysis_begin(e, n, M, t, record, tol, &x));
+        CSIM_TRY(obs_gram(e, n, M, t, x.screen ? x.s.status : nullptr, CSIM_OBS_USED, false, &out, &used));
+        for (size_t k = 0; k < ma * ma; ++k)
+            if (!std::isfinite(out[k]))
+                return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_etkf: the observation-space Gram matrix has a "
+                                            "non-finite entry; the members are unchanged");
+        CSIM_TRY(csim_etkf_weights(M, out.data(), inflation, W.data(), wbar.data(), gamma.data(), &dfs, nullptr));
+        // nothing to assimilate and nothing to inflate: W would be the identity up to rounding, the members keep their bits
+        if (used != 0 || inflation != 1.0) CSIM_TRY(csim_ensemble_transform(e, truth_member, 1, W.data(), wbar.data()));
+        csim_ensemble::Espace& s = e->espace;
+        s.etkf_gamma.swap(gamma);
+        s.etkf_used = used, s.etkf_chi2 = out[ma * ma - 1], s.etkf_dfs = dfs, s.etkf_valid = true;
+        return record ? analysis_record(e, n, x) : CSIM_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_etkf: out of host memory");
+    }
+}
+
+int csim_ensemble_etkf_info(const csim_ensemble* e, long long* n_used, double* chi2, double* dfs, double* gamma,
+                            int* n_gamma) {
+    CSIM_REQUIRE(e, "null ensemble");
+    const csim_ensemble::Espace& s = e->espace;
+    if (!s.etkf_valid)
+        return fail(CSIM_ERR_STATE, "csim_ensemble_etkf_info: the ensemble's last csim_ensemble_assimilate_etkf did not "
+                                    "complete, or there was none");
+    if (n_used) *n_used = s.etkf_used;
+    if (chi2) *chi2 = s.etkf_chi2;
+    if (dfs) *dfs = s.etkf_dfs;
+    if (gamma) std::copy(s.etkf_gamma.begin(), s.etkf_gamma.end(), gamma);
+    if (n_gamma) *n_gamma = static_cast<int>(s.etkf_gamma.size());
+    return CSIM_OK;
 }
 
 int csim_obs_network_local_info(csim_obs_network* n, int* max_local) {

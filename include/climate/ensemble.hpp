@@ -96,6 +96,37 @@ inline SymEigen sym_eigen(const std::vector<double>& A, int n) {
     return e;
 }
 
+// the observation-space Gram matrix of a network (see csim_ensemble_obs_gram): A (M + 1) x (M + 1) row-major, loglik M
+// values (empty when not asked for), and the observations used
+struct ObsGram {
+    std::vector<double> A, loglik;
+    long long n_used = 0;
+};
+// the ETKF's weights (see csim_etkf_weights): Ensemble::transform(W, wbar) is the analysis
+struct EtkfWeights {
+    std::vector<double> W, wbar, gamma;
+    double dfs = 0.0;
+    int sweeps = 0;
+};
+// from the (M + 1) x (M + 1) matrix of Ensemble::obs_gram(), host only
+inline EtkfWeights etkf_weights(const std::vector<double>& A, int M, double inflation = 1.0) {
+    if (M < 0 || A.size() != static_cast<std::size_t>(M + 1) * static_cast<std::size_t>(M + 1))
+        throw std::invalid_argument("etkf_weights: array size");
+    EtkfWeights w;
+    const std::size_t m = static_cast<std::size_t>(M);
+    w.W.resize(m * m), w.wbar.resize(m), w.gamma.resize(m);
+    if (csim_etkf_weights(M, A.data(), inflation, w.W.data(), w.wbar.data(), w.gamma.data(), &w.dfs, &w.sweeps) !=
+        CSIM_OK)
+        throw std::runtime_error(std::string("csim: ") + csim_last_error());
+    return w;
+}
+// what an ETKF analysis found (see csim_ensemble_etkf_info)
+struct EtkfAnalysis {
+    long long n_used = 0;
+    double chi2 = 0.0, dfs = 0.0;
+    std::vector<double> gamma;
+};
+
 // the leading modes of an ensemble's spread (see csim_ensemble_eofs): lambda and variance = lambda / (M - 1) per mode,
 // pcs M x n_modes row-major, patterns n_modes dense fields (empty when not asked for)
 struct EnsembleEOFs {
@@ -485,6 +516,28 @@ public:
     void assimilate_local(ObsNetwork& net, double inflation = 1.0, int t = -1, bool record = false,
                           double screen_tol = 0.0) {
         check(csim_ensemble_assimilate_local(h_, net.handle(), inflation, t, record ? 1 : 0, screen_tol));
+    }
+    // the observation-space Gram matrix of the forecast members over the network's active observations, and with loglik
+    // each member's sum of squared normalised departures; synchronous, writes nothing of the network (see
+    // csim_ensemble_obs_gram)
+    ObsGram obs_gram(ObsNetwork& net, int t = -1, bool loglik = false) {
+        const std::size_t M = forecast(t);
+        ObsGram g;
+        g.A.resize((M + 1) * (M + 1));
+        if (loglik) g.loglik.resize(M);
+        check(csim_ensemble_obs_gram(h_, net.handle(), t, g.A.data(), loglik ? g.loglik.data() : nullptr, &g.n_used));
+        return g;
+    }
+    // the global ETKF analysis with the network's observations: obs_gram() over the used ones, etkf_weights() and
+    // transform() composed in the library; waits for the Gram matrix, the transform is enqueued (see
+    // csim_ensemble_assimilate_etkf); the arguments as for assimilate(ObsNetwork&, ...)
+    EtkfAnalysis assimilate_etkf(ObsNetwork& net, double inflation = 1.0, int t = -1, bool record = false,
+                                 double screen_tol = 0.0) {
+        check(csim_ensemble_assimilate_etkf(h_, net.handle(), inflation, t, record ? 1 : 0, screen_tol));
+        EtkfAnalysis r;
+        r.gamma.resize(forecast(t));
+        check(csim_ensemble_etkf_info(h_, &r.n_used, &r.chi2, &r.dfs, r.gamma.data(), nullptr));
+        return r;
     }
     // the forecast impact of every observation of net's captured analysis on the error of the current state (EFSOI, see
     // csim_ensemble_obs_impact); weight = C (e_a + e_b), member_size() values of which the interior is read.  Synchronous

@@ -980,6 +980,65 @@ int csim_sym_eigen(int n, const double* A, double* lambda, double* V, int* sweep
 int csim_ensemble_eofs(csim_ensemble* e, int truth_member, int n_modes, double* lambda, double* pcs, double* patterns,
                        int* n_valid);
 int csim_ensemble_space_check(int members, int truth_member, int centered, int K, int has_wbar, int n_modes);
+/* ETKF: the global ensemble transform Kalman filter on a network, from an observation-space Gram matrix.  M forecast
+ * members in forecast order, truth member t stepped over, 2 <= M <= CSIM_ESPACE_MAX_MEMBERS (more:
+ * CSIM_ERR_UNSUPPORTED).  Every * + - / sqrt below is one IEEE fp64 operation, no FMA contraction; running sums start
+ * from +0 and take their terms in the stated order.
+ * obs_gram: reduces Y = H X' of a whole network (point or linear) to the ensemble space; synchronous.  The network must
+ *   have values (else CSIM_ERR_STATE); an observation is used when the network's current mask leaves it active; no
+ *   background check is made and nothing of the network is written: no status byte, no flag, no log.  Per plan position
+ *   q, the network's own order (level, then input index; csim_ensemble_assim_plan):
+ *       h_k = the operator value of forecast member k: the point cell's bits, or the tap sum of a linear observation
+ *             as in csim_obs_network_create_linear
+ *       s = sum_k h_k;   hb = s / M;   z_k = (h_k - hb) / sr_q  (k < M);   z_M = (y_q - hb) / sr_q
+ *       e_k = (y_q - h_k) / sr_q
+ *   with sr_q = sqrt(r_q) as the network stores it.  An observation that is not used is not read: all its z and e are
+ *   +0.  A (NULL: not wanted) is (M+1) x (M+1) row-major, A[a][b] = sum_q z_a z_b, symmetric bit for bit: C = A[:M,:M]
+ *   = Y^T R^-1 Y, c = A[:M,M] = Y^T R^-1 (y - hb), A[M][M] the innovation chi^2.  loglik (NULL: not wanted and not
+ *   computed) gets M values, loglik[k] = sum_q e_k e_k: a particle weight is exp(-loglik[k] / 2), normalised by the
+ *   caller.  *n_used (may be NULL): the used observations.  The order of every sum is that of csim_ensemble_gram with plan
+ *   positions in place of cells: segment s holds plan positions 64 s .. 64 s + 63, nseg = ceil(nobs / 64), Gc =
+ *   min(nseg, cap) with gram's cap; class g owns segments g, g + Gc, ... and keeps one running sum per entry in
+ *   increasing q, carried across its segments: acc = acc + (z_a * z_b), and acc = acc + (e_k * e_k); the result is
+ *   partial_0 + partial_1 + ... + partial_{Gc-1}, starting from partial 0.  Nothing depends on the launch geometry.
+ *   obs_gram_plan (host-only): *nseg and *classes = Gc (either may be NULL) for M >= 2 and nobs >= 1.
+ * etkf_weights (host-only): the symmetric square-root ETKF of Hunt et al. 2007 with the multiplicative inflation taken
+ *   in ensemble space.  A as above, C = A[:M,:M]; W is M x M and symmetric bit for bit, wbar and gamma M values; every
+ *   output may be NULL.
+ *       rho = inflation * inflation;   kappa = (double)(M-1) / rho;   (lam, V) = csim_sym_eigen(M, C)
+ *       G_r = lam_r > 0 ? lam_r : +0;   f_r = 1 / (kappa + G_r);   g_r = sqrt((double)(M-1) * f_r)
+ *       u_r = sum_a V[a][r] * A[a][M]  (a ascending);   wbar[a] = sum_r V[a][r] * (f_r * u_r)  (r ascending)
+ *       W[a][b] = sum_r (V[a][r] * g_r) * V[b][r]  for a <= b (r ascending), mirrored into W[b][a]
+ *       gamma[r] = G_r;   *dfs = sum_r G_r * f_r, the degrees of freedom for signal;   *sweeps: those of sym_eigen
+ *   CSIM_ERR_ARG: M < 2, inflation < 1 or not finite, A NULL or with a non-finite entry; CSIM_ERR_UNSUPPORTED: M above
+ *   the limit.  transform(centered = 1, W, wbar) is then the analysis: mean xb + X' wbar, perturbations X' W.
+ * assimilate_etkf: the analysis from these pieces; arguments and errors as csim_ensemble_assimilate_screened, in its
+ *   order and first, then M <= CSIM_ESPACE_MAX_MEMBERS (more: CSIM_ERR_UNSUPPORTED).
+ *   1. Screening exactly as in csim_ensemble_assimilate_screened: (hb, vb), the mask and the background check write the
+ *      status bytes, so status, screen_log and fetch behave as after csim_ensemble_assimilate_network.
+ *   2. A = obs_gram over the observations whose status is CSIM_OBS_USED (all, when nothing is screened); the call
+ *      waits for it.  A non-finite entry of A: CSIM_ERR_STATE, the members untouched and no record appended.
+ *   3. (W, wbar) = etkf_weights(A, inflation);  transform(centered = 1, W, wbar) is enqueued.  With no used
+ *      observation and inflation == 1 no transform is launched and the members keep their bits.
+ *   4. record = 1 appends the two log records as csim_ensemble_assimilate_screened does, (ha, va) taken after the
+ *      transform.
+ *   Where tol = 0 the members are bit for bit those of obs_gram -> etkf_weights -> transform through the public calls.
+ *   The filter is global: the network's loc plays no part.  No field is inflated: the inflation acts only through
+ *   kappa, which equals the other analyses' inflation of the prior perturbations up to rounding, not bit for bit.
+ *   etkf_info: n_used, chi2 = A[M][M], dfs and gamma (M values; *n_gamma = M) of the ensemble's last completed
+ *   assimilate_etkf, every pointer may be NULL; CSIM_ERR_STATE when there is none, or when the last call that passed
+ *   its argument and state checks failed after them.
+ * Not built: localisation of the ETKF, _begin / _wait forms, more than CSIM_ESPACE_MAX_MEMBERS members, a resampling
+ * particle filter on top of loglik, and the forecast impact (impact_capture / obs_impact) after an ETKF. */
+int csim_ensemble_obs_gram(csim_ensemble* e, csim_obs_network* n, int truth_member, double* A, double* loglik,
+                           long long* n_used);
+int csim_obs_gram_plan(int M, int nobs, long* nseg, int* classes);
+int csim_etkf_weights(int M, const double* A, double inflation, double* W, double* wbar, double* gamma, double* dfs,
+                      int* sweeps);
+int csim_ensemble_assimilate_etkf(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
+                                  int record, double tol);
+int csim_ensemble_etkf_info(const csim_ensemble* e, long long* n_used, double* chi2, double* dfs, double* gamma,
+                            int* n_gamma);
 /* options (unknown keys: CSIM_ERR_ARG; "contract": CSIM_ERR_UNSUPPORTED), results never depend on them:
  *   "fuse"        -1 (default) passes of the ensemble depth where the grid allows; 0 / 1 single steps only
  *   "fused_2c"    0/1 (default 1), as for csim_stepper_set_option
@@ -999,7 +1058,10 @@ int csim_ensemble_space_check(int members, int truth_member, int centered, int K
  *   "gram_form"             0 (default: chosen from M) or 1, 2, 3: 1, 2 or 4 blocks of 4 x 4 pairs per lane in the
  *                           class-partial kernel of csim_ensemble_gram; any other value is CSIM_ERR_ARG
  *   "project_form"          0 (default: a cell's members in registers up to M = 64, in LDS above) or 1 (in LDS whatever
- *                           M) in csim_ensemble_project and csim_ensemble_transform; any other value is CSIM_ERR_ARG */
+ *                           M) in csim_ensemble_project and csim_ensemble_transform; any other value is CSIM_ERR_ARG
+ *   "obs_gram_form"         0 (default: chosen from M) or 1, 2, 3: blocks per lane as "gram_form", in the class-partial
+ *                           kernel of csim_ensemble_obs_gram and csim_ensemble_assimilate_etkf; any other value is
+ *                           CSIM_ERR_ARG */
 int csim_ensemble_set_option(csim_ensemble* e, const char* key, long value);
 int csim_ensemble_get_option(const csim_ensemble* e, const char* key, long* value);
 /* host-only pass planner of csim_ensemble_run: out[0] = steps per fused pass (1: none; members with nx or ny below
