@@ -273,6 +273,12 @@ def lib() -> C.CDLL:
         "csim_etkf_weights": (i, [i, dp, d, dp, dp, dp, dp, ip]),
         "csim_ensemble_assimilate_etkf": (i, [vp, vp, d, i, i, d]),
         "csim_ensemble_etkf_info": (i, [vp, C.POINTER(C.c_longlong), dp, dp, dp, ip]),
+        "csim_sym_eigen_ordered": (i, [i, dp, i, dp, dp, ip]),
+        "csim_sym_eigen_batch_gpu": (i, [i, i, dp, dp, dp, ip, ip, i]),
+        "csim_sym_eigen_device_form": (i, [i, i, ip, ip]),
+        "csim_etkf_weights_ordered": (i, [i, dp, d, i, dp, dp, dp, dp, ip]),
+        "csim_ensemble_assimilate_etkf_device": (i, [vp, vp, d, i, i, d]),
+        "csim_ensemble_etkf_info2": (i, [vp, C.POINTER(C.c_longlong), dp, dp, dp, ip, ip, ip]),
         "csim_ensemble_set_option": (i, [vp, C.c_char_p, C.c_long]),
         "csim_ensemble_get_option": (i, [vp, C.c_char_p, C.POINTER(C.c_long)]),
         "csim_ensemble_plan": (i, [i, i, i, i, ip]),
@@ -981,16 +987,53 @@ EnsembleEOFs.__doc__ = """leading modes of an ensemble's spread: eigenvalues of 
 not null"""
 
 
-def sym_eigen(A) -> SymEigen:
+EIGEN_ORDERS = {"rows": 0, "round_robin": 1}  # CSIM_EIGEN_ROWS, CSIM_EIGEN_ROUND_ROBIN
+EIGEN_OK, EIGEN_NONFINITE, EIGEN_NOT_CONVERGED = 0, 1, 2  # CSIM_EIGEN_*
+SYM_EIGEN_MAX_BATCH = 65535  # CSIM_SYM_EIGEN_MAX_BATCH
+SymEigenBatch = collections.namedtuple("SymEigenBatch", "lambda_ V sweeps status")
+SymEigenBatch.__doc__ = """what sym_eigen_batch() returns: per matrix the eigenvalues (batch, n), the eigenvectors
+(batch, n, n), the sweeps made and the status EIGEN_OK, EIGEN_NONFINITE (NaN results) or EIGEN_NOT_CONVERGED"""
+
+
+def _eigen_order(order) -> int:
+    return EIGEN_ORDERS[order] if isinstance(order, str) and order in EIGEN_ORDERS else int(order)
+
+
+def sym_eigen(A, order="rows") -> SymEigen:
     """eigenvalues and eigenvectors of a symmetric matrix by the cyclic Jacobi method, bit for bit the same for every
-    caller (csim_sym_eigen) — host only"""
+    caller; order "rows" takes the pairs of a sweep by rows, "round_robin" in steps of disjoint pairs, the order of
+    sym_eigen_batch() (csim_sym_eigen_ordered) — host only"""
     a = np.ascontiguousarray(A, dtype=np.float64)
     if a.ndim != 2 or a.shape[0] != a.shape[1]:
         raise ValueError("A must be a square matrix")
     n = a.shape[0]
     lam, V, sweeps = np.empty(n), np.empty((n, n)), C.c_int()
-    _ck(lib().csim_sym_eigen(n, _dp(a), _dp(lam), _dp(V), C.byref(sweeps)))
+    _ck(lib().csim_sym_eigen_ordered(n, _dp(a), _eigen_order(order), _dp(lam), _dp(V), C.byref(sweeps)))
     return SymEigen(lam, V, sweeps.value)
+
+
+def sym_eigen_batch(A, form=0) -> SymEigenBatch:
+    """the symmetric matrices A[b] (batch, n, n) on the GPU, one workgroup per matrix, bit for bit
+    sym_eigen(A[b], order="round_robin"); form forces a storage form of sym_eigen_device_form()
+    (csim_sym_eigen_batch_gpu)"""
+    a = np.ascontiguousarray(A, dtype=np.float64)
+    if a.ndim != 3 or a.shape[1] != a.shape[2]:
+        raise ValueError("A must have shape (batch, n, n)")
+    batch, n = a.shape[0], a.shape[1]
+    lam, V = np.empty((batch, n)), np.empty((batch, n, n))
+    sweeps, status = np.zeros(batch, dtype=np.int32), np.zeros(batch, dtype=np.int32)
+    _ck(lib().csim_sym_eigen_batch_gpu(n, batch, _dp(a), _dp(lam), _dp(V), sweeps.ctypes.data_as(C.POINTER(C.c_int)),
+                                       status.ctypes.data_as(C.POINTER(C.c_int)), int(form)))
+    return SymEigenBatch(lam, V, sweeps, status)
+
+
+def sym_eigen_device_form(n: int, form: int = 0):
+    """(chosen, max_n): the storage form sym_eigen_batch() takes for n (1: both working matrices in LDS, 2: the matrix
+    in LDS and the vectors in global memory, 3: both in global memory) and the largest n that `form` admits
+    (csim_sym_eigen_device_form) — host only"""
+    chosen, most = C.c_int(), C.c_int()
+    _ck(lib().csim_sym_eigen_device_form(int(n), int(form), C.byref(chosen), C.byref(most)))
+    return chosen.value, most.value
 
 
 def ensemble_gram_plan(M: int, nx: int, ny: int):
@@ -1011,6 +1054,9 @@ eigenvalues of Y^T R^-1 Y clamped at 0, dfs the degrees of freedom for signal, s
 EtkfAnalysis = collections.namedtuple("EtkfAnalysis", "n_used chi2 gamma dfs")
 EtkfAnalysis.__doc__ = """what Ensemble.assimilate_etkf() returns: the observations used, the innovation chi^2, and gamma
 and dfs of its weights"""
+EtkfInfo = collections.namedtuple("EtkfInfo", "n_used chi2 gamma dfs sweeps status")
+EtkfInfo.__doc__ = """what Ensemble.etkf_info() returns: EtkfAnalysis' fields, and after assimilate_etkf(device=True) the
+device eigensolver's sweeps and status (EIGEN_OK or EIGEN_NOT_CONVERGED)"""
 
 
 def obs_gram_plan(M: int, nobs: int):
@@ -1021,17 +1067,17 @@ def obs_gram_plan(M: int, nobs: int):
     return nseg.value, gc.value
 
 
-def etkf_weights(A, inflation=1.0) -> EtkfWeights:
+def etkf_weights(A, inflation=1.0, order="rows") -> EtkfWeights:
     """the symmetric square-root ETKF in ensemble space from the (M+1, M+1) matrix of Ensemble.obs_gram(), inflation
-    taken in ensemble space (csim_etkf_weights) — host only"""
+    taken in ensemble space, on sym_eigen(order=order) (csim_etkf_weights_ordered) — host only"""
     a = np.ascontiguousarray(A, dtype=np.float64)
     if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 1:
         raise ValueError("A must be a square matrix, (M+1, M+1)")
     M = a.shape[0] - 1
     W, wbar, gamma = np.empty((M, M)), np.empty(M), np.empty(M)
     dfs, sweeps = C.c_double(), C.c_int()
-    _ck(lib().csim_etkf_weights(M, _dp(a), float(inflation), _dp(W), _dp(wbar), _dp(gamma), C.byref(dfs),
-                                C.byref(sweeps)))
+    _ck(lib().csim_etkf_weights_ordered(M, _dp(a), float(inflation), _eigen_order(order), _dp(W), _dp(wbar),
+                                        _dp(gamma), C.byref(dfs), C.byref(sweeps)))
     return EtkfWeights(W, wbar, gamma, dfs.value, sweeps.value)
 
 
@@ -1465,13 +1511,19 @@ class Ensemble:
         return ObsGram(A, ll, used.value)
 
     def assimilate_etkf(self, net: ObsNetwork, inflation=1.0, truth_member=None, record=False,
-                        screen=None) -> EtkfAnalysis:
+                        screen=None, device=False):
         """the global ETKF analysis with the network's observations: obs_gram() over the used ones, etkf_weights() and
         transform() composed in the library; waits for the Gram matrix, the transform is enqueued.  inflation (taken in
         ensemble space), truth_member, record and screen as in assimilate_network; the network's loc plays no part
-        (csim_ensemble_assimilate_etkf)"""
+        (csim_ensemble_assimilate_etkf).  device=True: the eigensolver and the weights run on the GPU in the
+        round-robin order, the call only enqueues and returns None; etkf_info() waits and tells what it found
+        (csim_ensemble_assimilate_etkf_device)"""
         tm, M = self._forecast(truth_member)
         rec = record if isinstance(record, int) else int(bool(record))
+        if device:
+            _ck(lib().csim_ensemble_assimilate_etkf_device(self._h, net._h, float(inflation), tm, rec,
+                                                           0.0 if screen is None else float(screen)))
+            return None
         _ck(lib().csim_ensemble_assimilate_etkf(self._h, net._h, float(inflation), tm, rec,
                                                 0.0 if screen is None else float(screen)))
         used, chi2, dfs, ng = C.c_longlong(), C.c_double(), C.c_double(), C.c_int()
@@ -1479,6 +1531,16 @@ class Ensemble:
         _ck(lib().csim_ensemble_etkf_info(self._h, C.byref(used), C.byref(chi2), C.byref(dfs), _dp(gamma),
                                           C.byref(ng)))
         return EtkfAnalysis(used.value, chi2.value, gamma, dfs.value)
+
+    def etkf_info(self) -> EtkfInfo:
+        """what the ensemble's last assimilate_etkf() found; after device=True it waits for the stream first, and a
+        non-finite Gram matrix, which left the members unchanged, raises CsimError (csim_ensemble_etkf_info2)"""
+        used, chi2, dfs, ng = C.c_longlong(), C.c_double(), C.c_double(), C.c_int()
+        sweeps, status = C.c_int(), C.c_int()
+        gamma = np.empty(ESPACE_MAX_MEMBERS)
+        _ck(lib().csim_ensemble_etkf_info2(self._h, C.byref(used), C.byref(chi2), C.byref(dfs), _dp(gamma),
+                                           C.byref(ng), C.byref(sweeps), C.byref(status)))
+        return EtkfInfo(used.value, chi2.value, gamma[:ng.value].copy(), dfs.value, sweeps.value, status.value)
 
     def obs_impact(self, net: ObsNetwork, weight) -> ObsImpact:
         """the forecast impact J_o of every observation of net's captured analysis on the error of the current

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "ensemble_host.hpp"
+#include "sym_eigen.hpp"
 
 using namespace csim;
 
@@ -330,6 +331,9 @@ int csim_ensemble_set_option(csim_ensemble* e, const char* key, long value) {
     } else if (k == "obs_gram_form") {
         CSIM_REQUIRE(value >= 0 && value <= OBS_GRAM_FORMS, "obs_gram_form must be 0 (automatic) or 1 .. 3");
         e->espace.obs_gram_form = static_cast<int>(value);
+    } else if (k == "eigen_form") {
+        CSIM_REQUIRE(value >= 0 && value <= EIGEN_FORMS, "eigen_form must be 0 (automatic) or 1 .. 3");
+        e->espace.eigen_form = static_cast<int>(value);
     } else if (k == "depth_used") {
         return fail(CSIM_ERR_ARG, "option depth_used is read-only");
     } else if (k == "contract") {
@@ -367,6 +371,8 @@ int csim_ensemble_get_option(const csim_ensemble* e, const char* key, long* valu
         *value = e->espace.project_form;
     else if (k == "obs_gram_form")
         *value = e->espace.obs_gram_form;
+    else if (k == "eigen_form")
+        *value = e->espace.eigen_form;
     else if (k == "contract")
         return fail(CSIM_ERR_UNSUPPORTED, "an ensemble is always bit-identical: no contract mode");
     else

@@ -330,9 +330,11 @@ hipError_t ens_launch_gram(const EnsGeom& g, const double* f, int forecast, int 
 hipError_t ens_launch_project(const EnsGeom& g, const double* f, int forecast, int truth_member, bool centered, int K,
                               const double* W, double* out, int form, hipStream_t st);
 // x_r <- (m + sum_k p_k wbar[k]) + sum_k p_k W[k M + r] (centered; wbar null: m) or sum_k p_k W[k M + r] on every
-// interior cell of the forecast members, in place
+// interior cell of the forecast members, in place.  gate (device, may be null): the status word of an EtkfRecord; the
+// kernel writes nothing when it reads ETKF_NONFINITE or ETKF_SKIP there
 hipError_t ens_launch_transform(const EnsGeom& g, double* f, int forecast, int truth_member, bool centered,
-                                const double* W, const double* wbar, int form, hipStream_t st);
+                                const double* W, const double* wbar, int form, hipStream_t st,
+                                const int* gate = nullptr);
 
 // the observation-space Gram matrix of csim_ensemble_obs_gram (ensemble_obsgram.hip): A = Z^T Z, (M + 1) x (M + 1), of
 // the normalised observation-space perturbations of a network, and the members' sums of squared normalised departures.
@@ -359,6 +361,27 @@ size_t ens_obs_gram_partial_doubles(int forecast, int nobs);
 // one long long.  form: 0 (the launcher's choice) or 1 .. OBS_GRAM_FORMS; the result does not depend on it
 hipError_t ens_launch_obs_gram(const EnsGeom& g, const double* f, const ObsGramArgs& a, bool want_loglik,
                                double* partial, double* out, int form, hipStream_t st);
+
+// the device eigensolver and the ETKF's weights on the device (sym_eigen_device.hip), in the round-robin order of
+// include/csim.h.  `batch` matrices of n x n (rows lda doubles apart, a_stride doubles from one to the next), one
+// workgroup each; work: 2 n^2 doubles per matrix; lambda: n, V: n x n per matrix; info: sweeps and status (EIGEN_*)
+// per matrix.  A matrix with a non-finite entry gets NaN in lambda and V.  form: 0 (by n) or 1 .. EIGEN_FORMS of
+// sym_eigen.hpp; the result does not depend on it
+hipError_t ens_launch_sym_eigen(int n, int batch, const double* A, int lda, long a_stride, double* work,
+                                double* lambda, double* V, int* info, int form, hipStream_t st);
+// what a device ETKF leaves for csim_ensemble_etkf_info, followed by gamma (M doubles)
+struct EtkfRecord {
+    double dfs, chi2;
+    long long n_used;
+    int sweeps, status;  // ETKF_*
+};
+constexpr int ETKF_OK = 0, ETKF_NONFINITE = 1, ETKF_NOT_CONVERGED = 2, ETKF_SKIP = 3;
+// W (M x M) and wbar of csim_etkf_weights_ordered(order = round robin) from the output of ens_launch_obs_gram (A) and
+// of ens_launch_sym_eigen on its leading M x M block (lambda, V, info); the record and gamma.  status: ETKF_NONFINITE
+// when an entry of A is not finite, else ETKF_SKIP with no used observation and inflation 1, else the solver's
+hipError_t ens_launch_etkf_weights(int M, const double* A, const double* lambda, const double* V, const int* info,
+                                   double inflation, double* W, double* wbar, EtkfRecord* rec, double* gamma,
+                                   hipStream_t st);
 
 // the rank histogram's tie-break: splitmix64's finaliser of the interior index g; a cell with `eq` members equal to the
 // truth goes to bin lt + mix(g) mod (eq + 1)

@@ -113,7 +113,16 @@ struct csim_ensemble {
         long long etkf_used = 0;
         double etkf_chi2 = 0.0, etkf_dfs = 0.0;
         std::vector<double> etkf_gamma;
-        void release() { partial.release(), gram.release(), out.release(), w.release(), stage.release(); }
+        // the device ETKF (csim_ensemble_assimilate_etkf_device): the solver's working matrices, V, lambda and info, and
+        // the record with gamma behind it (EtkfLayout); csim_ensemble_etkf_info fetches a pending record
+        csim::DeviceBuf eig;
+        int eigen_form = 0;                   // option eigen_form; 0: by the number of members
+        bool etkf_pending = false;            // the last ETKF was enqueued by the device path: its record is on the device
+        int etkf_m = 0;                       // its forecast members
+        int etkf_sweeps = 0, etkf_status = 0; // of the record fetched last (0 after a host-path ETKF)
+        void release() {
+            partial.release(), gram.release(), out.release(), w.release(), eig.release(), stage.release();
+        }
     } espace;
     // observation networks (csim_obs_network_*, ensemble_obs.cpp): the ones that are alive; each owns its device buffer
     struct Obs {
@@ -133,6 +142,15 @@ struct csim_ensemble {
 };
 
 namespace csim {
+// the doubles of Espace::eig for M forecast members
+struct EtkfLayout {
+    size_t work, V, lam, rec, gamma, info, doubles;
+    explicit EtkfLayout(int M) {
+        const size_t m = static_cast<size_t>(M);
+        static_assert(sizeof(EtkfRecord) == 4 * sizeof(double), "the record is four doubles, gamma follows it");
+        work = 0, V = 2 * m * m, lam = V + m * m, rec = lam + m, gamma = rec + 4, info = gamma + m, doubles = info + 1;
+    }
+};
 // cells of a dense per-cell field, ghost ring included
 inline size_t stats_cells(const csim_ensemble* e) { return static_cast<size_t>(e->g.nx + 2) * (e->g.ny + 2); }
 

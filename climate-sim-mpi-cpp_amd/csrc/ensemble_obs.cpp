@@ -21,6 +21,7 @@
 
 #include "ensemble_host.hpp"
 #include "ensemble_noise.hpp"
+#include "sym_eigen.hpp"
 
 using namespace csim;
 
@@ -295,9 +296,10 @@ int analysis_record(csim_ensemble* e, csim_obs_network* n, const Analysis& x) {
 
 // csim_ensemble_obs_gram and step 3 of csim_ensemble_assimilate_etkf: A, loglik (with want_ll) and the count of the
 // observations whose flag byte is `used` (flag null: all), synchronous.  *out: (M + 1)^2 + M doubles, A first.  The
-// class partials and the result use the buffers of csim_ensemble_gram, which is synchronous as well
-int obs_gram(csim_ensemble* e, csim_obs_network* n, int M, int t, const unsigned char* flag, int used, bool want_ll,
-             std::vector<double>* out, long long* n_used) {
+// class partials and the result use the buffers of csim_ensemble_gram, which is synchronous as well.
+// obs_gram_enqueue only launches and leaves the result in Espace::gram
+int obs_gram_enqueue(csim_ensemble* e, csim_obs_network* n, int M, int t, const unsigned char* flag, int used,
+                     bool want_ll) {
     csim_ensemble::Espace& x = e->espace;
     const ObsArgs oa = n->args();
     ObsGramArgs a{};
@@ -309,6 +311,14 @@ int obs_gram(csim_ensemble* e, csim_obs_network* n, int M, int t, const unsigned
     CSIM_TRY(x.partial.reserve(sizeof(double) * ens_obs_gram_partial_doubles(M, n->nobs), e->st));
     CSIM_TRY(x.gram.reserve(sizeof(double) * doubles, e->st));
     CSIM_HIP(ens_launch_obs_gram(e->g, e->base(e->cur), a, want_ll, x.partial.as(), x.gram.as(), x.obs_gram_form, e->st));
+    return CSIM_OK;
+}
+
+int obs_gram(csim_ensemble* e, csim_obs_network* n, int M, int t, const unsigned char* flag, int used, bool want_ll,
+             std::vector<double>* out, long long* n_used) {
+    csim_ensemble::Espace& x = e->espace;
+    const size_t ma = static_cast<size_t>(M) + 1, doubles = ma * ma + M + 1;
+    CSIM_TRY(obs_gram_enqueue(e, n, M, t, flag, used, want_ll));
     out->resize(doubles);
     CSIM_HIP(hipMemcpyAsync(out->data(), x.gram.p, sizeof(double) * doubles, hipMemcpyDeviceToHost, e->st));
     CSIM_HIP(hipStreamSynchronize(e->st));
@@ -550,7 +560,7 @@ int csim_ensemble_assimilate_etkf(csim_ensemble* e, csim_obs_network* n, double 
         long long used = 0;
         double dfs = 0.0;
         Analysis x;
-        e->espace.etkf_valid = false;
+        e->espace.etkf_valid = false, e->espace.etkf_pending = false;
         CSIM_TRY(analysis_begin(e, n, M, t, record, tol, &x));
         CSIM_TRY(obs_gram(e, n, M, t, x.screen ? x.s.status : nullptr, CSIM_OBS_USED, false, &out, &used));
         for (size_t k = 0; k < ma * ma; ++k)
@@ -563,16 +573,76 @@ int csim_ensemble_assimilate_etkf(csim_ensemble* e, csim_obs_network* n, double 
         csim_ensemble::Espace& s = e->espace;
         s.etkf_gamma.swap(gamma);
         s.etkf_used = used, s.etkf_chi2 = out[ma * ma - 1], s.etkf_dfs = dfs, s.etkf_valid = true;
+        s.etkf_sweeps = 0, s.etkf_status = CSIM_EIGEN_OK;
         return record ? analysis_record(e, n, x) : CSIM_OK;
     } catch (const std::bad_alloc&) {
         return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_etkf: out of host memory");
     }
 }
 
-int csim_ensemble_etkf_info(const csim_ensemble* e, long long* n_used, double* chi2, double* dfs, double* gamma,
-                            int* n_gamma) {
+int csim_ensemble_assimilate_etkf_device(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
+                                         int record, double tol) {
+    int M = 0, t = 0;
+    CSIM_TRY(analysis_check(e, n, inflation, truth_member, record, tol, &M, &t));
+    if (M > ESPACE_MAX_MEMBERS)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_etkf: at most CSIM_ESPACE_MAX_MEMBERS forecast "
+                                          "members");
+    CSIM_REQUIRE(e->g.slab <= 0x7fffffffL, "grid too large for the ensemble-space kernels");
+    csim_ensemble::Espace& s = e->espace;
+    if (!eigen_device_form(M, s.eigen_form))
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_etkf_device: the eigen_form that is set does not "
+                                          "admit this many forecast members");
+    const size_t m = static_cast<size_t>(M);
+    const EtkfLayout l(M);
+    s.etkf_valid = false, s.etkf_pending = false;
+    CSIM_TRY(s.w.reserve(sizeof(double) * (m * m + m), e->st));
+    CSIM_TRY(s.eig.reserve(sizeof(double) * l.doubles, e->st));
+    Analysis x;
+    CSIM_TRY(analysis_begin(e, n, M, t, record, tol, &x));
+    CSIM_TRY(obs_gram_enqueue(e, n, M, t, x.screen ? x.s.status : nullptr, CSIM_OBS_USED, false));
+    double* d = s.eig.as();
+    int* info = reinterpret_cast<int*>(d + l.info);
+    auto* rec = reinterpret_cast<EtkfRecord*>(d + l.rec);
+    CSIM_HIP(ens_launch_sym_eigen(M, 1, s.gram.as(), M + 1, 0, d + l.work, d + l.lam, d + l.V, info, s.eigen_form,
+                                  e->st));
+    CSIM_HIP(ens_launch_etkf_weights(M, s.gram.as(), d + l.lam, d + l.V, info, inflation, s.w.as(), s.w.as() + m * m,
+                                     rec, d + l.gamma, e->st));
+    // as csim_ensemble_transform: only interior cells of the forecast members in the current buffer are written; the
+    // kernel returns at once where the record says that there is nothing to do or that A is not finite
+    CSIM_HIP(ens_launch_transform(e->g, e->base(e->cur), M, t, true, s.w.as(), s.w.as() + m * m, s.project_form, e->st,
+                                  &rec->status));
+    s.etkf_pending = true, s.etkf_m = M;
+    return record ? analysis_record(e, n, x) : CSIM_OK;
+}
+
+int csim_ensemble_etkf_info2(csim_ensemble* e, long long* n_used, double* chi2, double* dfs, double* gamma,
+                             int* n_gamma, int* sweeps, int* status) {
     CSIM_REQUIRE(e, "null ensemble");
-    const csim_ensemble::Espace& s = e->espace;
+    csim_ensemble::Espace& s = e->espace;
+    if (s.etkf_pending) {
+        // the record of the device path: wait for the stream and fetch it, once
+        const EtkfLayout l(s.etkf_m);
+        try {
+            std::vector<double> got(4 + static_cast<size_t>(s.etkf_m));
+            CSIM_HIP(hipMemcpyAsync(got.data(), s.eig.as() + l.rec, sizeof(double) * got.size(), hipMemcpyDeviceToHost,
+                                    e->st));
+            CSIM_HIP(hipStreamSynchronize(e->st));
+            EtkfRecord rec;
+            std::memcpy(&rec, got.data(), sizeof rec);
+            s.etkf_pending = false;
+            s.etkf_sweeps = rec.sweeps;
+            s.etkf_status = rec.status == ETKF_NONFINITE        ? CSIM_EIGEN_NONFINITE
+                            : rec.status == ETKF_NOT_CONVERGED ? CSIM_EIGEN_NOT_CONVERGED
+                                                               : CSIM_EIGEN_OK;
+            if (rec.status == ETKF_NONFINITE)
+                return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_etkf: the observation-space Gram matrix has a "
+                                            "non-finite entry; the members are unchanged");
+            s.etkf_gamma.assign(got.begin() + 4, got.end());
+            s.etkf_used = rec.n_used, s.etkf_chi2 = rec.chi2, s.etkf_dfs = rec.dfs, s.etkf_valid = true;
+        } catch (const std::bad_alloc&) {
+            return fail(CSIM_ERR_STATE, "csim_ensemble_etkf_info: out of host memory");
+        }
+    }
     if (!s.etkf_valid)
         return fail(CSIM_ERR_STATE, "csim_ensemble_etkf_info: the ensemble's last csim_ensemble_assimilate_etkf did not "
                                     "complete, or there was none");
@@ -581,7 +651,15 @@ int csim_ensemble_etkf_info(const csim_ensemble* e, long long* n_used, double* c
     if (dfs) *dfs = s.etkf_dfs;
     if (gamma) std::copy(s.etkf_gamma.begin(), s.etkf_gamma.end(), gamma);
     if (n_gamma) *n_gamma = static_cast<int>(s.etkf_gamma.size());
+    if (sweeps) *sweeps = s.etkf_sweeps;
+    if (status) *status = s.etkf_status;
     return CSIM_OK;
+}
+
+int csim_ensemble_etkf_info(const csim_ensemble* e, long long* n_used, double* chi2, double* dfs, double* gamma,
+                            int* n_gamma) {
+    // a pending record of the device path is fetched into the handle, which this older signature declares const
+    return csim_ensemble_etkf_info2(const_cast<csim_ensemble*>(e), n_used, chi2, dfs, gamma, n_gamma, nullptr, nullptr);
 }
 
 int csim_obs_network_local_info(csim_obs_network* n, int* max_local) {

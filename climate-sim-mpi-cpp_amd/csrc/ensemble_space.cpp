@@ -92,6 +92,76 @@ int csim_sym_eigen(int n, const double* A, double* lambda, double* V, int* sweep
     return CSIM_OK;
 }
 
+int csim_sym_eigen_ordered(int n, const double* A, int order, double* lambda, double* V, int* sweeps) {
+    CSIM_REQUIRE(A && lambda && V, "null argument");
+    CSIM_REQUIRE(n >= 1, "n must be >= 1");
+    if (n > SYM_EIGEN_MAX_N) return fail(CSIM_ERR_UNSUPPORTED, "csim_sym_eigen: n is at most CSIM_SYM_EIGEN_MAX_N");
+    CSIM_REQUIRE(order == CSIM_EIGEN_ROWS || order == CSIM_EIGEN_ROUND_ROBIN,
+                 "order must be CSIM_EIGEN_ROWS or CSIM_EIGEN_ROUND_ROBIN");
+    CSIM_REQUIRE(sym_eigen_ordered(n, A, order, lambda, V, sweeps), "csim_sym_eigen: a non-finite entry");
+    return CSIM_OK;
+}
+
+int csim_sym_eigen_device_form(int n, int form, int* chosen, int* max_n) {
+    CSIM_REQUIRE(form >= 0 && form <= EIGEN_FORMS, "form must be 0 (automatic) or 1 .. 3");
+    CSIM_REQUIRE(n >= 1, "n must be >= 1");
+    if (n > SYM_EIGEN_MAX_N) return fail(CSIM_ERR_UNSUPPORTED, "csim_sym_eigen: n is at most CSIM_SYM_EIGEN_MAX_N");
+    if (max_n) *max_n = form ? eigen_form_max_n(form) : SYM_EIGEN_MAX_N;
+    if (!eigen_device_form(n, form))
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_sym_eigen_device_form: the form does not admit this n");
+    if (chosen) *chosen = eigen_device_form(n, form);
+    return CSIM_OK;
+}
+
+int csim_sym_eigen_batch_gpu(int n, int batch, const double* A, double* lambda, double* V, int* sweeps, int* status,
+                             int form) {
+    CSIM_REQUIRE(A && lambda && V, "null argument");
+    CSIM_REQUIRE(n >= 1, "n must be >= 1");
+    CSIM_REQUIRE(batch >= 1 && batch <= CSIM_SYM_EIGEN_MAX_BATCH, "batch must be 1 .. CSIM_SYM_EIGEN_MAX_BATCH");
+    CSIM_TRY(csim_sym_eigen_device_form(n, form, nullptr, nullptr));
+    // the call owns what it needs: a stream and one buffer for a chunk of the batch (inputs, working matrices, V, lambda
+    // and info), at most 512 MiB, so that any batch runs in bounded memory
+    const size_t nn = static_cast<size_t>(n) * n, per = 4 * nn + n + 1;  // doubles per matrix
+    const int chunk = static_cast<int>(std::clamp<size_t>((size_t(1) << 26) / per, 1, static_cast<size_t>(batch)));
+    DeviceBuf buf;
+    hipStream_t st = nullptr;
+    CSIM_HIP(hipStreamCreate(&st));
+    auto run = [&]() -> int {
+        CSIM_TRY(buf.reserve(sizeof(double) * per * chunk));
+        double* dA = buf.as();
+        double* work = dA + nn * chunk;
+        double* dV = work + 2 * nn * chunk;
+        double* dl = dV + nn * chunk;
+        int* info = reinterpret_cast<int*>(dl + static_cast<size_t>(n) * chunk);
+        std::vector<int> got(2 * static_cast<size_t>(chunk));
+        for (int b0 = 0; b0 < batch; b0 += chunk) {
+            const int nb = std::min(chunk, batch - b0);
+            CSIM_HIP(hipMemcpyAsync(dA, A + nn * b0, sizeof(double) * nn * nb, hipMemcpyHostToDevice, st));
+            CSIM_HIP(ens_launch_sym_eigen(n, nb, dA, n, static_cast<long>(nn), work, dl, dV, info, form, st));
+            CSIM_HIP(hipMemcpyAsync(lambda + static_cast<size_t>(n) * b0, dl, sizeof(double) * n * nb,
+                                    hipMemcpyDeviceToHost, st));
+            CSIM_HIP(hipMemcpyAsync(V + nn * b0, dV, sizeof(double) * nn * nb, hipMemcpyDeviceToHost, st));
+            CSIM_HIP(hipMemcpyAsync(got.data(), info, sizeof(int) * 2 * nb, hipMemcpyDeviceToHost, st));
+            CSIM_HIP(hipStreamSynchronize(st));
+            for (int b = 0; b < nb; ++b) {
+                if (sweeps) sweeps[b0 + b] = got[2 * static_cast<size_t>(b)];
+                if (status) status[b0 + b] = got[2 * static_cast<size_t>(b) + 1];
+            }
+        }
+        return CSIM_OK;
+    };
+    int rc = CSIM_OK;
+    try {
+        rc = run();
+    } catch (const std::bad_alloc&) {
+        rc = fail(CSIM_ERR_STATE, "csim_sym_eigen_batch_gpu: out of host memory");
+    }
+    (void)hipStreamSynchronize(st);
+    (void)hipStreamDestroy(st);
+    buf.release();
+    return rc;
+}
+
 int csim_ensemble_gram(csim_ensemble* e, int truth_member, int centered, double* G) {
     CSIM_REQUIRE(e && G, "null argument");
     int M = 0, t = 0;

@@ -161,8 +161,11 @@ constexpr int APPLY_WAVES = 4;  // LDS form: waves that share one tile of 64 cel
 template <int P, bool XFORM>
 __global__ __launch_bounds__(P > 0 ? 64 : 64 * APPLY_WAVES) void k_espace_apply(double* __restrict__ f, int nx, int ny, int pitch, long slab,
                                                      int M, int t, int centered, int K, const double* __restrict__ W,
-                                                     const double* __restrict__ wbar, double* __restrict__ out) {
+                                                     const double* __restrict__ wbar, double* __restrict__ out,
+                                                     const int* __restrict__ gate) {
     extern __shared__ __attribute__((aligned(16))) double held[];  // P = 0: [M][64]
+    // the transform of a device ETKF obeys the status its weights kernel left: the whole grid returns at once
+    if (XFORM && gate && (*gate == ETKF_NONFINITE || *gate == ETKF_SKIP)) return;
     constexpr int NW = P > 0 ? 1 : APPLY_WAVES;
     // the register form is one wave: `wave` is a constant 0 there, so the loop over the outputs keeps no state for it
     const int lane = threadIdx.x & 63, wave = P > 0 ? 0 : threadIdx.x >> 6;
@@ -276,7 +279,7 @@ unsigned apply_blocks(long cells) { return static_cast<unsigned>(std::min((cells
 
 template <bool XFORM>
 hipError_t launch_apply(const EnsGeom& g, double* f, int M, int t, bool centered, int K, const double* W,
-                        const double* wbar, double* out, int form, hipStream_t st) {
+                        const double* wbar, double* out, int form, hipStream_t st, const int* gate = nullptr) {
     const long cells = XFORM ? static_cast<long>(g.nx) * g.ny : static_cast<long>(g.nx + 2) * (g.ny + 2);
     auto launch = [&](auto s) {
         constexpr int P = decltype(s)::value;
@@ -287,7 +290,7 @@ hipError_t launch_apply(const EnsGeom& g, double* f, int M, int t, bool centered
             if (attr != hipSuccess) return attr;
         }
         hipLaunchKernelGGL((k_espace_apply<P, XFORM>), dim3(apply_blocks(cells)), dim3(P > 0 ? 64 : 64 * APPLY_WAVES), lds, st, f, g.nx, g.ny,
-                           g.pitch, g.slab, M, t, centered ? 1 : 0, K, W, wbar, out);
+                           g.pitch, g.slab, M, t, centered ? 1 : 0, K, W, wbar, out, gate);
         return hipGetLastError();
     };
     if (form == 1) return launch(Step<0>{});
@@ -315,9 +318,9 @@ hipError_t ens_launch_project(const EnsGeom& g, const double* f, int forecast, i
 }
 
 hipError_t ens_launch_transform(const EnsGeom& g, double* f, int forecast, int truth_member, bool centered,
-                                const double* W, const double* wbar, int form, hipStream_t st) {
+                                const double* W, const double* wbar, int form, hipStream_t st, const int* gate) {
     if (!espace_ok(forecast, form, PROJECT_FORMS) || (wbar && !centered)) return hipErrorInvalidValue;
-    return launch_apply<true>(g, f, forecast, truth_member, centered, forecast, W, wbar, nullptr, form, st);
+    return launch_apply<true>(g, f, forecast, truth_member, centered, forecast, W, wbar, nullptr, form, st, gate);
 }
 
 }  // namespace csim

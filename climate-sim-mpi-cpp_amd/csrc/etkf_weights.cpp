@@ -33,11 +33,18 @@ int csim_obs_gram_plan(int M, int nobs, long* nseg, int* classes) {
 
 int csim_etkf_weights(int M, const double* A, double inflation, double* W, double* wbar, double* gamma, double* dfs,
                       int* sweeps) {
+    return csim_etkf_weights_ordered(M, A, inflation, CSIM_EIGEN_ROWS, W, wbar, gamma, dfs, sweeps);
+}
+
+int csim_etkf_weights_ordered(int M, const double* A, double inflation, int order, double* W, double* wbar,
+                              double* gamma, double* dfs, int* sweeps) {
     OBS_REQUIRE(M >= 2, "M must be >= 2");
     if (M > OBS_GRAM_MAX_MEMBERS)
         return fail(CSIM_ERR_UNSUPPORTED, "csim_etkf_weights: at most CSIM_ESPACE_MAX_MEMBERS forecast members");
     OBS_REQUIRE(std::isfinite(inflation) && inflation >= 1.0, "inflation must be finite and >= 1");
     OBS_REQUIRE(A, "null argument");
+    OBS_REQUIRE(order == CSIM_EIGEN_ROWS || order == CSIM_EIGEN_ROUND_ROBIN, "order must be CSIM_EIGEN_ROWS or "
+                                                                             "CSIM_EIGEN_ROUND_ROBIN");
     const size_t m = static_cast<size_t>(M), ma = m + 1;
     for (size_t k = 0; k < ma * ma; ++k) OBS_REQUIRE(std::isfinite(A[k]), "csim_etkf_weights: a non-finite entry of A");
     try {
@@ -45,7 +52,8 @@ int csim_etkf_weights(int M, const double* A, double inflation, double* W, doubl
         for (size_t a = 0; a < m; ++a)
             for (size_t b = 0; b < m; ++b) C[a * m + b] = A[a * ma + b];
         int done = 0;
-        OBS_REQUIRE(sym_eigen(M, C.data(), lam.data(), V.data(), &done), "csim_etkf_weights: a non-finite entry of A");
+        OBS_REQUIRE(sym_eigen_ordered(M, C.data(), order, lam.data(), V.data(), &done),
+                    "csim_etkf_weights: a non-finite entry of A");
         const double rho = inflation * inflation;
         const double kappa = static_cast<double>(M - 1) / rho;
         double d = 0.0;

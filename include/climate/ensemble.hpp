@@ -84,14 +84,34 @@ struct SymEigen {
     std::vector<double> lambda, V;
     int sweeps = 0;
 };
-// cyclic Jacobi on the n x n row-major symmetric matrix A, host only (see csim_sym_eigen)
-inline SymEigen sym_eigen(const std::vector<double>& A, int n) {
+// cyclic Jacobi on the n x n row-major symmetric matrix A, host only (see csim_sym_eigen_ordered); order
+// CSIM_EIGEN_ROWS or CSIM_EIGEN_ROUND_ROBIN, the order of the device solver
+inline SymEigen sym_eigen(const std::vector<double>& A, int n, int order = CSIM_EIGEN_ROWS) {
     if (n < 0 || A.size() != static_cast<std::size_t>(n) * static_cast<std::size_t>(n))
         throw std::invalid_argument("sym_eigen: array size");
     SymEigen e;
     e.lambda.resize(static_cast<std::size_t>(n));
     e.V.resize(A.size());
-    if (csim_sym_eigen(n, A.data(), e.lambda.data(), e.V.data(), &e.sweeps) != CSIM_OK)
+    if (csim_sym_eigen_ordered(n, A.data(), order, e.lambda.data(), e.V.data(), &e.sweeps) != CSIM_OK)
+        throw std::runtime_error(std::string("csim: ") + csim_last_error());
+    return e;
+}
+// `batch` symmetric matrices, n x n row-major one after the other, on the GPU in the round-robin order, one workgroup
+// each (see csim_sym_eigen_batch_gpu); status per matrix: CSIM_EIGEN_OK, _NONFINITE (NaN results) or _NOT_CONVERGED
+struct SymEigenBatch {
+    std::vector<double> lambda, V;
+    std::vector<int> sweeps, status;
+};
+inline SymEigenBatch sym_eigen_batch(const std::vector<double>& A, int n, int batch, int form = 0) {
+    if (n < 0 || batch < 0 ||
+        A.size() != static_cast<std::size_t>(batch) * static_cast<std::size_t>(n) * static_cast<std::size_t>(n))
+        throw std::invalid_argument("sym_eigen_batch: array size");
+    SymEigenBatch e;
+    e.lambda.resize(static_cast<std::size_t>(batch) * static_cast<std::size_t>(n));
+    e.V.resize(A.size());
+    e.sweeps.resize(static_cast<std::size_t>(batch)), e.status.resize(static_cast<std::size_t>(batch));
+    if (csim_sym_eigen_batch_gpu(n, batch, A.data(), e.lambda.data(), e.V.data(), e.sweeps.data(), e.status.data(),
+                                 form) != CSIM_OK)
         throw std::runtime_error(std::string("csim: ") + csim_last_error());
     return e;
 }
@@ -108,15 +128,16 @@ struct EtkfWeights {
     double dfs = 0.0;
     int sweeps = 0;
 };
-// from the (M + 1) x (M + 1) matrix of Ensemble::obs_gram(), host only
-inline EtkfWeights etkf_weights(const std::vector<double>& A, int M, double inflation = 1.0) {
+// from the (M + 1) x (M + 1) matrix of Ensemble::obs_gram(), host only, on sym_eigen in the given order
+inline EtkfWeights etkf_weights(const std::vector<double>& A, int M, double inflation = 1.0,
+                                int order = CSIM_EIGEN_ROWS) {
     if (M < 0 || A.size() != static_cast<std::size_t>(M + 1) * static_cast<std::size_t>(M + 1))
         throw std::invalid_argument("etkf_weights: array size");
     EtkfWeights w;
     const std::size_t m = static_cast<std::size_t>(M);
     w.W.resize(m * m), w.wbar.resize(m), w.gamma.resize(m);
-    if (csim_etkf_weights(M, A.data(), inflation, w.W.data(), w.wbar.data(), w.gamma.data(), &w.dfs, &w.sweeps) !=
-        CSIM_OK)
+    if (csim_etkf_weights_ordered(M, A.data(), inflation, order, w.W.data(), w.wbar.data(), w.gamma.data(), &w.dfs,
+                                  &w.sweeps) != CSIM_OK)
         throw std::runtime_error(std::string("csim: ") + csim_last_error());
     return w;
 }
@@ -125,6 +146,7 @@ struct EtkfAnalysis {
     long long n_used = 0;
     double chi2 = 0.0, dfs = 0.0;
     std::vector<double> gamma;
+    int sweeps = 0, status = CSIM_EIGEN_OK;  // of the device eigensolver, after assimilate_etkf_device (else 0)
 };
 
 // the leading modes of an ensemble's spread (see csim_ensemble_eofs): lambda and variance = lambda / (M - 1) per mode,
@@ -537,6 +559,20 @@ public:
         EtkfAnalysis r;
         r.gamma.resize(forecast(t));
         check(csim_ensemble_etkf_info(h_, &r.n_used, &r.chi2, &r.dfs, r.gamma.data(), nullptr));
+        return r;
+    }
+    // the same analysis with the eigensolver and the weights on the GPU, in the round-robin order: no copy and no wait,
+    // without record the call only enqueues (see csim_ensemble_assimilate_etkf_device); etkf_info(t) tells what it found
+    void assimilate_etkf_device(ObsNetwork& net, double inflation = 1.0, int t = -1, bool record = false,
+                                double screen_tol = 0.0) {
+        check(csim_ensemble_assimilate_etkf_device(h_, net.handle(), inflation, t, record ? 1 : 0, screen_tol));
+    }
+    // what the last ETKF analysis found; after assimilate_etkf_device it waits for the stream first, and throws when
+    // the Gram matrix was not finite (the members are then unchanged; see csim_ensemble_etkf_info2)
+    EtkfAnalysis etkf_info(int t = -1) {
+        EtkfAnalysis r;
+        r.gamma.resize(forecast(t));
+        check(csim_ensemble_etkf_info2(h_, &r.n_used, &r.chi2, &r.dfs, r.gamma.data(), nullptr, &r.sweeps, &r.status));
         return r;
     }
     // the forecast impact of every observation of net's captured analysis on the error of the current state (EFSOI, see

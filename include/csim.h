@@ -962,6 +962,40 @@ int csim_obs_local_count(int nx, int ny, int nobs, const int* i, const int* j, i
  *   sweeps; *sweeps (may be NULL) = sweeps made.  lambda: the diagonal, sorted descending, ties to the lower original
  *   index; V (n x n row-major): column r is the vector of lambda[r], negated if its first component of largest
  *   magnitude is negative.  CSIM_ERR_ARG: n < 1, a non-finite entry; CSIM_ERR_UNSUPPORTED: n above the limit.
+ * sym_eigen_ordered (host-only): the same with the pairs of a sweep in the order `order`.  CSIM_EIGEN_ROWS is the order
+ *   above and gives csim_sym_eigen's bits.  CSIM_EIGEN_ROUND_ROBIN is a parallel order: a sweep is a sequence of steps,
+ *   each a set of disjoint pairs, and it is the order of the device solver below.
+ *   Pairing: m = n rounded up to even; a sweep is the steps t = 0 .. m-2; step t has the slots k = 0 .. m/2-1:
+ *     slot 0 = {m-1, t};  slot k >= 1 = {(t+k) mod (m-1), (t-k) mod (m-1)};  within a slot p < q.
+ *     Every pair p < q < m is in exactly one slot of a sweep.  A slot with q >= n (odd n: slot 0, whose p = t) is idle:
+ *     it has no rotation and its lone index p is rotated by nobody.
+ *   Parameters: per active slot, from a_pp, a_qq and a_pq as the matrix stands at the start of the step, by the decisions
+ *     and formulas above: a_pq == 0: no rotation;  the "tiny" test: a_pq <- a_qp <- 0 and no rotation;  otherwise t, c,
+ *     s, tau and h = t a_pq as above, a_pp <- a_pp - h, a_qq <- a_qq + h, a_pq <- a_qp <- 0.  These three entries belong
+ *     to the slot alone.
+ *   Applying the step: with rot(x, y; s, tau): xn = x - s (y + x tau), yn = y + s (x - y tau), for every two slots K < L
+ *     (by slot number) the block a[{p_K, q_K}][{p_L, q_L}] is first rotated as rows by K, that is rot(a[p_K][j],
+ *     a[q_K][j]) with K's (s, tau) for j = p_L and j = q_L, then the results are rotated as columns by L, that is
+ *     rot(a[i][p_L], a[i][q_L]) with L's (s, tau) for i = p_K and i = q_K; the four results are stored and mirrored
+ *     into a[j][i].  A slot without a rotation applies none, so a block of two such slots keeps its bits; against the
+ *     lone index of an idle slot only the other slot's rotation acts, on the two entries that exist.  For every slot with
+ *     a rotation, rot(v_jp, v_jq) for every j as above.  All of these act on disjoint entries, so the result depends on
+ *     no order among them: taking the slots of a step one after the other, each as one pair of the row order's loop
+ *     body, gives the same bits, and that is how the host computes it.  a is symmetric entry by entry after every step.
+ *   Stop, sort and sign as above.  CSIM_ERR_ARG also for an unknown order.
+ * sym_eigen_batch_gpu: `batch` matrices A[b] (n x n row-major, one after the other) by the round-robin order on the
+ *   device, one workgroup per matrix, 1 <= n <= CSIM_SYM_EIGEN_MAX_N, 1 <= batch <= CSIM_SYM_EIGEN_MAX_BATCH.  Host arrays
+ *   in and out, synchronous; the call creates and frees the stream and the device memory it needs (at most 512 MiB at a
+ *   time) and needs no ensemble.  lambda[b], V[b], sweeps[b] (may be NULL) are bit for bit those of
+ *   csim_sym_eigen_ordered(CSIM_EIGEN_ROUND_ROBIN) on A[b];  status[b] (may be NULL) is CSIM_EIGEN_OK, or
+ *   CSIM_EIGEN_NONFINITE: A[b] has a non-finite entry, lambda[b] and V[b] are NaN and sweeps[b] = 0 (the other matrices
+ *   are not affected), or CSIM_EIGEN_NOT_CONVERGED: all CSIM_SYM_EIGEN_MAX_SWEEPS sweeps were made (sweeps[b] says the
+ *   same on the host); lambda and V are then the current diagonal and vectors, as on the host.
+ *   form: 0, or the storage form of the working matrices to force: 1 = a and v in LDS (n <= 96), 2 = a in LDS and v in
+ *   global memory (n <= 128), 3 = both in global memory (any n); 0 takes the first that admits n.  Every form gives the
+ *   same bits.  sym_eigen_device_form (host-only): *chosen = the form taken for (n, form), *max_n = the largest n that
+ *   `form` admits (either may be NULL); CSIM_ERR_UNSUPPORTED when the form does not admit n.
+ *   Not built: a solver that spans workgroups, and eofs on the device order.
  * eofs: the leading patterns of the ensemble's spread, 1 <= n_modes <= M - 1:  G = gram(centered = 1);
  *   (lam, V) = sym_eigen(G);  lambda[r] = lam_r;  mode r is null when lam_r <= (M 2^-52) lam_0 or lam_r <= 0, else
  *   W[k][r] = V[k][r] / sqrt(lam_r) and pcs[k n_modes + r] = V[k][r] * sqrt(lam_r);  patterns (NULL: not wanted) =
@@ -972,11 +1006,21 @@ int csim_obs_local_count(int nx, int ny, int nobs, const int* i, const int* j, i
 #define CSIM_ESPACE_MAX_MEMBERS 256
 #define CSIM_SYM_EIGEN_MAX_N 256
 #define CSIM_SYM_EIGEN_MAX_SWEEPS 64
+#define CSIM_SYM_EIGEN_MAX_BATCH 65535
+#define CSIM_EIGEN_ROWS 0
+#define CSIM_EIGEN_ROUND_ROBIN 1
+#define CSIM_EIGEN_OK 0
+#define CSIM_EIGEN_NONFINITE 1
+#define CSIM_EIGEN_NOT_CONVERGED 2
 int csim_ensemble_gram(csim_ensemble* e, int truth_member, int centered, double* G);
 int csim_ensemble_gram_plan(int M, int nx, int ny, long* nseg, int* classes);
 int csim_ensemble_project(csim_ensemble* e, int truth_member, int centered, int K, const double* W, double* out);
 int csim_ensemble_transform(csim_ensemble* e, int truth_member, int centered, const double* W, const double* wbar);
 int csim_sym_eigen(int n, const double* A, double* lambda, double* V, int* sweeps);
+int csim_sym_eigen_ordered(int n, const double* A, int order, double* lambda, double* V, int* sweeps);
+int csim_sym_eigen_batch_gpu(int n, int batch, const double* A, double* lambda, double* V, int* sweeps, int* status,
+                             int form);
+int csim_sym_eigen_device_form(int n, int form, int* chosen, int* max_n);
 int csim_ensemble_eofs(csim_ensemble* e, int truth_member, int n_modes, double* lambda, double* pcs, double* patterns,
                        int* n_valid);
 int csim_ensemble_space_check(int members, int truth_member, int centered, int K, int has_wbar, int n_modes);
@@ -1012,6 +1056,8 @@ int csim_ensemble_space_check(int members, int truth_member, int centered, int K
  *       gamma[r] = G_r;   *dfs = sum_r G_r * f_r, the degrees of freedom for signal;   *sweeps: those of sym_eigen
  *   CSIM_ERR_ARG: M < 2, inflation < 1 or not finite, A NULL or with a non-finite entry; CSIM_ERR_UNSUPPORTED: M above
  *   the limit.  transform(centered = 1, W, wbar) is then the analysis: mean xb + X' wbar, perturbations X' W.
+ *   etkf_weights_ordered: the same on csim_sym_eigen_ordered(M, C, order); order CSIM_EIGEN_ROWS gives
+ *   csim_etkf_weights' bits; CSIM_ERR_ARG also for an unknown order.
  * assimilate_etkf: the analysis from these pieces; arguments and errors as csim_ensemble_assimilate_screened, in its
  *   order and first, then M <= CSIM_ESPACE_MAX_MEMBERS (more: CSIM_ERR_UNSUPPORTED).
  *   1. Screening exactly as in csim_ensemble_assimilate_screened: (hb, vb), the mask and the background check write the
@@ -1028,6 +1074,20 @@ int csim_ensemble_space_check(int members, int truth_member, int centered, int K
  *   etkf_info: n_used, chi2 = A[M][M], dfs and gamma (M values; *n_gamma = M) of the ensemble's last completed
  *   assimilate_etkf, every pointer may be NULL; CSIM_ERR_STATE when there is none, or when the last call that passed
  *   its argument and state checks failed after them.
+ * assimilate_etkf_device: the same analysis without a copy or a wait, for cycling on the device: checks, screening and
+ *   record as assimilate_etkf; then the obs_gram kernels, the device eigensolver on C (one workgroup; the ensemble's
+ *   option "eigen_form"), a kernel that computes etkf_weights_ordered(order = CSIM_EIGEN_ROUND_ROBIN) operation by
+ *   operation from A, lam and V on the device, and the transform are enqueued on the ensemble's stream.  Without record
+ *   the call only enqueues.  The members are bit for bit those of obs_gram -> etkf_weights_ordered(round robin) ->
+ *   transform through the public calls; they differ from assimilate_etkf's in the last bits, as the two orders do.
+ *   With no used observation and inflation == 1, or with a non-finite entry of A, the transform kernel reads that from
+ *   the device record and returns at once: the members keep their bits.  A non-finite A cannot fail this call: the
+ *   following etkf_info returns CSIM_ERR_STATE, and with record = 1 the cycle's log records have been appended, (ha, va)
+ *   taken from the unchanged members.  2 <= M <= CSIM_ESPACE_MAX_MEMBERS; CSIM_ERR_UNSUPPORTED also when the eigen_form
+ *   that is set does not admit M.
+ *   etkf_info after it waits for the stream and fetches the record.  etkf_info2 is etkf_info with two more outputs
+ *   (either may be NULL): *sweeps, the solver's sweeps, and *status, CSIM_EIGEN_OK or CSIM_EIGEN_NOT_CONVERGED (the
+ *   analysis was made with the current diagonal, as the host makes it); after assimilate_etkf both are 0.
  * Not built: localisation of the ETKF, _begin / _wait forms, more than CSIM_ESPACE_MAX_MEMBERS members, a resampling
  * particle filter on top of loglik, and the forecast impact (impact_capture / obs_impact) after an ETKF. */
 int csim_ensemble_obs_gram(csim_ensemble* e, csim_obs_network* n, int truth_member, double* A, double* loglik,
@@ -1039,6 +1099,12 @@ int csim_ensemble_assimilate_etkf(csim_ensemble* e, csim_obs_network* n, double 
                                   int record, double tol);
 int csim_ensemble_etkf_info(const csim_ensemble* e, long long* n_used, double* chi2, double* dfs, double* gamma,
                             int* n_gamma);
+int csim_etkf_weights_ordered(int M, const double* A, double inflation, int order, double* W, double* wbar,
+                              double* gamma, double* dfs, int* sweeps);
+int csim_ensemble_assimilate_etkf_device(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
+                                         int record, double tol);
+int csim_ensemble_etkf_info2(csim_ensemble* e, long long* n_used, double* chi2, double* dfs, double* gamma,
+                             int* n_gamma, int* sweeps, int* status);
 /* options (unknown keys: CSIM_ERR_ARG; "contract": CSIM_ERR_UNSUPPORTED), results never depend on them:
  *   "fuse"        -1 (default) passes of the ensemble depth where the grid allows; 0 / 1 single steps only
  *   "fused_2c"    0/1 (default 1), as for csim_stepper_set_option
@@ -1061,6 +1127,9 @@ int csim_ensemble_etkf_info(const csim_ensemble* e, long long* n_used, double* c
  *                           M) in csim_ensemble_project and csim_ensemble_transform; any other value is CSIM_ERR_ARG
  *   "obs_gram_form"         0 (default: chosen from M) or 1, 2, 3: blocks per lane as "gram_form", in the class-partial
  *                           kernel of csim_ensemble_obs_gram and csim_ensemble_assimilate_etkf; any other value is
+ *                           CSIM_ERR_ARG
+ *   "eigen_form"            0 (default: chosen from M) or 1, 2, 3: the storage form of the device eigensolver in
+ *                           csim_ensemble_assimilate_etkf_device (see sym_eigen_batch_gpu); any other value is
  *                           CSIM_ERR_ARG */
 int csim_ensemble_set_option(csim_ensemble* e, const char* key, long value);
 int csim_ensemble_get_option(const csim_ensemble* e, const char* key, long* value);

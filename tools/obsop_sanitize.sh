@@ -6,7 +6,8 @@
 # kernel's restated tile decode) and of the spatial verification (csrc/spatial_scores.cpp, csrc/spatial_scores.hpp: the
 # overflow bound at its edge, the finishing of the integer tables) and of the local analysis (csrc/assim_plan.cpp again:
 # csim_obs_local_count and the per-tile lookup against brute force) and of the ensemble-space eigensolver (csrc/sym_eigen.cpp,
-# csrc/sym_eigen.hpp: residual, orthogonality, ordering and sign rule up to the largest n) and of the ETKF
+# csrc/sym_eigen.hpp: residual, orthogonality, ordering and sign rule up to the largest n, in the row order and in the
+# round-robin order with its pairing) and of the ETKF
 # (csrc/etkf_weights.cpp, csrc/etkf_weights.hpp: the weights' residual, symmetry and row sums up to the largest M, the
 # plan of the observation-space Gram sum against brute force), each as a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.  The build goes to $TMP;
 # nothing in the tree is replaced.
@@ -23,6 +24,7 @@ CXX=(g++ -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined
 "${CXX[@]}" -o "$TMP/spatial_host_check" "$R/tools/spatial_host_check.cpp" "$S/spatial_scores.cpp"
 "${CXX[@]}" -o "$TMP/local_plan_host_check" "$R/tools/local_plan_host_check.cpp" "$S/assim_plan.cpp"
 "${CXX[@]}" -o "$TMP/sym_eigen_host_check" "$R/tools/sym_eigen_host_check.cpp" "$S/sym_eigen.cpp"
+"${CXX[@]}" -o "$TMP/sym_eigen_rr_host_check" "$R/tools/sym_eigen_rr_host_check.cpp" "$S/sym_eigen.cpp"
 "${CXX[@]}" -o "$TMP/etkf_host_check" "$R/tools/etkf_host_check.cpp" "$S/etkf_weights.cpp" "$S/sym_eigen.cpp"
 export ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1
 "$TMP/obsop_host_check"
@@ -31,4 +33,5 @@ export ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktra
 "$TMP/spatial_host_check"
 "$TMP/local_plan_host_check"
 "$TMP/sym_eigen_host_check"
+"$TMP/sym_eigen_rr_host_check"
 "$TMP/etkf_host_check"
