@@ -329,7 +329,7 @@ int csim_ensemble_set_option(csim_ensemble* e, const char* key, long value) {
         CSIM_REQUIRE(value >= 0 && value <= PROJECT_FORMS, "project_form must be 0 (automatic) or 1");
         e->espace.project_form = static_cast<int>(value);
     } else if (k == "obs_gram_form") {
-        CSIM_REQUIRE(value >= 0 && value <= OBS_GRAM_FORMS, "obs_gram_form must be 0 (automatic) or 1 .. 3");
+        CSIM_REQUIRE(value >= 0 && value <= GRAM_FORMS, "obs_gram_form must be 0 (automatic) or 1 .. 3");
         e->espace.obs_gram_form = static_cast<int>(value);
     } else if (k == "eigen_form") {
         CSIM_REQUIRE(value >= 0 && value <= EIGEN_FORMS, "eigen_form must be 0 (automatic) or 1 .. 3");

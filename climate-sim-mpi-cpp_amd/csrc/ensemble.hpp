@@ -7,6 +7,7 @@
 // Member m's row j = 0 is at  alloc + m * slab + GHOST_EXTRA * pitch.
 #pragma once
 
+#include "gram_plan.hpp"
 #include "internal.hpp"
 
 namespace csim {
@@ -309,18 +310,8 @@ hipError_t ens_launch_obs_screen_log_fill(double* slog, int cycles, int nobs, hi
 
 // ensemble space (ensemble_space.hip; csim_ensemble_gram, _project, _transform): the M x M space spanned by the forecast
 // members' perturbations p_k (x_k less the cell's mean when centered, x_k itself otherwise).
-constexpr int ESPACE_MAX_MEMBERS = 256;  // CSIM_ESPACE_MAX_MEMBERS
-constexpr int GRAM_SEG = 64;             // interior cells per segment
-constexpr int GRAM_FORMS = 3;            // gram_form 1 .. 3: 1, 2, 4 blocks of 4 x 4 pairs per lane
-constexpr int PROJECT_FORMS = 1;         // project_form 1: the members of a cell in LDS whatever M
-// classes of the Gram sum for M forecast members (0: M out of range), and the plan of csim_ensemble_gram_plan
-inline int gram_cap(int M) { return M < 1 ? 0 : M <= 64 ? 1024 : M <= 128 ? 256 : M <= ESPACE_MAX_MEMBERS ? 64 : 0; }
-inline long gram_segments(int nx, int ny) { return (static_cast<long>(nx) * ny + GRAM_SEG - 1) / GRAM_SEG; }
-inline int gram_classes(int M, int nx, int ny) {
-    const long nseg = gram_segments(nx, ny);
-    return static_cast<int>(nseg < gram_cap(M) ? nseg : gram_cap(M));
-}
-inline size_t gram_pairs(int M) { return static_cast<size_t>(M) * (M + 1) / 2; }  // packed upper triangle
+// The member limit ESPACE_MAX_MEMBERS, the Gram sum's plan (gram_classes, gram_pairs) and GRAM_FORMS: gram_plan.hpp.
+constexpr int PROJECT_FORMS = 1;  // project_form 1: the members of a cell in LDS whatever M
 // G (M x M, device) from the members; partial: gram_classes x gram_pairs doubles.  form: 0 (the launcher's choice)
 // or 1 .. GRAM_FORMS; the result does not depend on it
 hipError_t ens_launch_gram(const EnsGeom& g, const double* f, int forecast, int truth_member, bool centered,
@@ -340,7 +331,6 @@ hipError_t ens_launch_transform(const EnsGeom& g, double* f, int forecast, int t
 // the normalised observation-space perturbations of a network, and the members' sums of squared normalised departures.
 // Device arrays in plan order.  An observation is used iff flag is null or flag[q] == used: the mask (1: active) of
 // the stand-alone call, the status bytes (0: CSIM_OBS_USED) of an analysis.
-constexpr int OBS_GRAM_FORMS = GRAM_FORMS;  // obs_gram_form 1 .. 3: 1, 2, 4 blocks of 4 x 4 pairs per lane
 struct ObsGramArgs {
     int nobs;
     int forecast;                 // M
@@ -358,7 +348,7 @@ struct ObsGramArgs {
 // doubles of `partial` for a call: per class the packed upper triangle of A, M sums of loglik and one count
 size_t ens_obs_gram_partial_doubles(int forecast, int nobs);
 // out (device): A, then M values of loglik (written only with want_loglik), then the number of used observations as
-// one long long.  form: 0 (the launcher's choice) or 1 .. OBS_GRAM_FORMS; the result does not depend on it
+// one long long.  form: 0 (the launcher's choice) or 1 .. GRAM_FORMS; the result does not depend on it
 hipError_t ens_launch_obs_gram(const EnsGeom& g, const double* f, const ObsGramArgs& a, bool want_loglik,
                                double* partial, double* out, int form, hipStream_t st);
 

@@ -39,7 +39,7 @@ int gram(csim_ensemble* e, int M, int t, bool centered, double* G) {
     const EnsGeom& g = e->g;
     csim_ensemble::Espace& x = e->espace;
     const size_t gbytes = sizeof(double) * static_cast<size_t>(M) * M;
-    CSIM_TRY(x.partial.reserve(sizeof(double) * gram_classes(M, g.nx, g.ny) * gram_pairs(M), e->st));
+    CSIM_TRY(x.partial.reserve(sizeof(double) * gram_classes(M, static_cast<long>(g.nx) * g.ny) * gram_pairs(M), e->st));
     CSIM_TRY(x.gram.reserve(gbytes, e->st));
     CSIM_HIP(ens_launch_gram(g, e->base(e->cur), M, t, centered, x.partial.as(), x.gram.as(), x.gram_form, e->st));
     CSIM_HIP(hipMemcpyAsync(G, x.gram.p, gbytes, hipMemcpyDeviceToHost, e->st));
@@ -79,8 +79,9 @@ int csim_ensemble_gram_plan(int M, int nx, int ny, long* nseg, int* classes) {
     CSIM_REQUIRE(M >= 1 && nx >= 1 && ny >= 1, "M, nx and ny must be >= 1");
     if (M > ESPACE_MAX_MEMBERS)
         return fail(CSIM_ERR_UNSUPPORTED, "ensemble space: at most CSIM_ESPACE_MAX_MEMBERS forecast members");
-    if (nseg) *nseg = gram_segments(nx, ny);
-    if (classes) *classes = gram_classes(M, nx, ny);
+    const long cells = static_cast<long>(nx) * ny;
+    if (nseg) *nseg = gram_segments(cells);
+    if (classes) *classes = gram_classes(M, cells);
     return CSIM_OK;
 }
 

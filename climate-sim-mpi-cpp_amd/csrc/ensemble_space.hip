@@ -6,15 +6,9 @@
 //
 // Gram, two kernels:
 //   k_gram_partial  Workgroup (g, y) of 256 lanes serves class g: the segments g, g + Gc, ... of 64 interior cells.  It
-//                   stages a segment's perturbations in LDS as [cell][member] (row stride even, so a lane's four
-//                   members are one or two 16-byte reads; the lanes of a wave mostly share the a-side address, which
-//                   broadcasts, and read neighbouring 32-byte pieces on the b-side), then every lane walks the
-//                   segment's cells in order for its NB blocks of 4 x 4 pairs (a, b) of the upper triangle, block
-//                   (blockIdx.y NB + u) 256 + lane, and carries the 16 NB running sums on to the class's next segment.
-//                   Which lane owns which pair is geometry: the order of each pair's sum is that of the cells.
-//                   Each class writes the packed upper triangle of its partial.
-//   k_gram_fold     entry (a, b), a <= b: partial 0, then + partial 1, ... + partial Gc - 1; written to G[a][b] and
-//                   G[b][a].
+//                   stages a segment's perturbations in LDS as [cell][member]; the walk over them, the lanes' pairs
+//                   and the class's partial are the GramTile of gram_tile.hpp, the plan is gram_plan.hpp.
+//   k_gram_fold     entry (a, b), a <= b, folded over the classes (gram_fold_entry); written to G[a][b] and G[b][a].
 // Project / transform, one kernel template k_espace_apply<P, XFORM>: one cell per lane, p_k in registers (P > 0, the
 // steps of for_step) or in LDS as [member][lane] (P = 0: M > 64, or project_form 1).  W is read with wave-uniform
 // indices, so its loads are scalar; four outputs r share one pass over k, four independent chains.  In the LDS form
@@ -23,7 +17,7 @@
 // write the members it read.
 #include <algorithm>
 
-#include "ensemble_cell.hpp"
+#include "gram_tile.hpp"
 
 #pragma clang fp contract(off)
 
@@ -31,11 +25,7 @@ namespace csim {
 
 namespace {
 
-constexpr int GRAM_THREADS = 256;
-constexpr int GRAM_TB = 4;                   // pairs per block side
 constexpr long ESPACE_MAX_BLOCKS = 1L << 20;  // larger fields loop
-
-__host__ __device__ inline int gram_stride(int M) { return (M + GRAM_TB - 1) / GRAM_TB * GRAM_TB + 2; }
 
 template <int NB>
 __global__ __launch_bounds__(GRAM_THREADS) void k_gram_partial(const double* __restrict__ f, int nx, long cells,
@@ -45,29 +35,9 @@ __global__ __launch_bounds__(GRAM_THREADS) void k_gram_partial(const double* __r
     const int stride = gram_stride(M);
     double* __restrict__ mean = held + GRAM_SEG * stride;
     const int tid = threadIdx.x;
-    const int nblk = (M + GRAM_TB - 1) / GRAM_TB;
-    const int nblocks = nblk * (nblk + 1) / 2;
-    const int mpad = nblk * GRAM_TB;
-
-    // this lane's blocks (ia <= ib), row by row of the block triangle; past the end: the last one, computed and dropped
-    int ia[NB], ib[NB];
-    bool mine[NB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-        const int bidx = (blockIdx.y * NB + u) * GRAM_THREADS + tid;
-        mine[u] = bidx < nblocks;
-        int r = min(bidx, nblocks - 1), a = 0;
-        while (r >= nblk - a) r -= nblk - a, ++a;
-        ia[u] = a, ib[u] = a + r;
-    }
-    // a wave none of whose lanes owns a block only helps staging
-    const bool wave_on = blockIdx.y * NB * GRAM_THREADS + (tid & ~63) < nblocks;
-
-    double acc[NB][GRAM_TB * GRAM_TB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u)
-#pragma unroll
-        for (int v = 0; v < GRAM_TB * GRAM_TB; ++v) acc[u][v] = 0.0;
+    const int mpad = gram_nblk(M) * GRAM_TB;
+    GramTile<NB> tile;
+    tile.init(M);
 
     const int c = tid & 63, kq = tid >> 6;
     double* __restrict__ row = held + c * stride;
@@ -98,42 +68,10 @@ __global__ __launch_bounds__(GRAM_THREADS) void k_gram_partial(const double* __r
             }
             __syncthreads();
         }
-        if (wave_on) {
-#pragma unroll 2
-            for (int cc = 0; cc < nc; ++cc) {
-                const double* __restrict__ x = held + cc * stride;
-#pragma unroll
-                for (int u = 0; u < NB; ++u) {
-                    const double2* __restrict__ pa = reinterpret_cast<const double2*>(x + GRAM_TB * ia[u]);
-                    const double2* __restrict__ pb = reinterpret_cast<const double2*>(x + GRAM_TB * ib[u]);
-                    const double2 a0 = pa[0], a1 = pa[1], b0 = pb[0], b1 = pb[1];
-                    const double a[GRAM_TB] = {a0.x, a0.y, a1.x, a1.y};
-                    const double b[GRAM_TB] = {b0.x, b0.y, b1.x, b1.y};
-#pragma unroll
-                    for (int i = 0; i < GRAM_TB; ++i)
-#pragma unroll
-                        for (int j = 0; j < GRAM_TB; ++j)
-                            acc[u][i * GRAM_TB + j] = acc[u][i * GRAM_TB + j] + a[i] * b[j];
-                }
-            }
-        }
+        tile.walk(held, stride, nc);
         __syncthreads();
     }
-
-    double* __restrict__ mine_out = partial + static_cast<size_t>(blockIdx.x) * (static_cast<size_t>(M) * (M + 1) / 2);
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-        if (!mine[u]) continue;
-#pragma unroll
-        for (int i = 0; i < GRAM_TB; ++i)
-#pragma unroll
-            for (int j = 0; j < GRAM_TB; ++j) {
-                const int a = GRAM_TB * ia[u] + i, b = GRAM_TB * ib[u] + j;
-                if (a <= b && b < M)
-                    mine_out[static_cast<size_t>(a) * M - static_cast<size_t>(a) * (a - 1) / 2 + (b - a)] =
-                        acc[u][i * GRAM_TB + j];
-            }
-    }
+    tile.store(partial + static_cast<size_t>(blockIdx.x) * gram_pairs(M), M);
 }
 
 // grid (ceil(M / 64), M): row a = blockIdx.y, column b
@@ -141,11 +79,7 @@ __global__ __launch_bounds__(64) void k_gram_fold(const double* __restrict__ par
                                                   double* __restrict__ G) {
     const int a = blockIdx.y, b = blockIdx.x * 64 + threadIdx.x;
     if (b < a || b >= M) return;
-    const size_t pairs = static_cast<size_t>(M) * (M + 1) / 2;
-    const double* __restrict__ p = partial + (static_cast<size_t>(a) * M - static_cast<size_t>(a) * (a - 1) / 2 + (b - a));
-    double s = p[0];
-#pragma unroll 16
-    for (int g = 1; g < classes; ++g) s = s + p[static_cast<size_t>(g) * pairs];
+    const double s = gram_fold_entry(partial + gram_packed(a, b, M), classes, gram_pairs(M));
     G[static_cast<size_t>(a) * M + b] = s;
     G[static_cast<size_t>(b) * M + a] = s;
 }
@@ -258,17 +192,13 @@ template <int NB>
 hipError_t launch_gram(const EnsGeom& g, const double* f, int M, int t, bool centered, double* partial, double* G,
                        hipStream_t st) {
     const long cells = static_cast<long>(g.nx) * g.ny;
-    const long nseg = gram_segments(g.nx, g.ny);
-    const int classes = gram_classes(M, g.nx, g.ny);
-    const int nblk = (M + GRAM_TB - 1) / GRAM_TB;
-    const int nblocks = nblk * (nblk + 1) / 2;
-    const int shares = (nblocks + NB * GRAM_THREADS - 1) / (NB * GRAM_THREADS);
+    const int classes = gram_classes(M, cells);
     const size_t lds = sizeof(double) * (static_cast<size_t>(GRAM_SEG) * gram_stride(M) + GRAM_SEG);
     const hipError_t attr = dynamic_lds_once<k_gram_partial<NB>>(
         sizeof(double) * (static_cast<size_t>(GRAM_SEG) * gram_stride(ESPACE_MAX_MEMBERS) + GRAM_SEG));
     if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(k_gram_partial<NB>, dim3(classes, shares), dim3(GRAM_THREADS), lds, st, f, g.nx, cells, nseg,
-                       g.pitch, g.slab, M, t, centered ? 1 : 0, partial);
+    hipLaunchKernelGGL(k_gram_partial<NB>, dim3(classes, gram_shares(M, NB)), dim3(GRAM_THREADS), lds, st, f, g.nx,
+                       cells, gram_segments(cells), g.pitch, g.slab, M, t, centered ? 1 : 0, partial);
     hipError_t rc = hipGetLastError();
     if (rc != hipSuccess) return rc;
     hipLaunchKernelGGL(k_gram_fold, dim3((M + 63) / 64, M), dim3(64), 0, st, partial, classes, M, G);
@@ -304,10 +234,9 @@ bool espace_ok(int M, int form, int forms) { return M >= 1 && M <= ESPACE_MAX_ME
 hipError_t ens_launch_gram(const EnsGeom& g, const double* f, int forecast, int truth_member, bool centered,
                            double* partial, double* G, int form, hipStream_t st) {
     if (!espace_ok(forecast, form, GRAM_FORMS)) return hipErrorInvalidValue;
-    if (form == 0) form = forecast <= 64 ? 1 : forecast <= 128 ? 2 : 3;
-    if (form == 1) return launch_gram<1>(g, f, forecast, truth_member, centered, partial, G, st);
-    if (form == 2) return launch_gram<2>(g, f, forecast, truth_member, centered, partial, G, st);
-    return launch_gram<4>(g, f, forecast, truth_member, centered, partial, G, st);
+    return for_gram_form(form, forecast, [&](auto nb) {
+        return launch_gram<decltype(nb)::value>(g, f, forecast, truth_member, centered, partial, G, st);
+    });
 }
 
 hipError_t ens_launch_project(const EnsGeom& g, const double* f, int forecast, int truth_member, bool centered, int K,

@@ -1,7 +1,7 @@
 // etkf_weights.cpp — csim_etkf_weights and csim_obs_gram_plan: the symmetric square-root ETKF in ensemble space,
 // operation by operation as include/csim.h writes it, on top of sym_eigen.cpp.  No HIP headers, no contraction: C, C++
 // and Python callers get the same bits from the same input.
-#include "etkf_weights.hpp"
+#include "gram_plan.hpp"
 
 #include <cmath>
 #include <new>
@@ -17,17 +17,17 @@
 
 using namespace csim;
 
-static_assert(OBS_GRAM_MAX_MEMBERS == CSIM_ESPACE_MAX_MEMBERS && OBS_GRAM_MAX_MEMBERS <= SYM_EIGEN_MAX_N,
+static_assert(ESPACE_MAX_MEMBERS == CSIM_ESPACE_MAX_MEMBERS && ESPACE_MAX_MEMBERS <= SYM_EIGEN_MAX_N,
               "the ETKF's limit is that of the ensemble space");
 
 extern "C" {
 
 int csim_obs_gram_plan(int M, int nobs, long* nseg, int* classes) {
     OBS_REQUIRE(M >= 2 && nobs >= 1, "M must be >= 2 and nobs >= 1");
-    if (M > OBS_GRAM_MAX_MEMBERS)
+    if (M > ESPACE_MAX_MEMBERS)
         return fail(CSIM_ERR_UNSUPPORTED, "csim_obs_gram_plan: at most CSIM_ESPACE_MAX_MEMBERS forecast members");
-    if (nseg) *nseg = obs_gram_segments(nobs);
-    if (classes) *classes = obs_gram_classes(M, nobs);
+    if (nseg) *nseg = gram_segments(nobs);
+    if (classes) *classes = gram_classes(M, nobs);
     return CSIM_OK;
 }
 
@@ -39,7 +39,7 @@ int csim_etkf_weights(int M, const double* A, double inflation, double* W, doubl
 int csim_etkf_weights_ordered(int M, const double* A, double inflation, int order, double* W, double* wbar,
                               double* gamma, double* dfs, int* sweeps) {
     OBS_REQUIRE(M >= 2, "M must be >= 2");
-    if (M > OBS_GRAM_MAX_MEMBERS)
+    if (M > ESPACE_MAX_MEMBERS)
         return fail(CSIM_ERR_UNSUPPORTED, "csim_etkf_weights: at most CSIM_ESPACE_MAX_MEMBERS forecast members");
     OBS_REQUIRE(std::isfinite(inflation) && inflation >= 1.0, "inflation must be finite and >= 1");
     OBS_REQUIRE(A, "null argument");

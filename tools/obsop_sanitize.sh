@@ -8,8 +8,9 @@
 # csim_obs_local_count and the per-tile lookup against brute force) and of the ensemble-space eigensolver (csrc/sym_eigen.cpp,
 # csrc/sym_eigen.hpp: residual, orthogonality, ordering and sign rule up to the largest n, in the row order and in the
 # round-robin order with its pairing) and of the ETKF
-# (csrc/etkf_weights.cpp, csrc/etkf_weights.hpp: the weights' residual, symmetry and row sums up to the largest M, the
-# plan of the observation-space Gram sum against brute force), each as a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.  The build goes to $TMP;
+# (csrc/etkf_weights.cpp: the weights' residual, symmetry and row sums up to the largest M, the
+# plan of the observation-space Gram sum against brute force) and of the two Gram sums (csrc/gram_plan.hpp: the plan, and
+# which lane owns which block of pairs at every width and form), each as a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.  The build goes to $TMP;
 # nothing in the tree is replaced.
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -26,6 +27,7 @@ CXX=(g++ -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined
 "${CXX[@]}" -o "$TMP/sym_eigen_host_check" "$R/tools/sym_eigen_host_check.cpp" "$S/sym_eigen.cpp"
 "${CXX[@]}" -o "$TMP/sym_eigen_rr_host_check" "$R/tools/sym_eigen_rr_host_check.cpp" "$S/sym_eigen.cpp"
 "${CXX[@]}" -o "$TMP/etkf_host_check" "$R/tools/etkf_host_check.cpp" "$S/etkf_weights.cpp" "$S/sym_eigen.cpp"
+"${CXX[@]}" -o "$TMP/gram_plan_host_check" "$R/tools/gram_plan_host_check.cpp"
 export ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1
 "$TMP/obsop_host_check"
 "$TMP/assim_plan_host_check"
@@ -35,3 +37,4 @@ export ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktra
 "$TMP/sym_eigen_host_check"
 "$TMP/sym_eigen_rr_host_check"
 "$TMP/etkf_host_check"
+"$TMP/gram_plan_host_check"
