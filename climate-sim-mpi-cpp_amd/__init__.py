@@ -279,6 +279,11 @@ def lib() -> C.CDLL:
         "csim_etkf_weights_ordered": (i, [i, dp, d, i, dp, dp, dp, dp, ip]),
         "csim_ensemble_assimilate_etkf_device": (i, [vp, vp, d, i, i, d]),
         "csim_ensemble_etkf_info2": (i, [vp, C.POINTER(C.c_longlong), dp, dp, dp, ip, ip, ip]),
+        "csim_ensemble_assimilate_letkf": (i, [vp, vp, d, i, i, d, i]),
+        "csim_ensemble_letkf_info": (i, [vp, ip, ip, dp, ip, ip, ip]),
+        "csim_letkf_nodes": (i, [i, i, i, ip, ip, ip, ip]),
+        "csim_letkf_blend": (i, [i, i, i, i, i, ip, dp]),
+        "csim_letkf_plan": (i, [i, i, i, i, C.POINTER(C.c_long), C.POINTER(C.c_longlong)]),
         "csim_ensemble_set_option": (i, [vp, C.c_char_p, C.c_long]),
         "csim_ensemble_get_option": (i, [vp, C.c_char_p, C.POINTER(C.c_long)]),
         "csim_ensemble_plan": (i, [i, i, i, i, ip]),
@@ -1081,6 +1086,46 @@ def etkf_weights(A, inflation=1.0, order="rows") -> EtkfWeights:
     return EtkfWeights(W, wbar, gamma, dfs.value, sweeps.value)
 
 
+LETKF_MAX_NODES, LETKF_MAX_BYTES = 65535, 1 << 30  # CSIM_LETKF_MAX_NODES, CSIM_LETKF_MAX_BYTES
+LETKF_OK, LETKF_IDLE, LETKF_NONFINITE, LETKF_NOT_CONVERGED = 0, 1, 2, 3  # CSIM_LETKF_*
+LetkfNodes = collections.namedtuple("LetkfNodes", "nax nay xi yj")
+LetkfNodes.__doc__ = """the lattice of analysis nodes of Ensemble.assimilate_letkf(): nay x nax nodes, node (a, b) at the
+interior cell (xi[a], yj[b]) with index b * nax + a"""
+LetkfBlend = collections.namedtuple("LetkfBlend", "node beta")
+LetkfBlend.__doc__ = """the four nodes of a cell, (a, b), (a+1, b), (a, b+1), (a+1, b+1) by index, and their weights"""
+LetkfPlan = collections.namedtuple("LetkfPlan", "nodes bytes")
+LetkfInfo = collections.namedtuple("LetkfInfo", "dfs count sweeps status")
+LetkfInfo.__doc__ = """what Ensemble.letkf_info() returns, each (nay, nax): per node the degrees of freedom for signal, the
+local observations used, the eigensolver's sweeps and the status LETKF_OK, LETKF_IDLE (no local observation),
+LETKF_NONFINITE or LETKF_NOT_CONVERGED"""
+
+
+def letkf_nodes(nx: int, ny: int, spacing: int) -> LetkfNodes:
+    """the analysis nodes of an nx x ny grid with this spacing: the first cell of an axis, every spacing-th after it
+    and the last (csim_letkf_nodes) — host only"""
+    nax, nay = C.c_int(), C.c_int()
+    _ck(lib().csim_letkf_nodes(int(nx), int(ny), int(spacing), C.byref(nax), C.byref(nay), None, None))
+    xi, yj = np.zeros(nax.value, dtype=np.int32), np.zeros(nay.value, dtype=np.int32)
+    _ck(lib().csim_letkf_nodes(int(nx), int(ny), int(spacing), None, None, _ip(xi), _ip(yj)))
+    return LetkfNodes(nax.value, nay.value, xi, yj)
+
+
+def letkf_blend(nx: int, ny: int, spacing: int, i: int, j: int) -> LetkfBlend:
+    """the four nodes between which the interior cell (i, j) lies and the bilinear weights with which
+    Ensemble.assimilate_letkf() blends their analyses there (csim_letkf_blend) — host only"""
+    node, beta = np.zeros(4, dtype=np.int32), np.zeros(4)
+    _ck(lib().csim_letkf_blend(int(nx), int(ny), int(spacing), int(i), int(j), _ip(node), _dp(beta)))
+    return LetkfBlend(node, beta)
+
+
+def letkf_plan(M: int, nx: int, ny: int, spacing: int) -> LetkfPlan:
+    """(nodes, bytes): the analysis nodes of a call of Ensemble.assimilate_letkf() with M forecast members and the
+    device storage they take, held against LETKF_MAX_NODES and LETKF_MAX_BYTES (csim_letkf_plan) — host only"""
+    nodes, nbytes = C.c_long(), C.c_longlong()
+    _ck(lib().csim_letkf_plan(int(M), int(nx), int(ny), int(spacing), C.byref(nodes), C.byref(nbytes)))
+    return LetkfPlan(nodes.value, nbytes.value)
+
+
 class ObsNetwork:
     """observations that live on the device (csim_obs_network_*): planned once, their values drawn on the GPU
     from a member or set from the host, read by Ensemble.assimilate_network without staging.  Point observations of
@@ -1497,6 +1542,33 @@ class Ensemble:
         rec = record if isinstance(record, int) else int(bool(record))
         _ck(lib().csim_ensemble_assimilate_local(self._h, net._h, float(inflation), tm, rec,
                                                  0.0 if screen is None else float(screen)))
+
+    def assimilate_letkf(self, net: ObsNetwork, inflation=1.0, truth_member=None, record=False, screen=None, spacing=8):
+        """the LETKF with the network's observations, always enqueued: ensemble-space weights from the used observations
+        near each analysis node, R-localised with the network's loc, on the lattice letkf_nodes(nx, ny, spacing), blended
+        to the cells between the nodes; spacing=1 is the full LETKF.  inflation (on the field), truth_member, record and
+        screen as in assimilate_local, whose limits on the windows over one cell do not apply; CsimError (unsupported)
+        beyond LETKF_MAX_NODES nodes or LETKF_MAX_BYTES of node storage, see letkf_plan()
+        (csim_ensemble_assimilate_letkf)"""
+        tm = -1 if truth_member is None else int(truth_member)
+        rec = record if isinstance(record, int) else int(bool(record))
+        _ck(lib().csim_ensemble_assimilate_letkf(self._h, net._h, float(inflation), tm, rec,
+                                                 0.0 if screen is None else float(screen), int(spacing)))
+
+    def letkf_info(self) -> LetkfInfo:
+        """what the nodes of the ensemble's last assimilate_letkf() found; waits for the stream, and raises CsimError
+        when a node's Gram matrix was not finite (csim_ensemble_letkf_info)"""
+        nax, nay = C.c_int(), C.c_int()
+        rc = lib().csim_ensemble_letkf_info(self._h, C.byref(nax), C.byref(nay), None, None, None, None)
+        if nax.value == 0:  # there was no LETKF
+            _ck(rc)
+        shape = (nay.value, nax.value)
+        dfs = np.empty(shape)
+        count, sweeps, status = (np.zeros(shape, dtype=np.int32) for _ in range(3))
+        rc = lib().csim_ensemble_letkf_info(self._h, None, None, _dp(dfs), _ip(count), _ip(sweeps), _ip(status))
+        self.letkf_last = LetkfInfo(dfs, count, sweeps, status)  # filled even where the call fails
+        _ck(rc)
+        return self.letkf_last
 
     def obs_gram(self, net: ObsNetwork, truth_member=None, loglik=False) -> ObsGram:
         """the observation-space Gram matrix of the forecast members over the network's active observations, and with

@@ -6,6 +6,7 @@
 #include <unordered_map>
 
 #include "assim_plan.hpp"
+#include "letkf_nodes.hpp"
 
 using namespace csim;
 
@@ -190,9 +191,88 @@ bool local_tiles_build(int nx, int ny, const AssimPlan& p, int tile, LocalTiles*
     return true;
 }
 
+bool letkf_lookup_build(int nx, int ny, const AssimPlan& p, int spacing, LetkfLookup* out) {
+    const int nax = letkf_axis_nodes(nx, spacing), nay = letkf_axis_nodes(ny, spacing);
+    const size_t nn = static_cast<size_t>(nax) * nay;
+    // the nodes of an axis whose cell lies in lo .. hi: their cells increase strictly with the node
+    struct Range {
+        int first, last;  // empty: first > last
+    };
+    auto range = [&](long long lo, long long hi, int n, int na) {
+        int a0 = 0, a1 = na - 1;
+        while (a0 < na && letkf_node_at(a0, spacing, n) < lo) ++a0;
+        while (a1 >= 0 && letkf_node_at(a1, spacing, n) > hi) --a1;
+        return Range{a0, a1};
+    };
+    auto span = [&](int q, Range* rx, Range* ry) {
+        const long long i = p.pi[q], j = p.pj[q];
+        *rx = range(std::max(1LL, i - p.lx), std::min<long long>(nx, i + p.lx), nx, nax);
+        *ry = range(std::max(1LL, j - p.ly), std::min<long long>(ny, j + p.ly), ny, nay);
+    };
+    std::vector<long long> cnt(nn + 1, 0);
+    Range rx, ry;
+    for (int q = 0; q < p.nobs; ++q) {
+        span(q, &rx, &ry);
+        for (int b = ry.first; b <= ry.last; ++b)
+            for (int a = rx.first; a <= rx.last; ++a) ++cnt[static_cast<size_t>(b) * nax + a + 1];
+    }
+    for (size_t g = 0; g < nn; ++g) cnt[g + 1] += cnt[g];
+    if (cnt[nn] > 0x7fffffffLL) return false;
+    out->spacing = spacing, out->nax = nax, out->nay = nay;
+    out->start.assign(cnt.begin(), cnt.end());
+    out->pos.resize(static_cast<size_t>(cnt[nn]));
+    // in input order, so that every node's list comes out sorted by input index
+    std::vector<int> at(p.nobs);
+    for (int q = 0; q < p.nobs; ++q) at[p.idx[q]] = q;
+    std::vector<int> fill(out->start.begin(), out->start.end() - 1);
+    for (int o = 0; o < p.nobs; ++o) {
+        const int q = at[o];
+        span(q, &rx, &ry);
+        for (int b = ry.first; b <= ry.last; ++b)
+            for (int a = rx.first; a <= rx.last; ++a) out->pos[fill[static_cast<size_t>(b) * nax + a]++] = q;
+    }
+    return true;
+}
+
 }  // namespace csim
 
 extern "C" {
+
+int csim_letkf_nodes(int nx, int ny, int spacing, int* nax, int* nay, int* xi, int* yj) {
+    OBS_REQUIRE(nx >= 1 && ny >= 1, "empty grid");
+    OBS_REQUIRE(spacing >= 1, "spacing must be >= 1");
+    const int na = letkf_axis_nodes(nx, spacing), nb = letkf_axis_nodes(ny, spacing);
+    if (nax) *nax = na;
+    if (nay) *nay = nb;
+    for (int a = 0; xi && a < na; ++a) xi[a] = letkf_node_at(a, spacing, nx);
+    for (int b = 0; yj && b < nb; ++b) yj[b] = letkf_node_at(b, spacing, ny);
+    return CSIM_OK;
+}
+
+int csim_letkf_blend(int nx, int ny, int spacing, int i, int j, int node[4], double beta[4]) {
+    OBS_REQUIRE(nx >= 1 && ny >= 1, "empty grid");
+    OBS_REQUIRE(spacing >= 1, "spacing must be >= 1");
+    OBS_REQUIRE(i >= 1 && i <= nx && j >= 1 && j <= ny, "cell outside the interior");
+    OBS_REQUIRE(node && beta, "null argument");
+    const int na = letkf_axis_nodes(nx, spacing), nb = letkf_axis_nodes(ny, spacing);
+    const LetkfAxis x = letkf_axis_blend(i, spacing, nx, na), y = letkf_axis_blend(j, spacing, ny, nb);
+    const int a1 = std::min(x.a + 1, na - 1), b1 = std::min(y.a + 1, nb - 1);
+    node[0] = y.a * na + x.a, node[1] = y.a * na + a1, node[2] = b1 * na + x.a, node[3] = b1 * na + a1;
+    letkf_weights4(x.t, y.t, beta);
+    return CSIM_OK;
+}
+
+int csim_letkf_plan(int M, int nx, int ny, int spacing, long* nodes, long long* bytes) {
+    OBS_REQUIRE(M >= 2, "M must be >= 2");
+    OBS_REQUIRE(nx >= 1 && ny >= 1, "empty grid");
+    OBS_REQUIRE(spacing >= 1, "spacing must be >= 1");
+    if (M > CSIM_ESPACE_MAX_MEMBERS)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_letkf_plan: at most CSIM_ESPACE_MAX_MEMBERS forecast members");
+    const long nn = static_cast<long>(letkf_axis_nodes(nx, spacing)) * letkf_axis_nodes(ny, spacing);
+    if (nodes) *nodes = nn;
+    if (bytes) *bytes = static_cast<long long>(letkf_layout(M, nn, eigen_device_form(M, 0)).bytes);
+    return CSIM_OK;
+}
 
 int csim_ensemble_gc_table(double dx, double dy, double loc, int nx, int ny, int* lx, int* ly, double* table) {
     OBS_REQUIRE(lx && ly, "null argument");

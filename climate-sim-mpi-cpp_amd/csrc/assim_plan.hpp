@@ -1,6 +1,7 @@
 // assim_plan.hpp — the host mathematics of the ensemble analysis, without a device or the HIP headers (assim_plan.cpp):
 // the plan that csim_ensemble_assimilate and the observation networks both build, its batches, and behind include/csim.h
-// csim_ensemble_gc_table, csim_ensemble_assim_plan (the levels) and csim_ensemble_perturb_taps.
+// csim_ensemble_gc_table, csim_ensemble_assim_plan (the levels), csim_ensemble_perturb_taps and the host-only calls of
+// the LETKF (csim_letkf_nodes, csim_letkf_blend, csim_letkf_plan).
 // tools/assim_plan_host_check.cpp compiles it with plain g++ under AddressSanitizer.
 #pragma once
 #include <vector>
@@ -41,5 +42,15 @@ struct LocalTiles {
 };
 // false: more than 2^31 - 1 entries (nothing is built)
 bool local_tiles_build(int nx, int ny, const AssimPlan& p, int tile, LocalTiles* out);
+
+// The lookup of the LETKF (csim_ensemble_assimilate_letkf) for the lattice of letkf_nodes.hpp with this spacing: node g
+// = b nax + a holds pos[start[g] .. start[g + 1]): the plan positions of the observations whose window rectangle, clipped
+// to the interior, contains the node's cell, sorted by input index.
+struct LetkfLookup {
+    int spacing = 0, nax = 0, nay = 0;
+    std::vector<int> start, pos;
+};
+// false: more than 2^31 - 1 entries (nothing is built)
+bool letkf_lookup_build(int nx, int ny, const AssimPlan& p, int spacing, LetkfLookup* out);
 
 }  // namespace csim

@@ -11,7 +11,8 @@
 //   ensemble_da.cpp    data assimilation: the analysis of a plan, Philox / normal numbers, perturbations, relaxation
 //                      (prior capture, relax); the plan, the Gaspari-Cohn table and the taps: assim_plan.cpp, without HIP
 //   ensemble_obs.cpp   observation networks: create / destroy, values from the host or from a member, the analysis that
-//                      reads a network, its diagnostics and log
+//                      reads a network, its diagnostics and log; the local analysis, the ETKF and the LETKF on a network
+//                      (the LETKF's lattice and node storage: letkf_nodes.hpp, its lookup: assim_plan.cpp, without HIP)
 //   ensemble_space.cpp ensemble space: Gram matrix, projection, transform and EOFs; the eigensolver: sym_eigen.cpp,
 //                      without HIP
 #include <cmath>
@@ -150,6 +151,7 @@ int csim_ensemble_destroy(csim_ensemble* e) {
     e->assim.release();
     e->relax.release();
     e->espace.release();
+    e->letkf.release();
     e->own.release();
     delete e;
     return CSIM_OK;
@@ -334,6 +336,9 @@ int csim_ensemble_set_option(csim_ensemble* e, const char* key, long value) {
     } else if (k == "eigen_form") {
         CSIM_REQUIRE(value >= 0 && value <= EIGEN_FORMS, "eigen_form must be 0 (automatic) or 1 .. 3");
         e->espace.eigen_form = static_cast<int>(value);
+    } else if (k == "letkf_form") {
+        CSIM_REQUIRE(value >= 0 && value <= LETKF_FORMS, "letkf_form must be 0 (automatic) or 1");
+        e->letkf.form = static_cast<int>(value);
     } else if (k == "depth_used") {
         return fail(CSIM_ERR_ARG, "option depth_used is read-only");
     } else if (k == "contract") {
@@ -373,6 +378,8 @@ int csim_ensemble_get_option(const csim_ensemble* e, const char* key, long* valu
         *value = e->espace.obs_gram_form;
     else if (k == "eigen_form")
         *value = e->espace.eigen_form;
+    else if (k == "letkf_form")
+        *value = e->letkf.form;
     else if (k == "contract")
         return fail(CSIM_ERR_UNSUPPORTED, "an ensemble is always bit-identical: no contract mode");
     else

@@ -373,6 +373,37 @@ hipError_t ens_launch_etkf_weights(int M, const double* A, const double* lambda,
                                    double inflation, double* W, double* wbar, EtkfRecord* rec, double* gamma,
                                    hipStream_t st);
 
+// the LETKF of csim_ensemble_assimilate_letkf: the weights on a lattice of analysis nodes (letkf_nodes.hpp), interpolated
+// to the cells.  After ens_launch_local_prior: the node Gram matrices (ensemble_letkf.hip), ens_launch_sym_eigen on them
+// where they lie, the weights of every node (sym_eigen_device.hip), and the cell pass (ensemble_letkf.hip).
+struct LetkfGramArgs {
+    int nax, nay, spacing;        // the lattice: nay x nax nodes, node (a, b) at index b nax + a
+    const int* cstart;            // per node, one more than nodes: its candidates are cpos[cstart[g]] .. cpos[cstart[g + 1] - 1]
+    const int* cpos;              // plan positions, sorted by input index within a node
+    const double* prior;          // M per plan position: h_{o,k}
+    double* A;                    // (M + 1)^2 per node
+    int* count;                   // per node: |L(g)|
+};
+// A_g and count_g of every node; the AssimArgs as for ens_launch_local_prior.  form: 0 or 1 .. GRAM_FORMS, as
+// ens_launch_obs_gram; the result does not depend on it
+hipError_t ens_launch_letkf_gram(const EnsGeom& g, const AssimArgs& a, const LetkfGramArgs& l, int form, hipStream_t st);
+// per node: status LETKF_IDLE (count 0) or LETKF_NONFINITE (an entry of A is not finite) with dfs = +0 and sweeps = 0,
+// else W (M x M), wbar, dfs of csim_etkf_weights_ordered(M, A, 1.0, round robin) from the solver's lambda, V and info
+// (sweeps, status per node), with the solver's sweeps and LETKF_OK or LETKF_NOT_CONVERGED
+hipError_t ens_launch_letkf_weights(int M, int nodes, const double* A, const double* lambda, const double* V,
+                                    const int* info, const int* count, double* W, double* wbar, double* dfs, int* sweeps,
+                                    int* status, hipStream_t st);
+struct LetkfCellArgs {
+    int nax, nay, spacing;
+    const double* W;              // M^2 per node
+    const double* wbar;           // M per node
+    const int* status;            // per node
+};
+// the cell pass: every interior cell of the forecast members from the weights of its four nodes, in place.
+// form: 0 or 1 .. LETKF_FORMS of letkf_nodes.hpp; the result does not depend on it
+hipError_t ens_launch_letkf_cells(const EnsGeom& g, double* f, int M, int t, const LetkfCellArgs& l, int form,
+                                  hipStream_t st);
+
 // the rank histogram's tie-break: splitmix64's finaliser of the interior index g; a cell with `eq` members equal to the
 // truth goes to bin lt + mix(g) mod (eq + 1)
 __host__ __device__ inline unsigned long long verify_mix(unsigned long long z) {

@@ -8,6 +8,7 @@
 
 #include "assim_plan.hpp"
 #include "ensemble.hpp"
+#include "letkf_nodes.hpp"
 #include "stepper.hpp"
 
 namespace csim {
@@ -124,6 +125,16 @@ struct csim_ensemble {
             partial.release(), gram.release(), out.release(), w.release(), eig.release(), stage.release();
         }
     } espace;
+    // the LETKF (csim_ensemble_assimilate_letkf, ensemble_obs.cpp): the node storage of the last call (LetkfLayout) and
+    // what csim_ensemble_letkf_info needs to fetch its record; its launch option
+    struct Letkf {
+        csim::DeviceBuf buf;
+        csim::LetkfLayout l{};
+        int form = 0;            // option letkf_form; 0: automatic
+        bool valid = false;      // there was an LETKF, and `buf` still holds its record
+        int nax = 0, nay = 0;    // its lattice
+        void release() { buf.release(); }
+    } letkf;
     // observation networks (csim_obs_network_*, ensemble_obs.cpp): the ones that are alive; each owns its device buffer
     struct Obs {
         std::vector<csim_obs_network*> nets;

@@ -10,6 +10,9 @@
 // The local analysis (csim_ensemble_assimilate_local; kernels in ensemble_local.hip) shares the checks, the screening
 // and the recording of the serial one (analysis_check, analysis_begin, analysis_record) and differs in what runs between
 // them; its lookup and the observation priors are storage of the network's own, made at the first local analysis.
+// The LETKF (csim_ensemble_assimilate_letkf; kernels in ensemble_letkf.hip and sym_eigen_device.hip) is the fourth
+// analysis between the shared pieces: the priors of the local analysis, a Gram matrix per node of a lattice, the batched
+// eigensolver and weights, and a cell pass that interpolates the weights; its lookup is the network's, per spacing.
 // The observation-space Gram matrix (csim_ensemble_obs_gram; kernels in ensemble_obsgram.hip) reads a network and writes
 // nothing of it; the ETKF (csim_ensemble_assimilate_etkf) is the third analysis between the shared pieces: that matrix of
 // the used observations, csim_etkf_weights (etkf_weights.cpp) on the host, and csim_ensemble_transform.
@@ -90,6 +93,15 @@ struct csim_obs_network : AssimPlan {   // the plan: nobs, nlevels, lx, ly, off,
         size_t pos_at = 0;              // where the plan positions start, bytes
         void release() { prior.release(), tiles.release(), stage.release(); }
     } loc;
+    // the LETKF (csim_ensemble_assimilate_letkf): the lookup of the last spacing, made when the spacing is another one
+    // and kept until destroy; the observation priors are those of the local analysis (loc.prior)
+    struct Letkf {
+        DeviceBuf nodes;                // the lookup (LetkfLookup): its starts, then its plan positions
+        Staging stage;
+        int spacing = 0;                // of the lookup on the device (0: none)
+        size_t pos_at = 0;              // where the plan positions start, bytes
+        void release() { nodes.release(), stage.release(); }
+    } letkf;
     size_t imp_dn() const { return 0; }
     size_t imp_out() const { return up(sizeof(double) * nobs); }
     size_t imp_snap() const { return 2 * up(sizeof(double) * nobs); }
@@ -105,7 +117,7 @@ struct csim_obs_network : AssimPlan {   // the plan: nobs, nlevels, lx, ly, off,
         if (ntaps) a.tstart = at<int>(l.tstart), a.toff = at<int>(l.toff), a.tw = at<double>(l.tw);
         return a;
     }
-    ~csim_obs_network() { dev.release(), stage.release(), mstage.release(), imp.release(), loc.release(); }
+    ~csim_obs_network() { dev.release(), stage.release(), mstage.release(), imp.release(), loc.release(), letkf.release(); }
 };
 
 void csim_ensemble::Obs::release() {
@@ -660,6 +672,114 @@ int csim_ensemble_etkf_info(const csim_ensemble* e, long long* n_used, double* c
                             int* n_gamma) {
     // a pending record of the device path is fetched into the handle, which this older signature declares const
     return csim_ensemble_etkf_info2(const_cast<csim_ensemble*>(e), n_used, chi2, dfs, gamma, n_gamma, nullptr, nullptr);
+}
+
+int csim_ensemble_assimilate_letkf(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member, int record,
+                                   double tol, int spacing) {
+    int M = 0, t = 0;
+    CSIM_TRY(analysis_check(e, n, inflation, truth_member, record, tol, &M, &t));
+    CSIM_REQUIRE(spacing >= 1, "spacing must be >= 1");
+    const EnsGeom& g = e->g;
+    CSIM_REQUIRE(g.slab <= 0x7fffffffL, "grid too large for the ensemble-space kernels");
+    if (M > ESPACE_MAX_MEMBERS)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_letkf: at most CSIM_ESPACE_MAX_MEMBERS forecast "
+                                          "members");
+    const size_t doubles = static_cast<size_t>(n->nobs) * M;
+    if (doubles > static_cast<size_t>(CSIM_LOCAL_MAX_PRIOR_DOUBLES))
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_letkf: nobs times the forecast members exceeds "
+                                          "CSIM_LOCAL_MAX_PRIOR_DOUBLES");
+    const int nax = letkf_axis_nodes(g.nx, spacing), nay = letkf_axis_nodes(g.ny, spacing);
+    const long nodes = static_cast<long>(nax) * nay;
+    if (nodes > CSIM_LETKF_MAX_NODES)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_letkf: more than CSIM_LETKF_MAX_NODES analysis nodes; "
+                                          "take a larger spacing");
+    const int eform = eigen_device_form(M, e->espace.eigen_form);
+    if (!eform)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_letkf: the eigen_form that is set does not admit "
+                                          "this many forecast members");
+    // the limit is on the bytes that csim_letkf_plan reports; a forced eigen_form may keep more in global memory
+    if (static_cast<long long>(letkf_layout(M, nodes, eigen_device_form(M, 0)).bytes) > CSIM_LETKF_MAX_BYTES)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_letkf: the node storage exceeds CSIM_LETKF_MAX_BYTES "
+                                          "(csim_letkf_plan); take a larger spacing");
+    const LetkfLayout l = letkf_layout(M, nodes, eform);
+    csim_obs_network::Letkf& x = n->letkf;
+    csim_ensemble::Letkf& s = e->letkf;
+    try {
+        // the lookup for this spacing, made and uploaded when the spacing is another one than the last
+        if (x.spacing != spacing) {
+            LetkfLookup lk;
+            if (!letkf_lookup_build(g.nx, g.ny, *n, spacing, &lk))
+                return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_letkf: the lookup exceeds 2^31 entries");
+            const size_t pos_at = up(sizeof(int) * lk.start.size()), bytes = up(pos_at + sizeof(int) * lk.pos.size());
+            void* staged = nullptr;
+            CSIM_TRY(x.stage.acquire(bytes, &staged));
+            std::copy(lk.start.begin(), lk.start.end(), buf_at<int>(staged, 0));
+            std::copy(lk.pos.begin(), lk.pos.end(), buf_at<int>(staged, pos_at));
+            x.spacing = 0;  // from here on the last lookup is being replaced (after its readers)
+            CSIM_TRY(x.nodes.reserve(bytes, e->st));
+            CSIM_TRY(x.stage.send(x.nodes.p, bytes, e->st));
+            x.spacing = spacing, x.pos_at = pos_at;
+        }
+    } catch (const std::bad_alloc&) {
+        return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_letkf: out of host memory");
+    }
+    CSIM_TRY(n->loc.prior.reserve(sizeof(double) * doubles, e->st));
+    s.valid = false;  // from here on the last record is being overwritten (in stream order, after its readers)
+    CSIM_TRY(s.buf.reserve(l.bytes, e->st));
+    Analysis an;
+    CSIM_TRY(analysis_begin(e, n, M, t, record, tol, &an));
+    double* f = e->base(e->cur);
+    if (inflation != 1.0) CSIM_HIP(ens_launch_assim_inflate(g, f, M, t, inflation - 1.0, e->st));
+    CSIM_HIP(ens_launch_local_prior(g, f, an.a, n->nobs, n->loc.prior.as(), e->st));
+    void* const d = s.buf.p;
+    LetkfGramArgs ga{};
+    ga.nax = nax, ga.nay = nay, ga.spacing = spacing;
+    ga.cstart = buf_at<int>(x.nodes.p, 0), ga.cpos = buf_at<int>(x.nodes.p, x.pos_at);
+    ga.prior = n->loc.prior.as();
+    ga.A = buf_at<double>(d, l.A), ga.count = buf_at<int>(d, l.count);
+    CSIM_HIP(ens_launch_letkf_gram(g, an.a, ga, e->espace.obs_gram_form, e->st));
+    CSIM_HIP(ens_launch_sym_eigen(M, static_cast<int>(nodes), ga.A, M + 1, static_cast<long>(M + 1) * (M + 1),
+                                  buf_at<double>(d, l.work), buf_at<double>(d, l.lam), buf_at<double>(d, l.V),
+                                  buf_at<int>(d, l.info), e->espace.eigen_form, e->st));
+    CSIM_HIP(ens_launch_letkf_weights(M, static_cast<int>(nodes), ga.A, buf_at<double>(d, l.lam), buf_at<double>(d, l.V),
+                                      buf_at<int>(d, l.info), ga.count, buf_at<double>(d, l.W), buf_at<double>(d, l.wbar),
+                                      buf_at<double>(d, l.dfs), buf_at<int>(d, l.sweeps), buf_at<int>(d, l.status),
+                                      e->st));
+    LetkfCellArgs ca{};
+    ca.nax = nax, ca.nay = nay, ca.spacing = spacing;
+    ca.W = buf_at<double>(d, l.W), ca.wbar = buf_at<double>(d, l.wbar), ca.status = buf_at<int>(d, l.status);
+    CSIM_HIP(ens_launch_letkf_cells(g, f, M, t, ca, s.form, e->st));
+    s.valid = true, s.l = l, s.nax = nax, s.nay = nay;
+    return record ? analysis_record(e, n, an) : CSIM_OK;
+}
+
+int csim_ensemble_letkf_info(csim_ensemble* e, int* nax, int* nay, double* dfs, int* count, int* sweeps, int* status) {
+    CSIM_REQUIRE(e, "null ensemble");
+    csim_ensemble::Letkf& s = e->letkf;
+    if (!s.valid)
+        return fail(CSIM_ERR_STATE, "csim_ensemble_letkf_info: the ensemble has had no csim_ensemble_assimilate_letkf");
+    const size_t nodes = static_cast<size_t>(s.nax) * s.nay;
+    if (nax) *nax = s.nax;
+    if (nay) *nay = s.nay;
+    try {
+        std::vector<int> st(nodes);
+        if (dfs)
+            CSIM_HIP(hipMemcpyAsync(dfs, buf_at<char>(s.buf.p, s.l.dfs), sizeof(double) * nodes, hipMemcpyDeviceToHost, e->st));
+        if (count)
+            CSIM_HIP(hipMemcpyAsync(count, buf_at<char>(s.buf.p, s.l.count), sizeof(int) * nodes, hipMemcpyDeviceToHost, e->st));
+        if (sweeps)
+            CSIM_HIP(hipMemcpyAsync(sweeps, buf_at<char>(s.buf.p, s.l.sweeps), sizeof(int) * nodes, hipMemcpyDeviceToHost, e->st));
+        CSIM_HIP(hipMemcpyAsync(st.data(), buf_at<char>(s.buf.p, s.l.status), sizeof(int) * nodes, hipMemcpyDeviceToHost, e->st));
+        CSIM_HIP(hipStreamSynchronize(e->st));
+        if (status) std::copy(st.begin(), st.end(), status);
+        for (int v : st)
+            if (v == CSIM_LETKF_NONFINITE)
+                return fail(CSIM_ERR_STATE, "csim_ensemble_letkf_info: the Gram matrix of a node has a non-finite entry; "
+                                            "the cells that only such nodes feed are unchanged");
+        return CSIM_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(CSIM_ERR_STATE, "csim_ensemble_letkf_info: out of host memory");
+    }
 }
 
 int csim_obs_network_local_info(csim_obs_network* n, int* max_local) {

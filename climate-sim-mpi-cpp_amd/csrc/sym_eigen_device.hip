@@ -1,5 +1,6 @@
 // sym_eigen_device.hip — the Jacobi eigensolver on the device, in the round-robin order of include/csim.h
-// (CSIM_EIGEN_ROUND_ROBIN), and the ETKF's weights from its result.  One workgroup per matrix, blockIdx.x the matrix of
+// (CSIM_EIGEN_ROUND_ROBIN), and the ETKF's weights from its result: of one matrix (k_etkf_weights, the global ETKF) and
+// of a batch, one workgroup per node of an LETKF (k_letkf_weights), on the same arithmetic.  One workgroup per matrix, blockIdx.x the matrix of
 // a batch; nothing synchronises across workgroups.  Every * + - / sqrt is one IEEE fp64 operation (-ffp-contract=off;
 // fp64 division and square root are the correctly rounded ones), so the bits are those of sym_eigen_ordered and
 // csim_etkf_weights_ordered on the host.
@@ -17,6 +18,7 @@
 
 #include "ensemble.hpp"
 #include "ensemble_cell.hpp"
+#include "letkf_nodes.hpp"
 #include "sym_eigen.hpp"
 
 namespace csim {
@@ -228,6 +230,36 @@ hipError_t launch_eigen(const EigenArgs& g, int batch, hipStream_t st) {
 
 constexpr int WEIGHTS_THREADS = 256;
 
+// The arithmetic of csim_etkf_weights_ordered that k_etkf_weights and k_letkf_weights share, one function per line of
+// the csim.h block.  A is ma x ma, ma = M + 1; V is M x M.
+__device__ __forceinline__ double etkf_clamp(double lam) { return lam > 0.0 ? lam : 0.0; }
+__device__ __forceinline__ double etkf_f(double kappa, double G) { return 1.0 / (kappa + G); }
+__device__ __forceinline__ double etkf_g(int M, double f) { return sqrt(static_cast<double>(M - 1) * f); }
+__device__ __forceinline__ double etkf_u(int M, const double* __restrict__ V, const double* __restrict__ A, int r) {
+    const int ma = M + 1;
+    double u = 0.0;
+    for (int a = 0; a < M; ++a) u = u + V[static_cast<size_t>(a) * M + r] * A[static_cast<size_t>(a) * ma + M];
+    return u;
+}
+__device__ __forceinline__ double etkf_wbar_entry(int M, const double* __restrict__ V, const double* fu, int a) {
+    double s = 0.0;
+    for (int r = 0; r < M; ++r) s = s + V[static_cast<size_t>(a) * M + r] * fu[r];
+    return s;
+}
+__device__ __forceinline__ double etkf_dfs(int M, const double* __restrict__ lam, double kappa) {
+    double d = 0.0;
+    for (int r = 0; r < M; ++r) {
+        const double G = etkf_clamp(lam[r]);
+        d = d + G * etkf_f(kappa, G);
+    }
+    return d;
+}
+__device__ __forceinline__ double etkf_w_entry(int M, const double* __restrict__ V, const double* gs, int a, int b) {
+    double s = 0.0;
+    for (int r = 0; r < M; ++r) s = s + (V[static_cast<size_t>(a) * M + r] * gs[r]) * V[static_cast<size_t>(b) * M + r];
+    return s;
+}
+
 // The weights of csim_etkf_weights_ordered from A (ma x ma, ma = M + 1) and the solver's lambda, V and info.  Every
 // workgroup computes f and g of every mode into LDS and then takes entries (a, b >= a) of W in a grid stride, one lane
 // per entry.  Workgroup 0 also tests A, computes u, wbar, gamma and dfs and writes the record.
@@ -246,13 +278,11 @@ __global__ __launch_bounds__(WEIGHTS_THREADS) void k_etkf_weights(int M, const d
     if (tid == 0) bad = 0;
     __syncthreads();
     for (int r = tid; r < M; r += nt) {
-        const double G = lam[r] > 0.0 ? lam[r] : 0.0;
-        const double f = 1.0 / (kappa + G);
-        gs[r] = sqrt(static_cast<double>(M - 1) * f);
+        const double G = etkf_clamp(lam[r]);
+        const double f = etkf_f(kappa, G);
+        gs[r] = etkf_g(M, f);
         if (blockIdx.x == 0) {
-            double u = 0.0;
-            for (int a = 0; a < M; ++a) u = u + V[static_cast<size_t>(a) * M + r] * A[static_cast<size_t>(a) * ma + M];
-            fu[r] = f * u;
+            fu[r] = f * etkf_u(M, V, A, r);
             gamma[r] = G;
         }
     }
@@ -261,17 +291,9 @@ __global__ __launch_bounds__(WEIGHTS_THREADS) void k_etkf_weights(int M, const d
             if (!isfinite(A[k])) bad = 1;
     __syncthreads();
     if (blockIdx.x == 0) {
-        for (int a = tid; a < M; a += nt) {
-            double s = 0.0;
-            for (int r = 0; r < M; ++r) s = s + V[static_cast<size_t>(a) * M + r] * fu[r];
-            wbar[a] = s;
-        }
+        for (int a = tid; a < M; a += nt) wbar[a] = etkf_wbar_entry(M, V, fu, a);
         if (tid == 0) {
-            double d = 0.0;
-            for (int r = 0; r < M; ++r) {
-                const double G = lam[r] > 0.0 ? lam[r] : 0.0;
-                d = d + G * (1.0 / (kappa + G));
-            }
+            const double d = etkf_dfs(M, lam, kappa);
             long long used;
             memcpy(&used, A + static_cast<size_t>(ma) * ma + M, sizeof used);  // the count travels behind loglik
             rec->dfs = d, rec->chi2 = A[static_cast<size_t>(ma) * ma - 1], rec->n_used = used;
@@ -283,9 +305,59 @@ __global__ __launch_bounds__(WEIGHTS_THREADS) void k_etkf_weights(int M, const d
     for (long e = static_cast<long>(blockIdx.x) * nt + tid; e < pairs; e += static_cast<long>(gridDim.x) * nt) {
         const int a = static_cast<int>(e / M), b = static_cast<int>(e - static_cast<long>(a) * M);
         if (b < a) continue;
-        double s = 0.0;
-        for (int r = 0; r < M; ++r) s = s + (V[static_cast<size_t>(a) * M + r] * gs[r]) * V[static_cast<size_t>(b) * M + r];
-        W[static_cast<size_t>(a) * M + b] = W[static_cast<size_t>(b) * M + a] = s;
+        W[static_cast<size_t>(a) * M + b] = W[static_cast<size_t>(b) * M + a] = etkf_w_entry(M, V, gs, a, b);
+    }
+}
+
+// The weights of every node of an LETKF, one workgroup per node (blockIdx.x): csim_etkf_weights_ordered with inflation
+// 1 from the node's A, lambda and V.  A node without a local observation (count 0) is IDLE, one with a non-finite entry
+// of A NONFINITE; both report dfs = +0 and sweeps = 0, and their W and wbar are not written.
+__global__ __launch_bounds__(WEIGHTS_THREADS) void k_letkf_weights(int M, const double* __restrict__ Aall,
+                                                                   const double* __restrict__ lamall,
+                                                                   const double* __restrict__ Vall,
+                                                                   const int* __restrict__ info,
+                                                                   const int* __restrict__ count,
+                                                                   double* __restrict__ Wall, double* __restrict__ wbarall,
+                                                                   double* __restrict__ dfs, int* __restrict__ sweeps,
+                                                                   int* __restrict__ status) {
+    __shared__ double gs[ESPACE_MAX_MEMBERS], fu[ESPACE_MAX_MEMBERS];
+    __shared__ int bad;
+    const int tid = threadIdx.x, nt = blockDim.x, ma = M + 1;
+    const size_t node = blockIdx.x, mm = static_cast<size_t>(M) * M;
+    const double* __restrict__ A = Aall + node * ma * ma;
+    const double* __restrict__ lam = lamall + node * M;
+    const double* __restrict__ V = Vall + node * mm;
+    double* __restrict__ W = Wall + node * mm;
+    double* __restrict__ wbar = wbarall + node * M;
+    const int n = count[node];  // the same for every lane: the workgroup leaves together
+    if (tid == 0) bad = 0;
+    __syncthreads();
+    if (n != 0)
+        for (int k = tid; k < ma * ma; k += nt)
+            if (!isfinite(A[k])) bad = 1;
+    __syncthreads();
+    if (n == 0 || bad) {
+        if (tid == 0) dfs[node] = 0.0, sweeps[node] = 0, status[node] = n == 0 ? LETKF_IDLE : LETKF_NONFINITE;
+        return;
+    }
+    const double rho = 1.0 * 1.0;
+    const double kappa = static_cast<double>(M - 1) / rho;
+    for (int r = tid; r < M; r += nt) {
+        const double f = etkf_f(kappa, etkf_clamp(lam[r]));
+        gs[r] = etkf_g(M, f);
+        fu[r] = f * etkf_u(M, V, A, r);
+    }
+    __syncthreads();
+    for (int a = tid; a < M; a += nt) wbar[a] = etkf_wbar_entry(M, V, fu, a);
+    if (tid == 0) {
+        dfs[node] = etkf_dfs(M, lam, kappa);
+        sweeps[node] = info[2 * node];
+        status[node] = info[2 * node + 1] == EIGEN_NOT_CONVERGED ? LETKF_NOT_CONVERGED : LETKF_OK;
+    }
+    for (int e = tid; e < M * M; e += nt) {
+        const int a = e / M, b = e - a * M;
+        if (b < a) continue;
+        W[static_cast<size_t>(a) * M + b] = W[static_cast<size_t>(b) * M + a] = etkf_w_entry(M, V, gs, a, b);
     }
 }
 
@@ -311,6 +383,15 @@ hipError_t ens_launch_etkf_weights(int M, const double* A, const double* lambda,
     const int blocks = static_cast<int>(std::min<long>((pairs + WEIGHTS_THREADS - 1) / WEIGHTS_THREADS, 256));
     hipLaunchKernelGGL(k_etkf_weights, dim3(blocks), dim3(WEIGHTS_THREADS), 0, st, M, A, lambda, V, info, inflation, W,
                        wbar, rec, gamma);
+    return hipGetLastError();
+}
+
+hipError_t ens_launch_letkf_weights(int M, int nodes, const double* A, const double* lambda, const double* V,
+                                    const int* info, const int* count, double* W, double* wbar, double* dfs, int* sweeps,
+                                    int* status, hipStream_t st) {
+    if (M < 2 || M > ESPACE_MAX_MEMBERS || nodes < 1 || nodes > LETKF_MAX_NODES) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_letkf_weights, dim3(nodes), dim3(WEIGHTS_THREADS), 0, st, M, A, lambda, V, info, count, W, wbar,
+                       dfs, sweeps, status);
     return hipGetLastError();
 }
 

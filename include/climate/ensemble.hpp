@@ -149,6 +149,40 @@ struct EtkfAnalysis {
     int sweeps = 0, status = CSIM_EIGEN_OK;  // of the device eigensolver, after assimilate_etkf_device (else 0)
 };
 
+// the lattice of analysis nodes of Ensemble::assimilate_letkf (see csim_letkf_nodes): nay x nax nodes, node (a, b) at the
+// interior cell (xi[a], yj[b]) with index b nax + a.  Host only
+struct LetkfNodes {
+    int nax = 0, nay = 0;
+    std::vector<int> xi, yj;
+};
+inline LetkfNodes letkf_nodes(int nx, int ny, int spacing) {
+    LetkfNodes n;
+    if (csim_letkf_nodes(nx, ny, spacing, &n.nax, &n.nay, nullptr, nullptr) != CSIM_OK)
+        throw std::runtime_error(std::string("csim: ") + csim_last_error());
+    n.xi.resize(n.nax), n.yj.resize(n.nay);
+    if (csim_letkf_nodes(nx, ny, spacing, nullptr, nullptr, n.xi.data(), n.yj.data()) != CSIM_OK)
+        throw std::runtime_error(std::string("csim: ") + csim_last_error());
+    return n;
+}
+// the four nodes of the interior cell (i, j) and the weights with which their analyses are blended there (see
+// csim_letkf_blend).  Host only
+struct LetkfBlend {
+    int node[4] = {0, 0, 0, 0};
+    double beta[4] = {0.0, 0.0, 0.0, 0.0};
+};
+inline LetkfBlend letkf_blend(int nx, int ny, int spacing, int i, int j) {
+    LetkfBlend b;
+    if (csim_letkf_blend(nx, ny, spacing, i, j, b.node, b.beta) != CSIM_OK)
+        throw std::runtime_error(std::string("csim: ") + csim_last_error());
+    return b;
+}
+// what the nodes of an LETKF found (see csim_ensemble_letkf_info): nay x nax values each, row-major
+struct LetkfInfo {
+    int nax = 0, nay = 0;
+    std::vector<double> dfs;
+    std::vector<int> count, sweeps, status;  // status: CSIM_LETKF_*
+};
+
 // the leading modes of an ensemble's spread (see csim_ensemble_eofs): lambda and variance = lambda / (M - 1) per mode,
 // pcs M x n_modes row-major, patterns n_modes dense fields (empty when not asked for)
 struct EnsembleEOFs {
@@ -538,6 +572,25 @@ public:
     void assimilate_local(ObsNetwork& net, double inflation = 1.0, int t = -1, bool record = false,
                           double screen_tol = 0.0) {
         check(csim_ensemble_assimilate_local(h_, net.handle(), inflation, t, record ? 1 : 0, screen_tol));
+    }
+    // the LETKF with the network's observations, always enqueued: ensemble-space weights from the used observations near
+    // each node of the lattice letkf_nodes(nx, ny, spacing), R-localised, blended to the cells between the nodes;
+    // spacing 1 is the full LETKF (see csim_ensemble_assimilate_letkf); the other arguments as for assimilate_local
+    void assimilate_letkf(ObsNetwork& net, double inflation = 1.0, int t = -1, bool record = false,
+                          double screen_tol = 0.0, int spacing = 8) {
+        check(csim_ensemble_assimilate_letkf(h_, net.handle(), inflation, t, record ? 1 : 0, screen_tol, spacing));
+    }
+    // what the nodes of the last assimilate_letkf found; waits for the stream, and throws when a node's Gram matrix was
+    // not finite (see csim_ensemble_letkf_info)
+    LetkfInfo letkf_info() {
+        LetkfInfo r;
+        const int rc = csim_ensemble_letkf_info(h_, &r.nax, &r.nay, nullptr, nullptr, nullptr, nullptr);
+        if (r.nax == 0) check(rc);  // there was no LETKF
+        const std::size_t n = static_cast<std::size_t>(r.nax) * r.nay;
+        r.dfs.resize(n), r.count.resize(n), r.sweeps.resize(n), r.status.resize(n);
+        check(csim_ensemble_letkf_info(h_, nullptr, nullptr, r.dfs.data(), r.count.data(), r.sweeps.data(),
+                                       r.status.data()));
+        return r;
     }
     // the observation-space Gram matrix of the forecast members over the network's active observations, and with loglik
     // each member's sum of squared normalised departures; synchronous, writes nothing of the network (see

@@ -10,7 +10,8 @@
 # round-robin order with its pairing) and of the ETKF
 # (csrc/etkf_weights.cpp: the weights' residual, symmetry and row sums up to the largest M, the
 # plan of the observation-space Gram sum against brute force) and of the two Gram sums (csrc/gram_plan.hpp: the plan, and
-# which lane owns which block of pairs at every width and form), each as a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.  The build goes to $TMP;
+# which lane owns which block of pairs at every width and form) and of the LETKF (csrc/assim_plan.cpp once more and
+# csrc/letkf_nodes.hpp: the per-node lookup against brute force, the nodes and the blend at their seams), each as a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.  The build goes to $TMP;
 # nothing in the tree is replaced.
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -28,6 +29,7 @@ CXX=(g++ -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined
 "${CXX[@]}" -o "$TMP/sym_eigen_rr_host_check" "$R/tools/sym_eigen_rr_host_check.cpp" "$S/sym_eigen.cpp"
 "${CXX[@]}" -o "$TMP/etkf_host_check" "$R/tools/etkf_host_check.cpp" "$S/etkf_weights.cpp" "$S/sym_eigen.cpp"
 "${CXX[@]}" -o "$TMP/gram_plan_host_check" "$R/tools/gram_plan_host_check.cpp"
+"${CXX[@]}" -o "$TMP/letkf_plan_host_check" "$R/tools/letkf_plan_host_check.cpp" "$S/assim_plan.cpp"
 export ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1
 "$TMP/obsop_host_check"
 "$TMP/assim_plan_host_check"
@@ -38,3 +40,4 @@ export ASAN_OPTIONS=halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktra
 "$TMP/sym_eigen_rr_host_check"
 "$TMP/etkf_host_check"
 "$TMP/gram_plan_host_check"
+"$TMP/letkf_plan_host_check"
