@@ -1,5 +1,6 @@
 // assim_plan.cpp — the analysis plan on the host (assim_plan.hpp): the Gaspari-Cohn table that the analysis and the
-// perturbation taps share, the levels, the plan order and its batches.  No device, no HIP headers.
+// perturbation taps share, the levels, the plan order and its batches, and the lookups of the local analysis and of the
+// LETKF, one counting sort (lookup_build) behind both.  No device, no HIP headers.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -104,6 +105,46 @@ int assim_levels(int n, const int* oi, const int* oj, int lx, int ly, bool order
     return static_cast<int>(per.size());
 }
 
+// an inclusive rectangle of cells or of bins; empty where x0 > x1 or y0 > y1
+struct Rect {
+    int x0, x1, y0, y1;
+};
+
+// the window of the observation at plan position q, clipped to the interior
+Rect window_of(int nx, int ny, const AssimPlan& p, int q) {
+    const long long i = p.pi[q], j = p.pj[q];
+    return {static_cast<int>(std::max(1LL, i - p.lx)), static_cast<int>(std::min<long long>(nx, i + p.lx)),
+            static_cast<int>(std::max(1LL, j - p.ly)), static_cast<int>(std::min<long long>(ny, j + p.ly))};
+}
+
+// The lookup of local_tiles_build and letkf_lookup_build, a counting sort: bin y * width + x of `bins` bins lists the
+// plan positions q with (x, y) in bins_of(q), sorted by input index; bin b's are pos[start[b]] .. pos[start[b + 1] - 1].
+// False: more than 2^31 - 1 entries.
+template <class F>
+bool lookup_build(const AssimPlan& p, size_t bins, int width, std::vector<int>* start, std::vector<int>* pos, F&& bins_of) {
+    std::vector<long long> cnt(bins + 1, 0);
+    for (int q = 0; q < p.nobs; ++q) {
+        const Rect s = bins_of(q);
+        for (int y = s.y0; y <= s.y1; ++y)
+            for (int x = s.x0; x <= s.x1; ++x) ++cnt[static_cast<size_t>(y) * width + x + 1];
+    }
+    for (size_t b = 0; b < bins; ++b) cnt[b + 1] += cnt[b];
+    if (cnt[bins] > 0x7fffffffLL) return false;
+    start->assign(cnt.begin(), cnt.end());
+    pos->resize(static_cast<size_t>(cnt[bins]));
+    // in input order, so that every bin's list comes out sorted by input index
+    std::vector<int> at(p.nobs);
+    for (int q = 0; q < p.nobs; ++q) at[p.idx[q]] = q;
+    std::vector<int> fill(start->begin(), start->end() - 1);
+    for (int o = 0; o < p.nobs; ++o) {
+        const int q = at[o];
+        const Rect s = bins_of(q);
+        for (int y = s.y0; y <= s.y1; ++y)
+            for (int x = s.x0; x <= s.x1; ++x) (*pos)[fill[static_cast<size_t>(y) * width + x]++] = q;
+    }
+    return true;
+}
+
 }  // namespace
 
 namespace csim {
@@ -156,82 +197,33 @@ void assim_batches(int nx, int ny, const AssimPlan& p, int batch, std::vector<As
 
 bool local_tiles_build(int nx, int ny, const AssimPlan& p, int tile, LocalTiles* out) {
     const int ntx = (nx + tile - 1) / tile, nty = (ny + tile - 1) / tile;
-    const size_t nt = static_cast<size_t>(ntx) * nty;
-    // the tiles that the clipped rectangle of the observation at (i, j) meets
-    struct Span {
-        int x0, x1, y0, y1;
-    };
-    auto span = [&](int i, int j) {
-        const long long i0 = std::max(1LL, static_cast<long long>(i) - p.lx), i1 = std::min<long long>(nx, static_cast<long long>(i) + p.lx);
-        const long long j0 = std::max(1LL, static_cast<long long>(j) - p.ly), j1 = std::min<long long>(ny, static_cast<long long>(j) + p.ly);
-        return Span{static_cast<int>((i0 - 1) / tile), static_cast<int>((i1 - 1) / tile), static_cast<int>((j0 - 1) / tile),
-                    static_cast<int>((j1 - 1) / tile)};
-    };
-    std::vector<long long> cnt(nt + 1, 0);
-    for (int q = 0; q < p.nobs; ++q) {
-        const Span s = span(p.pi[q], p.pj[q]);
-        for (int ty = s.y0; ty <= s.y1; ++ty)
-            for (int tx = s.x0; tx <= s.x1; ++tx) ++cnt[static_cast<size_t>(ty) * ntx + tx + 1];
-    }
-    for (size_t t = 0; t < nt; ++t) cnt[t + 1] += cnt[t];
-    if (cnt[nt] > 0x7fffffffLL) return false;
-    out->tile = tile, out->ntx = ntx, out->nty = nty;
-    out->start.assign(cnt.begin(), cnt.end());
-    out->pos.resize(static_cast<size_t>(cnt[nt]));
-    // in input order, so that every tile's list comes out sorted by input index
-    std::vector<int> at(p.nobs);
-    for (int q = 0; q < p.nobs; ++q) at[p.idx[q]] = q;
-    std::vector<int> fill(out->start.begin(), out->start.end() - 1);
-    for (int o = 0; o < p.nobs; ++o) {
-        const int q = at[o];
-        const Span s = span(p.pi[q], p.pj[q]);
-        for (int ty = s.y0; ty <= s.y1; ++ty)
-            for (int tx = s.x0; tx <= s.x1; ++tx) out->pos[fill[static_cast<size_t>(ty) * ntx + tx]++] = q;
-    }
-    return true;
+    // the tiles that the clipped window meets
+    const bool ok = lookup_build(p, static_cast<size_t>(ntx) * nty, ntx, &out->start, &out->pos, [&](int q) {
+        const Rect w = window_of(nx, ny, p, q);
+        return Rect{(w.x0 - 1) / tile, (w.x1 - 1) / tile, (w.y0 - 1) / tile, (w.y1 - 1) / tile};
+    });
+    if (ok) out->tile = tile, out->ntx = ntx, out->nty = nty;
+    return ok;
 }
 
 bool letkf_lookup_build(int nx, int ny, const AssimPlan& p, int spacing, LetkfLookup* out) {
     const int nax = letkf_axis_nodes(nx, spacing), nay = letkf_axis_nodes(ny, spacing);
-    const size_t nn = static_cast<size_t>(nax) * nay;
     // the nodes of an axis whose cell lies in lo .. hi: their cells increase strictly with the node
-    struct Range {
-        int first, last;  // empty: first > last
-    };
-    auto range = [&](long long lo, long long hi, int n, int na) {
+    auto range = [&](int lo, int hi, int n, int na, int* first, int* last) {
         int a0 = 0, a1 = na - 1;
         while (a0 < na && letkf_node_at(a0, spacing, n) < lo) ++a0;
         while (a1 >= 0 && letkf_node_at(a1, spacing, n) > hi) --a1;
-        return Range{a0, a1};
+        *first = a0, *last = a1;
     };
-    auto span = [&](int q, Range* rx, Range* ry) {
-        const long long i = p.pi[q], j = p.pj[q];
-        *rx = range(std::max(1LL, i - p.lx), std::min<long long>(nx, i + p.lx), nx, nax);
-        *ry = range(std::max(1LL, j - p.ly), std::min<long long>(ny, j + p.ly), ny, nay);
-    };
-    std::vector<long long> cnt(nn + 1, 0);
-    Range rx, ry;
-    for (int q = 0; q < p.nobs; ++q) {
-        span(q, &rx, &ry);
-        for (int b = ry.first; b <= ry.last; ++b)
-            for (int a = rx.first; a <= rx.last; ++a) ++cnt[static_cast<size_t>(b) * nax + a + 1];
-    }
-    for (size_t g = 0; g < nn; ++g) cnt[g + 1] += cnt[g];
-    if (cnt[nn] > 0x7fffffffLL) return false;
-    out->spacing = spacing, out->nax = nax, out->nay = nay;
-    out->start.assign(cnt.begin(), cnt.end());
-    out->pos.resize(static_cast<size_t>(cnt[nn]));
-    // in input order, so that every node's list comes out sorted by input index
-    std::vector<int> at(p.nobs);
-    for (int q = 0; q < p.nobs; ++q) at[p.idx[q]] = q;
-    std::vector<int> fill(out->start.begin(), out->start.end() - 1);
-    for (int o = 0; o < p.nobs; ++o) {
-        const int q = at[o];
-        span(q, &rx, &ry);
-        for (int b = ry.first; b <= ry.last; ++b)
-            for (int a = rx.first; a <= rx.last; ++a) out->pos[fill[static_cast<size_t>(b) * nax + a]++] = q;
-    }
-    return true;
+    const bool ok = lookup_build(p, static_cast<size_t>(nax) * nay, nax, &out->start, &out->pos, [&](int q) {
+        const Rect w = window_of(nx, ny, p, q);
+        Rect b;
+        range(w.x0, w.x1, nx, nax, &b.x0, &b.x1);
+        range(w.y0, w.y1, ny, nay, &b.y0, &b.y1);
+        return b;
+    });
+    if (ok) out->spacing = spacing, out->nax = nax, out->nay = nay;
+    return ok;
 }
 
 }  // namespace csim

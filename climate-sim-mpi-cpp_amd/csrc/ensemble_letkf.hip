@@ -11,14 +11,15 @@
 //                  class, and the lanes' sums are carried from one 64 to the next.  A chunk without a local observation
 //                  costs its status bytes and nothing else.
 //   k_letkf_cells  The cells between four nodes, a patch, share the four W: a workgroup takes 64 cells of one patch,
-//                  one per lane, p_k in registers (P > 0, the steps of for_step) or in LDS as [member][lane] with four
-//                  waves dividing the outputs (P = 0: M > 64, or letkf_form 1), as k_espace_apply.  W, wbar and the
-//                  status of a node are read with wave-uniform addresses, so their loads are scalar; four outputs r
-//                  share one pass over k.  A node whose weight is zero at a lane's cell takes no part there; a node that
-//                  is IDLE or NONFINITE stands for the identity.  A member's value is written once all M have been read.
+//                  one per lane, its p_k held and applied by espace_cell.hpp as in k_espace_apply: in registers (P > 0,
+//                  the steps of for_step) or in LDS (P = 0: M > 64, or letkf_form 1).  The status of a node is read
+//                  with a wave-uniform address like its W and wbar.  A node whose weight is zero at a lane's cell takes
+//                  no part there; a node that is IDLE or NONFINITE stands for the identity.  A member's value is written
+//                  once all M have been read.
 // Every product and every sum is one rounded fp64 operation, no FMA contraction; / and sqrt are IEEE fp64.
 #include <algorithm>
 
+#include "espace_cell.hpp"
 #include "gram_tile.hpp"
 #include "letkf_nodes.hpp"
 
@@ -125,18 +126,15 @@ __global__ __launch_bounds__(GRAM_THREADS) void k_letkf_gram(int nx, int ny, Ass
     if (blockIdx.y == 0 && tid == 0) l.count[node] = cnt;
 }
 
-constexpr int CELLS_RB = 4;     // outputs r that share one pass over k
-constexpr int CELLS_WAVES = 4;  // LDS form: waves that share 64 cells, each taking every fourth group of outputs
-
 __device__ __forceinline__ bool letkf_active(int status) { return status == LETKF_OK || status == LETKF_NOT_CONVERGED; }
 
 // grid: patches x chunks; chunk c of a patch holds its cells 64 c .. 64 c + 63, row-major within the patch
 template <int P>
-__global__ __launch_bounds__(P > 0 ? 64 : 64 * CELLS_WAVES) void k_letkf_cells(
+__global__ __launch_bounds__(P > 0 ? 64 : 64 * CELL_WAVES) void k_letkf_cells(
     double* __restrict__ f, int nx, int ny, int pitch, long slab, int M, int t, int nax, int nay, int spacing,
     int chunks, const double* __restrict__ Wall, const double* __restrict__ wbarall, const int* __restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) double held[];  // P = 0: [M][64]
-    constexpr int NW = P > 0 ? 1 : CELLS_WAVES;
+    constexpr int NW = P > 0 ? 1 : CELL_WAVES;
     const int lane = threadIdx.x & 63, wave = P > 0 ? 0 : threadIdx.x >> 6;
     const int npx = max(nax - 1, 1), npy = max(nay - 1, 1);
     const int patch = blockIdx.x / chunks, chunk = blockIdx.x - patch * chunks;
@@ -169,53 +167,24 @@ __global__ __launch_bounds__(P > 0 ? 64 : 64 * CELLS_WAVES) void k_letkf_cells(
 
     double* __restrict__ p = cell_ptr(f, i, j, pitch);
     double x[P > 0 ? P : 1];
-    double m;
-    if constexpr (P > 0) {
-#pragma unroll
-        for (int k = 0; k < P; ++k) x[k] = p[static_cast<size_t>(forecast_member(min(k, M - 1), t)) * slab];
-        m = mean_regs<P>(x, M);
-#pragma unroll
-        for (int k = 0; k < P; ++k) x[k] = x[k] - m;
-    } else {
-#pragma unroll 8
-        for (int k = wave; k < M; k += NW) held[k * 64 + lane] = p[static_cast<size_t>(forecast_member(k, t)) * slab];
-        __syncthreads();
-        double s = 0.0;
-#pragma unroll 8
-        for (int k = 0; k < M; ++k) s = s + held[k * 64 + lane];
-        m = s / static_cast<double>(M);
-        __syncthreads();  // every wave has read the members it did not load before any is replaced
-#pragma unroll 8
-        for (int k = wave; k < M; k += NW) held[k * 64 + lane] = held[k * 64 + lane] - m;
-        __syncthreads();
-    }
+    const double m = cell_hold<P>(p, slab, M, t, true, lane, wave, x, held);
     const size_t mm = static_cast<size_t>(M) * M;
     double d[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
         if (!act[n]) continue;  // the same in every lane
-        const double* __restrict__ wb = wbarall + static_cast<size_t>(nd[n]) * M;
-        double s = 0.0;
-        if constexpr (P > 0) {
-#pragma unroll
-            for (int k = 0; k < P; ++k)
-                if (k < M) s = s + x[k] * wb[k];
-        } else {
-#pragma unroll 4
-            for (int k = 0; k < M; ++k) s = s + held[k * 64 + lane] * wb[k];
-        }
-        d[n] = s;
+        d[n] = cell_dot<P>(x, held, lane, M, wbarall + static_cast<size_t>(nd[n]) * M);
     }
-    for (int r0 = CELLS_RB * wave; r0 < M; r0 += CELLS_RB * NW) {
-        int rr[CELLS_RB];
-        double c[CELLS_RB], pr[CELLS_RB];
+    for (int r0 = CELL_RB * wave; r0 < M; r0 += CELL_RB * NW) {
+        int rr[CELL_RB];
+        double c[CELL_RB], pr[CELL_RB];
 #pragma unroll
-        for (int u = 0; u < CELLS_RB; ++u) rr[u] = min(r0 + u, M - 1), c[u] = 0.0, pr[u] = 0.0;
+        for (int u = 0; u < CELL_RB; ++u) rr[u] = min(r0 + u, M - 1), c[u] = 0.0, pr[u] = 0.0;
         if (idle) {
             // p_r of the outputs, for the nodes that stand for the identity: the register form reads the members again
             // (the same bits; they are written further down), the LDS form has them at hand
 #pragma unroll
-            for (int u = 0; u < CELLS_RB; ++u) {
+            for (int u = 0; u < CELL_RB; ++u) {
                 if constexpr (P > 0)
                     pr[u] = p[static_cast<size_t>(forecast_member(rr[u], t)) * slab] - m;
                 else
@@ -224,37 +193,23 @@ __global__ __launch_bounds__(P > 0 ? 64 : 64 * CELLS_WAVES) void k_letkf_cells(
         }
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
-            double s[CELLS_RB];
+            double s[CELL_RB];
             if (act[n]) {
+#pragma unroll
+                for (int u = 0; u < CELL_RB; ++u) s[u] = 0.0;
                 const double* __restrict__ W = Wall + static_cast<size_t>(nd[n]) * mm;
-#pragma unroll
-                for (int u = 0; u < CELLS_RB; ++u) s[u] = 0.0;
-                if constexpr (P > 0) {
-#pragma unroll
-                    for (int k = 0; k < P; ++k)
-                        if (k < M) {
-#pragma unroll
-                            for (int u = 0; u < CELLS_RB; ++u) s[u] = s[u] + x[k] * W[static_cast<size_t>(k) * M + rr[u]];
-                        }
-                } else {
-#pragma unroll 4
-                    for (int k = 0; k < M; ++k) {
-                        const double pk = held[k * 64 + lane];
-#pragma unroll
-                        for (int u = 0; u < CELLS_RB; ++u) s[u] = s[u] + pk * W[static_cast<size_t>(k) * M + rr[u]];
-                    }
-                }
+                CSIM_CELL_APPLY(P, x, held, lane, M, W, M, rr, s)
             } else {
 #pragma unroll
-                for (int u = 0; u < CELLS_RB; ++u) s[u] = pr[u];
+                for (int u = 0; u < CELL_RB; ++u) s[u] = pr[u];
             }
             if (use[n]) {
 #pragma unroll
-                for (int u = 0; u < CELLS_RB; ++u) c[u] = c[u] + beta[n] * (d[n] + s[u]);
+                for (int u = 0; u < CELL_RB; ++u) c[u] = c[u] + beta[n] * (d[n] + s[u]);
             }
         }
 #pragma unroll
-        for (int u = 0; u < CELLS_RB; ++u)
+        for (int u = 0; u < CELL_RB; ++u)
             if (r0 + u < M && write) p[static_cast<size_t>(forecast_member(r0 + u, t)) * slab] = m + c[u];
     }
 }
@@ -300,7 +255,7 @@ hipError_t ens_launch_letkf_cells(const EnsGeom& g, double* f, int M, int t, con
             const hipError_t attr = dynamic_lds_once<k_letkf_cells<P>>(sizeof(double) * 64 * ESPACE_MAX_MEMBERS);
             if (attr != hipSuccess) return attr;
         }
-        hipLaunchKernelGGL(k_letkf_cells<P>, dim3(static_cast<unsigned>(blocks)), dim3(P > 0 ? 64 : 64 * CELLS_WAVES), lds,
+        hipLaunchKernelGGL(k_letkf_cells<P>, dim3(static_cast<unsigned>(blocks)), dim3(P > 0 ? 64 : 64 * CELL_WAVES), lds,
                            st, f, g.nx, g.ny, g.pitch, g.slab, M, t, l.nax, l.nay, l.spacing, static_cast<int>(chunks),
                            l.W, l.wbar, l.status);
         return hipGetLastError();

@@ -7,15 +7,14 @@
 // The forecast impact (csim_obs_network_impact_capture, csim_ensemble_obs_impact; kernels in ensemble_impact.hip) keeps
 // a capture in storage of the network's own, made at the first capture: a_k per observation, dn and the status bytes,
 // and a device copy of the caller's weight; nothing that an analysis, observe or set_values writes.
-// The local analysis (csim_ensemble_assimilate_local; kernels in ensemble_local.hip) shares the checks, the screening
-// and the recording of the serial one (analysis_check, analysis_begin, analysis_record) and differs in what runs between
-// them; its lookup and the observation priors are storage of the network's own, made at the first local analysis.
-// The LETKF (csim_ensemble_assimilate_letkf; kernels in ensemble_letkf.hip and sym_eigen_device.hip) is the fourth
-// analysis between the shared pieces: the priors of the local analysis, a Gram matrix per node of a lattice, the batched
-// eigensolver and weights, and a cell pass that interpolates the weights; its lookup is the network's, per spacing.
-// The observation-space Gram matrix (csim_ensemble_obs_gram; kernels in ensemble_obsgram.hip) reads a network and writes
-// nothing of it; the ETKF (csim_ensemble_assimilate_etkf) is the third analysis between the shared pieces: that matrix of
-// the used observations, csim_etkf_weights (etkf_weights.cpp) on the host, and csim_ensemble_transform.
+// Four more analyses share the checks, the screening and the recording of the serial one (analysis_check,
+// analysis_begin, analysis_record) and differ in what runs between them:
+//   local  (ensemble_local.hip)  the observation priors and a lookup per tile, storage of the network's own
+//   ETKF   the observation-space Gram matrix of the used observations (csim_ensemble_obs_gram, ensemble_obsgram.hip,
+//          which writes nothing of the network), csim_etkf_weights on the host, csim_ensemble_transform; or, _device,
+//          the eigensolver and the weights of sym_eigen_device.hip with no host round trip
+//   LETKF  (ensemble_letkf.hip)  the local analysis's priors, a Gram matrix per node of a lattice, the batched
+//          eigensolver and weights, and a cell pass that interpolates the weights; a lookup per spacing
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -57,6 +56,29 @@ double impact_fold(const double* u, long n) {
     return l[0];
 }
 
+// a lookup on the device (LocalTiles, LetkfLookup): its starts, then its plan positions
+struct DeviceLookup {
+    DeviceBuf buf;
+    Staging stage;
+    size_t pos_at = 0;  // where the plan positions start, bytes
+    int key = 0;        // what it was built for (a tile, a spacing; 0: none)
+    void release() { buf.release(), stage.release(); }
+    const int* cstart() const { return buf_at<int>(buf.p, 0); }
+    const int* cpos() const { return buf_at<int>(buf.p, pos_at); }
+    int upload(const std::vector<int>& start, const std::vector<int>& pos, int k, hipStream_t st) {
+        const size_t at = up(sizeof(int) * start.size()), bytes = up(at + sizeof(int) * pos.size());
+        void* staged = nullptr;
+        CSIM_TRY(stage.acquire(bytes, &staged));
+        std::copy(start.begin(), start.end(), buf_at<int>(staged, 0));
+        std::copy(pos.begin(), pos.end(), buf_at<int>(staged, at));
+        key = 0;  // from here on the last lookup is being replaced (after its readers)
+        CSIM_TRY(buf.reserve(bytes, st));
+        CSIM_TRY(stage.send(buf.p, bytes, st));
+        key = k, pos_at = at;
+        return CSIM_OK;
+    }
+};
+
 }  // namespace
 
 struct csim_obs_network : AssimPlan {   // the plan: nobs, nlevels, lx, ly, off, idx, pi, pj
@@ -87,20 +109,15 @@ struct csim_obs_network : AssimPlan {   // the plan: nobs, nlevels, lx, ly, off,
     struct Local {
         int max_local = -1;             // the most window rectangles over one cell (-1: not counted yet)
         DeviceBuf prior;                // M doubles per plan position: h_{o,k}
-        DeviceBuf tiles;                // the lookup (LocalTiles): its starts, then its plan positions
-        Staging stage;
-        int tile = 0, ntx = 0, nty = 0; // of the lookup on the device (tile 0: none)
-        size_t pos_at = 0;              // where the plan positions start, bytes
-        void release() { prior.release(), tiles.release(), stage.release(); }
+        DeviceLookup tiles;             // the lookup (LocalTiles), its key the tile
+        int ntx = 0, nty = 0;           // of the lookup on the device
+        void release() { prior.release(), tiles.release(); }
     } loc;
     // the LETKF (csim_ensemble_assimilate_letkf): the lookup of the last spacing, made when the spacing is another one
     // and kept until destroy; the observation priors are those of the local analysis (loc.prior)
     struct Letkf {
-        DeviceBuf nodes;                // the lookup (LetkfLookup): its starts, then its plan positions
-        Staging stage;
-        int spacing = 0;                // of the lookup on the device (0: none)
-        size_t pos_at = 0;              // where the plan positions start, bytes
-        void release() { nodes.release(), stage.release(); }
+        DeviceLookup nodes;             // the lookup (LetkfLookup), its key the spacing
+        void release() { nodes.release(); }
     } letkf;
     size_t imp_dn() const { return 0; }
     size_t imp_out() const { return up(sizeof(double) * nobs); }
@@ -254,6 +271,20 @@ int analysis_check(csim_ensemble* e, csim_obs_network* n, double inflation, int 
                                                   : "csim_ensemble_assimilate_network: the network has no log");
     return CSIM_OK;
 }
+
+// analysis_check and the member limit of csim_ensemble_assimilate_etkf and _etkf_device
+int etkf_check(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member, int record, double tol, int* M,
+               int* t) {
+    CSIM_TRY(analysis_check(e, n, inflation, truth_member, record, tol, M, t));
+    if (*M > ESPACE_MAX_MEMBERS)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_etkf: at most CSIM_ESPACE_MAX_MEMBERS forecast "
+                                          "members");
+    return CSIM_OK;
+}
+
+// where A is not finite: the host path says so from the analysis, the device path from csim_ensemble_etkf_info
+constexpr const char* ETKF_NONFINITE_TEXT = "csim_ensemble_assimilate_etkf: the observation-space Gram matrix has a "
+                                            "non-finite entry; the members are unchanged";
 
 // an analysis between its screening and its record
 struct Analysis {
@@ -500,19 +531,12 @@ int csim_ensemble_assimilate_local(csim_ensemble* e, csim_obs_network* n, double
     const int tile = local_tile(e);
     try {
         // the lookup for this tile, made and uploaded when the tile is another one than the last
-        if (x.tile != tile) {
+        if (x.tiles.key != tile) {
             LocalTiles lt;
             if (!local_tiles_build(g.nx, g.ny, *n, tile, &lt))
                 return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_local: the lookup exceeds 2^31 entries");
-            const size_t pos_at = up(sizeof(int) * lt.start.size()), bytes = up(pos_at + sizeof(int) * lt.pos.size());
-            void* staged = nullptr;
-            CSIM_TRY(x.stage.acquire(bytes, &staged));
-            std::copy(lt.start.begin(), lt.start.end(), buf_at<int>(staged, 0));
-            std::copy(lt.pos.begin(), lt.pos.end(), buf_at<int>(staged, pos_at));
-            x.tile = 0;  // from here on the last lookup is being replaced (after its readers)
-            CSIM_TRY(x.tiles.reserve(bytes, e->st));
-            CSIM_TRY(x.stage.send(x.tiles.p, bytes, e->st));
-            x.tile = tile, x.ntx = lt.ntx, x.nty = lt.nty, x.pos_at = pos_at;
+            CSIM_TRY(x.tiles.upload(lt.start, lt.pos, tile, e->st));
+            x.ntx = lt.ntx, x.nty = lt.nty;
         }
     } catch (const std::bad_alloc&) {
         return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_local: out of host memory");
@@ -523,9 +547,9 @@ int csim_ensemble_assimilate_local(csim_ensemble* e, csim_obs_network* n, double
     double* f = e->base(e->cur);
     if (inflation != 1.0) CSIM_HIP(ens_launch_assim_inflate(g, f, M, t, inflation - 1.0, e->st));
     LocalArgs l{};
-    l.tile = x.tile, l.ntx = x.ntx, l.nty = x.nty, l.lmax = lmax;
+    l.tile = x.tiles.key, l.ntx = x.ntx, l.nty = x.nty, l.lmax = lmax;
     l.pack = ens_local_pack(M, lmax, e->local.pack);
-    l.cstart = buf_at<int>(x.tiles.p, 0), l.cpos = buf_at<int>(x.tiles.p, x.pos_at);
+    l.cstart = x.tiles.cstart(), l.cpos = x.tiles.cpos();
     l.prior = x.prior.as();
     CSIM_HIP(ens_launch_local_prior(g, f, an.a, n->nobs, x.prior.as(), e->st));
     CSIM_HIP(ens_launch_local_update(g, f, an.a, l, e->st));
@@ -562,10 +586,7 @@ int csim_ensemble_obs_gram(csim_ensemble* e, csim_obs_network* n, int truth_memb
 int csim_ensemble_assimilate_etkf(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
                                   int record, double tol) {
     int M = 0, t = 0;
-    CSIM_TRY(analysis_check(e, n, inflation, truth_member, record, tol, &M, &t));
-    if (M > ESPACE_MAX_MEMBERS)
-        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_etkf: at most CSIM_ESPACE_MAX_MEMBERS forecast "
-                                          "members");
+    CSIM_TRY(etkf_check(e, n, inflation, truth_member, record, tol, &M, &t));
     try {
         const size_t m = static_cast<size_t>(M), ma = m + 1;
         std::vector<double> out, W(m * m), wbar(m), gamma(m);
@@ -576,9 +597,7 @@ int csim_ensemble_assimilate_etkf(csim_ensemble* e, csim_obs_network* n, double 
         CSIM_TRY(analysis_begin(e, n, M, t, record, tol, &x));
         CSIM_TRY(obs_gram(e, n, M, t, x.screen ? x.s.status : nullptr, CSIM_OBS_USED, false, &out, &used));
         for (size_t k = 0; k < ma * ma; ++k)
-            if (!std::isfinite(out[k]))
-                return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_etkf: the observation-space Gram matrix has a "
-                                            "non-finite entry; the members are unchanged");
+            if (!std::isfinite(out[k])) return fail(CSIM_ERR_STATE, ETKF_NONFINITE_TEXT);
         CSIM_TRY(csim_etkf_weights(M, out.data(), inflation, W.data(), wbar.data(), gamma.data(), &dfs, nullptr));
         // nothing to assimilate and nothing to inflate: W would be the identity up to rounding, the members keep their bits
         if (used != 0 || inflation != 1.0) CSIM_TRY(csim_ensemble_transform(e, truth_member, 1, W.data(), wbar.data()));
@@ -595,10 +614,7 @@ int csim_ensemble_assimilate_etkf(csim_ensemble* e, csim_obs_network* n, double 
 int csim_ensemble_assimilate_etkf_device(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
                                          int record, double tol) {
     int M = 0, t = 0;
-    CSIM_TRY(analysis_check(e, n, inflation, truth_member, record, tol, &M, &t));
-    if (M > ESPACE_MAX_MEMBERS)
-        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_etkf: at most CSIM_ESPACE_MAX_MEMBERS forecast "
-                                          "members");
+    CSIM_TRY(etkf_check(e, n, inflation, truth_member, record, tol, &M, &t));
     CSIM_REQUIRE(e->g.slab <= 0x7fffffffL, "grid too large for the ensemble-space kernels");
     csim_ensemble::Espace& s = e->espace;
     if (!eigen_device_form(M, s.eigen_form))
@@ -646,9 +662,7 @@ int csim_ensemble_etkf_info2(csim_ensemble* e, long long* n_used, double* chi2, 
             s.etkf_status = rec.status == ETKF_NONFINITE        ? CSIM_EIGEN_NONFINITE
                             : rec.status == ETKF_NOT_CONVERGED ? CSIM_EIGEN_NOT_CONVERGED
                                                                : CSIM_EIGEN_OK;
-            if (rec.status == ETKF_NONFINITE)
-                return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_etkf: the observation-space Gram matrix has a "
-                                            "non-finite entry; the members are unchanged");
+            if (rec.status == ETKF_NONFINITE) return fail(CSIM_ERR_STATE, ETKF_NONFINITE_TEXT);
             s.etkf_gamma.assign(got.begin() + 4, got.end());
             s.etkf_used = rec.n_used, s.etkf_chi2 = rec.chi2, s.etkf_dfs = rec.dfs, s.etkf_valid = true;
         } catch (const std::bad_alloc&) {
@@ -706,19 +720,11 @@ int csim_ensemble_assimilate_letkf(csim_ensemble* e, csim_obs_network* n, double
     csim_ensemble::Letkf& s = e->letkf;
     try {
         // the lookup for this spacing, made and uploaded when the spacing is another one than the last
-        if (x.spacing != spacing) {
+        if (x.nodes.key != spacing) {
             LetkfLookup lk;
             if (!letkf_lookup_build(g.nx, g.ny, *n, spacing, &lk))
                 return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_letkf: the lookup exceeds 2^31 entries");
-            const size_t pos_at = up(sizeof(int) * lk.start.size()), bytes = up(pos_at + sizeof(int) * lk.pos.size());
-            void* staged = nullptr;
-            CSIM_TRY(x.stage.acquire(bytes, &staged));
-            std::copy(lk.start.begin(), lk.start.end(), buf_at<int>(staged, 0));
-            std::copy(lk.pos.begin(), lk.pos.end(), buf_at<int>(staged, pos_at));
-            x.spacing = 0;  // from here on the last lookup is being replaced (after its readers)
-            CSIM_TRY(x.nodes.reserve(bytes, e->st));
-            CSIM_TRY(x.stage.send(x.nodes.p, bytes, e->st));
-            x.spacing = spacing, x.pos_at = pos_at;
+            CSIM_TRY(x.nodes.upload(lk.start, lk.pos, spacing, e->st));
         }
     } catch (const std::bad_alloc&) {
         return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_letkf: out of host memory");
@@ -734,7 +740,7 @@ int csim_ensemble_assimilate_letkf(csim_ensemble* e, csim_obs_network* n, double
     void* const d = s.buf.p;
     LetkfGramArgs ga{};
     ga.nax = nax, ga.nay = nay, ga.spacing = spacing;
-    ga.cstart = buf_at<int>(x.nodes.p, 0), ga.cpos = buf_at<int>(x.nodes.p, x.pos_at);
+    ga.cstart = x.nodes.cstart(), ga.cpos = x.nodes.cpos();
     ga.prior = n->loc.prior.as();
     ga.A = buf_at<double>(d, l.A), ga.count = buf_at<int>(d, l.count);
     CSIM_HIP(ens_launch_letkf_gram(g, an.a, ga, e->espace.obs_gram_form, e->st));

@@ -9,14 +9,12 @@
 //                   stages a segment's perturbations in LDS as [cell][member]; the walk over them, the lanes' pairs
 //                   and the class's partial are the GramTile of gram_tile.hpp, the plan is gram_plan.hpp.
 //   k_gram_fold     entry (a, b), a <= b, folded over the classes (gram_fold_entry); written to G[a][b] and G[b][a].
-// Project / transform, one kernel template k_espace_apply<P, XFORM>: one cell per lane, p_k in registers (P > 0, the
-// steps of for_step) or in LDS as [member][lane] (P = 0: M > 64, or project_form 1).  W is read with wave-uniform
-// indices, so its loads are scalar; four outputs r share one pass over k, four independent chains.  In the LDS form
-// four waves share a tile of 64 cells and divide the outputs among them, so that the tile's LDS (512 B per member)
-// keeps four waves busy instead of one.  All M values of a cell are held before any is stored, so the transform may
-// write the members it read.
+// Project / transform, one kernel template k_espace_apply<P, XFORM>: one cell per lane, its p_k held and applied by
+// espace_cell.hpp, in registers (P > 0, the steps of for_step) or in LDS (P = 0: M > 64, or project_form 1).  All M
+// values of a cell are held before any is stored, so the transform may write the members it read.
 #include <algorithm>
 
+#include "espace_cell.hpp"
 #include "gram_tile.hpp"
 
 #pragma clang fp contract(off)
@@ -84,23 +82,17 @@ __global__ __launch_bounds__(64) void k_gram_fold(const double* __restrict__ par
     G[static_cast<size_t>(b) * M + a] = s;
 }
 
-constexpr int APPLY_RB = 4;     // outputs r that share one pass over k
-constexpr int APPLY_WAVES = 4;  // LDS form: waves that share one tile of 64 cells, each taking every fourth group of outputs
-
 // XFORM = false: project; cells are the dense cells of (ny+2) x (nx+2), out gets K fields.
 // XFORM = true: transform; cells are the interior cells, K = M, the members are written in place.
-// P > 0: one wave per workgroup.  P = 0: APPLY_WAVES waves load the tile's members together, every wave sums the mean
-// of its lane's cell (the same bits in each), the waves subtract it from a quarter of the members each, and wave w
-// computes the outputs r of groups w, w + APPLY_WAVES, ...
+// P > 0: one wave per workgroup.  P = 0: CELL_WAVES waves, wave w computes the outputs r of groups w, w + CELL_WAVES, ...
 template <int P, bool XFORM>
-__global__ __launch_bounds__(P > 0 ? 64 : 64 * APPLY_WAVES) void k_espace_apply(double* __restrict__ f, int nx, int ny, int pitch, long slab,
-                                                     int M, int t, int centered, int K, const double* __restrict__ W,
-                                                     const double* __restrict__ wbar, double* __restrict__ out,
-                                                     const int* __restrict__ gate) {
+__global__ __launch_bounds__(P > 0 ? 64 : 64 * CELL_WAVES) void k_espace_apply(
+    double* __restrict__ f, int nx, int ny, int pitch, long slab, int M, int t, int centered, int K,
+    const double* __restrict__ W, const double* __restrict__ wbar, double* __restrict__ out, const int* __restrict__ gate) {
     extern __shared__ __attribute__((aligned(16))) double held[];  // P = 0: [M][64]
     // the transform of a device ETKF obeys the status its weights kernel left: the whole grid returns at once
     if (XFORM && gate && (*gate == ETKF_NONFINITE || *gate == ETKF_SKIP)) return;
-    constexpr int NW = P > 0 ? 1 : APPLY_WAVES;
+    constexpr int NW = P > 0 ? 1 : CELL_WAVES;
     // the register form is one wave: `wave` is a constant 0 there, so the loop over the outputs keeps no state for it
     const int lane = threadIdx.x & 63, wave = P > 0 ? 0 : threadIdx.x >> 6;
     const int nx2 = nx + 2;
@@ -117,66 +109,17 @@ __global__ __launch_bounds__(P > 0 ? 64 : 64 * APPLY_WAVES) void k_espace_apply(
             p = cell_ptr(f, static_cast<int>(ec - static_cast<long>(j) * nx2), j, pitch);
         }
         double x[P > 0 ? P : 1];
-        double m = 0.0;
-        if constexpr (P > 0) {
-#pragma unroll
-            for (int k = 0; k < P; ++k) x[k] = p[static_cast<size_t>(forecast_member(min(k, M - 1), t)) * slab];
-            if (centered) {
-                m = mean_regs<P>(x, M);
-#pragma unroll
-                for (int k = 0; k < P; ++k) x[k] = x[k] - m;
-            }
-        } else {
-#pragma unroll 8
-            for (int k = wave; k < M; k += NW)
-                held[k * 64 + lane] = p[static_cast<size_t>(forecast_member(k, t)) * slab];
-            __syncthreads();
-            if (centered) {
-                double s = 0.0;
-#pragma unroll 8
-                for (int k = 0; k < M; ++k) s = s + held[k * 64 + lane];
-                m = s / static_cast<double>(M);
-                __syncthreads();  // every wave has read the members it did not load before any is replaced
-#pragma unroll 8
-                for (int k = wave; k < M; k += NW) held[k * 64 + lane] = held[k * 64 + lane] - m;
-                __syncthreads();
-            }
-        }
+        const double m = cell_hold<P>(p, slab, M, t, centered != 0, lane, wave, x, held);
         double mp = m;
-        if (XFORM && wbar) {
-            double d = 0.0;
-            if constexpr (P > 0) {
+        if (XFORM && wbar) mp = m + cell_dot<P>(x, held, lane, M, wbar);
+        for (int r0 = CELL_RB * wave; r0 < K; r0 += CELL_RB * NW) {
+            int rr[CELL_RB];
+            double s[CELL_RB];
 #pragma unroll
-                for (int k = 0; k < P; ++k)
-                    if (k < M) d = d + x[k] * wbar[k];
-            } else {
-#pragma unroll 4
-                for (int k = 0; k < M; ++k) d = d + held[k * 64 + lane] * wbar[k];
-            }
-            mp = m + d;
-        }
-        for (int r0 = APPLY_RB * wave; r0 < K; r0 += APPLY_RB * NW) {
-            int rr[APPLY_RB];
-            double s[APPLY_RB];
+            for (int u = 0; u < CELL_RB; ++u) rr[u] = min(r0 + u, K - 1), s[u] = 0.0;
+            CSIM_CELL_APPLY(P, x, held, lane, M, W, K, rr, s)
 #pragma unroll
-            for (int u = 0; u < APPLY_RB; ++u) rr[u] = min(r0 + u, K - 1), s[u] = 0.0;
-            if constexpr (P > 0) {
-#pragma unroll
-                for (int k = 0; k < P; ++k)
-                    if (k < M) {
-#pragma unroll
-                        for (int u = 0; u < APPLY_RB; ++u) s[u] = s[u] + x[k] * W[static_cast<size_t>(k) * K + rr[u]];
-                    }
-            } else {
-#pragma unroll 4
-                for (int k = 0; k < M; ++k) {
-                    const double pk = held[k * 64 + lane];
-#pragma unroll
-                    for (int u = 0; u < APPLY_RB; ++u) s[u] = s[u] + pk * W[static_cast<size_t>(k) * K + rr[u]];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < APPLY_RB; ++u) {
+            for (int u = 0; u < CELL_RB; ++u) {
                 if (r0 + u >= K || !valid) continue;
                 if (XFORM)
                     p[static_cast<size_t>(forecast_member(r0 + u, t)) * slab] = centered ? mp + s[u] : s[u];
@@ -219,7 +162,7 @@ hipError_t launch_apply(const EnsGeom& g, double* f, int M, int t, bool centered
                 dynamic_lds_once<k_espace_apply<P, XFORM>>(sizeof(double) * 64 * ESPACE_MAX_MEMBERS);
             if (attr != hipSuccess) return attr;
         }
-        hipLaunchKernelGGL((k_espace_apply<P, XFORM>), dim3(apply_blocks(cells)), dim3(P > 0 ? 64 : 64 * APPLY_WAVES), lds, st, f, g.nx, g.ny,
+        hipLaunchKernelGGL((k_espace_apply<P, XFORM>), dim3(apply_blocks(cells)), dim3(P > 0 ? 64 : 64 * CELL_WAVES), lds, st, f, g.nx, g.ny,
                            g.pitch, g.slab, M, t, centered ? 1 : 0, K, W, wbar, out, gate);
         return hipGetLastError();
     };

@@ -181,6 +181,7 @@ GRAM_FORMS = (1, 2, 3)
 PROJECT_CASES = [
     (7, 9, 3), (8, 8, 12), (5, 13, 48), (130, 67, 12), (257, 3, 64), (1, 300, 7), (257, 3, 20),
     (1, 1, 65), (7, 9, 65), (8, 8, 128), (5, 13, 256),
+    (7, 9, 8), (7, 9, 17), (7, 9, 33),  # a full register step, and the first M of a step, on one wave with a lane past the end
 ]
 PROJECT_FORMS = (0, 1)
 

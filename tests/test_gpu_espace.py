@@ -186,7 +186,9 @@ def test_project_takes_a_vector_and_leaves_the_members_alone(csim):
 # ---- transform -------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("nx,ny,M,form", with_forms([(7, 9, 3), (5, 13, 12), (130, 67, 12), (257, 3, 48), (8, 8, 64),
-                                                     (1, 300, 20), (7, 9, 65), (8, 8, 128), (5, 13, 256)]))
+                                                     (1, 300, 20), (7, 9, 65), (8, 8, 128), (5, 13, 256)] +
+                                                    # every register step full, and the first M of the next one
+                                                    [(7, 9, M) for M in (4, 8, 9, 16, 17, 32, 33, 49)]))
 def test_transform(csim, nx, ny, M, form):
     B = M + 1
     X = ref.members(B, nx, ny, seed=8)

@@ -127,9 +127,12 @@ def test_letkf_is_the_restatement(csim, eig, lattice, where, lam):
 
 
 # the register steps' ends, the register / LDS seam of the cell pass (64 | 65) and the solver's three forms (96 | 97,
-# 128 | 129); every eigen_form that admits M forced, and every letkf_form at M = 5 and 64
+# 128 | 129); every eigen_form that admits M forced, and every letkf_form at M = 5 and 64.  Then the cell pass's other
+# register steps, each full and at its first M, with one eigen_form; both letkf_forms at M = 16 and 33
 MEMBERS = [(2, "first", (1, 2, 3), (0,)), (5, None, (1, 2, 3), (0, 1)), (64, "first", (1, 2, 3), (0, 1)),
-           (65, None, (1, 2, 3), (0,)), (97, None, (2, 3), (0,)), (129, "middle", (3,), (0,))]
+           (65, None, (1, 2, 3), (0,)), (97, None, (2, 3), (0,)), (129, "middle", (3,), (0,)),
+           (8, "middle", (1,), (0,)), (9, None, (1,), (0,)), (16, "first", (1,), (0, 1)), (17, "middle", (1,), (0,)),
+           (33, None, (1,), (0, 1)), (49, "first", (1,), (0,))]
 
 
 @pytest.mark.parametrize("case", MEMBERS, ids=lambda c: f"M{c[0]}_t{c[1]}")
