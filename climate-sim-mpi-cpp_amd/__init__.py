@@ -258,6 +258,8 @@ def lib() -> C.CDLL:
         "csim_obs_network_impact_capture": (i, [vp, i]),
         "csim_ensemble_obs_impact": (i, [vp, vp, dp, dp, C.POINTER(CsimObsImpactSummary)]),
         "csim_obs_impact_fold": (i, [dp, C.c_long, dp]),
+        "csim_ensemble_obs_impact_global": (i, [vp, vp, dp, dp, C.POINTER(CsimObsImpactSummary)]),
+        "csim_obs_impact_global_value": (i, [i, dp, dp, d, dp]),
         "csim_ensemble_assimilate_local": (i, [vp, vp, d, i, i, d]),
         "csim_obs_network_local_info": (i, [vp, ip]),
         "csim_obs_local_count": (i, [i, i, i, ip, ip, i, i, ip, ip]),
@@ -265,6 +267,7 @@ def lib() -> C.CDLL:
         "csim_ensemble_gram_plan": (i, [i, i, i, C.POINTER(C.c_long), ip]),
         "csim_ensemble_project": (i, [vp, i, i, i, dp, dp]),
         "csim_ensemble_transform": (i, [vp, i, i, dp, dp]),
+        "csim_ensemble_dot": (i, [vp, i, i, i, dp, dp]),
         "csim_sym_eigen": (i, [i, dp, dp, dp, ip]),
         "csim_ensemble_eofs": (i, [vp, i, i, dp, dp, dp, ip]),
         "csim_ensemble_space_check": (i, [i] * 6),
@@ -953,6 +956,18 @@ def obs_impact_fold(u) -> float:
     return out.value
 
 
+def obs_impact_global_value(a, g, dn) -> float:
+    """J_o of Ensemble.obs_impact_global() for one observation from its captured perturbations a, the M values g and
+    dn: c = sum a_k g_k from +0 in member order, J = dn (c / (M-1)) (csim_obs_impact_global_value) — host only, no
+    device needed"""
+    aa, gg = np.ascontiguousarray(a, dtype=np.float64).ravel(), np.ascontiguousarray(g, dtype=np.float64).ravel()
+    if aa.shape != gg.shape:
+        raise ValueError("a and g must have the same length")
+    out = C.c_double()
+    _ck(lib().csim_obs_impact_global_value(len(aa), _dp(aa), _dp(gg), float(dn), C.byref(out)))
+    return out.value
+
+
 def impact_weight(mean_a, mean_b, truth) -> np.ndarray:
     """the weight C (e_a + e_b) of Ensemble.obs_impact() for the mean squared error of the interior: from the mean
     forecasts from the analysis and from the background and the truth at verification time, (ny+2, nx+2) each,
@@ -983,6 +998,7 @@ def obs_local_count(nx, ny, i, j, lx, ly):
 
 
 ESPACE_MAX_MEMBERS, SYM_EIGEN_MAX_N, SYM_EIGEN_MAX_SWEEPS = 256, 256, 64  # CSIM_ESPACE_MAX_MEMBERS, CSIM_SYM_EIGEN_*
+DOT_MAX_FIELDS = 16  # CSIM_DOT_MAX_FIELDS
 
 SymEigen = collections.namedtuple("SymEigen", "lambda_ V sweeps")
 SymEigen.__doc__ = """eigenvalues (descending), eigenvectors (column r belongs to lambda_[r]) and the sweeps made"""
@@ -1625,6 +1641,17 @@ class Ensemble:
         _ck(lib().csim_ensemble_obs_impact(self._h, net._h, _dp(w), _dp(out), C.byref(sm)))
         return ObsImpact(out, ObsImpactSummary(sm.used, sm.beneficial, sm.total))
 
+    def obs_impact_global(self, net: ObsNetwork, weight) -> ObsImpact:
+        """obs_impact() without localisation, for a capture made after a global analysis (assimilate_etkf, either
+        path), whose gain satisfies the estimate's premise exactly: one read of the members whatever the network,
+        g = dot(weight), then J_o = dn_o sum_k a_{o,k} g_k / (M-1).  Synchronous (csim_ensemble_obs_impact_global)"""
+        w = np.ascontiguousarray(weight, dtype=np.float64)
+        if w.shape != (self.ny + 2, self.nx + 2):
+            raise ValueError(f"weight must have shape {(self.ny + 2, self.nx + 2)}")
+        out, sm = np.empty(net.nobs), CsimObsImpactSummary()
+        _ck(lib().csim_ensemble_obs_impact_global(self._h, net._h, _dp(w), _dp(out), C.byref(sm)))
+        return ObsImpact(out, ObsImpactSummary(sm.used, sm.beneficial, sm.total))
+
     def perturb(self, sigma, corr_len, seed, draw=0, centered=False, truth_member=None):
         """adds sigma times a seeded Gaussian random field of correlation length corr_len to the interior of every
         forecast member; a pure function of (seed, draw, member, cell), enqueued without waiting
@@ -1676,6 +1703,20 @@ class Ensemble:
             raise ValueError(f"W must have {M} rows")
         out = np.empty((w.shape[1], self.ny + 2, self.nx + 2))
         _ck(lib().csim_ensemble_project(self._h, tm, int(bool(centered)), w.shape[1], _dp(w), _dp(out)))
+        return out
+
+    def dot(self, fields, truth_member=None, centered=True) -> np.ndarray:
+        """(M, K): out[k, r] = sum over the interior of p_k fields[r], the adjoint of project(); fields is
+        (K, ny+2, nx+2) or one (ny+2, nx+2) field (K = 1), of which only the interior is read; summed in the order of
+        gram() (csim_ensemble_dot)"""
+        tm, M = self._forecast(truth_member)
+        f = np.ascontiguousarray(fields, dtype=np.float64)
+        if f.ndim == 2:
+            f = np.ascontiguousarray(f[None])
+        if f.ndim != 3 or f.shape[1:] != (self.ny + 2, self.nx + 2):
+            raise ValueError(f"fields must have shape (K, {self.ny + 2}, {self.nx + 2})")
+        out = np.empty((max(M, 0), f.shape[0]))
+        _ck(lib().csim_ensemble_dot(self._h, tm, int(bool(centered)), f.shape[0], _dp(f), _dp(out)))
         return out
 
     def transform(self, W, wbar=None, truth_member=None, centered=True):

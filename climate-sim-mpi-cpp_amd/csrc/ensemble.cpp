@@ -13,8 +13,8 @@
 //   ensemble_obs.cpp   observation networks: create / destroy, values from the host or from a member, the analysis that
 //                      reads a network, its diagnostics and log; the local analysis, the ETKF and the LETKF on a network
 //                      (the LETKF's lattice and node storage: letkf_nodes.hpp, its lookup: assim_plan.cpp, without HIP)
-//   ensemble_space.cpp ensemble space: Gram matrix, projection, transform and EOFs; the eigensolver: sym_eigen.cpp,
-//                      without HIP
+//   ensemble_space.cpp ensemble space: Gram matrix, projection, transform, dot and EOFs; the eigensolver:
+//                      sym_eigen.cpp, without HIP
 #include <cmath>
 #include <string>
 #include <vector>

@@ -327,6 +327,26 @@ hipError_t ens_launch_transform(const EnsGeom& g, double* f, int forecast, int t
                                 const double* W, const double* wbar, int form, hipStream_t st,
                                 const int* gate = nullptr);
 
+// the adjoint of the projection (ensemble_dot.hip; csim_ensemble_dot): out[k K + r] = sum over the interior of p_k f_r,
+// M x K on the device, in the order of the Gram sum.  fields (device): K fields of nx ny values, interior cell
+// e = (j - 1) nx + (i - 1) of field r at r nx ny + e; partial: ens_dot_partial_doubles doubles.  One geometry
+constexpr int DOT_MAX_FIELDS = 16;  // CSIM_DOT_MAX_FIELDS
+size_t ens_dot_partial_doubles(const EnsGeom& g, int forecast, int K);
+hipError_t ens_launch_dot(const EnsGeom& g, const double* f, int forecast, int truth_member, bool centered, int K,
+                          const double* fields, double* partial, double* out, hipStream_t st);
+// the forecast impact without localisation (ensemble_dot.hip; csim_ensemble_obs_impact_global): J_o of every
+// observation, by input index, from a capture (ImpactCapture, plan order) and g (M values, device)
+struct ImpactGlobalArgs {
+    int nobs;
+    int forecast;                 // M of the capture, 2 .. ESPACE_MAX_MEMBERS
+    const int* idx;
+    const unsigned char* snap;
+    const double* pert;
+    const double* dn;
+    const double* g;
+};
+hipError_t ens_launch_obs_impact_global(const ImpactGlobalArgs& a, double* out, hipStream_t st);
+
 // the observation-space Gram matrix of csim_ensemble_obs_gram (ensemble_obsgram.hip): A = Z^T Z, (M + 1) x (M + 1), of
 // the normalised observation-space perturbations of a network, and the members' sums of squared normalised departures.
 // Device arrays in plan order.  An observation is used iff flag is null or flag[q] == used: the mask (1: active) of

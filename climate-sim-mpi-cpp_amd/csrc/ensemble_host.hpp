@@ -4,6 +4,8 @@
 // side is the table at the top of ensemble.cpp.
 #pragma once
 #include <algorithm>
+#include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "assim_plan.hpp"
@@ -121,8 +123,12 @@ struct csim_ensemble {
         bool etkf_pending = false;            // the last ETKF was enqueued by the device path: its record is on the device
         int etkf_m = 0;                       // its forecast members
         int etkf_sweeps = 0, etkf_status = 0; // of the record fetched last (0 after a host-path ETKF)
+        // csim_ensemble_dot (and the g of csim_ensemble_obs_impact_global): the fields' interiors, the class partials
+        // and the M x K result; a host call stages its fields through `stage`
+        csim::DeviceBuf dot_fields, dot_partial, dot_out;
         void release() {
             partial.release(), gram.release(), out.release(), w.release(), eig.release(), stage.release();
+            dot_fields.release(), dot_partial.release(), dot_out.release();
         }
     } espace;
     // the LETKF (csim_ensemble_assimilate_letkf, ensemble_obs.cpp): the node storage of the last call (LetkfLayout) and
@@ -188,4 +194,23 @@ inline void split_pairs(const double* pairs, int n, double* mean, double* var) {
 }
 // the inflation (when != 1), then assim_prior and assim_update of every batch in turn, on the ensemble's stream
 int assim_enqueue(csim_ensemble* e, const AssimArgs& a, double inflation, const std::vector<AssimBatch>& batches);
+// csim_ensemble_dot in two steps (ensemble_space.cpp), shared with csim_ensemble_obs_impact_global: the interiors of K
+// host fields of the layout (ny+2) x (nx+2) to espace.dot_fields, copied before the call returns; then the two
+// launches for M forecast members without member t, which leave the M x K result in espace.dot_out
+int dot_stage_fields(csim_ensemble* e, int K, const double* fields);
+// every interior value of a host field of the layout (ny+2) x (nx+2) is finite: no exponent field is all ones.  A row
+// at a time without a branch per value, so that the check of a large field costs a pass over it and no more
+inline bool interior_finite(const double* field, int nx, int ny) {
+    std::uint64_t bad = 0;
+    for (int j = 1; j <= ny; ++j) {
+        const double* row = field + static_cast<size_t>(j) * (static_cast<size_t>(nx) + 2) + 1;
+        for (int i = 0; i < nx; ++i) {
+            std::uint64_t b;
+            std::memcpy(&b, row + i, sizeof b);
+            bad |= static_cast<std::uint64_t>(((b >> 52) & 0x7ff) == 0x7ff);
+        }
+    }
+    return bad == 0;
+}
+int dot_enqueue(csim_ensemble* e, int M, int t, bool centered, int K);
 }  // namespace csim

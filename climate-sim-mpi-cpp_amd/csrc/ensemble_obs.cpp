@@ -7,6 +7,8 @@
 // The forecast impact (csim_obs_network_impact_capture, csim_ensemble_obs_impact; kernels in ensemble_impact.hip) keeps
 // a capture in storage of the network's own, made at the first capture: a_k per observation, dn and the status bytes,
 // and a device copy of the caller's weight; nothing that an analysis, observe or set_values writes.
+// csim_ensemble_obs_impact_global reads the same capture without the localisation: the weight goes through the
+// ensemble-space dot (dot_stage_fields, dot_enqueue of ensemble_space.cpp), then one kernel of ensemble_dot.hip.
 // Four more analyses share the checks, the screening and the recording of the serial one (analysis_check,
 // analysis_begin, analysis_record) and differ in what runs between them:
 //   local  (ensemble_local.hip)  the observation priors and a lookup per tile, storage of the network's own
@@ -882,6 +884,68 @@ int csim_ensemble_obs_impact(csim_ensemble* e, csim_obs_network* n, const double
     } catch (const std::bad_alloc&) {
         return fail(CSIM_ERR_STATE, "csim_ensemble_obs_impact: out of host memory");
     }
+}
+
+int csim_ensemble_obs_impact_global(csim_ensemble* e, csim_obs_network* n, const double* weight, double* out_impact,
+                                    csim_obs_impact_summary* summary) {
+    CSIM_REQUIRE(e, "null ensemble");
+    CSIM_REQUIRE(n, "null network");
+    CSIM_REQUIRE(n->e == e, "the network belongs to another ensemble");
+    CSIM_REQUIRE(weight, "null weight");
+    const EnsGeom& g = e->g;
+    csim_obs_network::Impact& x = n->imp;
+    if (!x.valid)
+        return fail(CSIM_ERR_STATE, "csim_ensemble_obs_impact_global: the network has no capture "
+                                    "(csim_obs_network_impact_capture)");
+    CSIM_REQUIRE(interior_finite(weight, g.nx, g.ny), "every interior value of the weight must be finite");
+    if (x.M > ESPACE_MAX_MEMBERS)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_obs_impact_global: at most CSIM_ESPACE_MAX_MEMBERS forecast "
+                                          "members");
+    try {
+        std::vector<double> J(n->nobs);
+        std::vector<unsigned char> snap(n->nobs);
+        // g = dot(centered, the weight) stays on the device between the fold and the impact kernel
+        CSIM_TRY(dot_stage_fields(e, 1, weight));
+        CSIM_TRY(dot_enqueue(e, x.M, x.t, true, 1));
+        ImpactGlobalArgs a{};
+        a.nobs = n->nobs, a.forecast = x.M, a.idx = n->args().idx;
+        a.snap = buf_at<unsigned char>(x.aux.p, n->imp_snap());
+        a.pert = x.pert.as(), a.dn = buf_at<double>(x.aux.p, n->imp_dn()), a.g = e->espace.dot_out.as();
+        double* out = buf_at<double>(x.aux.p, n->imp_out());
+        CSIM_HIP(ens_launch_obs_impact_global(a, out, e->st));
+        CSIM_HIP(hipMemcpyAsync(J.data(), out, sizeof(double) * J.size(), hipMemcpyDeviceToHost, e->st));
+        CSIM_HIP(hipMemcpyAsync(snap.data(), a.snap, snap.size(), hipMemcpyDeviceToHost, e->st));
+        CSIM_HIP(hipStreamSynchronize(e->st));
+        if (out_impact) std::copy(J.begin(), J.end(), out_impact);
+        if (summary) {
+            summary->used = summary->beneficial = 0;
+            for (unsigned char s : snap) summary->used += s == CSIM_OBS_USED;
+            // the chunks of csim_obs_cycle, as csim_ensemble_obs_impact
+            double total = 0.0;
+            for (int c0 = 0; c0 < n->nobs; c0 += OBS_CHUNK) {
+                double T = 0.0;
+                for (int o = c0; o < std::min(n->nobs, c0 + OBS_CHUNK); ++o) {
+                    T = T + J[o];
+                    summary->beneficial += J[o] < 0.0;
+                }
+                total = total + T;
+            }
+            summary->total = total;
+        }
+        return CSIM_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(CSIM_ERR_STATE, "csim_ensemble_obs_impact_global: out of host memory");
+    }
+}
+
+int csim_obs_impact_global_value(int M, const double* a, const double* g, double dn, double* J) {
+    CSIM_REQUIRE(a && g && J, "null argument");
+    CSIM_REQUIRE(M >= 2, "M must be >= 2");
+    double c = 0.0;
+    for (int k = 0; k < M; ++k) c = c + a[k] * g[k];
+    const double S = c / static_cast<double>(M - 1);
+    *J = dn * S;
+    return CSIM_OK;
 }
 
 int csim_obs_impact_fold(const double* u, long n, double* S) {

@@ -1,6 +1,7 @@
 // ensemble_space.cpp — the ensemble-space calls: csim_ensemble_gram, _project, _transform and their composite
-// csim_ensemble_eofs (kernels in ensemble_space.hip, the eigensolver in sym_eigen.cpp).  Every argument check is
-// csim_ensemble_space_check, which needs no device.
+// csim_ensemble_eofs (kernels in ensemble_space.hip, the eigensolver in sym_eigen.cpp), and csim_ensemble_dot (kernels
+// in ensemble_dot.hip; its two steps are shared with csim_ensemble_obs_impact_global of ensemble_obs.cpp).  Every
+// argument check on the members is csim_ensemble_space_check, which needs no device.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -60,6 +61,36 @@ int project(csim_ensemble* e, int M, int t, bool centered, int K, const double* 
 }
 
 }  // namespace
+
+namespace csim {
+
+int dot_stage_fields(csim_ensemble* e, int K, const double* fields) {
+    csim_ensemble::Espace& x = e->espace;
+    const EnsGeom& g = e->g;
+    const size_t nx = static_cast<size_t>(g.nx), nx2 = nx + 2, inner = nx * g.ny, dense = stats_cells(e);
+    const size_t bytes = sizeof(double) * inner * K;
+    void* h = nullptr;
+    CSIM_TRY(x.dot_fields.reserve(bytes, e->st));
+    CSIM_TRY(x.stage.acquire(bytes, &h));
+    auto* packed = static_cast<double*>(h);
+    for (int r = 0; r < K; ++r)
+        for (int j = 1; j <= g.ny; ++j) {
+            const double* src = fields + r * dense + j * nx2 + 1;
+            std::copy(src, src + nx, packed + r * inner + (j - 1) * nx);
+        }
+    return x.stage.send(x.dot_fields.p, bytes, e->st);
+}
+
+int dot_enqueue(csim_ensemble* e, int M, int t, bool centered, int K) {
+    csim_ensemble::Espace& x = e->espace;
+    CSIM_TRY(x.dot_partial.reserve(sizeof(double) * ens_dot_partial_doubles(e->g, M, K), e->st));
+    CSIM_TRY(x.dot_out.reserve(sizeof(double) * static_cast<size_t>(M) * K, e->st));
+    CSIM_HIP(ens_launch_dot(e->g, e->base(e->cur), M, t, centered, K, x.dot_fields.as(), x.dot_partial.as(),
+                            x.dot_out.as(), e->st));
+    return CSIM_OK;
+}
+
+}  // namespace csim
 
 extern "C" {
 
@@ -176,6 +207,23 @@ int csim_ensemble_project(csim_ensemble* e, int truth_member, int centered, int 
     int M = 0, t = 0;
     CSIM_TRY(space_check(e, truth_member, centered, K, 0, 0, &M, &t));
     return project(e, M, t, centered == 1, K, W, out);
+}
+
+int csim_ensemble_dot(csim_ensemble* e, int truth_member, int centered, int K, const double* fields, double* out) {
+    CSIM_REQUIRE(e, "null ensemble");
+    int M = 0, t = 0;
+    CSIM_TRY(space_check(e, truth_member, centered, 0, 0, 0, &M, &t));
+    CSIM_REQUIRE(K >= 1 && K <= DOT_MAX_FIELDS, "K must be 1 .. CSIM_DOT_MAX_FIELDS");
+    CSIM_REQUIRE(fields && out, "null argument");
+    for (int r = 0; r < K; ++r)
+        CSIM_REQUIRE(interior_finite(fields + r * stats_cells(e), e->g.nx, e->g.ny),
+                     "every interior value of a field must be finite");
+    CSIM_TRY(dot_stage_fields(e, K, fields));
+    CSIM_TRY(dot_enqueue(e, M, t, centered == 1, K));
+    CSIM_HIP(hipMemcpyAsync(out, e->espace.dot_out.p, sizeof(double) * static_cast<size_t>(M) * K,
+                            hipMemcpyDeviceToHost, e->st));
+    CSIM_HIP(hipStreamSynchronize(e->st));
+    return CSIM_OK;
 }
 
 int csim_ensemble_transform(csim_ensemble* e, int truth_member, int centered, const double* W, const double* wbar) {

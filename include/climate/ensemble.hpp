@@ -636,6 +636,14 @@ public:
         check(csim_ensemble_obs_impact(h_, net.handle(), sized(weight, 1), r.impact.data(), &r.summary));
         return r;
     }
+    // the same without localisation, for a capture made after a global analysis (assimilate_etkf, either path): one read
+    // of the members whatever the network (see csim_ensemble_obs_impact_global).  Synchronous
+    ObsImpact obs_impact_global(ObsNetwork& net, const std::vector<double>& weight) {
+        ObsImpact r;
+        r.impact.resize(net.size());
+        check(csim_ensemble_obs_impact_global(h_, net.handle(), sized(weight, 1), r.impact.data(), &r.summary));
+        return r;
+    }
     // adds sigma times a seeded Gaussian random field of correlation length corr_len to the interior of every forecast
     // member (t = -1: all members, else member t is left alone); enqueued on the ensemble's stream, so that run() follows
     // without a host wait (see csim_ensemble_perturb)
@@ -669,6 +677,15 @@ public:
             throw std::invalid_argument("ensemble: W must be M x K");
         std::vector<double> out(member_size() * static_cast<std::size_t>(K));
         check(csim_ensemble_project(h_, t, centered ? 1 : 0, K, W.data(), out.data()));
+        return out;
+    }
+    // the adjoint of project: out[k K + r] = sum over the interior of p_k f_r, M x K row-major; fields holds K dense
+    // fields, member_size() values each, of which the interior is read (see csim_ensemble_dot).  Synchronous
+    std::vector<double> dot(const std::vector<double>& fields, int K, int t = -1, bool centered = true) {
+        if (K < 0 || fields.size() != member_size() * static_cast<std::size_t>(K))
+            throw std::invalid_argument("ensemble: fields must be K dense fields");
+        std::vector<double> out(forecast(t) * static_cast<std::size_t>(K));
+        check(csim_ensemble_dot(h_, t, centered ? 1 : 0, K, fields.data(), out.data()));
         return out;
     }
     // the forecast members replaced on the interior by a linear combination of them, W is M x M row-major and wbar

@@ -862,7 +862,24 @@ int csim_obs_screen_decide(double y, double hb, double vb, double r, double tol,
  * Neither call writes a member, a ghost ring or the other ping-pong buffer, nor the network's values, mask, logs or
  * diagnostics.
  * impact_fold (host-only, needs no device): *S = fold(u_0 .. u_{n-1}); n == 0 gives +0.  CSIM_ERR_ARG for n < 0, a null
- *   S, a null u with n > 0. */
+ *   S, a null u with n > 0.
+ * obs_impact_global: the same estimate without localisation (rho = 1 over the whole domain; Kalnay et al. 2012 as
+ *   written), for a global filter.  The capture, the weight, out_impact, summary with its chunk rule, the synchrony and
+ *   the "writes nothing" clause are those of obs_impact.  Without rho the sum over the cells factors, and the members
+ *   are read once, whatever the network:  M and truth_member are the capture's;
+ *       g_k = csim_ensemble_dot(centered = 1, K = 1, weight)[k]        (k = 0 .. M-1)
+ *   and per USED observation o, with the captured a_{o,k} and dn_o:
+ *       c = +0;  c = c + a_{o,k} * g_k  (k = 0 .. M-1);   S_o = c / (M-1);   J_o = dn_o * S_o
+ *   An observation that is not USED gets J_o = +0; nothing of its capture is read.
+ *   Errors: those of obs_impact, in its order; then CSIM_ERR_UNSUPPORTED when the capture has more than
+ *   CSIM_ESPACE_MAX_MEMBERS forecast members.
+ *   What is claimed.  The call does not know which filter made the capture.  The estimate's premise is the gain
+ *   K = Xa Ya' R^-1 / (M-1).  After csim_ensemble_assimilate_etkf and _etkf_device that holds exactly, whatever the
+ *   inflation, and where the forecast is linear in the state (all members with one (D, dt, vx, vy), static sides) the
+ *   total equals the actual change of the squared error of the mean forecast up to rounding.  After
+ *   csim_ensemble_assimilate_letkf, _local and the serial filter the gain is localised: use obs_impact.
+ * obs_impact_global_value (host-only, needs no device): the three operations above for one observation, M >= 2 values
+ *   a and g; CSIM_ERR_ARG for M < 2 and a null pointer. */
 #define CSIM_IMPACT_MAX_DOUBLES (1L << 27)
 typedef struct csim_obs_impact_summary {
     long long used, beneficial;
@@ -872,6 +889,9 @@ int csim_obs_network_impact_capture(csim_obs_network* n, int truth_member);
 int csim_ensemble_obs_impact(csim_ensemble* e, csim_obs_network* n, const double* weight, double* out_impact,
                              csim_obs_impact_summary* summary);
 int csim_obs_impact_fold(const double* u, long n, double* S);
+int csim_ensemble_obs_impact_global(csim_ensemble* e, csim_obs_network* n, const double* weight, double* out_impact,
+                                    csim_obs_impact_summary* summary);
+int csim_obs_impact_global_value(int M, const double* a, const double* g, double dn, double* J);
 /* local analysis: every interior cell is analysed on its own from all observations of a network near it, with the
  * localisation applied to the observation error (R-localisation; Hunt et al. 2007, the LETKF).  Cells are independent,
  * so a call is one pass over the observations and one over the cells whatever the network: the levels of the plan play
@@ -949,6 +969,18 @@ int csim_obs_local_count(int nx, int ny, int nobs, const int* i, const int* j, i
  *   is an exact copy or resampling of members (up to the sign of a zero).  The call only enqueues on the ensemble's
  *   stream: W and wbar are copied to staging before it returns, so run -> gram -> transform -> run needs no
  *   synchronisation beyond the one gram makes.
+ * dot: the adjoint of project, the inner product of every member's perturbation with K fields, 1 <= K <=
+ *   CSIM_DOT_MAX_FIELDS.  fields: K host fields in the reference layout (ny+2) x (nx+2), one after the other; only the
+ *   interior is read (ghost values may be NaN), and it is copied before any kernel runs.  out is M x K row-major:
+ *   out[k K + r] = sum over the interior cells of p_k f_r.  Synchronous, writes no member.  The order is gram's, word
+ *   for word: the same cells e, segments, Gc = min(nseg, cap) with the cap taken from M alone, class g owning segments
+ *   g, g + Gc, ...; for each (k, r) the class partial is one running sum over the class's cells in increasing e, carried
+ *   across its segments: acc = acc + (p_k * f_r); out[k K + r] = partial_0 + partial_1 + ... + partial_{Gc-1}.
+ *   csim_ensemble_gram_plan is its plan; nothing depends on the launch geometry.  So with centered = 0 and f_r the
+ *   field of forecast member b, out[k K + r] is gram(centered = 0)[k][b] bit for bit.
+ *   Errors, in this order, before anything is enqueued: CSIM_ERR_ARG for a null ensemble; those of this block for
+ *   truth_member, M and centered; CSIM_ERR_ARG for K outside 1 .. CSIM_DOT_MAX_FIELDS, a null fields or out, and a
+ *   non-finite interior value of a field.
  * sym_eigen (host-only): the eigenvalues and vectors of the symmetric n x n matrix A (row-major; the upper triangle is
  *   read), 1 <= n <= CSIM_SYM_EIGEN_MAX_N, by the cyclic Jacobi method.  a = A (kept symmetric entry by entry),
  *   v = I.  A sweep takes the pairs p < q in row-cyclic order (p = 0 .. n-2, q = p+1 .. n-1); with g = |a_pq|:
@@ -1004,6 +1036,7 @@ int csim_obs_local_count(int nx, int ny, int nobs, const int* i, const int* j, i
  * space_check (host-only): the argument checks of the four calls for an ensemble of `members` members, in the order
  *   truth_member, M, centered, K (0: not a projection), wbar, n_modes (0: not eofs). */
 #define CSIM_ESPACE_MAX_MEMBERS 256
+#define CSIM_DOT_MAX_FIELDS 16
 #define CSIM_SYM_EIGEN_MAX_N 256
 #define CSIM_SYM_EIGEN_MAX_SWEEPS 64
 #define CSIM_SYM_EIGEN_MAX_BATCH 65535
@@ -1016,6 +1049,7 @@ int csim_ensemble_gram(csim_ensemble* e, int truth_member, int centered, double*
 int csim_ensemble_gram_plan(int M, int nx, int ny, long* nseg, int* classes);
 int csim_ensemble_project(csim_ensemble* e, int truth_member, int centered, int K, const double* W, double* out);
 int csim_ensemble_transform(csim_ensemble* e, int truth_member, int centered, const double* W, const double* wbar);
+int csim_ensemble_dot(csim_ensemble* e, int truth_member, int centered, int K, const double* fields, double* out);
 int csim_sym_eigen(int n, const double* A, double* lambda, double* V, int* sweeps);
 int csim_sym_eigen_ordered(int n, const double* A, int order, double* lambda, double* V, int* sweeps);
 int csim_sym_eigen_batch_gpu(int n, int batch, const double* A, double* lambda, double* V, int* sweeps, int* status,
@@ -1088,8 +1122,10 @@ int csim_ensemble_space_check(int members, int truth_member, int centered, int K
  *   etkf_info after it waits for the stream and fetches the record.  etkf_info2 is etkf_info with two more outputs
  *   (either may be NULL): *sweeps, the solver's sweeps, and *status, CSIM_EIGEN_OK or CSIM_EIGEN_NOT_CONVERGED (the
  *   analysis was made with the current diagonal, as the host makes it); after assimilate_etkf both are 0.
- * Not built: _begin / _wait forms, more than CSIM_ESPACE_MAX_MEMBERS members, a resampling particle filter on top of
- * loglik, and the forecast impact (impact_capture / obs_impact) after an ETKF. */
+ * The forecast impact after an ETKF: impact_capture after a recorded one, then csim_ensemble_obs_impact_global, the
+ *   estimate whose premise this filter satisfies exactly (see there), on the host path and the device path alike.
+ * Not built: _begin / _wait forms, more than CSIM_ESPACE_MAX_MEMBERS members, and a resampling particle filter on top
+ * of loglik. */
 int csim_ensemble_obs_gram(csim_ensemble* e, csim_obs_network* n, int truth_member, double* A, double* loglik,
                            long long* n_used);
 int csim_obs_gram_plan(int M, int nobs, long* nseg, int* classes);
@@ -1143,7 +1179,12 @@ int csim_ensemble_etkf_info2(csim_ensemble* e, long long* n_used, double* chi2, 
  *      All M values of a cell are read before any is written.  Ghost ring, member t and the other ping-pong buffer are
  *      never touched.
  *   6. record = 1: as step 5 of csim_ensemble_assimilate_local; fetch, log, screen_log, status and impact_capture
- *      behave as after a recorded local analysis.  Nothing is claimed for the forecast impact after an LETKF.
+ *      behave as after a recorded local analysis.  The forecast impact after an LETKF is the localised
+ *      csim_ensemble_obs_impact, not the global one.  In the OSSE of DESIGN 7z (21 members of 33 x 17, 40 stations,
+ *      six steps, eight seeds, on the CPU restatements) its total has the sign of the actual change of the forecast
+ *      error for every seed; total / actual is 0.86 .. 0.90 at spacing 1 and 2.19 .. 3.25 at spacing 4, where the
+ *      interpolated weights are not the gain the estimate assumes: with a coarse lattice take the sign and the ranking
+ *      of the observations from it, not the size.
  *      csim_ensemble_etkf_info is not affected by this call.
  *   With s = 1 every cell is a node with beta = (1, 0, 0, 0) and the analysis mean and variance are those of
  *   csim_ensemble_assimilate_local in exact arithmetic.
@@ -1164,8 +1205,7 @@ int csim_ensemble_etkf_info2(csim_ensemble* e, long long* n_used, double* chi2, 
  *   16 against 0.94 ms for 1024 random observations on 256^2, 20.0 ms and 8.3 ms against 0.31 ms on 512^2.  64 members
  *   need spacing >= 8 on 512^2 and >= 4 on 256^2, 256 members spacing >= 16 on 256^2 (CSIM_LETKF_MAX_BYTES).  The
  *   analysis mean differs from that of spacing 1 by 6.5 %, 23 % and 62 % of the RMS increment at spacing 4, 8 and 16.
- * Not built: more than CSIM_LETKF_MAX_NODES nodes in one call (the lattice taken in parts), and the forecast impact
- * after an LETKF. */
+ * Not built: more than CSIM_LETKF_MAX_NODES nodes in one call (the lattice taken in parts). */
 #define CSIM_LETKF_MAX_NODES 65535
 #define CSIM_LETKF_MAX_BYTES (1LL << 30)
 #define CSIM_LETKF_OK 0
