@@ -1630,27 +1630,25 @@ class Ensemble:
                                            C.byref(ng), C.byref(sweeps), C.byref(status)))
         return EtkfInfo(used.value, chi2.value, gamma[:ng.value].copy(), dfs.value, sweeps.value, status.value)
 
-    def obs_impact(self, net: ObsNetwork, weight) -> ObsImpact:
-        """the forecast impact J_o of every observation of net's captured analysis on the error of the current
-        (verification-time) state, EFSOI: weight is C (e_a + e_b) as a (ny+2, nx+2) field, impact_weight() for the mean
-        squared error; J_o < 0: the observation reduced the forecast error.  Synchronous (csim_ensemble_obs_impact)"""
+    def _obs_impact(self, call, net, weight) -> ObsImpact:
         w = np.ascontiguousarray(weight, dtype=np.float64)
         if w.shape != (self.ny + 2, self.nx + 2):
             raise ValueError(f"weight must have shape {(self.ny + 2, self.nx + 2)}")
         out, sm = np.empty(net.nobs), CsimObsImpactSummary()
-        _ck(lib().csim_ensemble_obs_impact(self._h, net._h, _dp(w), _dp(out), C.byref(sm)))
+        _ck(call(self._h, net._h, _dp(w), _dp(out), C.byref(sm)))
         return ObsImpact(out, ObsImpactSummary(sm.used, sm.beneficial, sm.total))
+
+    def obs_impact(self, net: ObsNetwork, weight) -> ObsImpact:
+        """the forecast impact J_o of every observation of net's captured analysis on the error of the current
+        (verification-time) state, EFSOI: weight is C (e_a + e_b) as a (ny+2, nx+2) field, impact_weight() for the mean
+        squared error; J_o < 0: the observation reduced the forecast error.  Synchronous (csim_ensemble_obs_impact)"""
+        return self._obs_impact(lib().csim_ensemble_obs_impact, net, weight)
 
     def obs_impact_global(self, net: ObsNetwork, weight) -> ObsImpact:
         """obs_impact() without localisation, for a capture made after a global analysis (assimilate_etkf, either
         path), whose gain satisfies the estimate's premise exactly: one read of the members whatever the network,
         g = dot(weight), then J_o = dn_o sum_k a_{o,k} g_k / (M-1).  Synchronous (csim_ensemble_obs_impact_global)"""
-        w = np.ascontiguousarray(weight, dtype=np.float64)
-        if w.shape != (self.ny + 2, self.nx + 2):
-            raise ValueError(f"weight must have shape {(self.ny + 2, self.nx + 2)}")
-        out, sm = np.empty(net.nobs), CsimObsImpactSummary()
-        _ck(lib().csim_ensemble_obs_impact_global(self._h, net._h, _dp(w), _dp(out), C.byref(sm)))
-        return ObsImpact(out, ObsImpactSummary(sm.used, sm.beneficial, sm.total))
+        return self._obs_impact(lib().csim_ensemble_obs_impact_global, net, weight)
 
     def perturb(self, sigma, corr_len, seed, draw=0, centered=False, truth_member=None):
         """adds sigma times a seeded Gaussian random field of correlation length corr_len to the interior of every

@@ -310,7 +310,8 @@ hipError_t ens_launch_obs_screen_log_fill(double* slog, int cycles, int nobs, hi
 
 // ensemble space (ensemble_space.hip; csim_ensemble_gram, _project, _transform): the M x M space spanned by the forecast
 // members' perturbations p_k (x_k less the cell's mean when centered, x_k itself otherwise).
-// The member limit ESPACE_MAX_MEMBERS, the Gram sum's plan (gram_classes, gram_pairs) and GRAM_FORMS: gram_plan.hpp.
+// The limits ESPACE_MAX_MEMBERS and DOT_MAX_FIELDS, the Gram sum's plan (gram_classes, gram_pairs) and GRAM_FORMS:
+// gram_plan.hpp.
 constexpr int PROJECT_FORMS = 1;  // project_form 1: the members of a cell in LDS whatever M
 // G (M x M, device) from the members; partial: gram_classes x gram_pairs doubles.  form: 0 (the launcher's choice)
 // or 1 .. GRAM_FORMS; the result does not depend on it
@@ -330,7 +331,6 @@ hipError_t ens_launch_transform(const EnsGeom& g, double* f, int forecast, int t
 // the adjoint of the projection (ensemble_dot.hip; csim_ensemble_dot): out[k K + r] = sum over the interior of p_k f_r,
 // M x K on the device, in the order of the Gram sum.  fields (device): K fields of nx ny values, interior cell
 // e = (j - 1) nx + (i - 1) of field r at r nx ny + e; partial: ens_dot_partial_doubles doubles.  One geometry
-constexpr int DOT_MAX_FIELDS = 16;  // CSIM_DOT_MAX_FIELDS
 size_t ens_dot_partial_doubles(const EnsGeom& g, int forecast, int K);
 hipError_t ens_launch_dot(const EnsGeom& g, const double* f, int forecast, int truth_member, bool centered, int K,
                           const double* fields, double* partial, double* out, hipStream_t st);

@@ -6,13 +6,14 @@
 //
 // Dot, out[k][r] = sum over the interior of p_k f_r, two kernels with the plan of the Gram sum (gram_plan.hpp: segments
 // of 64 interior cells, gram_classes(M, cells) classes):
-//   k_dot_partial  Workgroup g of 256 lanes serves class g.  It stages a segment's perturbations in LDS as
-//                  [cell][member] exactly as k_gram_partial does (+0 from member M up to the padded width), and beside
-//                  them the K field values of each cell as [cell][field] (+0 from field K up).  The M x K sums are cut
-//                  into blocks of 4 x 4, DotTile: lane l owns block l, member block l / nbk and field block l % nbk, at
-//                  most 64 x 4 = 256 of them, so one workgroup per class holds them all and there is one geometry.  A
-//                  wave whose lanes own no block only helps staging.  The walk adds a segment's cells in order and the
-//                  sums are carried from segment to segment of the class: the order of each sum is that of the cells.
+//   k_dot_partial  Workgroup g of 256 lanes serves class g.  A segment's perturbations are staged in LDS as
+//                  [cell][member] by the routine that k_gram_partial calls (gram_stage_cells of gram_tile.hpp), and
+//                  beside them, its own, the K field values of each cell as [cell][field] (+0 from field K up).  The
+//                  M x K sums are cut into blocks of 4 x 4, DotTile, over the rectangle of gram_plan.hpp (dot_owned:
+//                  one workgroup per class holds all blocks, so there is one geometry); a row's step onto a block is
+//                  gram_block_step, GramTile's.  A wave whose lanes own no block only helps staging.  The walk adds a
+//                  segment's cells in order and the sums are carried from segment to segment of the class: the order of
+//                  each sum is that of the cells.
 //   k_dot_fold     entry (k, r) folded over the classes in class order (gram_fold_entry).
 // With K = 1 and M = 64 only 16 lanes walk, and the walk is short next to the staging: at 37 KiB of LDS four
 // workgroups share a CU and one's staging runs beside another's walk.
@@ -33,9 +34,6 @@ namespace csim {
 
 namespace {
 
-// doubles between the field rows of a segment in LDS: even and past the padded width, as gram_stride
-__host__ __device__ inline int dot_fstride(int K) { return gram_nblk(K) * GRAM_TB + 2; }
-
 struct DotTile {
     int im, ik;    // member block, field block
     bool mine;
@@ -43,10 +41,9 @@ struct DotTile {
     double acc[GRAM_TB * GRAM_TB];
 
     __device__ __forceinline__ void init(int M, int K) {
-        const int lane = threadIdx.x, nbk = gram_nblk(K), nblocks = gram_nblk(M) * nbk;
-        const int b = lane < nblocks ? lane : nblocks - 1;
-        im = b / nbk, ik = b - im * nbk, mine = lane < nblocks;
-        wave_on = (lane & ~63) < nblocks;
+        const DotOwned o = dot_owned(threadIdx.x, M, K);
+        im = o.im, ik = o.ik, mine = o.mine;
+        wave_on = dot_wave_on(threadIdx.x, M, K);
 #pragma unroll
         for (int v = 0; v < GRAM_TB * GRAM_TB; ++v) acc[v] = 0.0;
     }
@@ -56,17 +53,8 @@ struct DotTile {
                                          int fstride, int nc) {
         if (!wave_on) return;
 #pragma unroll 2
-        for (int cc = 0; cc < nc; ++cc) {
-            const double2* __restrict__ pa = reinterpret_cast<const double2*>(held + cc * stride + GRAM_TB * im);
-            const double2* __restrict__ pb = reinterpret_cast<const double2*>(fl + cc * fstride + GRAM_TB * ik);
-            const double2 a0 = pa[0], a1 = pa[1], b0 = pb[0], b1 = pb[1];
-            const double a[GRAM_TB] = {a0.x, a0.y, a1.x, a1.y};
-            const double b[GRAM_TB] = {b0.x, b0.y, b1.x, b1.y};
-#pragma unroll
-            for (int i = 0; i < GRAM_TB; ++i)
-#pragma unroll
-                for (int j = 0; j < GRAM_TB; ++j) acc[i * GRAM_TB + j] = acc[i * GRAM_TB + j] + a[i] * b[j];
-        }
+        for (int cc = 0; cc < nc; ++cc)
+            gram_block_step(held + cc * stride + GRAM_TB * im, fl + cc * fstride + GRAM_TB * ik, acc);
     }
 
     // the class's partial, M x K row-major
@@ -88,47 +76,22 @@ __global__ __launch_bounds__(GRAM_THREADS) void k_dot_partial(const double* __re
                                                               int centered, int K, const double* __restrict__ fields,
                                                               double* __restrict__ partial) {
     extern __shared__ __attribute__((aligned(16))) double held[];  // [64][stride], the 64 means, [64][fstride]
-    const int stride = gram_stride(M), fstride = dot_fstride(K);
-    double* __restrict__ mean = held + GRAM_SEG * stride;
-    double* __restrict__ fl = mean + GRAM_SEG;
-    const int tid = threadIdx.x;
-    const int mpad = gram_nblk(M) * GRAM_TB, kpad = gram_nblk(K) * GRAM_TB;
+    const int fstride = dot_fstride(K), kpad = gram_nblk(K) * GRAM_TB;
+    double* __restrict__ fl = held + gram_lds_doubles(M);
     DotTile tile;
     tile.init(M, K);
 
-    const int c = tid & 63, kq = tid >> 6;
-    double* __restrict__ row = held + c * stride;
+    const int c = threadIdx.x & 63, kq = threadIdx.x >> 6;
     double* __restrict__ frow = fl + c * fstride;
     for (long q = blockIdx.x; q < nseg; q += gridDim.x) {
         const long e0 = q * GRAM_SEG;
         const int nc = static_cast<int>(min(static_cast<long>(GRAM_SEG), cells - e0));
         if (c < nc) {
-            const Cell cc = cell_of(e0 + c, nx, pitch);
-            const double* __restrict__ p = f + static_cast<size_t>(cc.off);
-#pragma unroll 8
-            for (int k = kq; k < M; k += 4) row[k] = p[static_cast<size_t>(forecast_member(k, t)) * slab];
-            for (int k = M + kq; k < mpad; k += 4) row[k] = 0.0;
             for (int r = kq; r < K; r += 4) frow[r] = fields[static_cast<size_t>(r) * cells + (e0 + c)];
             for (int r = K + kq; r < kpad; r += 4) frow[r] = 0.0;
         }
-        __syncthreads();
-        if (centered) {
-            if (tid < nc) {
-                const double* __restrict__ x = held + tid * stride;
-                double s = 0.0;
-#pragma unroll 8
-                for (int k = 0; k < M; ++k) s = s + x[k];
-                mean[tid] = s / static_cast<double>(M);
-            }
-            __syncthreads();
-            if (c < nc) {
-                const double m = mean[c];
-#pragma unroll 8
-                for (int k = kq; k < M; k += 4) row[k] = row[k] - m;
-            }
-            __syncthreads();
-        }
-        tile.walk(held, stride, fl, fstride, nc);
+        gram_stage_cells(f, nx, pitch, slab, M, t, centered, e0, nc, held);
+        tile.walk(held, gram_stride(M), fl, fstride, nc);
         __syncthreads();
     }
     tile.store(partial + static_cast<size_t>(blockIdx.x) * M * K, M, K);
@@ -189,12 +152,10 @@ hipError_t ens_launch_dot(const EnsGeom& g, const double* f, int forecast, int t
         return hipErrorInvalidValue;
     const long cells = static_cast<long>(g.nx) * g.ny;
     const int classes = gram_classes(M, cells);
-    auto lds_of = [](int m, int k) {
-        return sizeof(double) * (static_cast<size_t>(GRAM_SEG) * (gram_stride(m) + dot_fstride(k)) + GRAM_SEG);
-    };
-    const hipError_t attr = dynamic_lds_once<k_dot_partial>(lds_of(ESPACE_MAX_MEMBERS, DOT_MAX_FIELDS));
+    const hipError_t attr =
+        dynamic_lds_once<k_dot_partial>(sizeof(double) * dot_lds_doubles(ESPACE_MAX_MEMBERS, DOT_MAX_FIELDS));
     if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(k_dot_partial, dim3(classes), dim3(GRAM_THREADS), lds_of(M, K), st, f, g.nx, cells,
+    hipLaunchKernelGGL(k_dot_partial, dim3(classes), dim3(GRAM_THREADS), sizeof(double) * dot_lds_doubles(M, K), st, f, g.nx, cells,
                        gram_segments(cells), g.pitch, g.slab, M, truth_member, centered ? 1 : 0, K, fields, partial);
     const hipError_t rc = hipGetLastError();
     if (rc != hipSuccess) return rc;

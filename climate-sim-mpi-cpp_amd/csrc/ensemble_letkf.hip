@@ -87,13 +87,7 @@ __global__ __launch_bounds__(GRAM_THREADS) void k_letkf_gram(int nx, int ny, Ass
             for (int k = MA + lane; k < mpad; k += 64) row[k] = 0.0;
         }
         __syncthreads();
-        if (tid < nc) {
-            const double* __restrict__ x = held + tid * stride;
-            double s = 0.0;
-#pragma unroll 8
-            for (int k = 0; k < M; ++k) s = s + x[k];
-            hbs[tid] = s / static_cast<double>(M);
-        }
+        if (tid < nc) hbs[tid] = gram_row_mean(held + tid * stride, M);
         __syncthreads();
         for (int r = wave; r < nc; r += GRAM_THREADS / 64) {
             double* __restrict__ row = held + r * stride;

@@ -8,7 +8,9 @@
 // a capture in storage of the network's own, made at the first capture: a_k per observation, dn and the status bytes,
 // and a device copy of the caller's weight; nothing that an analysis, observe or set_values writes.
 // csim_ensemble_obs_impact_global reads the same capture without the localisation: the weight goes through the
-// ensemble-space dot (dot_stage_fields, dot_enqueue of ensemble_space.cpp), then one kernel of ensemble_dot.hip.
+// ensemble-space dot (dot_stage_fields, dot_enqueue of ensemble_space.cpp), then one kernel of ensemble_dot.hip.  The
+// two calls differ in that, the staging of the weight and the launch; their checks and what they bring back are one
+// text (impact_check, impact_run).
 // Four more analyses share the checks, the screening and the recording of the serial one (analysis_check,
 // analysis_begin, analysis_record) and differ in what runs between them:
 //   local  (ensemble_local.hip)  the observation priors and a lookup per tile, storage of the network's own
@@ -387,6 +389,59 @@ int local_tile(const csim_ensemble* e) {
     if (e->local.tile) return e->local.tile;
     const long cells = static_cast<long>(e->g.nx) * e->g.ny;
     return cells >= 2048L * 2048 ? 16 : cells >= 128L * 128 ? 8 : 4;
+}
+
+// what both impact calls check first, in this order
+int impact_check(const char* call, csim_ensemble* e, csim_obs_network* n, const double* weight) {
+    CSIM_REQUIRE(e, "null ensemble");
+    CSIM_REQUIRE(n, "null network");
+    CSIM_REQUIRE(n->e == e, "the network belongs to another ensemble");
+    CSIM_REQUIRE(weight, "null weight");
+    if (!n->imp.valid)
+        return fail(CSIM_ERR_STATE, std::string(call) + ": the network has no capture (csim_obs_network_impact_capture)");
+    CSIM_REQUIRE(interior_finite(weight, e->g.nx, e->g.ny), "every interior value of the weight must be finite");
+    return CSIM_OK;
+}
+
+// and what both end with.  Args: ImpactArgs or ImpactGlobalArgs, of which the capture's part is filled in here;
+// enqueue(a, out) stages the weight its own way, fills in the rest and launches the kernels that leave J in plan
+// order's `out`.  Then J and the status snapshot come back, and the summary is made of them
+template <class Args, class Enqueue>
+int impact_run(const char* call, csim_ensemble* e, csim_obs_network* n, double* out_impact,
+               csim_obs_impact_summary* summary, Enqueue&& enqueue) {
+    csim_obs_network::Impact& x = n->imp;
+    try {
+        std::vector<double> J(n->nobs);
+        std::vector<unsigned char> snap(n->nobs);
+        Args a{};
+        a.nobs = n->nobs, a.forecast = x.M, a.idx = n->args().idx;
+        a.snap = buf_at<unsigned char>(x.aux.p, n->imp_snap());
+        a.pert = x.pert.as(), a.dn = buf_at<double>(x.aux.p, n->imp_dn());
+        double* out = buf_at<double>(x.aux.p, n->imp_out());
+        CSIM_TRY(enqueue(a, out));
+        CSIM_HIP(hipMemcpyAsync(J.data(), out, sizeof(double) * J.size(), hipMemcpyDeviceToHost, e->st));
+        CSIM_HIP(hipMemcpyAsync(snap.data(), a.snap, snap.size(), hipMemcpyDeviceToHost, e->st));
+        CSIM_HIP(hipStreamSynchronize(e->st));
+        if (out_impact) std::copy(J.begin(), J.end(), out_impact);
+        if (summary) {
+            summary->used = summary->beneficial = 0;
+            for (unsigned char s : snap) summary->used += s == CSIM_OBS_USED;
+            // the chunks of csim_obs_cycle: T_c from +0 in input order, their running sum from +0 in chunk order
+            double total = 0.0;
+            for (int c0 = 0; c0 < n->nobs; c0 += OBS_CHUNK) {
+                double T = 0.0;
+                for (int o = c0; o < std::min(n->nobs, c0 + OBS_CHUNK); ++o) {
+                    T = T + J[o];
+                    summary->beneficial += J[o] < 0.0;
+                }
+                total = total + T;
+            }
+            summary->total = total;
+        }
+        return CSIM_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(CSIM_ERR_STATE, std::string(call) + ": out of host memory");
+    }
 }
 
 }  // namespace
@@ -829,22 +884,11 @@ int csim_obs_network_impact_capture(csim_obs_network* n, int truth_member) {
 
 int csim_ensemble_obs_impact(csim_ensemble* e, csim_obs_network* n, const double* weight, double* out_impact,
                              csim_obs_impact_summary* summary) {
-    CSIM_REQUIRE(e, "null ensemble");
-    CSIM_REQUIRE(n, "null network");
-    CSIM_REQUIRE(n->e == e, "the network belongs to another ensemble");
-    CSIM_REQUIRE(weight, "null weight");
-    const EnsGeom& g = e->g;
-    csim_obs_network::Impact& x = n->imp;
-    if (!x.valid)
-        return fail(CSIM_ERR_STATE, "csim_ensemble_obs_impact: the network has no capture "
-                                    "(csim_obs_network_impact_capture)");
-    const size_t nx2 = static_cast<size_t>(g.nx) + 2, cells = stats_cells(e);
-    for (int j = 1; j <= g.ny; ++j)
-        for (int i = 1; i <= g.nx; ++i)
-            CSIM_REQUIRE(std::isfinite(weight[j * nx2 + i]), "every interior value of the weight must be finite");
-    try {
-        std::vector<double> J(n->nobs);
-        std::vector<unsigned char> snap(n->nobs);
+    CSIM_TRY(impact_check("csim_ensemble_obs_impact", e, n, weight));
+    auto enqueue = [&](ImpactArgs& a, double* out) -> int {
+        const EnsGeom& g = e->g;
+        csim_obs_network::Impact& x = n->imp;
+        const size_t nx2 = static_cast<size_t>(g.nx) + 2, cells = stats_cells(e);
         // the interior of the weight, +0 on the ghost ring, copied before any kernel runs
         void* staged = nullptr;
         CSIM_TRY(x.wstage.acquire(sizeof(double) * cells, &staged));
@@ -854,88 +898,29 @@ int csim_ensemble_obs_impact(csim_ensemble* e, csim_obs_network* n, const double
         CSIM_TRY(x.w.reserve(sizeof(double) * cells, e->st));
         CSIM_TRY(x.wstage.send(x.w.p, sizeof(double) * cells, e->st));
         const ObsArgs oa = n->args();
-        ImpactArgs a{};
-        a.nobs = n->nobs, a.forecast = x.M, a.truth_member = x.t, a.lx = n->lx, a.ly = n->ly;
-        a.rho = n->at<double>(n->l.rho), a.i = oa.i, a.j = oa.j, a.idx = oa.idx;
-        a.snap = buf_at<unsigned char>(x.aux.p, n->imp_snap());
-        a.pert = x.pert.as(), a.dn = buf_at<double>(x.aux.p, n->imp_dn()), a.w = x.w.as();
-        double* out = buf_at<double>(x.aux.p, n->imp_out());
+        a.truth_member = x.t, a.lx = n->lx, a.ly = n->ly;
+        a.rho = n->at<double>(n->l.rho), a.i = oa.i, a.j = oa.j, a.w = x.w.as();
         CSIM_HIP(ens_launch_obs_impact(g, e->base(e->cur), a, out, e->st));
-        CSIM_HIP(hipMemcpyAsync(J.data(), out, sizeof(double) * J.size(), hipMemcpyDeviceToHost, e->st));
-        CSIM_HIP(hipMemcpyAsync(snap.data(), a.snap, snap.size(), hipMemcpyDeviceToHost, e->st));
-        CSIM_HIP(hipStreamSynchronize(e->st));
-        if (out_impact) std::copy(J.begin(), J.end(), out_impact);
-        if (summary) {
-            summary->used = summary->beneficial = 0;
-            for (unsigned char s : snap) summary->used += s == CSIM_OBS_USED;
-            // the chunks of csim_obs_cycle: T_c from +0 in input order, their running sum from +0 in chunk order
-            double total = 0.0;
-            for (int c0 = 0; c0 < n->nobs; c0 += OBS_CHUNK) {
-                double T = 0.0;
-                for (int o = c0; o < std::min(n->nobs, c0 + OBS_CHUNK); ++o) {
-                    T = T + J[o];
-                    summary->beneficial += J[o] < 0.0;
-                }
-                total = total + T;
-            }
-            summary->total = total;
-        }
         return CSIM_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(CSIM_ERR_STATE, "csim_ensemble_obs_impact: out of host memory");
-    }
+    };
+    return impact_run<ImpactArgs>("csim_ensemble_obs_impact", e, n, out_impact, summary, enqueue);
 }
 
 int csim_ensemble_obs_impact_global(csim_ensemble* e, csim_obs_network* n, const double* weight, double* out_impact,
                                     csim_obs_impact_summary* summary) {
-    CSIM_REQUIRE(e, "null ensemble");
-    CSIM_REQUIRE(n, "null network");
-    CSIM_REQUIRE(n->e == e, "the network belongs to another ensemble");
-    CSIM_REQUIRE(weight, "null weight");
-    const EnsGeom& g = e->g;
-    csim_obs_network::Impact& x = n->imp;
-    if (!x.valid)
-        return fail(CSIM_ERR_STATE, "csim_ensemble_obs_impact_global: the network has no capture "
-                                    "(csim_obs_network_impact_capture)");
-    CSIM_REQUIRE(interior_finite(weight, g.nx, g.ny), "every interior value of the weight must be finite");
-    if (x.M > ESPACE_MAX_MEMBERS)
+    CSIM_TRY(impact_check("csim_ensemble_obs_impact_global", e, n, weight));
+    if (n->imp.M > ESPACE_MAX_MEMBERS)
         return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_obs_impact_global: at most CSIM_ESPACE_MAX_MEMBERS forecast "
                                           "members");
-    try {
-        std::vector<double> J(n->nobs);
-        std::vector<unsigned char> snap(n->nobs);
+    auto enqueue = [&](ImpactGlobalArgs& a, double* out) -> int {
         // g = dot(centered, the weight) stays on the device between the fold and the impact kernel
         CSIM_TRY(dot_stage_fields(e, 1, weight));
-        CSIM_TRY(dot_enqueue(e, x.M, x.t, true, 1));
-        ImpactGlobalArgs a{};
-        a.nobs = n->nobs, a.forecast = x.M, a.idx = n->args().idx;
-        a.snap = buf_at<unsigned char>(x.aux.p, n->imp_snap());
-        a.pert = x.pert.as(), a.dn = buf_at<double>(x.aux.p, n->imp_dn()), a.g = e->espace.dot_out.as();
-        double* out = buf_at<double>(x.aux.p, n->imp_out());
+        CSIM_TRY(dot_enqueue(e, n->imp.M, n->imp.t, true, 1));
+        a.g = e->espace.dot_out.as();
         CSIM_HIP(ens_launch_obs_impact_global(a, out, e->st));
-        CSIM_HIP(hipMemcpyAsync(J.data(), out, sizeof(double) * J.size(), hipMemcpyDeviceToHost, e->st));
-        CSIM_HIP(hipMemcpyAsync(snap.data(), a.snap, snap.size(), hipMemcpyDeviceToHost, e->st));
-        CSIM_HIP(hipStreamSynchronize(e->st));
-        if (out_impact) std::copy(J.begin(), J.end(), out_impact);
-        if (summary) {
-            summary->used = summary->beneficial = 0;
-            for (unsigned char s : snap) summary->used += s == CSIM_OBS_USED;
-            // the chunks of csim_obs_cycle, as csim_ensemble_obs_impact
-            double total = 0.0;
-            for (int c0 = 0; c0 < n->nobs; c0 += OBS_CHUNK) {
-                double T = 0.0;
-                for (int o = c0; o < std::min(n->nobs, c0 + OBS_CHUNK); ++o) {
-                    T = T + J[o];
-                    summary->beneficial += J[o] < 0.0;
-                }
-                total = total + T;
-            }
-            summary->total = total;
-        }
         return CSIM_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(CSIM_ERR_STATE, "csim_ensemble_obs_impact_global: out of host memory");
-    }
+    };
+    return impact_run<ImpactGlobalArgs>("csim_ensemble_obs_impact_global", e, n, out_impact, summary, enqueue);
 }
 
 int csim_obs_impact_global_value(int M, const double* a, const double* g, double dn, double* J) {

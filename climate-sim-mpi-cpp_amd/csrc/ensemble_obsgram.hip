@@ -88,13 +88,7 @@ __global__ __launch_bounds__(GRAM_THREADS) void k_obsgram_partial(
                 }
             }
         }
-        if (tid < nc) {
-            const double* __restrict__ x = held + tid * stride;
-            double s = 0.0;
-#pragma unroll 8
-            for (int k = 0; k < M; ++k) s = s + x[k];
-            hbs[tid] = s / static_cast<double>(M);
-        }
+        if (tid < nc) hbs[tid] = gram_row_mean(held + tid * stride, M);
         __syncthreads();
         if (c < nc) {
             const double hb = hbs[c], sr = srs[c];

@@ -5,9 +5,9 @@
 // otherwise.  Every product and every sum is one rounded fp64 operation, no FMA contraction.
 //
 // Gram, two kernels:
-//   k_gram_partial  Workgroup (g, y) of 256 lanes serves class g: the segments g, g + Gc, ... of 64 interior cells.  It
-//                   stages a segment's perturbations in LDS as [cell][member]; the walk over them, the lanes' pairs
-//                   and the class's partial are the GramTile of gram_tile.hpp, the plan is gram_plan.hpp.
+//   k_gram_partial  Workgroup (g, y) of 256 lanes serves class g: the segments g, g + Gc, ... of 64 interior cells.  A
+//                   segment's perturbations staged in LDS as [cell][member] (gram_stage_cells), the walk over them,
+//                   the lanes' pairs and the class's partial (GramTile) are gram_tile.hpp, the plan is gram_plan.hpp.
 //   k_gram_fold     entry (a, b), a <= b, folded over the classes (gram_fold_entry); written to G[a][b] and G[b][a].
 // Project / transform, one kernel template k_espace_apply<P, XFORM>: one cell per lane, its p_k held and applied by
 // espace_cell.hpp, in registers (P > 0, the steps of for_step) or in LDS (P = 0: M > 64, or project_form 1).  All M
@@ -30,43 +30,13 @@ __global__ __launch_bounds__(GRAM_THREADS) void k_gram_partial(const double* __r
                                                                long nseg, int pitch, long slab, int M, int t,
                                                                int centered, double* __restrict__ partial) {
     extern __shared__ __attribute__((aligned(16))) double held[];  // [64][stride], then the 64 means
-    const int stride = gram_stride(M);
-    double* __restrict__ mean = held + GRAM_SEG * stride;
-    const int tid = threadIdx.x;
-    const int mpad = gram_nblk(M) * GRAM_TB;
     GramTile<NB> tile;
     tile.init(M);
-
-    const int c = tid & 63, kq = tid >> 6;
-    double* __restrict__ row = held + c * stride;
     for (long q = blockIdx.x; q < nseg; q += gridDim.x) {
         const long e0 = q * GRAM_SEG;
         const int nc = static_cast<int>(min(static_cast<long>(GRAM_SEG), cells - e0));
-        if (c < nc) {
-            const Cell cc = cell_of(e0 + c, nx, pitch);
-            const double* __restrict__ p = f + static_cast<size_t>(cc.off);
-#pragma unroll 8
-            for (int k = kq; k < M; k += 4) row[k] = p[static_cast<size_t>(forecast_member(k, t)) * slab];
-            for (int k = M + kq; k < mpad; k += 4) row[k] = 0.0;
-        }
-        __syncthreads();
-        if (centered) {
-            if (tid < nc) {
-                const double* __restrict__ x = held + tid * stride;
-                double s = 0.0;
-#pragma unroll 8
-                for (int k = 0; k < M; ++k) s = s + x[k];
-                mean[tid] = s / static_cast<double>(M);
-            }
-            __syncthreads();
-            if (c < nc) {
-                const double m = mean[c];
-#pragma unroll 8
-                for (int k = kq; k < M; k += 4) row[k] = row[k] - m;
-            }
-            __syncthreads();
-        }
-        tile.walk(held, stride, nc);
+        gram_stage_cells(f, nx, pitch, slab, M, t, centered, e0, nc, held);
+        tile.walk(held, gram_stride(M), nc);
         __syncthreads();
     }
     tile.store(partial + static_cast<size_t>(blockIdx.x) * gram_pairs(M), M);
@@ -136,9 +106,8 @@ hipError_t launch_gram(const EnsGeom& g, const double* f, int M, int t, bool cen
                        hipStream_t st) {
     const long cells = static_cast<long>(g.nx) * g.ny;
     const int classes = gram_classes(M, cells);
-    const size_t lds = sizeof(double) * (static_cast<size_t>(GRAM_SEG) * gram_stride(M) + GRAM_SEG);
-    const hipError_t attr = dynamic_lds_once<k_gram_partial<NB>>(
-        sizeof(double) * (static_cast<size_t>(GRAM_SEG) * gram_stride(ESPACE_MAX_MEMBERS) + GRAM_SEG));
+    const size_t lds = sizeof(double) * gram_lds_doubles(M);
+    const hipError_t attr = dynamic_lds_once<k_gram_partial<NB>>(sizeof(double) * gram_lds_doubles(ESPACE_MAX_MEMBERS));
     if (attr != hipSuccess) return attr;
     hipLaunchKernelGGL(k_gram_partial<NB>, dim3(classes, gram_shares(M, NB)), dim3(GRAM_THREADS), lds, st, f, g.nx,
                        cells, gram_segments(cells), g.pitch, g.slab, M, t, centered ? 1 : 0, partial);

@@ -6,6 +6,8 @@
 // and the classes' partials are folded in class order.  The geometry: the upper triangle of G in blocks of GRAM_TB x
 // GRAM_TB pairs, nblk per side, numbered row by row; workgroup `share` of a class gives its lane `lane` the NB blocks
 // (share NB + u) GRAM_THREADS + lane, u < NB, and a lane past the end works on the last block and stores nothing.
+// The ensemble-space dot (csim_ensemble_dot: rows interior cells, M columns against K field columns) takes the plan as
+// it is and has a rectangle for a geometry: its blocks, its field rows in LDS and its LDS size are at the end.
 #pragma once
 
 #include <cstddef>
@@ -19,6 +21,7 @@
 namespace csim {
 
 constexpr int ESPACE_MAX_MEMBERS = 256;  // CSIM_ESPACE_MAX_MEMBERS
+constexpr int DOT_MAX_FIELDS = 16;       // CSIM_DOT_MAX_FIELDS
 constexpr int GRAM_SEG = 64;             // rows per segment
 constexpr int GRAM_FORMS = 3;            // gram_form, obs_gram_form 1 .. 3: 1, 2, 4 blocks of 4 x 4 pairs per lane
 constexpr int GRAM_THREADS = 256;        // lanes of a workgroup
@@ -69,6 +72,30 @@ CSIM_GRAM_HD inline GramOwned gram_owned(int share, int NB, int u, int lane, int
 // false: none of the lanes of this lane's wave owns a block
 CSIM_GRAM_HD inline bool gram_wave_on(int share, int NB, int lane, int cols) {
     return share * NB * GRAM_THREADS + (lane & ~63) < gram_nblocks(cols);
+}
+
+// doubles of LDS for a segment's rows of `cols` columns and their GRAM_SEG means
+CSIM_GRAM_HD inline size_t gram_lds_doubles(int cols) { return static_cast<size_t>(GRAM_SEG) * gram_stride(cols) + GRAM_SEG; }
+
+// The rectangle of the dot, M x K sums in blocks of GRAM_TB x GRAM_TB numbered row by row, nbk = gram_nblk(K) per
+// row: at most 64 x 4 = GRAM_THREADS of them, so one workgroup per class holds them all.  Lane l owns block l, member
+// block l / nbk and field block l % nbk; a lane past the end works on the last block and stores nothing.
+struct DotOwned {
+    int im, ik;
+    bool mine;
+};
+CSIM_GRAM_HD inline DotOwned dot_owned(int lane, int M, int K) {
+    const int nbk = gram_nblk(K), nblocks = gram_nblk(M) * nbk;
+    const int b = lane < nblocks ? lane : nblocks - 1;
+    return {b / nbk, b % nbk, lane < nblocks};
+}
+// false: none of the lanes of this lane's wave owns a block
+CSIM_GRAM_HD inline bool dot_wave_on(int lane, int M, int K) { return (lane & ~63) < gram_nblk(M) * gram_nblk(K); }
+// doubles between the field rows of a segment in LDS: even and past the padded width, as gram_stride
+CSIM_GRAM_HD inline int dot_fstride(int K) { return gram_nblk(K) * GRAM_TB + 2; }
+// doubles of LDS: the rows and the means of the Gram sum, then the field rows
+CSIM_GRAM_HD inline size_t dot_lds_doubles(int M, int K) {
+    return gram_lds_doubles(M) + static_cast<size_t>(GRAM_SEG) * dot_fstride(K);
 }
 
 }  // namespace csim

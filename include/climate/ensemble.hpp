@@ -631,18 +631,12 @@ public:
     // the forecast impact of every observation of net's captured analysis on the error of the current state (EFSOI, see
     // csim_ensemble_obs_impact); weight = C (e_a + e_b), member_size() values of which the interior is read.  Synchronous
     ObsImpact obs_impact(ObsNetwork& net, const std::vector<double>& weight) {
-        ObsImpact r;
-        r.impact.resize(net.size());
-        check(csim_ensemble_obs_impact(h_, net.handle(), sized(weight, 1), r.impact.data(), &r.summary));
-        return r;
+        return obs_impact_by(csim_ensemble_obs_impact, net, weight);
     }
     // the same without localisation, for a capture made after a global analysis (assimilate_etkf, either path): one read
     // of the members whatever the network (see csim_ensemble_obs_impact_global).  Synchronous
     ObsImpact obs_impact_global(ObsNetwork& net, const std::vector<double>& weight) {
-        ObsImpact r;
-        r.impact.resize(net.size());
-        check(csim_ensemble_obs_impact_global(h_, net.handle(), sized(weight, 1), r.impact.data(), &r.summary));
-        return r;
+        return obs_impact_by(csim_ensemble_obs_impact_global, net, weight);
     }
     // adds sigma times a seeded Gaussian random field of correlation length corr_len to the interior of every forecast
     // member (t = -1: all members, else member t is left alone); enqueued on the ensemble's stream, so that run() follows
@@ -722,6 +716,12 @@ private:
     const double* sized(const std::vector<double>& a, int n) const {
         if (a.size() != member_size() * static_cast<std::size_t>(n)) throw std::invalid_argument("ensemble: array size");
         return a.data();
+    }
+    ObsImpact obs_impact_by(decltype(&csim_ensemble_obs_impact) call, ObsNetwork& net, const std::vector<double>& weight) {
+        ObsImpact r;
+        r.impact.resize(net.size());
+        check(call(h_, net.handle(), sized(weight, 1), r.impact.data(), &r.summary));
+        return r;
     }
     EnsembleVerification verify_any(const double* truth, int t, int forecast, const std::vector<double>& thresholds,
                                     bool fair) {

@@ -175,6 +175,10 @@ GRAM_SEAMS = [
     (64, 256, 65), (64, 257, 65), (64, 256, 128), (64, 257, 128),
     (64, 64, 129), (64, 65, 129), (64, 64, 256), (64, 65, 256),
 ]
+# and a class that carries its sums from a full segment into a ragged last one, of 2, 1 and 1 cells: the staged rows
+# past the last cell are then the previous segment's, and none of them may be walked
+GRAM_CARRY_RAGGED = [(2, 32769, 3), (29, 565, 65), (17, 241, 129)]
+GRAM_SEAMS += GRAM_CARRY_RAGGED
 GRAM_FORMS = (1, 2, 3)
 
 # (nx, ny, M): small shapes and (257, 3); the large M on the smallest shapes; 7 and 20 reach the register steps 8 and 32

@@ -66,8 +66,9 @@ _seam_cache = {}
 
 
 # seams above 64 members where the raw members are compared too: one for each of the two launch forms taken there
-# (65 members: two blocks per lane, 129: four); the others compare the centered matrix only, to stay quick
-SEAMS_BOTH = {(64, 257, 65), (64, 65, 129)}
+# (65 members: two blocks per lane, 129: four), and the ragged last segments after a full one, whose stale rows either
+# staging could walk; the others compare the centered matrix only, to stay quick
+SEAMS_BOTH = {(64, 257, 65), (64, 65, 129), *ref.GRAM_CARRY_RAGGED}
 
 
 def seam_case(nx, ny, M):

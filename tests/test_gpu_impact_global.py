@@ -64,13 +64,17 @@ def fields_of(K, nx, ny, seed):
 # (nx, ny, M, truth, centered, K).  Interiors of 1, 63, 64 and 65 cells; one segment past each class cap (cap 1024 at
 # M = 3, 256 at M = 65, 64 at M = 129); every M at which the lanes' blocks, the padded width or the cap change, on 13 x 9;
 # K at both sides of a block of four and at the limit; both centerings; the truth member first, in the middle, last and
-# nowhere
+# nowhere; and a class that carries its sums from a full segment into a ragged last one (espace.GRAM_CARRY_RAGGED),
+# centered and raw, K = 3 and K = 16
 DOT = [(1, 1, 1, "none", 1, 1), (1, 1, 2, "first", 0, 3), (9, 7, 3, "middle", 1, 4), (8, 8, 5, "last", 0, 5),
        (13, 5, 12, "none", 1, 16), (13, 5, 3, "first", 0, 1),
        (257, 256, 3, "middle", 1, 3), (129, 128, 65, "last", 0, 5), (65, 64, 129, "first", 1, 16),
        (13, 9, 1, "first", 0, 4), (13, 9, 2, "none", 1, 5), (13, 9, 63, "middle", 0, 16), (13, 9, 64, "last", 1, 1),
        (13, 9, 65, "none", 0, 3), (13, 9, 128, "first", 1, 4), (13, 9, 129, "middle", 1, 5), (13, 9, 255, "last", 0, 1),
        (13, 9, 256, "none", 1, 16), (13, 9, 256, "last", 0, 3)]
+DOT += [(nx, ny, M, where, centered, K)
+        for (nx, ny, M), where in zip(espace.GRAM_CARRY_RAGGED, ("middle", "none", "last"))
+        for centered in (1, 0) for K in (3, 16)]
 
 
 @pytest.mark.parametrize("case", DOT, ids=[f"{c[0]}x{c[1]}_M{c[2]}_t{c[3]}_c{c[4]}_K{c[5]}" for c in DOT])

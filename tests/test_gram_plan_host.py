@@ -1,7 +1,8 @@
 """The plan and the lane-to-block geometry of the two Gram sums (csrc/gram_plan.hpp), checked on the CPU:
 tools/gram_plan_host_check.cpp runs every cols = 1 .. 257 and every NB through conditions A-E (the block triangle,
-ownership, idle waves, the packed triangle, the LDS row) and the plan against brute force at the cap seams.  No device,
-no library: the program is the header and the check, compiled here with g++."""
+ownership, idle waves, the packed triangle, the LDS row), every M = 1 .. 256 and K = 1 .. 16 of the ensemble-space dot's
+rectangle through F-H (ownership, idle waves, the LDS rows and size) and the plan against brute force at the cap seams.
+No device, no library: the program is the header and the check, compiled here with g++."""
 import os
 import shutil
 import subprocess

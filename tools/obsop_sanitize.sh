@@ -10,7 +10,7 @@
 # round-robin order with its pairing) and of the ETKF
 # (csrc/etkf_weights.cpp: the weights' residual, symmetry and row sums up to the largest M, the
 # plan of the observation-space Gram sum against brute force) and of the two Gram sums (csrc/gram_plan.hpp: the plan, and
-# which lane owns which block of pairs at every width and form) and of the LETKF (csrc/assim_plan.cpp once more and
+# which lane owns which block of pairs at every width and form, and of the ensemble-space dot's rectangle) and of the LETKF (csrc/assim_plan.cpp once more and
 # csrc/letkf_nodes.hpp: the per-node lookup against brute force, the nodes and the blend at their seams), each as a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.  The build goes to $TMP;
 # nothing in the tree is replaced.
 set -e
