@@ -10,9 +10,12 @@
 //                      host-only finishing of the tables into scores
 //   ensemble_da.cpp    data assimilation: the analysis of a plan, Philox / normal numbers, perturbations, relaxation
 //                      (prior capture, relax); the plan, the Gaspari-Cohn table and the taps: assim_plan.cpp, without HIP
-//   ensemble_obs.cpp   observation networks: create / destroy, values from the host or from a member, the analysis that
-//                      reads a network, its diagnostics and log; the local analysis, the ETKF and the LETKF on a network
-//                      (the LETKF's lattice and node storage: letkf_nodes.hpp, its lookup: assim_plan.cpp, without HIP)
+//   ensemble_obs.cpp   observation networks (obs_network.hpp): create / destroy, values from the host or from a member,
+//                      the mask, fetch, the logs and the status bytes
+//   ensemble_analysis.cpp  the analyses that read a network: the serial one with its diagnostics and log, the local
+//                      analysis, the ETKF and the LETKF (the LETKF's lattice and node storage: letkf_nodes.hpp, its
+//                      lookup: assim_plan.cpp, without HIP)
+//   ensemble_obs_impact.cpp  the forecast impact of a network's observations: capture, local and global impact
 //   ensemble_space.cpp ensemble space: Gram matrix, projection, transform, dot and EOFs; the eigensolver:
 //                      sym_eigen.cpp, without HIP
 #include <cmath>

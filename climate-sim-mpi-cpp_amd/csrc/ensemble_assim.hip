@@ -8,7 +8,8 @@
 //                 It runs apart from the update so that no workgroup of an observation can overwrite the observed cell
 //                 while another workgroup of that observation still reads it.  Linear observations (a.tstart, the
 //                 taps of csim_obs_network_create_linear) differ only in h_k = sum_s w_s x_k(anchor + tap s):
-//                 linear_h of ensemble_linear.hpp; the taps lie outside every other window of the level, so the same holds for them.
+//                 obs_h of obs_wave.hpp; the taps lie outside every other window of the level, so the same holds for
+//                 them.
 //   assim_update  one wave per 64 cells of one observation's window (blockIdx.y: the observation, blockIdx.x: which
 //                 64 cells of its window clipped to the interior, row-major), so h'_k and the scalars are the same in
 //                 every lane of a wave, and lanes that follow i within a window row load each member coalesced.
@@ -17,13 +18,14 @@
 // Screening (a.status, csim_ensemble_assimilate_screened): a byte per plan position; the block of an observation whose
 // byte is not 0 leaves at once in assim_prior and skips it in assim_update, so it reads and writes nothing.  The
 // pointer is a kernel argument (null: as before), the test a scalar one: no instantiation of its own is needed.
-// Forecast members, cell addressing, the register and memory forms of a cell's members and their running sums are
-// those of ensemble_cell.hpp; the covariance with h'_k and the update are summed and rounded the same way, / and sqrt
+// Forecast members, cell addressing, the register and memory forms of a cell's members and their running sums, the
+// covariance with h'_k among them, are those of ensemble_cell.hpp; a window's cells and their rho are those of
+// obs_wave.hpp, which the impact walks too; the update is summed and rounded the same way, / and sqrt
 // are IEEE fp64 (no fast-math), so the numpy restatement of the csim.h block gives the same bits.  Only interior cells
 // of the forecast members are written; ghost rings, member t and the other ping-pong buffer are never touched.
 #include <algorithm>
 
-#include "ensemble_linear.hpp"
+#include "obs_wave.hpp"
 
 #pragma clang fp contract(off)
 
@@ -33,25 +35,17 @@ namespace {
 
 constexpr int ASSIM_GRID_Y = 65535;  // observations per launch row (larger batches loop)
 
-// LIN: linear observations (h_k from linear_h); the point instantiation is the kernel as it was before they existed
+// LIN: linear observations (obs_h); the point instantiation is the kernel as it was before they existed
 template <bool LIN>
 __global__ __launch_bounds__(64) void k_assim_prior(const double* __restrict__ f, int pitch, long slab, AssimArgs a,
                                                     int first) {
     extern __shared__ double sh[];  // M values (dynamic: a small ensemble does not pay for 1024); LIN: linear_lds
     const int lane = threadIdx.x;
-    const int M = a.forecast, t = a.truth_member;
+    const int M = a.forecast;
     const int q = first + blockIdx.x;
     if (a.status && a.status[q]) return;  // screened out: the whole block, before any barrier
-    const double* p = cell_ptr(f, a.obs.i[q], a.obs.j[q], pitch);
-    if constexpr (LIN) {
-        linear_h(p, slab, a, q, sh, sh + M);
-    } else {
-        for (int k = lane; k < M; k += 64) sh[k] = p[static_cast<ptrdiff_t>(forecast_member(k, t)) * slab];
-        __syncthreads();
-    }
-    double s = 0.0;
-    for (int k = 0; k < M; ++k) s = s + sh[k];
-    const double hbar = s / static_cast<double>(M);
+    obs_h<LIN>(f, pitch, slab, a, q, sh);
+    const double hbar = obs_hbar(sh, M);
     __syncthreads();
     double* __restrict__ hp = a.hp + static_cast<size_t>(blockIdx.x) * M;
     for (int k = lane; k < M; k += 64) {
@@ -86,14 +80,13 @@ __global__ __launch_bounds__(64) void k_assim_update(double* __restrict__ f, int
                                                      AssimArgs a, int first, int count) {
     extern __shared__ double sh[];  // M values
     const int lane = threadIdx.x;
-    const int M = a.forecast, t = a.truth_member, lx = a.lx, ly = a.ly, tw = 2 * lx + 1;
+    const int M = a.forecast, t = a.truth_member;
     const double cden = static_cast<double>(M - 1);
     for (int o = blockIdx.y; o < count; o += gridDim.y) {
         const int q = first + o;
         if (a.status && a.status[q]) continue;  // screened out: the same in every lane, nothing of it is read
-        const int io = a.obs.i[q], jo = a.obs.j[q];
-        const int i0 = max(1, io - lx), i1 = min(nx, io + lx), j0 = max(1, jo - ly), j1 = min(ny, jo + ly);
-        const long W = i1 - i0 + 1, cells = W * (j1 - j0 + 1);
+        const ObsWindow<long> win = obs_window<long>(a.obs.i[q], a.obs.j[q], a.lx, a.ly, nx, ny);
+        const long cells = win.cells;
         if (static_cast<long>(blockIdx.x) * 64 >= cells) continue;  // the same in every lane
         const double d = a.scal[3 * static_cast<size_t>(q)], alpha = a.scal[3 * static_cast<size_t>(q) + 1];
         const double delta = a.scal[3 * static_cast<size_t>(q) + 2];
@@ -101,20 +94,13 @@ __global__ __launch_bounds__(64) void k_assim_update(double* __restrict__ f, int
         for (int k = lane; k < M; k += 64) sh[k] = a.hp[static_cast<size_t>(o) * M + k];
         __syncthreads();
         for (long e0 = static_cast<long>(blockIdx.x) * 64; e0 < cells; e0 += static_cast<long>(gridDim.x) * 64) {
-            const long e = std::min(e0 + lane, cells - 1);  // lanes past the end redo the last cell and store nothing
-            const int row = static_cast<int>(e / W);
-            const int ci = i0 + static_cast<int>(e - row * W), cj = j0 + row;
-            const double rho = a.rho[static_cast<size_t>(cj - jo + ly) * tw + (ci - io + lx)];
+            const auto [ci, cj, rho] = window_cell(win, e0 + lane, a.rho, a.lx, a.ly);  // past the end: stores nothing
             const bool act = e0 + lane < cells && rho > 0.0;
             if constexpr (P > 0) {
                 double x[P];
                 const unsigned off = cell_off(ci, cj, pitch);
                 load_members<P>(f, slab, off, M, t, x);
-                const double xbar = mean_regs<P>(x, M);
-                double c = 0.0;
-#pragma unroll
-                for (int k = 0; k < P; ++k)
-                    if (k < M) c = c + (x[k] - xbar) * sh[k];
+                const double c = cov_regs<P>(x, M, mean_regs<P>(x, M), sh);
                 const double g = (rho * (c / cden)) / d;
                 const double beta = alpha * g;
                 __syncthreads();
@@ -124,10 +110,7 @@ __global__ __launch_bounds__(64) void k_assim_update(double* __restrict__ f, int
                         f[static_cast<size_t>(forecast_member(k, t)) * slab + off] = x[k] + (g * delta - beta * sh[k]);
             } else {
                 double* p = cell_ptr(f, ci, cj, pitch);
-                const double xbar = mean_mem(p, slab, 0u, M, t);
-                double c = 0.0;
-                for (int k = 0; k < M; ++k)
-                    c = c + (p[static_cast<ptrdiff_t>(forecast_member(k, t)) * slab] - xbar) * sh[k];
+                const double c = cov_mem<1>(p, slab, M, t, mean_mem(p, slab, 0u, M, t), sh);
                 const double g = (rho * (c / cden)) / d;
                 const double beta = alpha * g;
                 if (act)
@@ -176,7 +159,7 @@ __global__ __launch_bounds__(64) void k_assim_post_linear(const double* __restri
     extern __shared__ double sh[];  // linear_lds
     const int M = a.forecast;
     const int q = blockIdx.x;
-    linear_h(cell_ptr(f, a.obs.i[q], a.obs.j[q], pitch), slab, a, q, sh, sh + M);
+    obs_h<true>(f, pitch, slab, a, q, sh);
     double m, v;
     mv(sh, M, m, v);
     if (threadIdx.x == 0) {
@@ -192,14 +175,11 @@ hipError_t ens_launch_assim_prior(const EnsGeom& g, const double* f, const Assim
                                   hipStream_t st) {
     if (count <= 0) return hipSuccess;
     if (a.forecast < 2 || a.forecast > ASSIM_MAX_MEMBERS) return hipErrorInvalidValue;
-    if (a.tstart) {
-        if (a.tmax < 1 || a.tmax > OBS_MAX_TAPS) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(k_assim_prior<true>, dim3(count), dim3(64), linear_lds(a), st, f, g.pitch, g.slab, a, first);
-    } else {
-        hipLaunchKernelGGL(k_assim_prior<false>, dim3(count), dim3(64), sizeof(double) * a.forecast, st, f, g.pitch,
-                           g.slab, a, first);
-    }
-    return hipGetLastError();
+    return for_obs_form(a, sizeof(double) * a.forecast, [&](auto lin, size_t lds) {
+        hipLaunchKernelGGL(k_assim_prior<decltype(lin)::value>, dim3(count), dim3(64), lds, st, f, g.pitch, g.slab, a,
+                           first);
+        return hipGetLastError();
+    });
 }
 
 hipError_t ens_launch_assim_update(const EnsGeom& g, double* f, const AssimArgs& a, int first, int count,

@@ -117,6 +117,26 @@ __device__ __forceinline__ double var_mem(const double* __restrict__ f, long sla
     return q / static_cast<double>(M - 1);
 }
 
+// c = sum (x_k - xbar) h_k, h wave-uniform (LDS): the covariance of a cell with an observation, before its / (M - 1)
+template <int P>
+__device__ __forceinline__ double cov_regs(const double (&x)[P], int M, double xbar, const double* h) {
+    double c = 0.0;
+#pragma unroll
+    for (int k = 0; k < P; ++k)
+        if (k < M) c = c + (x[k] - xbar) * h[k];
+    return c;
+}
+
+// (p: the cell's own address in member 0.)  U: the loop's unroll count.  The impact takes the 8 of the other P = 0
+// loops; the update, which writes the members afterwards, keeps 1: with 8 it needs 66 VGPRs, not 48
+template <int U>
+__device__ __forceinline__ double cov_mem(const double* p, long slab, int M, int t, double xbar, const double* h) {
+    double c = 0.0;
+#pragma unroll U
+    for (int k = 0; k < M; ++k) c = c + (p[static_cast<ptrdiff_t>(forecast_member(k, t)) * slab] - xbar) * h[k];
+    return c;
+}
+
 // m and v of M values that are already in LDS, every lane the same
 __device__ __forceinline__ void mv(const double* x, int M, double& m, double& v) {
     double s = 0.0;

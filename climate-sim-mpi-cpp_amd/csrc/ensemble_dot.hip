@@ -1,5 +1,5 @@
 // ensemble_dot.hip — the kernels of csim_ensemble_dot and csim_ensemble_obs_impact_global (host side in
-// ensemble_space.cpp and ensemble_obs.cpp; the definitions are in csim.h).  Needs only the slab layout of ensemble.hpp.
+// ensemble_space.cpp and ensemble_obs_impact.cpp; the definitions are in csim.h).  Needs only the slab layout of ensemble.hpp.
 // All three kernels only read the members.
 //
 // p_k of a cell as in ensemble_space.hip.  Every product and every sum is one rounded fp64 operation, no FMA contraction.

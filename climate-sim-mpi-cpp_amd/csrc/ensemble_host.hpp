@@ -109,7 +109,7 @@ struct csim_ensemble {
         csim::DeviceBuf partial, gram, out, w;
         csim::Staging stage;
         int gram_form = 0, project_form = 0;  // options gram_form, project_form; 0: automatic
-        // the observation-space Gram matrix (csim_ensemble_obs_gram, ensemble_obs.cpp) shares `partial` and `gram`;
+        // the observation-space Gram matrix (csim_ensemble_obs_gram, ensemble_analysis.cpp) shares `partial` and `gram`;
         // what the last completed csim_ensemble_assimilate_etkf found, for csim_ensemble_etkf_info
         int obs_gram_form = 0;                // option obs_gram_form; 0: automatic
         bool etkf_valid = false;
@@ -131,7 +131,7 @@ struct csim_ensemble {
             dot_fields.release(), dot_partial.release(), dot_out.release();
         }
     } espace;
-    // the LETKF (csim_ensemble_assimilate_letkf, ensemble_obs.cpp): the node storage of the last call (LetkfLayout) and
+    // the LETKF (csim_ensemble_assimilate_letkf, ensemble_analysis.cpp): the node storage of the last call (LetkfLayout) and
     // what csim_ensemble_letkf_info needs to fetch its record; its launch option
     struct Letkf {
         csim::DeviceBuf buf;
@@ -141,7 +141,7 @@ struct csim_ensemble {
         int nax = 0, nay = 0;    // its lattice
         void release() { buf.release(); }
     } letkf;
-    // observation networks (csim_obs_network_*, ensemble_obs.cpp): the ones that are alive; each owns its device buffer
+    // observation networks (csim_obs_network_*, ensemble_obs.cpp; the type: obs_network.hpp): the ones that are alive; each owns its device buffer
     struct Obs {
         std::vector<csim_obs_network*> nets;
         void release();  // destroys them

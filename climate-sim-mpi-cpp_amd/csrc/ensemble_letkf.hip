@@ -1,5 +1,5 @@
 // ensemble_letkf.hip — the two kernels of csim_ensemble_assimilate_letkf that make the ETKF local (host side in
-// ensemble_obs.cpp; the definition is the LETKF block of csim.h; the lattice of nodes is letkf_nodes.hpp).  Between them
+// ensemble_analysis.cpp; the definition is the LETKF block of csim.h; the lattice of nodes is letkf_nodes.hpp).  Between them
 // run the batched eigensolver and the batched weights of sym_eigen_device.hip.
 //   k_letkf_gram   Workgroup (g, y) of 256 lanes serves node g: A_g = Z^T Z over L(g), the used observations whose
 //                  window holds the node's cell, with the localisation in the observation error.  The node's
@@ -22,6 +22,7 @@
 #include "espace_cell.hpp"
 #include "gram_tile.hpp"
 #include "letkf_nodes.hpp"
+#include "obs_wave.hpp"
 
 #pragma clang fp contract(off)
 
@@ -48,7 +49,6 @@ __global__ __launch_bounds__(GRAM_THREADS) void k_letkf_gram(int nx, int ny, Ass
     const int node = blockIdx.x;
     const int nb = node / l.nax, na = node - nb * l.nax;
     const int ci = letkf_node_at(na, l.spacing, nx), cj = letkf_node_at(nb, l.spacing, ny);
-    const int tw = 2 * a.lx + 1;
     GramTile<NB> tile;
     tile.init(MA);
     int cnt = 0;
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(GRAM_THREADS) void k_letkf_gram(int nx, int ny, Ass
             if (!(a.status && a.status[q])) {
                 const int di = ci - a.obs.i[q], dj = cj - a.obs.j[q];
                 if (abs(di) <= a.lx && abs(dj) <= a.ly) {
-                    const double rho = a.rho[static_cast<size_t>(dj + a.ly) * tw + (di + a.lx)];
+                    const double rho = window_rho(a.rho, a.lx, a.ly, di, dj);
                     if (rho > 0.0) {
                         re = a.obs.r[q] / rho;
                         used = __builtin_isfinite(re);

@@ -1,8 +1,8 @@
-// ensemble_local.hip — the local analysis of csim_ensemble_assimilate_local (host side in ensemble_obs.cpp): every
+// ensemble_local.hip — the local analysis of csim_ensemble_assimilate_local (host side in ensemble_analysis.cpp): every
 // interior cell analysed on its own from the used observations near it, R-localised, in increasing input index; the
 // text of the csim.h block.  Two launches after the screening and the inflation of the serial analysis:
 //   local_prior   one wave per observation: h_{o,k} of the M forecast members to `prior` (M doubles per plan
-//                 position); a point observation is its cell, a linear one linear_h of ensemble_linear.hpp.  A
+//                 position); a point observation is its cell, a linear one obs_h<true> of obs_wave.hpp.  A
 //                 screened-out observation leaves at once.  It runs apart from the update so that no cell is rewritten
 //                 while an observation still reads it.
 //   local_update  one wave per `pack` = G cells of one tile of the host's lookup (LocalTiles of assim_plan.hpp).  The
@@ -27,7 +27,7 @@
 // Only interior cells of the forecast members with a non-empty list are written.
 #include <algorithm>
 
-#include "ensemble_linear.hpp"
+#include "obs_wave.hpp"
 
 #pragma clang fp contract(off)
 
@@ -55,12 +55,12 @@ __global__ __launch_bounds__(64) void k_local_prior(const double* __restrict__ f
     const int M = a.forecast, t = a.truth_member;
     const int q = blockIdx.x;
     if (a.status && a.status[q]) return;  // screened out: the whole block, before any barrier
-    const double* p = cell_ptr(f, a.obs.i[q], a.obs.j[q], pitch);
     double* __restrict__ out = prior + static_cast<size_t>(q) * M;
     if constexpr (LIN) {
-        linear_h(p, slab, a, q, sh, sh + M);
+        obs_h<true>(f, pitch, slab, a, q, sh);
         for (int k = lane; k < M; k += 64) out[k] = sh[k];
-    } else {
+    } else {  // straight to `prior`: nothing reads the values here, so they need no LDS and no barrier
+        const double* p = cell_ptr(f, a.obs.i[q], a.obs.j[q], pitch);
         for (int k = lane; k < M; k += 64) out[k] = p[static_cast<ptrdiff_t>(forecast_member(k, t)) * slab];
     }
 }
@@ -96,7 +96,6 @@ __global__ __launch_bounds__(64) void k_local_update(double* __restrict__ f, int
     const int cr = cidx / l.tile, cc = cidx - cr * l.tile;
     const int ci = tx * l.tile + cc + 1, cj = ty * l.tile + cr + 1;
     const bool lists = lane_on && slot == 0 && cr < l.tile && ci <= nx && cj <= ny;
-    const int tw = 2 * a.lx + 1;
     const int c0 = l.cstart[tileid], c1 = l.cstart[tileid + 1];
     int n = 0;
     sn[lane] = 0;
@@ -115,7 +114,7 @@ __global__ __launch_bounds__(64) void k_local_update(double* __restrict__ f, int
             for (int u = 0; u < m && n < l.lmax; ++u) {
                 const int di = ci - ei[u], dj = cj - ej[u];
                 if (abs(di) > a.lx || abs(dj) > a.ly || es[u]) continue;
-                const double rho = a.rho[static_cast<size_t>(dj + a.ly) * tw + (di + a.lx)];
+                const double rho = window_rho(a.rho, a.lx, a.ly, di, dj);
                 if (!(rho > 0.0)) continue;
                 const double re = er[u] / rho;
                 if (!__builtin_isfinite(re)) continue;
@@ -253,13 +252,11 @@ hipError_t ens_launch_local_prior(const EnsGeom& g, const double* f, const Assim
                                   hipStream_t st) {
     if (nobs <= 0) return hipSuccess;
     if (a.forecast < 2 || a.forecast > ASSIM_MAX_MEMBERS) return hipErrorInvalidValue;
-    if (a.tstart) {
-        if (a.tmax < 1 || a.tmax > OBS_MAX_TAPS) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(k_local_prior<true>, dim3(nobs), dim3(64), linear_lds(a), st, f, g.pitch, g.slab, a, prior);
-    } else {
-        hipLaunchKernelGGL(k_local_prior<false>, dim3(nobs), dim3(64), 0, st, f, g.pitch, g.slab, a, prior);
-    }
-    return hipGetLastError();
+    return for_obs_form(a, 0, [&](auto lin, size_t lds) {
+        hipLaunchKernelGGL(k_local_prior<decltype(lin)::value>, dim3(nobs), dim3(64), lds, st, f, g.pitch, g.slab, a,
+                           prior);
+        return hipGetLastError();
+    });
 }
 
 hipError_t ens_launch_local_update(const EnsGeom& g, double* f, const AssimArgs& a, const LocalArgs& l, hipStream_t st) {

@@ -1,4 +1,4 @@
-// ensemble_obsgram.hip — the observation-space Gram matrix of csim_ensemble_obs_gram (host side in ensemble_obs.cpp;
+// ensemble_obsgram.hip — the observation-space Gram matrix of csim_ensemble_obs_gram (host side in ensemble_analysis.cpp;
 // the definition is the ETKF block of csim.h).  Needs the slab layout of ensemble.hpp; the plan is gram_plan.hpp, and
 // the lanes' pairs, the walk over a segment's rows, the class's partial and the fold of an entry are gram_tile.hpp, as
 // for k_gram_partial (ensemble_space.hip).  Here: the rows of a segment are 64 consecutive plan positions of a network,

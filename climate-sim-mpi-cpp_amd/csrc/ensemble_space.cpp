@@ -1,6 +1,6 @@
 // ensemble_space.cpp — the ensemble-space calls: csim_ensemble_gram, _project, _transform and their composite
 // csim_ensemble_eofs (kernels in ensemble_space.hip, the eigensolver in sym_eigen.cpp), and csim_ensemble_dot (kernels
-// in ensemble_dot.hip; its two steps are shared with csim_ensemble_obs_impact_global of ensemble_obs.cpp).  Every
+// in ensemble_dot.hip; its two steps are shared with csim_ensemble_obs_impact_global of ensemble_obs_impact.cpp).  Every
 // argument check on the members is csim_ensemble_space_check, which needs no device.
 #include <algorithm>
 #include <cmath>

@@ -4,7 +4,9 @@ and the screened form) at its launch seams, bit for bit against numpy restatemen
      within the batch and everything else by plan position;
   B. more than 65535 observations in one launch, where the update's grid wraps and a block handles two observations
      in turn;
-  C. every register step of the update (P = 4 .. 64) with M = P and M = P + 1 against the per-observation restatement.
+  C. every register step of the update (P = 4 .. 64) with M = P and M = P + 1 against the per-observation restatement;
+  D. a window that covers the whole grid, with lanes of its only wave past its end, then the impact of the same
+     analysis (tests/impact_restatement.py): the update and the impact take the same cells of the same windows.
 A and B use the level-vectorised restatement of tests/assim_level_restatement.py, which
 tests/test_assim_level_restatement_host.py pins to the per-observation ones and which also pins the preconditions of the
 cases here (half-widths, level sizes) from the planner alone.  No tolerance anywhere."""
@@ -12,6 +14,7 @@ import numpy as np
 import pytest
 
 import assim_level_restatement as lvl
+import impact_restatement as imp
 import obsnet_restatement as obsnet
 import screen_restatement as screen
 from __graft_entry__ import load_package
@@ -414,3 +417,45 @@ def test_register_steps(csim, M, truth, lam, ordered, spacing, nasty):
     for name, a, b in (("prior_mean", got.prior_mean, pm), ("prior_var", got.prior_var, pv),
                        ("post_mean", got.post_mean, qm), ("post_var", got.post_var, qv)):
         assert same_bits(a, b), name
+
+
+# ---- D. a window over the whole grid, and the impact of the same analysis --------------------------------------------
+
+D_GRID = dict(nx=9, ny=5, dx=1.0, dy=2.0, loc=2.25)        # support 4.5: lx = 4 (4 < 4.5), ly = 2 (2 * 2.0 < 4.5)
+D_OBS = [(1, 1), (1, 3), (5, 3)]                           # a corner, the left edge, the middle
+D_CELLS = [15, 25, 45]                                     # their windows; 45 = the grid: 19 lanes lie past its end
+
+
+@pytest.mark.parametrize("M,truth", [(4, None), (5, "last")], ids=["M4_P4_full", "M5_P8_first"])
+def test_window_covers_the_grid(csim, M, truth):
+    nx, ny, dx, dy, loc = (D_GRID[k] for k in ("nx", "ny", "dx", "dy", "loc"))
+    rho = csim.ensemble_gc_table(dx, dy, loc, nx, ny)
+    assert rho.shape == (5, 9)                             # half-widths (4, 2): the full window is the grid
+    i, j = (np.array(v, dtype=np.int32) for v in zip(*D_OBS))
+    cells = [(min(nx, a + 4) - max(1, a - 4) + 1) * (min(ny, b + 2) - max(1, b - 2) + 1) for a, b in D_OBS]
+    assert cells == D_CELLS and nx * ny == 45
+    B = M if truth is None else M + 1
+    t = None if truth is None else B - 1
+    rng = np.random.default_rng(900 + M)
+    X = rng.standard_normal((B, ny + 2, nx + 2))
+    y, r = rng.standard_normal(3), rng.uniform(0.05, 2.0, 3)
+    e = csim.Ensemble(B, nx, ny, dx, dy, (0, 0, 0, 0))
+    e.upload_all(X)
+    net = e.obs_network(i, j, r, loc, log_cycles=1)
+    net.set_values(y)
+    e.assimilate_network(net, truth_member=t, record=True)
+    net.impact_capture(truth_member=t)
+    G = e.download_all()
+    W, _, _, _, _, nl = restate(csim, X, dx, dy, i, j, y, r, loc, 1.0, -1 if t is None else t, False)
+    assert (net.info.lx, net.info.ly) == (4, 2)
+    assert net.info.nlevels == nl == 3                     # every window holds the middle cell: one level each
+    assert_members(G, W, X, t)
+    w = np.full((ny + 2, nx + 2), np.nan)                  # only the interior is read
+    w[1:-1, 1:-1] = rng.standard_normal((ny, nx))
+    got = e.obs_impact(net, w)
+    e.close()
+    hb, _ = obsnet.mv(X, t, i, j)                          # the recorded background: before any observation
+    cap = imp.capture(G, t, i, j, None, y, hb, r)
+    J = imp.impact(G, cap, rho, i, j, w)
+    assert np.count_nonzero(J) == 3 and exact_bits(got.impact, J)
+    assert exact_bits(got.summary.total, imp.summary(J, cap.status)[2])

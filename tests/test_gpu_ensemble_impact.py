@@ -11,6 +11,7 @@ import impact_restatement as ref
 import obsnet_restatement as obsnet
 import obsop_restatement as obsop
 import screen_restatement as screen
+import test_gpu_ensemble_obsop as obsop_net
 from __graft_entry__ import load_package
 
 pytestmark = pytest.mark.gpu
@@ -158,6 +159,39 @@ def test_impact_is_the_restatement(csim, case):
     # the same call again: nothing was consumed
     check_result(e.obs_impact(net, w), J, cap.status)
     e.close()
+
+
+@pytest.mark.parametrize("M,where", [(5, "middle"), (65, "last")], ids=["M5_one_part_tile", "M65_two_tiles_reread"])
+def test_network_of_1_to_64_taps(csim, M, where):
+    """the 40 observations of tests/test_gpu_ensemble_obsop.py on their grid, 1, 4, 25 and 64 taps among them: the
+    capture's h_k through one partly filled tile of 64 members, and through a second tile with the truth member last"""
+    grid = (obsop_net.NX, obsop_net.NY, obsop_net.DX, obsop_net.DY, obsop_net.LOC)
+    nx, ny, dx, dy, loc = grid
+    B = M + 1
+    t = truth_of(where, B)
+    rng = np.random.default_rng(77 + M)
+    X = rng.standard_normal((B, ny + 2, nx + 2))
+    i, j, taps, r = obsop_net.network()
+    nobs = len(i)
+    rho = csim.ensemble_gc_table(dx, dy, loc, nx, ny)
+    assert rho.shape == (2 * obsop_net.LY + 1, 2 * obsop_net.LX + 1)
+    hb, vb = obsop.mv(X, t, i, j, taps)
+    y = hb + np.sqrt(vb + r) * rng.standard_normal(nobs)
+    e = ensemble(csim, X, grid)
+    net = e.obs_network(i, j, r, loc, log_cycles=1, taps=taps)
+    net.set_values(y)
+    e.assimilate_network(net, truth_member=t, record=True)
+    net.impact_capture(truth_member=t)
+    A = e.download_all()
+    e.run(2)
+    Xf = e.download_all()
+    w = weight_field(rng, grid)
+    got = e.obs_impact(net, w)
+    e.close()
+    cap = ref.capture(A, t, i, j, taps, y, hb, r)
+    J = ref.impact(Xf, cap, rho, i, j, w)
+    assert np.isfinite(J).all() and np.count_nonzero(J) == nobs
+    check_result(got, J, cap.status)
 
 
 def test_more_observations_than_waves(csim):

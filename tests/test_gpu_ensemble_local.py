@@ -13,13 +13,15 @@ import local_analysis_restatement as ref
 import obsnet_restatement as obsnet
 import obsop_restatement as obsop
 import screen_restatement as screen
+import test_gpu_ensemble_obsop as obsop_net
 from __graft_entry__ import load_package
 
 pytestmark = pytest.mark.gpu
 
-# nx, ny, dx, dy, loc: half-widths (4, 4), (4, 4) and, anisotropic, (3, 4)
-GRIDS = [(37, 21, 1.0, 1.0, 2.5), (16, 16, 1.0, 1.0, 2.5), (37, 21, 1.0, 0.8, 2.0)]
-HALF = [(4, 4), (4, 4), (3, 4)]
+# nx, ny, dx, dy, loc: half-widths (4, 4), (4, 4) and, anisotropic, (3, 4); last the grid of the `net40` network
+GRIDS = [(37, 21, 1.0, 1.0, 2.5), (16, 16, 1.0, 1.0, 2.5), (37, 21, 1.0, 0.8, 2.0),
+         (obsop_net.NX, obsop_net.NY, obsop_net.DX, obsop_net.DY, obsop_net.LOC)]
+HALF = [(4, 4), (4, 4), (3, 4), (obsop_net.LX, obsop_net.LY)]
 NOBS = 40
 
 
@@ -81,8 +83,12 @@ def cells_of(rng, grid, nobs):
 
 def make_network(csim, rng, grid, kind, nobs=NOBS):
     """(i, j, taps or None, r): point observations; bilinear stations between grid points; 3 x 3 footprints clipped at
-    the sides; `custom`: hand-made operators with a repeated cell and a negative weight"""
+    the sides; `custom`: hand-made operators with a repeated cell and a negative weight; `net40`: the 40 observations
+    of tests/test_gpu_ensemble_obsop.py on their grid, 1, 4, 25 and 64 taps among them"""
     nx, ny = grid[0], grid[1]
+    if kind == "net40":
+        assert nobs == 40 and grid == GRIDS[3]
+        return obsop_net.network()
     r = rng.uniform(0.05, 2.0, nobs)
     if kind == "bilinear":
         x, y = rng.uniform(1, nx, nobs), rng.uniform(1, ny, nobs)
@@ -157,7 +163,7 @@ def test_local_analysis_is_the_restatement(csim, case):
 # ---- 2. linear networks ------------------------------------------------------------------------------------------------
 
 LINEAR = [("bilinear", 5, "middle", 0, 1.1), ("box", 8, None, 1, 1.0), ("custom", 33, "last", 2, 1.1),
-          ("box", 65, None, 1, 1.0), ("bilinear", 64, "first", 2, 1.0)]
+          ("box", 65, None, 1, 1.0), ("bilinear", 64, "first", 2, 1.0), ("net40", 65, "last", 3, 1.0)]
 
 
 @pytest.mark.parametrize("case", LINEAR, ids=[f"{c[0]}_M{c[1]}_t{c[2]}_grid{c[3]}_lam{c[4]}" for c in LINEAR])
@@ -169,7 +175,7 @@ def test_linear_networks(csim, case):
     t = truth_of(where, B)
     rng = np.random.default_rng(200 * M + gi)
     X = rng.standard_normal((B, ny + 2, nx + 2))
-    nobs = 30
+    nobs = 40 if kind == "net40" else 30      # net40 at M = 65: 64 taps through two tiles of the linear prior
     i, j, taps, r = make_network(csim, rng, grid, kind, nobs)
     if kind == "custom":
         assert (taps[3] < 0).any()
