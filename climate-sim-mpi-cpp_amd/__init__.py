@@ -142,6 +142,7 @@ def lib() -> C.CDLL:
         "csim_device_name": (i, [C.c_char_p, C.c_size_t]),
         "csim_safe_dt": (d, [d] * 5),
         "csim_pow2_velocity_screen": (i, [d] * 6 + [C.POINTER(d)]),
+        "csim_screen_lease_bounds": (i, [d] * 6 + [C.c_long, C.POINTER(d)]),
         "csim_decomp_init": (i, [i, i, i, i, C.POINTER(Decomp)]),
         "csim_exchange_plan": (i, [C.POINTER(Decomp), i, C.POINTER(Msg), ip, C.POINTER(Msg), ip]),
         "csim_field_create": (i, [i, i, i, d, d, C.POINTER(vp)]),
@@ -294,7 +295,7 @@ def lib() -> C.CDLL:
         "csim_ensemble_classes": (i, [i, ip, ip]),
     }
     for name, (res, args) in sig.items():
-        if name == "csim_pow2_velocity_screen" and os.environ.get("CSIM_LIB") and not hasattr(L, name):
+        if name in ("csim_pow2_velocity_screen", "csim_screen_lease_bounds") and os.environ.get("CSIM_LIB") and not hasattr(L, name):
             continue  # CSIM_LIB: the build of an earlier revision in an A/B measurement (tools/gpu_lib_ab.sh)
         fn = getattr(L, name)
         fn.restype = res
@@ -361,6 +362,14 @@ def pow2_velocity_screen(D, dt, vx, vy, dx=1.0, dy=1.0):
     """(L, upper, q, K) of the stepper option "pow2_v" for these parameters, L == 0.0: the form is off (csim.h)"""
     out = (C.c_double * 4)()
     _ck(lib().csim_pow2_velocity_screen(dx, dy, D, dt, vx, vy, out))
+    return tuple(out)
+
+
+def screen_lease_bounds(D, dt, vx, vy, dx=1.0, dy=1.0, R=1024):
+    """(M_req, m_req, eta, a0) of the stepper option "screen_lease" for these parameters and a lease of R steps;
+    M_req == 0.0: no lease, m_req == 0.0: the 12-operation body is not leased (csim.h)"""
+    out = (C.c_double * 4)()
+    _ck(lib().csim_screen_lease_bounds(dx, dy, D, dt, vx, vy, int(R), out))
     return tuple(out)
 
 

@@ -16,6 +16,49 @@ static bool pow2(double x) {
     return std::frexp(x, &e) == 0.5 && std::isnormal(1.0 / x);
 }
 
+// g, the bound on the growth of max|u| per step: the sum of the magnitudes of what multiplies the five points, with
+// room for the 15 roundings (make_phys: fast_thr; lease_bounds: M_req)
+static double growth_per_step(const Phys& p) {
+    return (1.0 + 4.0 * std::fabs(p.kdiff) * (1.0 / p.dx2 + 1.0 / p.dy2) +
+            2.0 * std::fabs(p.mdt) * (std::fabs(p.vx) / std::fabs(p.dx) + std::fabs(p.vy) / std::fabs(p.dy))) * (1.0 + 1e-9);
+}
+
+// The screen lease's bounds (internal.hpp; derivation: DESIGN.md §4), in exponents like slow_thr above so that nothing
+// under- or overflows on the way: both come out as powers of two, M_req rounded down and m_req rounded up by a whole
+// binade more than the logarithms' own error could ask for.
+//   upper: max|u| grows by at most g per step whatever the signs, so max|u| <= U / g^(R + MAX_FUSE) now keeps every
+//     value a pass loads within R steps below U = p2_hi (fast_thr where the 12-operation form is off) — and the
+//     thresholds themselves carry the levels inside a pass.
+//   lower: with a0, aW, aE, aS, aN > 0 and a field of one sign (ring zeros allowed) the exact update of a cell is at
+//     least a0 c and at least a_min max_local.  Each of the at most 15 roundings of either form is relative to an
+//     intermediate that, carried through the factors still to come, is at most g max_local, so
+//     |computed - exact| <= 16 g eps max_local <= (16 g eps / a_min) exact; eta doubles that for the rounding of the
+//     coefficients themselves.  Hence min|u| shrinks by at most a0 (1 - eta) per step, and min|u| >= 2 slow_thr /
+//     (a0 (1 - eta))^(R + MAX_FUSE) now keeps every non-zero value a pass loads within R steps at or above 2 slow_thr.
+//     (No bit is lost to the subnormal range on the way: that is slow_thr's own grid argument.)
+LeaseBounds lease_bounds(const Phys& p, long R) {
+    LeaseBounds b;
+    if (R < 1 || p.div_mode > 1 || !(p.fast_thr > 0.0)) return b;
+    const double g = growth_per_step(p);
+    if (!std::isfinite(g) || !(g >= 1.0)) return b;
+    const double n = static_cast<double>(R) + MAX_FUSE;
+    const double upper = p.slow_thr > 0.0 ? p.p2_hi : p.fast_thr;
+    const double eM = std::floor(std::log2(upper) - n * std::log2(g)) - 1.0;
+    if (!(eM >= -1000.0)) return b;  // a lease this long leaves no field to admit
+    b.M_req = std::ldexp(1.0, static_cast<int>(eM));
+    const double coef[5] = {p.a0, p.aW, p.aE, p.aS, p.aN};
+    double a_min = coef[0];
+    for (double c : coef) a_min = (c > 0.0 && std::isfinite(c)) ? std::min(a_min, c) : 0.0;
+    if (!(p.slow_thr > 0.0) || !(a_min > 0.0)) return b;
+    const double eta = 32.0 * g * std::ldexp(1.0, -53) / a_min;
+    if (!(eta <= std::ldexp(1.0, -20)) || !(p.a0 < 1.0)) return b;  // a coefficient so small that rounding could eat the bound
+    const double em = std::ceil(std::log2(p.slow_thr) + 1.0 - n * (std::log2(p.a0) + std::log1p(-eta) / std::log(2.0))) + 1.0;
+    if (!(em <= eM)) return b;  // no value could satisfy both
+    b.m_req = std::ldexp(1.0, static_cast<int>(em));
+    b.eta = eta;
+    return b;
+}
+
 Phys make_phys(double dx, double dy, double D, double dt, double vx, double vy, bool contract) {
     Phys p;
     p.kdiff = dt * D;
@@ -55,8 +98,7 @@ Phys make_phys(double dx, double dy, double D, double dt, double vx, double vy, 
     // 2^1022 / g^MAX_FUSE cannot reach 2^1023 at any level of a pass.  Parameters so far from stable that
     // this bound drops below 2^900 switch the fused form off.
     {
-        const double g = (1.0 + 4.0 * std::fabs(p.kdiff) * (1.0 / p.dx2 + 1.0 / p.dy2) +
-                          2.0 * std::fabs(p.mdt) * (std::fabs(vx) / std::fabs(dx) + std::fabs(vy) / std::fabs(dy))) * (1.0 + 1e-9);
+        const double g = growth_per_step(p);
         const double thr = std::ldexp(1.0, 1022) / std::pow(g, MAX_FUSE);
         p.fast_thr = (std::isfinite(g) && thr >= std::ldexp(1.0, 900)) ? thr : 0.0;
     }
@@ -229,6 +271,17 @@ int csim_pow2_velocity_screen(double dx, double dy, double D, double dt, double 
     CSIM_REQUIRE(out, "null argument");
     const Phys p = make_phys(dx, dy, D, dt, vx, vy);
     out[0] = p.slow_thr, out[1] = p.p2_hi, out[2] = p.p2_q, out[3] = p.p2_k;
+    return CSIM_OK;
+}
+
+// host arithmetic only: what a stepper with these parameters (and "pow2_v" on) asks of a field before it leases the
+// screen for R steps — out[0] = M_req, out[1] = m_req (0: no lease of that kind), out[2] = eta, out[3] = a0
+int csim_screen_lease_bounds(double dx, double dy, double D, double dt, double vx, double vy, long R, double out[4]) {
+    CSIM_REQUIRE(out, "null argument");
+    CSIM_REQUIRE(R >= 1, "R must be >= 1");
+    const Phys p = make_phys(dx, dy, D, dt, vx, vy);
+    const LeaseBounds b = lease_bounds(p, R);
+    out[0] = b.M_req, out[1] = b.m_req, out[2] = b.eta, out[3] = p.a0;
     return CSIM_OK;
 }
 

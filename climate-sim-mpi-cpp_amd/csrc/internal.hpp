@@ -63,6 +63,16 @@ struct Phys {
     double p2_q, p2_k;  // q = (vx/dx)/(vy/dy) or its reciprocal, K = (-dt) * the velocity factored out (see cell)
 };
 Phys make_phys(double dx, double dy, double D, double dt, double vx, double vy, bool contract = false);
+// Screen lease: what a whole field has to satisfy NOW so that, R + MAX_FUSE steps on, every value still
+// passes the screen of the interior bodies — pure host arithmetic on a Phys (api.cpp).
+//   M_req  max|u| <= M_req keeps every value below p2_hi (fast_thr where the 12-operation form is off); 0: no lease
+//   m_req  with all five stencil coefficients positive and the field of one sign: min|u| >= m_req keeps every value
+//          at or above 2 slow_thr; 0: no lease of the 12-operation body for these parameters
+//   eta    the relative loss of one computed update against the exact one that m_req allows for (32 g eps / a_min)
+struct LeaseBounds {
+    double M_req = 0.0, m_req = 0.0, eta = 0.0;
+};
+LeaseBounds lease_bounds(const Phys& p, long R);
 // upwind-sign flavour of these parameters, 3 * cx + cy with per axis 0: v < 0, 1: v >= 0, 2: v == 0 on a screened run
 // (fast_thr > 0 and dx, dy without IEEE division): which k_sweepO_dpp<., ., SX, SY> / k_ensemble_sweepO<., ., SX, SY>
 // a launch runs, and the class an ensemble member is launched with (ENS_CLASSES of them)
@@ -124,7 +134,8 @@ struct FrameSync {
 };
 hipError_t launch_sweepO(const double* in, double* out, int pitch, const Phys& p, const SweepCfg& cfg,
                          const int kind[4], double value, const SweepPlan& plan, hipStream_t st,
-                         double* const fin_lines[4] = nullptr, const FrameSync* sync = nullptr);
+                         double* const fin_lines[4] = nullptr, const FrameSync* sync = nullptr,
+                         const unsigned* lease = nullptr);  // lease: the verdict word of launch_lease below, or nullptr
 // depth with the lowest measured cost per time step (tools/depth_ab.py, profiles/r02_depth_ab.jsonl): 7 on tiles
 // of >= 2e8 cells (+0.9 % over 6 at 16384^2 and 32768^2); 6 in between (7 loses 7 % on a 4096 x 8192 tile, which is
 // a single round of wavefronts: more overhead rows per chunk and nothing to amortise them); 4 on tiles below
@@ -193,6 +204,14 @@ hipError_t launch_sum(const double* f, int nx, int ny, int pitch, double* scratc
                       const Members& mb = {});
 hipError_t launch_linf(const double* a, const double* b, int nx, int ny, int pitch, double* scratch,
                        hipStream_t st);
+// k_reduce<3>, the screen lease's verdict: over rows 0..ny+1 and columns 0..nx+1 (ring cells told from interior ones)
+// max|u|, min|u| over non-zero values and the sign / zero / non-finite flags; the block that finishes last folds the
+// partials and stores the verdict into lease[0] — bit 0 (LEASE_FAST): max|u| <= M_req and nothing non-finite; bit 1
+// (LEASE_P2): also m_req > 0, min|u| >= m_req, the interior strictly of one sign and no ring value of the other sign
+// or a zero of the other sign.  lease[1] is the kernel's ticket counter (zero between launches).  Nothing comes back to the host.
+constexpr int LEASE_BLOCKS = 512;  // three partials per block in the same scratch
+hipError_t launch_lease(const double* f, int nx, int ny, int pitch, double* scratch, double M_req, double m_req,
+                        unsigned* lease, hipStream_t st);
 // max that keeps a NaN (fmax drops one): every stage of the L-inf reduction — lane, wave, block (k_reduce<2>) and the
 // host merge (fold_partials) — goes through it, so max |a-b| is NaN as soon as one |a-b| is
 __host__ __device__ __forceinline__ double max_nan(double r, double d) { return (d > r || d != d) ? d : r; }

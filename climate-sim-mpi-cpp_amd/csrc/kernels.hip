@@ -17,7 +17,7 @@ namespace csim {
 // only declares the template: launch_sweepO below links against them.
 template <int T>
 hipError_t sweepO_T(const double* in, double* out, int pitch, const Phys& p, const SweepCfg& cfg, const Bc2& bc,
-                    const FinLines& fin, const SweepPlan& plan, hipStream_t st, const FrameSync& fs);
+                    const FinLines& fin, const SweepPlan& plan, hipStream_t st, const FrameSync& fs, const unsigned* lease);
 
 // -------------------------------------------------------------------------------------------
 // VAR_DPP — the default fused sweep.
@@ -379,7 +379,7 @@ __global__ __launch_bounds__(256) void k_gaussian(double* __restrict__ f, int nx
 }
 
 // ---- reductions: Field, Stepper (gridDim.y == 1, slab == 0) and ensemble (blockIdx.y = member, slab = its stride) ----
-// KIND 0: min/max over i0..i1, j0..j1 ; KIND 1: sum ; KIND 2: max |a-b|
+// KIND 0: min/max over i0..i1, j0..j1 ; KIND 1: sum ; KIND 2: max |a-b| ; KIND 3: the screen lease's verdict (below)
 // Block b of a member takes rows j0 + b, j0 + b + G, ... (G = gridDim.x); its result goes to partial[m * G + b], the
 // maximum of KIND 0 to partial[gridDim.y * G + m * G + b]; fold_partials (api.cpp) merges a member's blocks in order.
 // NaN: min/max skip it (fmin / fmax; all NaN gives +inf, -inf), the sum carries it, and max |a-b| is NaN as soon as
@@ -406,17 +406,77 @@ __device__ __forceinline__ double wave_max_nan(double v) {
     for (int m = 32; m >= 1; m >>= 1) v = max_nan(v, __shfl_xor(v, m, 64));
     return v;
 }
+// KIND 3 (launch_lease; gridDim.y == 1): the window is the whole field with its ring, i0 = j0 = 0, i1 = nx + 1,
+// j1 = ny + 1, and a cell on the window's rim is a ring cell.  r0 / r1 are min / max of |v| over the non-zero finite
+// values, and a third partial carries the flags LF_* (as a small integer in a double).  Each block adds itself to a
+// ticket after its partials are out (release fence, agent scope); the block that draws the last ticket folds all
+// partials (read past the caches) and stores the verdict — the host never reads it on the step path.
+enum : unsigned {
+    LF_POS = 1, LF_NEG = 2,            // an interior value > 0 / < 0
+    LF_ZERO = 4,                       // an interior value that is a zero of either sign
+    LF_RING_POS = 8, LF_RING_NEG = 16, // a ring value > 0 / < 0
+    LF_RING_PZ = 32, LF_RING_NZ = 64,  // a ring value that is +0 / -0
+    LF_NONFINITE = 128                 // any value that is Inf or NaN
+};
+struct LeaseOut {
+    double M_req = 0.0, m_req = 0.0;
+    unsigned* word = nullptr;  // word[0]: the verdict, word[1]: the ticket counter
+};
+__device__ __forceinline__ unsigned lease_verdict(double lo, double hi, unsigned f, const LeaseOut& q) {
+    const bool upper = q.M_req > 0.0 && !(f & LF_NONFINITE) && hi <= q.M_req;
+    // one sign throughout: the interior strictly, the ring with zeros of that sign allowed
+    const bool pos = !(f & (LF_NEG | LF_RING_NEG | LF_RING_NZ)) && (f & LF_POS);
+    const bool neg = !(f & (LF_POS | LF_RING_POS | LF_RING_PZ)) && (f & LF_NEG);
+    const bool lower = q.m_req > 0.0 && !(f & LF_ZERO) && (pos || neg) && lo >= q.m_req;
+    return (upper ? 1u : 0u) | (upper && lower ? 2u : 0u);
+}
+
 template <int KIND>
 __global__ __launch_bounds__(256) void k_reduce(const double* __restrict__ a,
                                                 const double* __restrict__ b, int i0, int i1,
                                                 int j0, int j1, int pitch, long slab,
-                                                double* __restrict__ partial) {
+                                                double* __restrict__ partial, LeaseOut lease) {
     __shared__ double sh[2][4];
+    __shared__ unsigned shf[4];
     a += static_cast<ptrdiff_t>(blockIdx.y) * slab;
     if (KIND == 2) b += static_cast<ptrdiff_t>(blockIdx.y) * slab;
-    double r0 = KIND == 0 ? INFINITY : 0.0;  // min | sum | linf
-    double r1 = -INFINITY;                   // max
-    for (int j = j0 + blockIdx.x; j <= j1; j += gridDim.x) {
+    double r0 = (KIND == 0 || KIND == 3) ? INFINITY : 0.0;  // min | sum | linf | min |v|
+    double r1 = KIND == 3 ? 0.0 : -INFINITY;                // max | max |v|
+    unsigned fl = 0;
+    if (KIND == 3) {
+        // A row's interior starts on a 128-byte boundary at column 1 (internal.hpp): the lanes take it as double2 pairs,
+        // eight in flight each (the launch is one read of the field and should run at HBM speed); thread 0 adds the two
+        // ring columns and the last column of an odd width.
+        auto take = [&](double v, bool ring) {
+            const double m = fabs(v);
+            if (!(m < INFINITY)) {  // Inf or NaN
+                fl |= LF_NONFINITE;
+            } else if (m == 0.0) {
+                fl |= ring ? (signbit(v) ? LF_RING_NZ : LF_RING_PZ) : LF_ZERO;
+            } else {
+                fl |= ring ? (v > 0.0 ? LF_RING_POS : LF_RING_NEG) : (v > 0.0 ? LF_POS : LF_NEG);
+                r0 = fmin(r0, m);
+                r1 = fmax(r1, m);
+            }
+        };
+        const int nx = i1 - i0 - 1, npair = nx >> 1;
+        for (int j = j0 + blockIdx.x; j <= j1; j += gridDim.x) {
+            const bool ring_row = j == j0 || j == j1;
+            const double* row = a + at(i0 + 1, j, pitch);
+#pragma unroll 8
+            for (int k = threadIdx.x; k < npair; k += 256) {
+                const double2 v = *reinterpret_cast<const double2*>(row + 2 * k);
+                take(v.x, ring_row);
+                take(v.y, ring_row);
+            }
+            if (threadIdx.x == 0) {
+                take(row[-1], true);
+                take(row[nx], true);
+                if (nx & 1) take(row[nx - 1], ring_row);
+            }
+        }
+    }
+    for (int j = j0 + blockIdx.x; KIND != 3 && j <= j1; j += gridDim.x) {
         for (int i = i0 + threadIdx.x; i <= i1; i += 256) {
             const size_t o = at(i, j, pitch);
             const double v = a[o];
@@ -430,9 +490,13 @@ __global__ __launch_bounds__(256) void k_reduce(const double* __restrict__ a,
             }
         }
     }
-    if (KIND == 0) {
+    if (KIND == 0 || KIND == 3) {
         r0 = wave_min(r0);
         r1 = wave_max(r1);
+        if (KIND == 3) {
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) fl |= __shfl_xor(fl, m, 64);
+        }
     } else if (KIND == 1) {
         r0 = wave_sum(r0);
     } else {
@@ -442,12 +506,13 @@ __global__ __launch_bounds__(256) void k_reduce(const double* __restrict__ a,
     if (lane == 0) {
         sh[0][wave] = r0;
         sh[1][wave] = r1;
+        shf[wave] = fl;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         double x0 = sh[0][0], x1 = sh[1][0];
         for (int w = 1; w < 4; ++w) {
-            if (KIND == 0) {
+            if (KIND == 0 || KIND == 3) {
                 x0 = fmin(x0, sh[0][w]);
                 x1 = fmax(x1, sh[1][w]);
             } else if (KIND == 1) {
@@ -458,7 +523,41 @@ __global__ __launch_bounds__(256) void k_reduce(const double* __restrict__ a,
         }
         const size_t k = static_cast<size_t>(blockIdx.y) * gridDim.x + blockIdx.x;
         partial[k] = x0;
-        if (KIND == 0) partial[static_cast<size_t>(gridDim.y) * gridDim.x + k] = x1;
+        if (KIND == 0 || KIND == 3) partial[static_cast<size_t>(gridDim.y) * gridDim.x + k] = x1;
+        if (KIND == 3) partial[2 * static_cast<size_t>(gridDim.x) + k] = static_cast<double>(shf[0] | shf[1] | shf[2] | shf[3]);
+    }
+    if (KIND == 3) {
+        // the last block to arrive folds: its wave 0 reads every block's three partials (agent-scope loads, past this
+        // XCD's caches; the writers' fences came before their tickets) and one lane stores the verdict
+        __shared__ bool is_last;
+        if (threadIdx.x == 0) {
+            __threadfence();
+            is_last = atomicAdd(lease.word + 1, 1u) == gridDim.x - 1;
+        }
+        __syncthreads();
+        if (is_last && wave == 0) {
+            __threadfence();
+            const int G = gridDim.x;
+            auto ld = [&](int idx) {
+                return __longlong_as_double(static_cast<long long>(__hip_atomic_load(
+                    reinterpret_cast<const unsigned long long*>(partial + idx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
+            };
+            double lo = INFINITY, hi = 0.0;
+            unsigned f = 0;
+            for (int k = lane; k < G; k += 64) {
+                lo = fmin(lo, ld(k));
+                hi = fmax(hi, ld(G + k));
+                f |= static_cast<unsigned>(ld(2 * G + k));
+            }
+            lo = wave_min(lo);
+            hi = wave_max(hi);
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) f |= __shfl_xor(f, m, 64);
+            if (lane == 0) {
+                lease.word[0] = lease_verdict(lo, hi, f, lease);
+                lease.word[1] = 0u;  // the ticket counter, for the next launch
+            }
+        }
     }
 }
 
@@ -530,7 +629,7 @@ static hipError_t sweep_div(const double* in, double* out, int nx, int ny, int p
 // overlapped-strip multi-step sweep, T = 2..7 (kind[] / part: see internal.hpp)
 hipError_t launch_sweepO(const double* in, double* out, int pitch, const Phys& p, const SweepCfg& cfg,
                          const int kind[4], double value, const SweepPlan& plan, hipStream_t st,
-                         double* const fin_lines[4], const FrameSync* sync) {
+                         double* const fin_lines[4], const FrameSync* sync, const unsigned* lease) {
     Bc2 bc;
     for (int s = 0; s < 4; ++s) bc.kind[s] = kind[s];
     bc.value = value;
@@ -538,12 +637,12 @@ hipError_t launch_sweepO(const double* in, double* out, int pitch, const Phys& p
     for (int s = 0; s < 4; ++s) fin.line[s] = fin_lines ? fin_lines[s] : nullptr;
     const FrameSync fs = sync ? *sync : FrameSync{};
     switch (plan.T) {
-        case 2: return sweepO_T<2>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
-        case 3: return sweepO_T<3>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
-        case 4: return sweepO_T<4>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
-        case 5: return sweepO_T<5>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
-        case 6: return sweepO_T<6>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
-        default: return sweepO_T<7>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
+        case 2: return sweepO_T<2>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
+        case 3: return sweepO_T<3>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
+        case 4: return sweepO_T<4>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
+        case 5: return sweepO_T<5>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
+        case 6: return sweepO_T<6>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
+        default: return sweepO_T<7>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
     }
 }
 
@@ -657,18 +756,27 @@ hipError_t launch_gaussian(double* f, int nx, int ny, int pitch, int x_off, int 
 
 hipError_t launch_minmax(const double* f, int nx, int ny, int pitch, double* scratch, hipStream_t st, const Members& mb) {
     hipLaunchKernelGGL(k_reduce<0>, dim3(reduce_blocks(ny + 2, mb.cap), mb.count), dim3(256), 0, st, f, nullptr, 0,
-                       nx + 1, 0, ny + 1, pitch, mb.slab, scratch);
+                       nx + 1, 0, ny + 1, pitch, mb.slab, scratch, LeaseOut{});
     return hipGetLastError();
 }
 hipError_t launch_sum(const double* f, int nx, int ny, int pitch, double* scratch, hipStream_t st, const Members& mb) {
     hipLaunchKernelGGL(k_reduce<1>, dim3(reduce_blocks(ny, mb.cap), mb.count), dim3(256), 0, st, f, nullptr, 1, nx, 1,
-                       ny, pitch, mb.slab, scratch);
+                       ny, pitch, mb.slab, scratch, LeaseOut{});
     return hipGetLastError();
 }
 hipError_t launch_linf(const double* a, const double* b, int nx, int ny, int pitch, double* scratch,
                        hipStream_t st) {
     hipLaunchKernelGGL(k_reduce<2>, dim3(reduce_blocks(ny, REDUCE_BLOCKS)), dim3(256), 0, st, a, b, 1, nx, 1, ny, pitch,
-                       0L, scratch);
+                       0L, scratch, LeaseOut{});
+    return hipGetLastError();
+}
+
+hipError_t launch_lease(const double* f, int nx, int ny, int pitch, double* scratch, double M_req, double m_req,
+                        unsigned* lease, hipStream_t st) {
+    LeaseOut q;
+    q.M_req = M_req, q.m_req = m_req, q.word = lease;
+    hipLaunchKernelGGL(k_reduce<3>, dim3(reduce_blocks(ny + 2, LEASE_BLOCKS)), dim3(256), 0, st, f, nullptr, 0, nx + 1, 0,
+                       ny + 1, pitch, 0L, scratch, q);
     return hipGetLastError();
 }
 

@@ -33,13 +33,68 @@ static int fill_from_fin_lines(csim_stepper* s, hipStream_t st) {
     return CSIM_OK;
 }
 
+// ---- screen lease -------------------------------------------------------------------------------------------------
+// Which launches may be handed the verdict word at all: a single-rank stepper that moves no halos, parameters whose
+// interior body is a screened one with both velocity components non-zero (the flavours that carry M_LEASED /
+// M_LEASED_P2, sweep_core.hpp), and a depth at which those bodies are compiled.
+static bool lease_params_ok(const csim_stepper* s, const Phys& p) {
+    return s->lease_dev && s->screen_lease && !s->multi && !s->external && p.div_mode <= 1 && p.fast_thr > 0.0 &&
+           p.vx != 0.0 && p.vy != 0.0;
+}
+static bool lease_depth_ok(int T) { return specialise_edges(0, T); }
+
+// The word for a launch of depth T on the CURRENT state that advances nothing (tune_rows, keep_warm) — the same
+// pointer a pass would get now, or nullptr; never a reduction.
+static const unsigned* lease_now(const csim_stepper* s, const Phys& p, int T) {
+    if (!lease_params_ok(s, p) || !lease_depth_ok(T) || !s->lease_held) return nullptr;
+    if (std::memcmp(&s->lease_p, &p, sizeof(Phys)) != 0 || s->lease_R != s->lease_steps) return nullptr;
+    return s->lease_age + T <= s->lease_R ? s->lease_dev : nullptr;
+}
+
+// The word for the pass of depth T about to be launched on `st` from the current state, with the bookkeeping that keeps
+// it true.  Called after the pass's ghost fill, so a reduction enqueued here reads the ring the sweep will read.
+//   * WHERE THE WORD'S VALIDITY IS GUARANTEED: a verdict is computed from the state n0 steps into the run of the field
+//     and promises (lease_bounds) that every value of every state n0 .. n0 + R passes the screens with MAX_FUSE levels
+//     to spare.  A pass of depth T starting from state n loads state n only — the levels inside it are what the
+//     thresholds' own MAX_FUSE margin covers — and it is handed the word only while (n - n0) + T <= R; the pass that
+//     would step past R gets a renewal in front of it.  Everything that changes the field outside a pass (upload,
+//     init_*) or what it is judged against (the Phys of the run, which carries "fused_2c", "pow2_v" and "contract";
+//     "lease_steps"; "screen_lease") clears the word in stream order before the next launch (lease_drop).  Boundary
+//     kinds and the boundary value are fixed at creation.
+//   * a refused verdict is a held lease like any other (the host never reads the word): the kernel finds the bits
+//     missing and takes its screened chain, and the next attempt is the renewal a whole R later.
+//   * cost cap: a reduction is spent only when the field has been advanced lease_acquire_after steps since it was set
+//     or since the last reduction, whichever is later — at most one reduction per min(R, lease_acquire_after) steps in
+//     any pattern of calls, uploads and parameter changes.
+static int lease_for_pass(csim_stepper* s, const Phys& p, int T, hipStream_t st, const unsigned** word) {
+    *word = nullptr;
+    if (!lease_params_ok(s, p)) return lease_drop(s, st, false);
+    if (s->lease_held && (std::memcmp(&s->lease_p, &p, sizeof(Phys)) != 0 || s->lease_R != s->lease_steps))
+        CSIM_TRY(lease_drop(s, st, false));
+    if (!lease_depth_ok(T)) return CSIM_OK;  // a shallow remainder pass: no leased body, and nothing to invalidate
+    const bool renew = s->lease_held && s->lease_age + T > s->lease_R;
+    const bool acquire = !s->lease_held && s->lease_idle >= s->lease_acquire_after;
+    if (renew || acquire) {
+        const LeaseBounds b = lease_bounds(p, s->lease_steps);
+        CSIM_HIP(launch_lease(s->cur, s->nx, s->ny, s->pitch, s->scratch, b.M_req, b.m_req, s->lease_dev, st));
+        s->lease_held = true;
+        s->lease_p = p;
+        s->lease_R = s->lease_steps;
+        s->lease_age = 0;
+        s->lease_idle = 0;
+        ++s->lease_reductions;
+    }
+    if (s->lease_held) *word = s->lease_dev;
+    return CSIM_OK;
+}
+
 // T = 2..7 reference steps in one HBM pass.  Several ranks: faces of depth T (8 directions) are
 // staged in recv2[]; when the next pass is fused too (with `next_T` steps), the frame tiles are
 // computed first and the comm stream packs and exchanges their depth-next_T faces while the bulk
 // of the sweep is still running.
 static hipError_t launch_fused(csim_stepper* s, const Phys& p, const int kind[4], int T, int part,
                                hipStream_t st, bool final_pass = false, int lds_bytes = 0,
-                               const FrameSync* sync = nullptr) {
+                               const FrameSync* sync = nullptr, const unsigned* lease = nullptr) {
     SweepCfg cfg = s->cfg;
     if (lds_bytes > 0) cfg.lds_bytes = lds_bytes;
     if (T >= 2 && T <= MAX_FUSE && s->tuned_T[T] > 0) cfg.tuned_rows = s->tuned_T[T];  // this depth had its own trial
@@ -51,7 +106,7 @@ static hipError_t launch_fused(csim_stepper* s, const Phys& p, const int kind[4]
         kept.valid = true;
     }
     if (part != 1) s->last_rows = kept.plan.rows;  // the frame's heights are fixed
-    return launch_sweepO(s->cur, s->nxt, s->pitch, p, cfg, kind, s->bc_value, kept.plan, st, final_pass ? s->fin : nullptr, sync);
+    return launch_sweepO(s->cur, s->nxt, s->pitch, p, cfg, kind, s->bc_value, kept.plan, st, final_pass ? s->fin : nullptr, sync, lease);
 }
 
 // final_pass (overlapped-strip kernels only): the last pass of a run.  The kernel also emits the
@@ -301,7 +356,9 @@ int pass_fused(csim_stepper* s, const Phys& p, int T, int next_T, bool final_pas
         if (!merged_launch) CSIM_HIP(launch_fused(s, p, kind, T, 2, s->s_comp));
         s->faces_depth = next_T;
     } else {
-        CSIM_HIP(launch_fused(s, p, kind, T, 0, s->s_comp, final_pass));
+        const unsigned* lease = nullptr;
+        CSIM_TRY(lease_for_pass(s, p, T, s->s_comp, &lease));
+        CSIM_HIP(launch_fused(s, p, kind, T, 0, s->s_comp, final_pass, 0, nullptr, lease));
         s->faces_depth = 0;
     }
     CSIM_TRY(prof_end(s));
@@ -341,7 +398,8 @@ int tune_rows(csim_stepper* s, const Phys& p, int T, bool preferred_depth) {
         cfg.tuned_rows = ry;
         CSIM_HIP(hipEventRecord(e0, s->s_comp));
         CSIM_HIP(launch_sweepO(s->cur, s->nxt, s->pitch, p, cfg, kind, s->bc_value,
-                               plan_sweepO(s->nx, s->ny, T, p, cfg, kind, part), s->s_comp));
+                               plan_sweepO(s->nx, s->ny, T, p, cfg, kind, part), s->s_comp, nullptr, nullptr,
+                               lease_now(s, p, T)));
         CSIM_HIP(hipEventRecord(e1, s->s_comp));
         CSIM_HIP(hipEventSynchronize(e1));
         CSIM_HIP(hipEventElapsedTime(ms, e0, e1));
@@ -390,9 +448,15 @@ int tune_rows(csim_stepper* s, const Phys& p, int T, bool preferred_depth) {
 // saves (16384^2 +8.5 %, 8192^2 +6.4 %); a launch of one round or less runs as long as its slowest wavefront, and there
 // the body was measured SLOWER (4096 x 8192 -4 %, 4096^2 -17 %; profiles/pow2_velocity_ab.jsonl) — why is not established
 // (the listing differs in the screen: three compares per value instead of one, each handed to the scalar unit).
+// With the screen lease the same comparison on single-round tiles comes out the other way (profiles/screen_lease_ab.jsonl,
+// five interleaved rounds): the leased 12-operation body beat the 14-operation one, leased or screened, in every round at
+// 4096^2 (+5...+11 %), 4096 x 8192 (+3...+8 %) and 8192^2 (+3...+4 %), so steppers that lease take it from 4096^2 on.
+// Smaller tiles were not measured and keep the 14 operations.
 constexpr long P2_MIN_CELLS = 60000000L;
+constexpr long P2_MIN_CELLS_LEASED = 16000000L;
 static bool pow2_v_wanted(const csim_stepper* s) {
-    return s->pow2_v == 1 || (s->pow2_v == 2 && static_cast<long>(s->nx) * s->ny >= P2_MIN_CELLS);
+    const bool leases = s->lease_dev && s->screen_lease && !s->multi && !s->external;
+    return s->pow2_v == 1 || (s->pow2_v == 2 && static_cast<long>(s->nx) * s->ny >= (leases ? P2_MIN_CELLS_LEASED : P2_MIN_CELLS));
 }
 
 static void note_flavour(csim_stepper* s, const Phys& p) {
@@ -451,7 +515,8 @@ int csim_stepper_keep_warm(csim_stepper* s, double D, double dt, double vx, doub
     for (int n = 0; n < 100000; ++n) {
         const double before = elapsed();
         if (before + 1.25 * last >= seconds) break;  // the next launch would run past the deadline
-        CSIM_HIP(launch_sweepO(s->cur, s->nxt, s->pitch, p, s->cfg, kind, s->bc_value, plan, s->s_comp));
+        CSIM_HIP(launch_sweepO(s->cur, s->nxt, s->pitch, p, s->cfg, kind, s->bc_value, plan, s->s_comp, nullptr, nullptr,
+                               lease_now(s, p, depth)));
         CSIM_HIP(hipStreamSynchronize(s->s_comp));
         last = elapsed() - before;
     }
@@ -513,6 +578,7 @@ int csim_stepper_run(csim_stepper* s, double D, double dt, double vx, double vy,
         const bool last = k + 1 == plan.size();
         const int nt = last ? 0 : plan.at(k + 1);
         CSIM_TRY(t >= 2 ? pass_fused(s, p, t, nt >= 2 ? nt : 0, last) : pass_single(s, p, g));
+        s->lease_age += t, s->lease_idle += t;  // the screen lease counts steps, whatever kind of pass took them
     }
     return prof_close(s);
 }

@@ -21,6 +21,13 @@ int settle(csim_stepper* s) {
     return CSIM_OK;
 }
 
+int lease_drop(csim_stepper* s, hipStream_t st, bool field_set) {
+    if (s->lease_dev && (s->lease_held || field_set)) CSIM_HIP(hipMemsetAsync(s->lease_dev, 0, sizeof(unsigned), st));
+    s->lease_held = false;
+    if (field_set) s->lease_idle = 0;
+    return CSIM_OK;
+}
+
 // deep-face flavour of the external transport, for csim_stepper_run(.., depth) in external mode
 bool depth_ok(const csim_stepper* s, int depth) {
     return depth >= 2 && depth <= MAX_FUSE && depth <= s->nx && depth <= s->ny;
@@ -80,6 +87,7 @@ int wait_streams(csim_stepper* s) {
 // The field was replaced (upload, initialisation): both ping-pong buffers start with the same ghost ring (reference
 // main.cpp:104 copies u->tmp), and nothing staged or filled for the old field is valid any more.  Waits for the copy.
 static int field_replaced(csim_stepper* s) {
+    CSIM_TRY(lease_drop(s, s->s_comp, true));  // before the next pass: the new field has not been judged
     CSIM_HIP(hipMemcpyAsync(s->base(s->nxt), s->base(s->cur), s->bytes(), hipMemcpyDeviceToDevice, s->s_comp));
     CSIM_HIP(hipStreamSynchronize(s->s_comp));
     s->halo_fresh = false;
@@ -123,6 +131,7 @@ static int make_resources(csim_stepper* s) {
     CSIM_TRY(o.device(&s->buf[0], s->bytes(), true));
     CSIM_TRY(o.device(&s->buf[1], s->bytes(), true));
     CSIM_TRY(o.device(&s->scratch, sizeof(double) * 2 * REDUCE_BLOCKS));
+    if (!s->multi) CSIM_TRY(o.device(&s->lease_dev, 2 * sizeof(unsigned), true));  // verdict word and ticket, zeroed
     CSIM_TRY(o.event(&s->ev_tail));
     CSIM_TRY(o.event(&s->ev_relay_ready, hipEventDisableTiming | hipEventDisableSystemFence));
     CSIM_TRY(o.event(&s->ev_relay_bulk, hipEventDisableTiming | hipEventDisableSystemFence));
@@ -482,7 +491,18 @@ int csim_stepper_set_option(csim_stepper* s, const char* key, long value) {
     } else if (k == "pow2_v") {
         CSIM_REQUIRE(value >= 0 && value <= 2, "pow2_v must be 0 (off), 1 (on) or 2 (on where it pays: large tiles)");
         s->pow2_v = static_cast<int>(value);
-    } else if (k == "pow2_v_active") {
+    } else if (k == "screen_lease") {
+        CSIM_REQUIRE(value == 0 || value == 1, "screen_lease must be 0 or 1");
+        CSIM_SETTLE(s);
+        if (!value) CSIM_TRY(lease_drop(s, s->s_comp, false));
+        s->screen_lease = static_cast<int>(value);
+    } else if (k == "lease_steps") {
+        CSIM_REQUIRE(value >= 1 && value <= (1L << 24), "lease_steps must be 1..2^24");
+        s->lease_steps = value;  // a held lease of another length is dropped by the next pass (lease_for_pass)
+    } else if (k == "lease_acquire_after") {
+        CSIM_REQUIRE(value >= 0, "lease_acquire_after must be >= 0");
+        s->lease_acquire_after = value;
+    } else if (k == "pow2_v_active" || k == "lease_word" || k == "lease_reductions") {
         return fail(CSIM_ERR_ARG, k + " is read-only");
     } else if (k == "external_halo") {
         s->external = value != 0;
@@ -552,6 +572,18 @@ int csim_stepper_get_option(const csim_stepper* s, const char* key, long* value)
     else if (k == "pow2_v") *value = s->pow2_v;
     else if (k == "pow2_v_active") *value = s->pow2_v_active;
     else if (k == "diffusion_only_active") *value = s->diffusion_only_active;
+    else if (k == "screen_lease") *value = s->screen_lease;
+    else if (k == "lease_steps") *value = s->lease_steps;
+    else if (k == "lease_acquire_after") *value = s->lease_acquire_after;
+    else if (k == "lease_reductions") *value = s->lease_reductions;
+    else if (k == "lease_word") {  // for tests: waits for everything enqueued, then reads the device word (0: no lease machinery)
+        unsigned w = 0;
+        if (s->lease_dev) {
+            CSIM_HIP(hipStreamSynchronize(s->tail ? s->tail : s->s_comp));
+            CSIM_HIP(hipMemcpy(&w, s->lease_dev, sizeof(w), hipMemcpyDeviceToHost));
+        }
+        *value = w;
+    }
     else if (k == "frame_rows") *value = s->cfg.frame_rows;
     else if (k == "external_halo") *value = s->external;
     else if (k == "fuse") *value = s->fuse;

@@ -91,6 +91,20 @@ struct csim_stepper {
     int pow2_v = 2;           // ... and the five-operation advection term of power-of-two velocities under its screen (Phys::slow_thr):
                               // 0 off, 1 on, 2 on for tiles of at least P2_MIN_CELLS cells (passes.cpp)
     int pow2_v_active = 0;    // read-only: whether the last run's parameters enabled it
+    // Screen lease (single-rank steppers that are not on the external transport; lease_for_pass in passes.cpp): one
+    // reduction over the field judges what the interior bodies' screens ask of every loaded value and leaves the verdict
+    // in lease_dev[0]; while the host's bookkeeping says that verdict still holds, passes hand the kernel its address.
+    int screen_lease = 1;            // option: 0 off
+    long lease_steps = 1024;         // option: R, the steps a verdict is held for
+    long lease_acquire_after = 512;  // option: steps the field must have been advanced since it was set, or since the last
+                                     // reduction, before a reduction is spent on it (the 1 % cost cap)
+    unsigned* lease_dev = nullptr;   // [0] the verdict word, [1] the reduction's ticket counter
+    bool lease_held = false;         // a reduction under lease_p / lease_R is enqueued and nothing has invalidated it since
+    csim::Phys lease_p{};            // the parameters it judged against
+    long lease_R = 0;
+    long lease_age = 0;              // steps advanced since that reduction
+    long lease_idle = 0;             // steps advanced since the field was set or a reduction was enqueued
+    long lease_reductions = 0;       // read-only option: reductions enqueued so far
     int diffusion_only_active = 0;  // read-only: the last run had v == 0 and swept with the advection term left out of the screened body
     int direct_faces = 1;                 // merged launch: the frame wavefronts fill send2[] themselves (no pack kernel)
     bool bulk_first_run = false;          // the current csim_stepper_run uses pass_fused_bulk_first
@@ -165,6 +179,9 @@ bool valid_bc(const int bc[4]);
 // stepper.cpp
 int settle(csim_stepper* s);  // the field state back onto the compute stream (see csim_stepper::tail)
 int wait_streams(csim_stepper* s);  // host wait for s_comp, s_relay[], s_comm: polls the communicator, honours sync_timeout_ms
+// the screen lease ends: the verdict word is cleared in stream order on `st` (whatever is enqueued behind it sees 0).
+// field_set: the field itself was replaced, so the steps counted towards "lease_acquire_after" start again too
+int lease_drop(csim_stepper* s, hipStream_t st, bool field_set);
 bool depth_ok(const csim_stepper* s, int depth);
 int fused_depth(const csim_stepper* s);
 

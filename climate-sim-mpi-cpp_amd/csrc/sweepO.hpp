@@ -135,7 +135,33 @@ __global__ __launch_bounds__(256) void k_sweepO_dpp(const double* __restrict__ i
     } else {
         bool redo = true;
         if (DIV != 3 && a.p.fast_thr > 0.0) {
-            if constexpr (P2_BODY<DIV, T, SX, SY>::value) {
+            // The verdict word, once per wavefront and wave-uniform (a scalar load through the kernel argument): the
+            // stepper guarantees that it holds for every step of this pass (lease_for_pass, passes.cpp), so a leased
+            // body needs neither the screen nor a repeat.  Leased P2, else leased FAST, else the screened chain.
+            unsigned lease = 0;
+            if constexpr (LEASE_BODY<DIV, T, SX, SY>::value) {
+                if (a.lease != nullptr) lease = __builtin_amdgcn_readfirstlane(*a.lease);
+            }
+            bool leased = false;
+            if constexpr (LEASE_P2_BODY<DIV, T, SX, SY>::value) {
+                if (a.p.slow_thr > 0.0 && (lease & LEASE_P2) != 0) {
+                    keep_branch();
+                    CSIM_MARCH(M_LEASED_P2);
+                    leased = true;
+                }
+            }
+            if constexpr (LEASE_BODY<DIV, T, SX, SY>::value) {
+                // (not where the host enabled the 12-operation form and only its lease was refused: the screened
+                // M_FAST_P2 is still fewer instructions than the unscreened 14-operation body)
+                if (!leased && (lease & LEASE_FAST) != 0 && !(a.p.slow_thr > 0.0)) {
+                    keep_branch();
+                    CSIM_MARCH(M_LEASED);
+                    leased = true;
+                }
+            }
+            if (leased) {
+                redo = false;
+            } else if constexpr (P2_BODY<DIV, T, SX, SY>::value) {
                 if (a.p.slow_thr > 0.0) {
                     keep_branch();
                     redo = CSIM_MARCH(M_FAST_P2);
@@ -228,7 +254,7 @@ __global__ __launch_bounds__(256) void k_sweepO_dpp(const double* __restrict__ i
 // three steps: take the plan (sweep_plan.cpp: the launcher's caller built it), fill SweepArgs, dispatch on the sign class
 template <int DIV, int T>
 hipError_t sweepO_div(const double* in, double* out, int pitch, const Phys& p, const SweepCfg& cfg, const Bc2& bc,
-                      const FinLines& fin, const SweepPlan& plan, hipStream_t st, FrameSync fs) {
+                      const FinLines& fin, const SweepPlan& plan, hipStream_t st, FrameSync fs, const unsigned* lease) {
     if (plan.empty) return hipSuccess;
     if (plan.signals)
         fs.nframe = plan.nframe;
@@ -237,7 +263,7 @@ hipError_t sweepO_div(const double* in, double* out, int pitch, const Phys& p, c
     const dim3 grid(plan.nblocks), block(256);
     SweepArgs ka;
     ka.nx = plan.nx, ka.ny = plan.ny, ka.pitch = pitch, ka.nstrips = plan.nstrips, ka.swz = cfg.xcd_swizzle;
-    ka.tl = plan.tl, ka.p = p, ka.bc = bc, ka.fin = fin, ka.fs = fs;
+    ka.tl = plan.tl, ka.p = p, ka.bc = bc, ka.lease = lease, ka.fin = fin, ka.fs = fs;
 #define CSIM_LAUNCH_O(SXV, SYV) \
     hipLaunchKernelGGL((k_sweepO_dpp<DIV, T, SXV, SYV>), grid, block, cfg.lds_bytes, st, in, out, ka)
 #ifdef CSIM_ISA_PROBE
@@ -266,18 +292,18 @@ hipError_t sweepO_div(const double* in, double* out, int pitch, const Phys& p, c
 
 template <int T>
 hipError_t sweepO_T(const double* in, double* out, int pitch, const Phys& p, const SweepCfg& cfg, const Bc2& bc,
-                    const FinLines& fin, const SweepPlan& plan, hipStream_t st, const FrameSync& fs) {
+                    const FinLines& fin, const SweepPlan& plan, hipStream_t st, const FrameSync& fs, const unsigned* lease) {
 #ifdef CSIM_ISA_PROBE  // tools: only the instantiation bench.py runs (dx = dy = 1, vx, vy >= 0), for a readable listing
     // the plan took its edge rule from p.div_mode (plan_sweepO): a probe build run with another mode would pair a plan
     // without bands with a kernel that specialises its edges
     if (p.div_mode != 0) return hipErrorInvalidValue;
-    return sweepO_div<0, T>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
+    return sweepO_div<0, T>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
 #else
     switch (p.div_mode) {
-        case 0: return sweepO_div<0, T>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
-        case 1: return sweepO_div<1, T>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
-        case 3: return sweepO_div<3, T>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
-        default: return sweepO_div<2, T>(in, out, pitch, p, cfg, bc, fin, plan, st, fs);
+        case 0: return sweepO_div<0, T>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
+        case 1: return sweepO_div<1, T>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
+        case 3: return sweepO_div<3, T>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
+        default: return sweepO_div<2, T>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
     }
 #endif
 }

@@ -9,6 +9,6 @@ namespace csim {
 
 template hipError_t sweepO_T<CSIM_INST_T>(const double* in, double* out, int pitch, const Phys& p, const SweepCfg& cfg,
                                           const Bc2& bc, const FinLines& fin, const SweepPlan& plan, hipStream_t st,
-                                          const FrameSync& fs);
+                                          const FrameSync& fs, const unsigned* lease);
 
 }  // namespace csim

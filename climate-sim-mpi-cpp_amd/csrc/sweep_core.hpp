@@ -259,6 +259,7 @@ struct SweepArgs {
     Tiling tl;
     Phys p;
     Bc2 bc;
+    const unsigned* lease;  // the stepper's verdict word (M_LEASED below), nullptr where no lease machinery applies
     FinLines fin;
     FrameSync fs;
 };
@@ -322,6 +323,10 @@ __device__ __forceinline__ void pin2(double2& v) { asm volatile("" : "+v"(v.x), 
 //   M_FAST / M_PLAIN  interior body with / without the fused E - 2c (see FAST above)
 //   M_FAST_P2         M_FAST with the five-operation advection term of power-of-two velocities (cell, P2) and its
 //                     wider screen; compiled where P2_BODY says so, tried first where the host enabled it (p.slow_thr > 0)
+//   M_LEASED /        M_FAST / M_FAST_P2 with the screen compiled out: what the screen asks of every loaded value the
+//   M_LEASED_P2       stepper has checked for the whole field, once, and holds as a lease over the steps for which the
+//                     answer provably persists (the verdict word, SweepArgs::lease; bounds: lease_bounds in api.cpp,
+//                     DESIGN.md §4).  They never ask for a repeat.  Compiled where LEASE_BODY / LEASE_P2_BODY say so
 //   M_GENERIC         edge body with every patch behind run-time tests: tiles that can produce ghost ROWS of a
 //                     physical edge (the launcher keeps them thin: bottom / top bands) and strips that hold BOTH ghost
 //                     columns; also every edge tile of the instantiations that are not specialised (SPECIALISE_EDGES)
@@ -329,7 +334,8 @@ __device__ __forceinline__ void pin2(double2& v) { asm volatile("" : "+v"(v.x), 
 //                     straight-line like the interior body: 0 none (a final pass's frame tile that only emits
 //                     FinLines), 1 / 2 left ghost kept / Neumann, 3 / 4 right ghost kept in .x / .y, 5 / 6 right
 //                     ghost Neumann in .x / .y
-constexpr int M_FAST_P2 = -4, M_FAST = -3, M_PLAIN = -2, M_GENERIC = -1;
+constexpr int M_LEASED_P2 = -6, M_LEASED = -5, M_FAST_P2 = -4, M_FAST = -3, M_PLAIN = -2, M_GENERIC = -1;
+constexpr unsigned LEASE_FAST = 1u, LEASE_P2 = 2u;  // bits of the verdict word: what M_FAST's / M_FAST_P2's screen asks holds field-wide
 
 template <int DIV, int T, int MODE, int SX, int SY>
 __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, double* __restrict__ out,
@@ -338,7 +344,8 @@ __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, doub
                                              LateArgs late, bool fin_any, bool fin_l, bool fin_r, bool wt) {
     constexpr int TP = OverlapGeom<T>::TP;
     constexpr int STRIDE = OverlapGeom<T>::STRIDE;
-    constexpr bool EDGE = MODE >= M_GENERIC, P2 = MODE == M_FAST_P2, FAST = MODE == M_FAST || P2, GENERIC = MODE == M_GENERIC;
+    constexpr bool EDGE = MODE >= M_GENERIC, P2 = MODE == M_FAST_P2 || MODE == M_LEASED_P2, GENERIC = MODE == M_GENERIC;
+    constexpr bool FAST = MODE == M_FAST || MODE == M_LEASED || P2, SCREEN = MODE == M_FAST || MODE == M_FAST_P2;
     constexpr int CASE = MODE;
     // this lane's two columns, 0-based interior index (-1 = left ghost, nx = right ghost)
     const int gx = g0 + 2 * lane, gy = gx + 1;
@@ -371,7 +378,7 @@ __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, doub
     double2 L[T][3];
 #pragma unroll
     for (int q = 0; q < 6; ++q) L0[q] = load(min(r_first - 1 + q, last_row));
-    bool big = false;  // FAST: some loaded value is not below the threshold
+    bool big = false;  // SCREEN: some loaded value is not below the threshold
     auto screen = [&](const double2& v) {
         big |= !(__builtin_fabs(v.x) < (P2 ? p.p2_hi : p.fast_thr));
         big |= !(__builtin_fabs(v.y) < (P2 ? p.p2_hi : p.fast_thr));
@@ -384,7 +391,7 @@ __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, doub
             big |= __builtin_amdgcn_class(v.y, 0x20);
         }
     };
-    if (FAST) {  // every later row is screened when it is the `n` of level 1
+    if (SCREEN) {  // every later row is screened when it is the `n` of level 1
         screen(L0[0]);
         screen(L0[1]);
     }
@@ -424,7 +431,7 @@ __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, doub
                         const double Ey = shift_from_next(c.x);
                         o.x = cell<DIV, SX, SY, FAST, P2>(c.x, Wx, c.y, s.x, n.x, p);
                         o.y = cell<DIV, SX, SY, FAST, P2>(c.y, c.x, Ey, s.y, n.y, p);
-                        if (FAST && l == 1) screen(n);
+                        if (SCREEN && l == 1) screen(n);
                     }
                     if (EDGE && !GENERIC && l < T) {  // the strip's one ghost column, unconditionally
                         if (CASE == 1) o.y = ghost_ly ? c.y : o.y;
@@ -535,7 +542,7 @@ __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, doub
         if (niter > 6) group(std::integral_constant<int, 1>{}, 6);
         for (int k0 = 12; k0 < niter; k0 += 6) group(G2{}, k0);
     }
-    return FAST && __builtin_amdgcn_ballot_w64(big) != 0;
+    return SCREEN && __builtin_amdgcn_ballot_w64(big) != 0;
 }
 
 // Which instantiations get the straight-line edge flavours: the rule is specialise_edges (sweep_plan.hpp), which the
@@ -550,6 +557,18 @@ struct SPECIALISE_EDGES {
 template <int DIV, int T, int SX, int SY>
 struct P2_BODY {
     static constexpr bool value = SPECIALISE_EDGES<DIV, T>::value && (SX == 0 || SX == 1) && (SY == 0 || SY == 1);
+};
+
+// Which carry the unscreened bodies: M_LEASED wherever M_FAST is the whole screen (both velocity components non-zero;
+// the zero-velocity flavours also screen for a loaded -0 and keep their screened body), M_LEASED_P2 wherever M_FAST_P2
+// is, except SX = SY = 0, whose screen has the -0 test too.
+template <int DIV, int T, int SX, int SY>
+struct LEASE_BODY {
+    static constexpr bool value = P2_BODY<DIV, T, SX, SY>::value;
+};
+template <int DIV, int T, int SX, int SY>
+struct LEASE_P2_BODY {
+    static constexpr bool value = P2_BODY<DIV, T, SX, SY>::value && !(SX == 0 && SY == 0);
 };
 
 // -------------------------------------------------------------------------------------------

@@ -77,6 +77,13 @@ double csim_safe_dt(double dx, double dy, double vx, double vy, double D);
  * out[0] = L, the smallest non-zero magnitude a tile may load and still take the 12-operation body (0 = the form is off
  * for these parameters), out[1] = its upper bound, out[2] = q, out[3] = K */
 int csim_pow2_velocity_screen(double dx, double dy, double D, double dt, double vx, double vy, double out[4]);
+/* host arithmetic only: the bounds of the stepper option "screen_lease" for these parameters and a lease of R steps —
+ * out[0] = M_req: max|u| <= M_req now keeps every value below the screen's upper bound for R + 7 steps (0 = no lease);
+ * out[1] = m_req: with all five stencil coefficients positive and a field of one sign, min|u| >= m_req now keeps
+ * every value at or above twice the L of csim_pow2_velocity_screen for R + 7 steps (0 = the 12-operation body is not
+ * leased for these parameters); out[2] = eta, the relative loss per step the lower bound allows for rounding;
+ * out[3] = a0, the centre coefficient (min|u| shrinks by at most a0 (1 - eta) per step).  DESIGN.md section 4 */
+int csim_screen_lease_bounds(double dx, double dy, double D, double dt, double vx, double vy, long R, double out[4]);
 /* reference src/decomp.cpp:5-34  Decomp2D::init(comm, nx_global, ny_global), MPI-free:
  * MPI_Dims_create(size,2) + MPI_Cart_create(periods 0,0, reorder 0) are re-derived. */
 int csim_decomp_init(int size, int rank, int nx_global, int ny_global, csim_decomp* out);
@@ -251,7 +258,23 @@ int csim_stepper_sum(csim_stepper* s, double* out);
  *                    bench physics, csim_pow2_velocity_screen; derivation: DESIGN.md section 4); other tiles are recomputed
  *                    with the reference's sequence.  Needs "fused_2c"; passes of 2 or 3 steps, edge tiles, IEEE division,
  *                    "contract" and the ensemble keep their bodies.  "pow2_v_active" (read-only): whether the last run's
- *                    parameters and tile size enabled it.  0 restores the 14-operation body everywhere
+ *                    parameters and tile size enabled it.  0 restores the 14-operation body everywhere.  Steppers that
+ *                    lease their screen ("screen_lease") take the form from 1.6e7 cells on: without the screen it won
+ *                    every round at 4096^2, 4096 x 8192 and 8192^2
+ *   "screen_lease"   0/1 (default 1), bit-identical either way; single-rank steppers that are not on the external halo
+ *                    transport.  What the interior bodies' screens ask of every value of every tile in every pass —
+ *                    below the upper bound; for "pow2_v" also non-zero and at least L — is a property of the whole
+ *                    field that provably persists: max|u| grows by at most g per step, and with all five stencil
+ *                    coefficients positive and a field of one sign min|u| shrinks by at most a0 (1 - eta) per step
+ *                    (csim_screen_lease_bounds).  One reduction over the field and its ghost ring,
+ *                    enqueued in front of a pass, leaves a verdict in a device word (bit 0: upper bound, bit 1: all of
+ *                    it), and for "lease_steps" steps (default 1024) interior tiles of passes of 4..7 steps run the same
+ *                    march without the screen.  The host never reads the word; a refused verdict just leaves the
+ *                    screened bodies in charge until the renewal.  Upload, init_*, other run parameters and the
+ *                    options that change the arithmetic end a lease.  "lease_acquire_after" (default 512): steps a field
+ *                    must have been advanced, since it was set or last judged, before a reduction is spent on it —
+ *                    short upload / run / download cycles never pay one.  Read-only: "lease_word" (synchronises; for
+ *                    tests), "lease_reductions" (reductions enqueued so far)
  *   "fuse"           time steps per HBM pass: -1 auto (the cheapest split of a run into passes of 2..7 steps, e.g.
  *                    1000 = 166 x 6 + 4, 20 = 7 + 7 + 6), 0/1 off, 2..7 balanced passes of at most that depth
  *   "variant"        single-step kernel family: 0 auto, 1 dpp, 2 lds, 3 naive
