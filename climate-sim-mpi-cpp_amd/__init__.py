@@ -615,6 +615,8 @@ class Stepper:
         return o.value
 
     def set_option(self, key: str, value: int):
+        """the options of include/csim.h, e.g. "fuse", "pow2_v", "screen_lease", "wide_strips" (0 off, 1 wherever a wide
+        strip fits, 2 = default: on tiles where it was measured to pay)"""
         _ck(lib().csim_stepper_set_option(self._h, key.encode(), int(value)))
 
     def tune(self, D, dt, vx, vy):

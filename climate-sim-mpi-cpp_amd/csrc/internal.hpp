@@ -97,11 +97,12 @@ struct SweepCfg {
     int tail_split = 1;        // fused launches of two or more rounds of wavefronts end with a region of half-height
                                // chunks (see Tiling); 0 off, 2 experiment (half + quarter height)
     int frame_rows = 0;        // multi-rank pass: chunk height of the frame's side strips (0 = as thin as the bands)
+    int wide = 0;              // whole-field launch: wide strips wherever one fits (set per launch, passes.cpp: wide_wanted)
 };
 // what the tile plan (sweep_plan.hpp) of one launch_sweepO with these settings is made from, and the plan
 inline SweepPlanIn plan_in_sweepO(int nx, int ny, int T, const Phys& p, const SweepCfg& cfg, const int kind[4], int part) {
     return SweepPlanIn{nx, ny, T, p.div_mode, {kind[0], kind[1], kind[2], kind[3]}, part,
-                       cfg.rows_per_chunk, cfg.tuned_rows, cfg.tail_split, cfg.frame_rows};
+                       cfg.rows_per_chunk, cfg.tuned_rows, cfg.tail_split, cfg.frame_rows, cfg.wide};
 }
 inline SweepPlan plan_sweepO(int nx, int ny, int T, const Phys& p, const SweepCfg& cfg, const int kind[4], int part) {
     return sweep_plan(plan_in_sweepO(nx, ny, T, p, cfg, kind, part));

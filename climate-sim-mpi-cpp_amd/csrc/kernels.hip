@@ -18,6 +18,10 @@ namespace csim {
 template <int T>
 hipError_t sweepO_T(const double* in, double* out, int pitch, const Phys& p, const SweepCfg& cfg, const Bc2& bc,
                     const FinLines& fin, const SweepPlan& plan, hipStream_t st, const FrameSync& fs, const unsigned* lease);
+// ... and two more for the plans with wide strips (sweepO_wide_T<6>, <7>: sweepO_inst.hip with -DCSIM_INST_WIDE)
+template <int T>
+hipError_t sweepO_wide_T(const double* in, double* out, int pitch, const Phys& p, const SweepCfg& cfg, const Bc2& bc,
+                         const FinLines& fin, const SweepPlan& plan, hipStream_t st, const FrameSync& fs, const unsigned* lease);
 
 // -------------------------------------------------------------------------------------------
 // VAR_DPP — the default fused sweep.
@@ -636,6 +640,11 @@ hipError_t launch_sweepO(const double* in, double* out, int pitch, const Phys& p
     FinLines fin;
     for (int s = 0; s < 4; ++s) fin.line[s] = fin_lines ? fin_lines[s] : nullptr;
     const FrameSync fs = sync ? *sync : FrameSync{};
+    if (plan.wide) {  // a missing instantiation is an error, not another kernel
+        if (plan.T == 6) return sweepO_wide_T<6>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
+        if (plan.T == 7) return sweepO_wide_T<7>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
+        return hipErrorInvalidValue;
+    }
     switch (plan.T) {
         case 2: return sweepO_T<2>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
         case 3: return sweepO_T<3>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);

@@ -88,6 +88,31 @@ static int lease_for_pass(csim_stepper* s, const Phys& p, int T, hipStream_t st,
     return CSIM_OK;
 }
 
+// ---- wide strips --------------------------------------------------------------------------------------------------
+// Option "wide_strips": whether a whole-field launch of depth T asks its plan for wide strips (sweep_plan.cpp decides
+// whether one fits).  Only where the wide kernel exists and its unscreened bodies are what the launch would run anyway:
+// a stepper that leases its screen (lease_params_ok), the 12-operation form enabled by the host, velocities not both
+// negative (LEASE_P2_BODY), depths 6 and 7, dx and dy without IEEE division.  `lease`: the word the launch is handed.
+// The host never reads it: a refused verdict costs nothing but speed, the wide tiles then run the reference's own
+// sequence.  2 (default): from WIDE_MIN_CELLS cells on, and only for launches that are handed a word at all — the
+// passes before a field's first reduction have no unscreened body to run and keep the narrow kernel's screened one.
+constexpr long WIDE_MIN_CELLS = 60000000L;
+static bool wide_wanted(const csim_stepper* s, const Phys& p, int T, const unsigned* lease) {
+    if (s->wide_strips == 0 || !lease_params_ok(s, p) || !(p.slow_thr > 0.0) || (p.vx < 0.0 && p.vy < 0.0)) return false;
+    if (!wide_strips_compiled(p.div_mode, T)) return false;
+    return s->wide_strips == 1 || (lease != nullptr && static_cast<long>(s->nx) * s->ny >= WIDE_MIN_CELLS);
+}
+
+// The settings a launch of depth T over `part` of the tile goes out with — a pass, and the trial and the warm-up
+// launches that stand for one: wide strips where wanted, and the chunk height its own trial found for that kernel
+static SweepCfg launch_cfg(const csim_stepper* s, const Phys& p, int T, int part, const unsigned* lease) {
+    SweepCfg cfg = s->cfg;
+    cfg.wide = part == 0 && wide_wanted(s, p, T, lease);
+    const int* tuned = cfg.wide ? s->tuned_W : s->tuned_T;
+    if (T >= 2 && T <= MAX_FUSE && tuned[T] > 0) cfg.tuned_rows = tuned[T];  // this depth had its own trial
+    return cfg;
+}
+
 // T = 2..7 reference steps in one HBM pass.  Several ranks: faces of depth T (8 directions) are
 // staged in recv2[]; when the next pass is fused too (with `next_T` steps), the frame tiles are
 // computed first and the comm stream packs and exchanges their depth-next_T faces while the bulk
@@ -95,9 +120,8 @@ static int lease_for_pass(csim_stepper* s, const Phys& p, int T, hipStream_t st,
 static hipError_t launch_fused(csim_stepper* s, const Phys& p, const int kind[4], int T, int part,
                                hipStream_t st, bool final_pass = false, int lds_bytes = 0,
                                const FrameSync* sync = nullptr, const unsigned* lease = nullptr) {
-    SweepCfg cfg = s->cfg;
+    SweepCfg cfg = launch_cfg(s, p, T, part, lease);
     if (lds_bytes > 0) cfg.lds_bytes = lds_bytes;
-    if (T >= 2 && T <= MAX_FUSE && s->tuned_T[T] > 0) cfg.tuned_rows = s->tuned_T[T];  // this depth had its own trial
     const SweepPlanIn in = plan_in_sweepO(s->nx, s->ny, T, p, cfg, kind, part);
     csim_stepper::KeptPlan& kept = s->plans[T >= 2 && T <= MAX_FUSE ? T : MAX_FUSE][part & 3];  // launch_sweepO: any other T runs as 7
     if (!kept.valid || std::memcmp(&kept.in, &in, sizeof(in)) != 0) {
@@ -106,6 +130,7 @@ static hipError_t launch_fused(csim_stepper* s, const Phys& p, const int kind[4]
         kept.valid = true;
     }
     if (part != 1) s->last_rows = kept.plan.rows;  // the frame's heights are fixed
+    if (part == 0 && kept.plan.wide) s->wide_strips_active = 1;  // of this run (csim_stepper_run clears it)
     return launch_sweepO(s->cur, s->nxt, s->pitch, p, cfg, kind, s->bc_value, kept.plan, st, final_pass ? s->fin : nullptr, sync, lease);
 }
 
@@ -287,6 +312,13 @@ int pass_fused(csim_stepper* s, const Phys& p, int T, int next_T, bool final_pas
     if (rccl && s->bulk_first_run && s->faces_depth == 0)
         return pass_fused_bulk_first(s, p, T, final_pass);
     CSIM_SETTLE(s);
+    // The chunk-height trial of the wide kernel, once per depth: run()'s own trial comes before a field's first
+    // reduction, when the passes still launch the narrow kernel.  Here a lease from an earlier pass covers this one, so
+    // the trial launches what this pass will.
+    if (!s->multi && s->autotune && s->tuned && s->cfg.rows_per_chunk == 0 && s->tuned_W[T] == 0) {
+        const unsigned* held = lease_now(s, p, T);
+        if (held && wide_wanted(s, p, T, held)) CSIM_TRY(tune_rows(s, p, T, false));
+    }
     const SideKinds kind(s);
     const GhostArgs g = deep_ghost_args(s);
     // the two option sets of the frame-first schedules
@@ -390,10 +422,11 @@ int tune_rows(csim_stepper* s, const Phys& p, int T, bool preferred_depth) {
     CSIM_TRY(timing.event(&e0, hipEventDisableSystemFence));  // timing only
     CSIM_TRY(timing.event(&e1, hipEventDisableSystemFence));
     CSIM_HIP(hipStreamSynchronize(s->s_comp));
-    SweepCfg cfg = s->cfg;
     // what a pass of this stepper launches with the chunk height under trial: the whole tile on one rank, the BULK of
-    // the tile (everything but the thin frame tiles, whose height is fixed) on a rank with neighbours
+    // the tile (everything but the thin frame tiles, whose height is fixed) on a rank with neighbours — on the kernel
+    // the pass will launch: with wide strips where the pass has them, and the result is kept apart from the narrow one
     const int part = s->multi ? 2 : 0;
+    SweepCfg cfg = launch_cfg(s, p, T, part, lease_now(s, p, T));
     auto trial = [&](int ry, float* ms) -> int {
         cfg.tuned_rows = ry;
         CSIM_HIP(hipEventRecord(e0, s->s_comp));
@@ -433,7 +466,7 @@ int tune_rows(csim_stepper* s, const Phys& p, int T, bool preferred_depth) {
     size_t arg = order[0];
     for (size_t q = 1; q < finalists; ++q)
         if (best[order[q]] < best[arg]) arg = order[q];
-    s->tuned_T[T] = cand[arg];
+    (cfg.wide ? s->tuned_W : s->tuned_T)[T] = cand[arg];
     if (preferred_depth) s->cfg.tuned_rows = cand[arg];
     return CSIM_OK;
 }
@@ -491,7 +524,7 @@ int csim_stepper_tune(csim_stepper* s, double D, double dt, double vx, double vy
     // balance of overhead rows per chunk against rounds of wavefronts, so each gets its own trial
     if (s->fuse < 0)
         for (int T = std::min(MAX_FUSE, s->fuse_cap); T >= 4; --T)
-            if (T != depth && s->tuned_T[T] == 0) CSIM_TRY(tune_rows(s, p, T, false));
+            if (T != depth && (wide_wanted(s, p, T, lease_now(s, p, T)) ? s->tuned_W : s->tuned_T)[T] == 0) CSIM_TRY(tune_rows(s, p, T, false));
     return CSIM_OK;
 }
 
@@ -510,12 +543,13 @@ int csim_stepper_keep_warm(csim_stepper* s, double D, double dt, double vx, doub
     const SideKinds kind(s);
     CSIM_HIP(hipStreamSynchronize(s->s_comm));
     CSIM_HIP(hipStreamSynchronize(s->s_comp));
-    const SweepPlan plan = plan_sweepO(s->nx, s->ny, depth, p, s->cfg, kind, 0);
+    const SweepCfg cfg = launch_cfg(s, p, depth, 0, lease_now(s, p, depth));
+    const SweepPlan plan = plan_sweepO(s->nx, s->ny, depth, p, cfg, kind, 0);
     double last = 0.0;
     for (int n = 0; n < 100000; ++n) {
         const double before = elapsed();
         if (before + 1.25 * last >= seconds) break;  // the next launch would run past the deadline
-        CSIM_HIP(launch_sweepO(s->cur, s->nxt, s->pitch, p, s->cfg, kind, s->bc_value, plan, s->s_comp, nullptr, nullptr,
+        CSIM_HIP(launch_sweepO(s->cur, s->nxt, s->pitch, p, cfg, kind, s->bc_value, plan, s->s_comp, nullptr, nullptr,
                                lease_now(s, p, depth)));
         CSIM_HIP(hipStreamSynchronize(s->s_comp));
         last = elapsed() - before;
@@ -527,6 +561,7 @@ int csim_stepper_run(csim_stepper* s, double D, double dt, double vx, double vy,
     CSIM_REQUIRE(s, "null stepper");
     CSIM_REQUIRE(nsteps >= 0, "nsteps must be >= 0");
     const Phys p = run_phys(s, D, dt, vx, vy);  // before the depth: the diffusion-only flavour prefers 7 steps per pass at every size
+    s->wide_strips_active = 0;
     // Up to MAX_FUSE steps per HBM pass where possible (across ranks: a tile at least as large as
     // the face depth).
     const int depth = fused_depth(s);

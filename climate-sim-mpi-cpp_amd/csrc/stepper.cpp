@@ -491,6 +491,10 @@ int csim_stepper_set_option(csim_stepper* s, const char* key, long value) {
     } else if (k == "pow2_v") {
         CSIM_REQUIRE(value >= 0 && value <= 2, "pow2_v must be 0 (off), 1 (on) or 2 (on where it pays: large tiles)");
         s->pow2_v = static_cast<int>(value);
+    } else if (k == "wide_strips") {
+        CSIM_REQUIRE(value >= 0 && value <= 2, "wide_strips must be 0 (off), 1 (wherever one fits) or 2 (where it pays)");
+        if (s->wide_strips != static_cast<int>(value)) s->forget_tuning();  // another kernel: its best chunk height is found anew
+        s->wide_strips = static_cast<int>(value);
     } else if (k == "screen_lease") {
         CSIM_REQUIRE(value == 0 || value == 1, "screen_lease must be 0 or 1");
         CSIM_SETTLE(s);
@@ -502,7 +506,7 @@ int csim_stepper_set_option(csim_stepper* s, const char* key, long value) {
     } else if (k == "lease_acquire_after") {
         CSIM_REQUIRE(value >= 0, "lease_acquire_after must be >= 0");
         s->lease_acquire_after = value;
-    } else if (k == "pow2_v_active" || k == "lease_word" || k == "lease_reductions") {
+    } else if (k == "pow2_v_active" || k == "lease_word" || k == "lease_reductions" || k == "wide_strips_active") {
         return fail(CSIM_ERR_ARG, k + " is read-only");
     } else if (k == "external_halo") {
         s->external = value != 0;
@@ -559,6 +563,8 @@ int csim_stepper_get_option(const csim_stepper* s, const char* key, long* value)
     else if (k == "tuned_rows") *value = s->cfg.tuned_rows;
     else if (k.size() == 12 && k.compare(0, 11, "tuned_rows_") == 0 && k[11] >= '2' && k[11] <= '0' + MAX_FUSE)
         *value = s->tuned_T[k[11] - '0'];  // "tuned_rows_2" .. "tuned_rows_7": the trial's result for passes of that depth (0 = none)
+    else if (k.size() == 17 && k.compare(0, 16, "tuned_rows_wide_") == 0 && k[16] >= '2' && k[16] <= '0' + MAX_FUSE)
+        *value = s->tuned_W[k[16] - '0'];  // the same for launches with wide strips ("wide_strips")
     else if (k == "last_rows") *value = s->last_rows;
     else if (k == "prefetch") *value = s->cfg.prefetch;
     else if (k == "xcd_swizzle") *value = s->cfg.xcd_swizzle;
@@ -572,6 +578,8 @@ int csim_stepper_get_option(const csim_stepper* s, const char* key, long* value)
     else if (k == "pow2_v") *value = s->pow2_v;
     else if (k == "pow2_v_active") *value = s->pow2_v_active;
     else if (k == "diffusion_only_active") *value = s->diffusion_only_active;
+    else if (k == "wide_strips") *value = s->wide_strips;
+    else if (k == "wide_strips_active") *value = s->wide_strips_active;
     else if (k == "screen_lease") *value = s->screen_lease;
     else if (k == "lease_steps") *value = s->lease_steps;
     else if (k == "lease_acquire_after") *value = s->lease_acquire_after;

@@ -105,6 +105,10 @@ struct csim_stepper {
     long lease_age = 0;              // steps advanced since that reduction
     long lease_idle = 0;             // steps advanced since the field was set or a reduction was enqueued
     long lease_reductions = 0;       // read-only option: reductions enqueued so far
+    // Wide strips (passes.cpp: wide_wanted): whole-field launches of a stepper that leases its screen cut the interior
+    // into strips of four columns per lane and run them through the wide kernel's unscreened bodies; bit-identical
+    int wide_strips = 2;             // option: 0 off, 1 wherever a wide strip fits, 2 on tiles where it was measured to pay
+    int wide_strips_active = 0;      // read-only: some launch of the last run had wide strips
     int diffusion_only_active = 0;  // read-only: the last run had v == 0 and swept with the advection term left out of the screened body
     int direct_faces = 1;                 // merged launch: the frame wavefronts fill send2[] themselves (no pack kernel)
     bool bulk_first_run = false;          // the current csim_stepper_run uses pass_fused_bulk_first
@@ -141,10 +145,12 @@ struct csim_stepper {
     int autotune = 1;     // pick rows_per_chunk (when 0 = auto) by timing trial launches on this GPU
     bool tuned = false;
     int tuned_T[csim::MAX_FUSE + 1]{};  // chunk height found by the trial for passes of that depth (0 = not tried: cfg.tuned_rows re-snapped)
+    int tuned_W[csim::MAX_FUSE + 1]{};  // the same for launches with wide strips: half as many wavefronts, another best height
     void forget_tuning() {
         tuned = false;
         cfg.tuned_rows = 0;
         for (int& t : tuned_T) t = 0;
+        for (int& t : tuned_W) t = 0;
     }
     std::vector<hipEvent_t> ev_pool;  // start/stop pairs around sweep launches
     std::vector<int> ev_steps;        // time steps covered by each timed launch

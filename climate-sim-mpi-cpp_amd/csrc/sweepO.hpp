@@ -51,11 +51,15 @@ struct WaveTrace {
 };
 #endif
 
-template <int DIV, int T, int SX, int SY>
+// WIDE: the instantiation that also carries the wide strips' bodies (sweepO_march, NC = 4) for the regions a wide plan
+// marks (sweep_plan.cpp); it is register-allocated for those (two wavefronts per SIMD), and the narrow tiles of such a
+// launch — the left and right strips, the bands — run every body below at that occupancy.  Compiled where
+// WIDE_KERNEL says so; a plan without wide regions is launched with WIDE = false.
+template <int DIV, int T, int SX, int SY, bool WIDE = false>
 __global__ __launch_bounds__(256) void k_sweepO_dpp(const double* __restrict__ in, double* __restrict__ out, SweepArgs a) {
     constexpr int TP = OverlapGeom<T>::TP;
     constexpr int STRIDE = OverlapGeom<T>::STRIDE;
-    const int nx = a.nx, ny = a.ny, pitch = a.pitch, nstrips = a.nstrips;
+    const int nx = a.nx, ny = a.ny, pitch = a.pitch;
     const LateArgs late = LateArgs::get();
     const int lane = threadIdx.x & 63;
     // readfirstlane: tells the compiler the wave index (and the strip, edge kinds and row range
@@ -82,20 +86,47 @@ __global__ __launch_bounds__(256) void k_sweepO_dpp(const double* __restrict__ i
         }
     }
     if (tile >= a.tl.ntiles) return;  // wave-uniform
-    int t0 = 0, strip0 = a.tl.r[0].strip0, nstrip = a.tl.r[0].nstrip, j0 = a.tl.r[0].j0, j1 = a.tl.r[0].j1, ry = a.tl.r[0].ry;
+    int t0 = 0, x0 = a.tl.r[0].x0, wide = a.tl.r[0].wide, nstrip = a.tl.r[0].nstrip, j0 = a.tl.r[0].j0, j1 = a.tl.r[0].j1, ry = a.tl.r[0].ry;
 #pragma unroll
     for (int q = 1; q < 8; ++q)
         if (q < a.tl.nregions && tile >= a.tl.r[q - 1].t_end) {
             t0 = a.tl.r[q - 1].t_end;
-            strip0 = a.tl.r[q].strip0, nstrip = a.tl.r[q].nstrip, j0 = a.tl.r[q].j0, j1 = a.tl.r[q].j1, ry = a.tl.r[q].ry;
+            x0 = a.tl.r[q].x0, wide = a.tl.r[q].wide, nstrip = a.tl.r[q].nstrip, j0 = a.tl.r[q].j0, j1 = a.tl.r[q].j1, ry = a.tl.r[q].ry;
         }
+    (void)wide;  // read by the WIDE instantiation only
     const int local = tile - t0;
-    const int strip = strip0 + local % nstrip;
+    const int strip = local % nstrip;  // within its region
     const int chunk = local / nstrip;
-    const bool first = strip == 0, last = strip == nstrips - 1;
     const int jb = j0 + chunk * ry;
     const int je = min(jb + ry - 1, j1);
-    const int g0 = strip * STRIDE - TP;
+    if constexpr (WIDE) {
+        if (wide) {
+            // A wide tile is interior by construction (sweep_plan.cpp: its 256 loaded columns are interior columns, no
+            // level of it meets a ghost row, it is no frame tile), and its bodies have no screen: the verdict word picks
+            // the leased 12-operation body, else the leased 14-operation one, else the reference's own sequence, which
+            // needs neither a screen nor a repeat.
+            const int g0w = x0 + strip * strip_stride(T, 4) - TP;
+            unsigned lease = 0;
+            if (a.lease != nullptr) lease = __builtin_amdgcn_readfirstlane(*a.lease);
+#define CSIM_MARCH_WIDE(MODE_) \
+    sweepO_march<DIV, T, MODE_, SX, SY, 4>(in, out, nx, ny, pitch, jb, je, g0w, lane, 3, 3, a.p, 3, 3, late, false, false, false, false)
+            if (a.p.slow_thr > 0.0 && (lease & LEASE_P2) != 0) {
+                keep_branch();
+                CSIM_MARCH_WIDE(M_LEASED_P2);
+            } else if (a.p.fast_thr > 0.0 && (lease & LEASE_FAST) != 0) {
+                keep_branch();
+                CSIM_MARCH_WIDE(M_LEASED);
+            } else {
+                keep_branch();
+                CSIM_MARCH_WIDE(M_PLAIN);
+            }
+#undef CSIM_MARCH_WIDE
+            return;
+        }
+    }
+    const int g0 = x0 + strip * STRIDE - TP;
+    // the first strip holds the left ghost column, the last one stores column nx - 1
+    const bool first = g0 == -TP, last = g0 + TP + STRIDE >= nx;
     // a strip meets the left ghost column iff it is the first one; the right ghost column (index
     // nx) lies inside every strip whose 128 loaded columns reach it
     const int kl = first ? a.bc.kind[CSIM_LEFT] : 3;
@@ -252,10 +283,11 @@ __global__ __launch_bounds__(256) void k_sweepO_dpp(const double* __restrict__ i
 // ============================================================================================
 
 // three steps: take the plan (sweep_plan.cpp: the launcher's caller built it), fill SweepArgs, dispatch on the sign class
-template <int DIV, int T>
+template <int DIV, int T, bool WIDE = false>
 hipError_t sweepO_div(const double* in, double* out, int pitch, const Phys& p, const SweepCfg& cfg, const Bc2& bc,
                       const FinLines& fin, const SweepPlan& plan, hipStream_t st, FrameSync fs, const unsigned* lease) {
     if (plan.empty) return hipSuccess;
+    if (plan.wide != WIDE) return hipErrorInvalidValue;  // wide regions are decoded by the WIDE kernel only
     if (plan.signals)
         fs.nframe = plan.nframe;
     else
@@ -265,11 +297,18 @@ hipError_t sweepO_div(const double* in, double* out, int pitch, const Phys& p, c
     ka.nx = plan.nx, ka.ny = plan.ny, ka.pitch = pitch, ka.nstrips = plan.nstrips, ka.swz = cfg.xcd_swizzle;
     ka.tl = plan.tl, ka.p = p, ka.bc = bc, ka.lease = lease, ka.fin = fin, ka.fs = fs;
 #define CSIM_LAUNCH_O(SXV, SYV) \
-    hipLaunchKernelGGL((k_sweepO_dpp<DIV, T, SXV, SYV>), grid, block, cfg.lds_bytes, st, in, out, ka)
+    hipLaunchKernelGGL((k_sweepO_dpp<DIV, T, SXV, SYV, WIDE>), grid, block, cfg.lds_bytes, st, in, out, ka)
 #ifdef CSIM_ISA_PROBE
     CSIM_LAUNCH_O(1, 1);
 #else
-    if (DIV == 3) {  // coefficient form: the upwind directions are folded into the coefficients
+    if constexpr (WIDE) {  // only the flavours WIDE_KERNEL names exist: a plan asked for another one by mistake
+        switch (sign_class(p)) {
+            case 4: CSIM_LAUNCH_O(1, 1); break;
+            case 3: CSIM_LAUNCH_O(1, 0); break;
+            case 1: CSIM_LAUNCH_O(0, 1); break;
+            default: return hipErrorInvalidValue;
+        }
+    } else if (DIV == 3) {  // coefficient form: the upwind directions are folded into the coefficients
         CSIM_LAUNCH_O(1, 1);
     } else {
         // zero velocity components (DIV 0 / 1; the IEEE-division form keeps its four sign flavours): code 2 per axis
@@ -306,6 +345,21 @@ hipError_t sweepO_T(const double* in, double* out, int pitch, const Phys& p, con
         default: return sweepO_div<2, T>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
     }
 #endif
+}
+
+// the same for a plan with wide regions: depths 6 and 7, DIV 0 / 1 (wide_strips_compiled), both velocities non-zero and
+// not both negative (LEASE_P2_BODY) — anything else is an error, never another kernel
+template <int T>
+hipError_t sweepO_wide_T(const double* in, double* out, int pitch, const Phys& p, const SweepCfg& cfg, const Bc2& bc,
+                         const FinLines& fin, const SweepPlan& plan, hipStream_t st, const FrameSync& fs, const unsigned* lease) {
+    static_assert(wide_strips_compiled(0, T) && wide_strips_compiled(1, T), "see wide_strips_compiled");
+    switch (p.div_mode) {
+        case 0: return sweepO_div<0, T, true>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
+#ifndef CSIM_ISA_PROBE
+        case 1: return sweepO_div<1, T, true>(in, out, pitch, p, cfg, bc, fin, plan, st, fs, lease);
+#endif
+        default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace csim

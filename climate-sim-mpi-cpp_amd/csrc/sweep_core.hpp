@@ -286,10 +286,25 @@ struct LateArgs {
     __device__ __forceinline__ double* fin_line(int side) const { return here()->fin.line[side]; }
 };
 
-template <int T>
+template <int T, int NC = 2>
 struct OverlapGeom {
-    static constexpr int TP = strip_overlap(T);     // T rounded up to even
-    static constexpr int STRIDE = strip_stride(T);  // output columns per wavefront
+    static constexpr int TP = strip_overlap(T);         // T rounded up to even
+    static constexpr int STRIDE = strip_stride(T, NC);  // output columns per wavefront
+};
+
+// One row of one level in a lane: NC consecutive columns as NC / 2 aligned pairs.  NC = 2 is the strip every body was
+// written for; NC = 4 is the WIDE strip of the unscreened interior bodies (sweepO_march).
+template <int NC>
+struct LaneRow {
+    static_assert(NC == 2 || NC == 4, "columns per lane");
+    double2 h[NC / 2];
+    __device__ __forceinline__ double col(int q) const { return (q & 1) ? h[q >> 1].y : h[q >> 1].x; }
+    __device__ __forceinline__ void set(int q, double v) {
+        if (q & 1)
+            h[q >> 1].y = v;
+        else
+            h[q >> 1].x = v;
+    }
 };
 
 // FAST (interior body only): the cell update with E - 2c, N - 2c fused (diffuse_term<., true>), bit-identical to
@@ -337,23 +352,34 @@ __device__ __forceinline__ void pin2(double2& v) { asm volatile("" : "+v"(v.x), 
 constexpr int M_LEASED_P2 = -6, M_LEASED = -5, M_FAST_P2 = -4, M_FAST = -3, M_PLAIN = -2, M_GENERIC = -1;
 constexpr unsigned LEASE_FAST = 1u, LEASE_P2 = 2u;  // bits of the verdict word: what M_FAST's / M_FAST_P2's screen asks holds field-wide
 
-template <int DIV, int T, int MODE, int SX, int SY>
+// NC: columns per lane.  Every body exists with NC = 2; the bodies without a screen and without patches (M_LEASED_P2,
+// M_LEASED, M_PLAIN) also with NC = 4, for tiles whose 256 loaded columns and whose rows of every level are interior
+// cells (the WIDE regions of sweep_plan.cpp).  A lane imports two doubles per level-row whatever NC is — W of its first
+// column from the previous lane's last, E of its last column from the next lane's first — and a strip loses 2 TP
+// columns whatever its width: with four columns per lane the same 4 DPP moves and the same 16 lost columns are paid
+// for 256 columns instead of 128.  The in-lane neighbours are plain registers.
+template <int DIV, int T, int MODE, int SX, int SY, int NC = 2>
 __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, double* __restrict__ out,
                                              int nx, int ny, int pitch, int jb, int je, int g0, int lane,
                                              int kl, int kr, const Phys& p, int kb, int kt,
                                              LateArgs late, bool fin_any, bool fin_l, bool fin_r, bool wt) {
-    constexpr int TP = OverlapGeom<T>::TP;
-    constexpr int STRIDE = OverlapGeom<T>::STRIDE;
+    constexpr int TP = OverlapGeom<T, NC>::TP;
+    constexpr int STRIDE = OverlapGeom<T, NC>::STRIDE;
     constexpr bool EDGE = MODE >= M_GENERIC, P2 = MODE == M_FAST_P2 || MODE == M_LEASED_P2, GENERIC = MODE == M_GENERIC;
     constexpr bool FAST = MODE == M_FAST || MODE == M_LEASED || P2, SCREEN = MODE == M_FAST || MODE == M_FAST_P2;
     constexpr int CASE = MODE;
-    // this lane's two columns, 0-based interior index (-1 = left ghost, nx = right ghost)
-    const int gx = g0 + 2 * lane, gy = gx + 1;
+    static_assert(NC == 2 || (!EDGE && !SCREEN), "four columns per lane: interior bodies without a screen only");
+    using Row = LaneRow<NC>;
+    // this lane's first two columns, 0-based interior index (-1 = left ghost, nx = right ghost)
+    const int gx = g0 + NC * lane, gy = gx + 1;
     const ptrdiff_t xoff = LPAD + gx;
     // kb / kt: kind of the bottom / top side, 3 = neighbour rank: plain stencil
     // output lanes: local columns [TP, TP + STRIDE), clipped to the interior
-    const bool out_lane = 2 * lane >= TP && 2 * lane < TP + STRIDE && gx < nx;
+    const bool out_lane = NC * lane >= TP && NC * lane < TP + STRIDE && gx < nx;
     const int nvalid = nx - gx;
+    // NC = 4: the lane's second pair.  TP is even, so a pair is an output as a whole; at TP = 6 the first and the last
+    // output lane store one pair, at TP = 8 and TP = 4 every output lane stores both.  No clipping to nx: see above
+    const bool out_pair1 = NC == 4 && NC * lane + 2 >= TP && NC * lane + 2 < TP + STRIDE;
     // lanes that hold a ghost column of a physical edge (EDGE bodies only).  g0 is even, so the right ghost column
     // (index nx) is the .x of its lane when nx is even and the .y when nx is odd: wave-uniform
     const bool ghost_ly = kl != 3 && gy == -1;
@@ -362,7 +388,11 @@ __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, doub
     const bool ghost_cols = kl != 3 || kr != 3;  // wave-uniform
 
     auto load = [&](int j) {
-        return *reinterpret_cast<const double2*>(in + static_cast<ptrdiff_t>(j) * pitch + xoff);
+        Row r;
+#pragma unroll
+        for (int h = 0; h < NC / 2; ++h)
+            r.h[h] = *reinterpret_cast<const double2*>(in + static_cast<ptrdiff_t>(j) * pitch + xoff + 2 * h);
+        return r;
     };
 
     const int r_first = jb - (T - 1);
@@ -374,8 +404,8 @@ __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, doub
     // (s_waitcnt vmcnt(0)) at the top of every iteration, which would serialise the row prefetch.
     // The <= 5 surplus iterations of a chunk whose niter is not a multiple of six compute rows
     // beyond je that are never stored (the host picks ry so that only a ragged last chunk has any).
-    double2 L0[6];
-    double2 L[T][3];
+    Row L0[6];
+    Row L[T][3];
 #pragma unroll
     for (int q = 0; q < 6; ++q) L0[q] = load(min(r_first - 1 + q, last_row));
     bool big = false;  // SCREEN: some loaded value is not below the threshold
@@ -392,13 +422,15 @@ __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, doub
         }
     };
     if (SCREEN) {  // every later row is screened when it is the `n` of level 1
-        screen(L0[0]);
-        screen(L0[1]);
+        screen(L0[0].h[0]);
+        screen(L0[1].h[0]);
     }
 #pragma unroll
     for (int l = 0; l < T; ++l)
 #pragma unroll
-        for (int q = 0; q < 3; ++q) L[l][q] = make_double2(0.0, 0.0);
+        for (int q = 0; q < 3; ++q)
+#pragma unroll
+            for (int h = 0; h < NC / 2; ++h) L[l][q].h[h] = make_double2(0.0, 0.0);
 
     // One group = six iterations.  Level l has nothing valid to produce before iteration 2 (l - 1)
     // (its first needed row, jb - (T - l), comes out exactly then), so the first two groups are
@@ -419,20 +451,26 @@ __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, doub
                 for (int l = 1; l <= T; ++l) {
                     if (G < 2 && 6 * G + u < 2 * (l - 1)) continue;  // compile-time: level not started yet
                     const int rho = r - l + 1;
-                    const double2 s = (l == 1) ? L0[u % 6] : L[l - 1][(u + 1) % 3];
-                    const double2 c = (l == 1) ? L0[(u + 1) % 6] : L[l - 1][(u + 2) % 3];
-                    const double2 n = (l == 1) ? L0[(u + 2) % 6] : L[l - 1][u % 3];
+                    const Row sr = (l == 1) ? L0[u % 6] : L[l - 1][(u + 1) % 3];
+                    const Row cr = (l == 1) ? L0[(u + 1) % 6] : L[l - 1][(u + 2) % 3];
+                    const Row nr = (l == 1) ? L0[(u + 2) % 6] : L[l - 1][u % 3];
                     // The stencil is evaluated on every lane and row (branch-free, the same code as
                     // the interior body); where the result is a ghost cell of a physical edge it is
                     // then replaced by the boundary rule.
-                    double2 o;
+                    Row orow;
                     {
-                        const double Wx = shift_from_prev(c.y);
-                        const double Ey = shift_from_next(c.x);
-                        o.x = cell<DIV, SX, SY, FAST, P2>(c.x, Wx, c.y, s.x, n.x, p);
-                        o.y = cell<DIV, SX, SY, FAST, P2>(c.y, c.x, Ey, s.y, n.y, p);
-                        if (SCREEN && l == 1) screen(n);
+                        const double Wx = shift_from_prev(cr.col(NC - 1));
+                        const double Ey = shift_from_next(cr.col(0));
+#pragma unroll
+                        for (int q = 0; q < NC; ++q)
+                            orow.set(q, cell<DIV, SX, SY, FAST, P2>(cr.col(q), q == 0 ? Wx : cr.col(q - 1), q == NC - 1 ? Ey : cr.col(q + 1),
+                                                                    sr.col(q), nr.col(q), p));
+                        if (SCREEN && l == 1) screen(nr.h[0]);
                     }
+                    // the patches below, the FinLines and the write-through stores are the narrow strip's (EDGE bodies and
+                    // frame tiles: NC = 2): they work on the row's one pair
+                    const double2 c = cr.h[0];
+                    double2 o = orow.h[0];
                     if (EDGE && !GENERIC && l < T) {  // the strip's one ghost column, unconditionally
                         if (CASE == 1) o.y = ghost_ly ? c.y : o.y;
                         if (CASE == 2) {
@@ -459,7 +497,7 @@ __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, doub
                                     pin2(t);
                                     o = t;
                                 } else if (gt) {  // Neumann top: row ny of this level
-                                    double2 t = L[l][(u + 2) % 3];
+                                    double2 t = L[l][(u + 2) % 3].h[0];
                                     pin2(t);
                                     o = t;
                                 }
@@ -518,9 +556,16 @@ __device__ __forceinline__ bool sweepO_march(const double* __restrict__ in, doub
                         if (GENERIC && rows_here && rho == 1 && kb == CSIM_BC_NEUMANN) {  // ghost row 0 := row 1
                             double2 t = o;
                             pin2(t);
-                            L[l][(u + 2) % 3] = t;
+                            L[l][(u + 2) % 3].h[0] = t;
                         }
-                        L[l][u % 3] = o;
+                        if (NC == 2) orow.h[0] = o;
+                        L[l][u % 3] = orow;
+                    } else if (NC == 4) {  // whole pairs, never clipped
+                        if (rho >= jb && rho <= je) {
+                            double* dst = out + static_cast<ptrdiff_t>(rho) * pitch + xoff;
+                            if (out_lane) *reinterpret_cast<double2*>(dst) = orow.h[0];
+                            if (out_pair1) *reinterpret_cast<double2*>(dst + 2) = orow.h[NC / 2 - 1];
+                        }
                     } else if (rho >= jb && rho <= je && out_lane) {
                         if (wt) {  // wave-uniform: frame tile of a merged launch
                             keep_branch();

@@ -53,12 +53,28 @@ SweepPlan sweep_plan(const SweepPlanIn& in) {
     const int hfb = thin(CSIM_BOTTOM) ? std::min(hf, hphys) : hf;
     const int hft = thin(CSIM_TOP) ? std::min(hf, hphys) : hf;
     Tiling& tl = plan.tl;
-    auto add = [&](int strip0, int nstrip, int j0, int j1, int rows) {
+    auto add_at = [&](int strip0, int nstrip, int j0, int j1, int rows, int x0, int wide) {
         if (nstrip <= 0 || j1 < j0) return;
         TileRegion& r = tl.r[tl.nregions++];
-        r.strip0 = strip0, r.nstrip = nstrip, r.j0 = j0, r.j1 = j1, r.ry = rows;
+        r.strip0 = strip0, r.nstrip = nstrip, r.j0 = j0, r.j1 = j1, r.ry = rows, r.x0 = x0, r.wide = wide;
         tl.ntiles += nstrip * cdiv(j1 - j0 + 1, rows);
         r.t_end = tl.ntiles;
+    };
+    // WIDE strips (in.wide, part 0 of a field whose four sides are physical): the rows between the bottom and top bands
+    // are cut into one narrow strip on the left (it holds the left ghost column), as many wide strips as fit, and narrow
+    // strips with an origin of their own from where the wide ones end to nx (the last holds the right ghost column).
+    // A wide strip loads wave_cols(4) columns from TP left of its first output: all of them interior columns, so
+    // x0 >= TP (the left narrow strip sees to that) and x0 + STRIDE4 + TP <= nx.  Its rows lie between the bands, so
+    // no level of it meets a ghost row and it is never a frame tile of a final pass.
+    const int TP = strip_overlap(T), STRIDE4 = strip_stride(T, 4);
+    int nwide = 0;  // wide strips per row of tiles: set below, once the bands are known
+    auto add = [&](int strip0, int nstrip, int j0, int j1, int rows) { add_at(strip0, nstrip, j0, j1, rows, strip0 * STRIDE, 0); };
+    auto add_cols = [&](int strip0, int nstrip, int j0, int j1, int rows) {  // add, or all columns cut left / wide / right
+        if (nwide == 0) return add(strip0, nstrip, j0, j1, rows);
+        const int xr = STRIDE + nwide * STRIDE4;
+        add_at(0, 1, j0, j1, rows, 0, 0);
+        add_at(1, nwide, j0, j1, rows, STRIDE, 1);
+        add_at(1 + nwide, cdiv(nx - xr, STRIDE), j0, j1, rows, xr, 0);
     };
     // rows j0..j1 of `nstrip` strips: full-height chunks, or — on launches of two or more rounds of wavefronts —
     // a main region of 7/8 of the chunks (a multiple of four, so that its tiles fill whole blocks whatever the
@@ -67,8 +83,10 @@ SweepPlan sweep_plan(const SweepPlanIn& in) {
         const int nrows = j1 - j0 + 1;
         if (nstrip <= 0 || nrows <= 0) return 0;
         const int nchunks = cdiv(nrows, rows);
-        if (!in.tail_split || rows < 48 || nchunks < 16 || static_cast<long>(nstrip) * nchunks < 8192) {
-            add(strip0, nstrip, j0, j1, rows);
+        // a round of the wide kernel is half as many wavefronts (two per SIMD), and a wide plan has about half as many strips
+        const long per_row = nwide ? 1 + nwide + cdiv(nx - STRIDE - nwide * STRIDE4, STRIDE) : nstrip;
+        if (!in.tail_split || rows < 48 || nchunks < 16 || per_row * nchunks < (nwide ? 4096 : 8192)) {
+            add_cols(strip0, nstrip, j0, j1, rows);
             return 0;
         }
         const bool two_level = in.tail_split != 2;  // default: 7/8 of the chunks full height + the rest at half height;
@@ -78,10 +96,10 @@ SweepPlan sweep_plan(const SweepPlanIn& in) {
         const int half = whole_groups(T, rows / 2), quarter = whole_groups(T, rows / 4);
         const int rest = j1 - j_main;                       // rows left for the tail regions
         const int j_half = two_level ? j1 : j_main + (rest * 2 / 3) / half * half;  // about two thirds of them at half height
-        add(strip0, nstrip, j0, j_main, rows);
+        add_cols(strip0, nstrip, j0, j_main, rows);
         const int before = tl.ntiles;
-        add(strip0, nstrip, j_main + 1, j_half, half);
-        add(strip0, nstrip, j_half + 1, j1, quarter);
+        add_cols(strip0, nstrip, j_main + 1, j_half, half);
+        add_cols(strip0, nstrip, j_half + 1, j1, quarter);
         return tl.ntiles - before;
     };
     int tail_tiles = 0;
@@ -93,11 +111,17 @@ SweepPlan sweep_plan(const SweepPlanIn& in) {
         const int hb = whole_groups(T, T - 1);
         const bool bands = specialised && ny >= 2 * hb + 6;
         const bool band_b = bands && in.kind[CSIM_BOTTOM] != 3, band_t = bands && in.kind[CSIM_TOP] != 3;
+        // (tail_split 2 would need nine regions with wide strips: it keeps the narrow plan)
+        const bool lone = in.kind[CSIM_LEFT] != 3 && in.kind[CSIM_RIGHT] != 3;
+        if (in.wide && part == 0 && wide_strips_compiled(in.div_mode, T) && band_b && band_t && lone && in.tail_split != 2)
+            nwide = std::max(0, (nx - TP - STRIDE) / STRIDE4);
+        plan.wide = nwide > 0;
         tail_tiles = add_rows(0, nstrips, band_b ? hb + 1 : 1, band_t ? ny - hb : ny, ry);
         const int before = tl.ntiles;
         if (band_b) add(0, nstrips, 1, hb, hb);
         if (band_t) add(0, nstrips, ny - hb + 1, ny, hb);
         tail_tiles += tl.ntiles - before;
+        nwide = 0;
     } else if (part == 1 || part == 3) {
         add(0, nstrips, 1, hfb, hfb);
         add(0, nstrips, ny - hft + 1, ny, hft);

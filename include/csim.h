@@ -275,6 +275,18 @@ int csim_stepper_sum(csim_stepper* s, double* out);
  *                    must have been advanced, since it was set or last judged, before a reduction is spent on it —
  *                    short upload / run / download cycles never pay one.  Read-only: "lease_word" (synchronises; for
  *                    tests), "lease_reductions" (reductions enqueued so far)
+ *   "wide_strips"    0/1/2 (default 2), bit-identical either way; steppers that lease their screen, with "pow2_v" in
+ *                    force and velocities not both negative, at 6 or 7 steps per pass.  The interior between the
+ *                    left-most strip, the right-most strips and the thin bottom and top bands is swept in strips of four
+ *                    columns per lane (256 loaded columns per wavefront instead of 128): the lane shifts and the
+ *                    columns lost to the overlap of neighbouring strips are the same per wavefront, so a wide strip
+ *                    issues 14 % fewer instructions per cell update, at two wavefronts per SIMD instead of four.  The
+ *                    wide bodies have no screen: the verdict word picks the leased 12-operation body, else the leased
+ *                    14-operation one, else the reference's own sequence.  1 = wherever a wide strip fits; 2 = on
+ *                    tiles of at least 6e7 cells and only in passes that are handed a verdict word (measured: 16384^2
+ *                    +5.5 %, 8192^2 +4 % in every round; 4096 x 8192 within the noise: DESIGN.md section 4).  The chunk
+ *                    height of such launches has its own trial ("tuned_rows_wide_6", "tuned_rows_wide_7", read-only).
+ *                    "wide_strips_active" (read-only): some launch of the last run had wide strips
  *   "fuse"           time steps per HBM pass: -1 auto (the cheapest split of a run into passes of 2..7 steps, e.g.
  *                    1000 = 166 x 6 + 4, 20 = 7 + 7 + 6), 0/1 off, 2..7 balanced passes of at most that depth
  *   "variant"        single-step kernel family: 0 auto, 1 dpp, 2 lds, 3 naive

@@ -16,10 +16,18 @@
 //                             nframe == frame_tiles == ntiles(part 1); parts 0, 1, 2 do not signal
 //   E  frame reach            on every side of kind 3 the part-1 tiles hold the min(MAX_FUSE, nx or ny) interior lines
 //                             next to it over its full length (the next pass's faces are packed from them)
+//   F  wide tiles interior    (plans with wide strips, SweepPlanIn::wide) every tile of a wide region loads 256 interior
+//                             columns from an even column on, no level of it meets a ghost row, and it is no frame tile
+//                             of a final pass (not the first or last strip, not the first or last row); wide regions
+//                             exist only in part 0 of a field without neighbours, at the depths the wide kernel has
 // and folds every plan into one 64-bit hash, in enumeration order, which must be the recorded one: a plan that
-// changes is then a decision, not an accident.  Prints "sweep plan host ok" and returns 0, or says what failed.
+// changes is then a decision, not an accident.  The plans asked for wide strips are a second enumeration with a hash
+// of its own (which also folds each region's origin and kind); there C counts every interior CELL, since strips of
+// two widths share a row, and a request that no wide strip fits must give the narrow plan unchanged.
+// Prints "sweep plan host ok" and returns 0, or says what failed.
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <utility>
 #include <vector>
 
@@ -33,6 +41,8 @@ using csim::Tiling;
 
 constexpr std::uint64_t EXPECT_HASH = 0xeec39933f7ad892cull;  // of the run that agreed with the planner as it was inside sweepO_div
 constexpr long EXPECT_PLANS = 485400;
+constexpr std::uint64_t EXPECT_HASH_WIDE = 0xc292f82455edc798ull;  // of the enumeration that asks for wide strips
+constexpr long EXPECT_PLANS_WIDE = 207376;
 
 int g_fail = 0;
 SweepPlanIn g_in;  // the plan under check, for the report
@@ -67,27 +77,43 @@ int block_tile(const Tiling& tl, int nblocks, int swz, int b, int wave) {
     }
     return tile >= tl.ntiles ? -1 : tile;
 }
+// strip: the region's strip0 + the strip's place in its region (what conditions C - E of the narrow plans count by);
+// g0, wide: what the kernel marches from — the first loaded column (0-based interior index, -TP for the first strip)
+// and the strip's kind
 struct Tile {
-    int strip, jb, je;
-    bool operator==(const Tile& o) const { return strip == o.strip && jb == o.jb && je == o.je; }
+    int strip, jb, je, g0, wide;
+    bool operator==(const Tile& o) const { return strip == o.strip && jb == o.jb && je == o.je && g0 == o.g0 && wide == o.wide; }
 };
-Tile locate(const Tiling& tl, int tile) {
+Tile locate(const Tiling& tl, int tile, int T) {
     int t0 = 0, q_used = 0;
     for (int q = 1; q < 8; ++q)
         if (q < tl.nregions && tile >= tl.r[q - 1].t_end) t0 = tl.r[q - 1].t_end, q_used = q;
     const csim::TileRegion& r = tl.r[q_used];
     const int local = tile - t0;
     const int jb = r.j0 + local / r.nstrip * r.ry;
-    return Tile{r.strip0 + local % r.nstrip, jb, jb + r.ry - 1 < r.j1 ? jb + r.ry - 1 : r.j1};
+    const int g0 = r.x0 + local % r.nstrip * csim::strip_stride(T, r.wide ? 4 : 2) - csim::strip_overlap(T);
+    return Tile{r.strip0 + local % r.nstrip, jb, jb + r.ry - 1 < r.j1 ? jb + r.ry - 1 : r.j1, g0, r.wide};
 }
 
 // ---- the conditions ------------------------------------------------------------------------------------------------
-std::uint64_t g_hash = 0xcbf29ce484222325ull;
-long g_plans = 0;
-void fold(std::uint64_t v) { g_hash = (g_hash ^ v) * 0x100000001b3ull; }
+std::uint64_t g_hash = 0xcbf29ce484222325ull, g_hash_wide = 0xcbf29ce484222325ull;
+long g_plans = 0, g_plans_wide = 0, g_wide_tiles = 0;
+bool g_wide_run = false;  // the second enumeration: its own hash and count
+void fold(std::uint64_t v) {
+    std::uint64_t& h = g_wide_run ? g_hash_wide : g_hash;
+    h = (h ^ v) * 0x100000001b3ull;
+}
 void fold_plan(const SweepPlan& p) {
-    for (const csim::TileRegion& r : p.tl.r)
+    for (const csim::TileRegion& r : p.tl.r) {
         for (int v : {r.t_end, r.strip0, r.nstrip, r.j0, r.j1, r.ry}) fold(static_cast<std::uint32_t>(v));
+        if (g_wide_run)
+            for (int v : {r.x0, r.wide}) fold(static_cast<std::uint32_t>(v));
+    }
+    if (g_wide_run) {
+        fold(static_cast<std::uint32_t>(p.wide));
+        ++g_plans_wide;
+        --g_plans;
+    }
     for (int v : {p.tl.nregions, p.tl.ntiles, p.tl.frame_tiles, p.tl.frame_blocks, p.tl.tail_blocks, p.nstrips, p.rows,
                   p.nblocks, static_cast<int>(p.nframe), static_cast<int>(p.signals), static_cast<int>(p.empty)})
         fold(static_cast<std::uint32_t>(v));
@@ -113,7 +139,20 @@ bool check_plan(const SweepPlanIn& in, const SweepPlan& p) {
         EXPECT(r.t_end > (q ? tl.r[q - 1].t_end : 0));
         EXPECT(r.nstrip >= 1 && r.strip0 >= 0 && r.strip0 + r.nstrip <= p.nstrips);
         EXPECT(1 <= r.j0 && r.j0 <= r.j1 && r.j1 <= in.ny && r.ry >= 1);
+        EXPECT((r.wide == 0 || r.wide == 1) && r.x0 >= 0 && r.x0 % 2 == 0 && (p.wide || r.wide == 0));
+        if (!p.wide) EXPECT(r.x0 == r.strip0 * csim::strip_stride(in.T));  // a narrow plan: every strip of the field's own grid
     }
+    {
+        bool any = false;
+        for (int q = 0; q < tl.nregions; ++q) any = any || tl.r[q].wide;
+        EXPECT(any == p.wide);
+        // where a wide region may exist at all
+        if (p.wide) {
+            EXPECT(in.wide && in.part == 0 && csim::wide_strips_compiled(in.div_mode, in.T));
+            for (int k = 0; k < 4; ++k) EXPECT(in.kind[k] != 3);
+        }
+    }
+    const int TP = csim::strip_overlap(in.T);
     EXPECT(tl.r[tl.nregions - 1].t_end == tl.ntiles);
     EXPECT(tl.frame_tiles >= 0 && tl.frame_tiles <= tl.ntiles && tl.frame_blocks >= 0 && tl.tail_blocks >= 0);
     EXPECT(tl.frame_blocks + tl.tail_blocks <= p.nblocks);
@@ -126,8 +165,16 @@ bool check_plan(const SweepPlanIn& in, const SweepPlan& p) {
                 EXPECT(tile < tl.ntiles);
                 EXPECT(g_seen[tile]++ == 0);
                 EXPECT((b < tl.frame_blocks) == (tile < tl.frame_tiles));  // the kernel's frame_tile
-                const Tile t = locate(tl, tile);
+                const Tile t = locate(tl, tile, in.T);
                 EXPECT(t.jb <= t.je && t.jb >= 1 && t.je <= in.ny && t.strip >= 0 && t.strip < p.nstrips);
+                EXPECT(t.g0 >= -TP && t.g0 % 2 == 0 && t.g0 + TP < in.nx);  // aligned pairs; at least one output column
+                if (t.wide) {  // F
+                    EXPECT(t.g0 >= 0 && t.g0 + csim::wave_cols(4) <= in.nx);
+                    EXPECT(t.jb - (in.T - 1) >= 1 && t.je + (in.T - 1) <= in.ny);
+                    EXPECT(tile >= tl.frame_tiles && tl.frame_tiles == 0);
+                    EXPECT(t.g0 != -TP && t.g0 + TP + csim::strip_stride(in.T, 4) < in.nx && t.jb != 1 && t.je != in.ny);
+                    g_wide_tiles += swz;
+                }
             }
         for (int t = 0; t < tl.ntiles; ++t) EXPECT(g_seen[t] == 1);
     }
@@ -137,9 +184,23 @@ bool check_plan(const SweepPlanIn& in, const SweepPlan& p) {
 // += 1 on every (strip, row) a tile of the plan writes
 void cover(const SweepPlan& p, std::vector<int>* c) {
     for (int t = 0; t < p.tl.ntiles; ++t) {
-        const Tile x = locate(p.tl, t);
+        const Tile x = locate(p.tl, t, p.T);
         for (int j = x.jb; j <= x.je; ++j) (*c)[static_cast<size_t>(x.strip) * (p.ny + 1) + j] += 1;
     }
+}
+// the same by CELL, from what the kernel stores: columns [g0 + TP, g0 + TP + STRIDE) of the strip's kind, clipped to nx
+bool cells_once(const SweepPlan& p) {
+    std::vector<unsigned char> c(static_cast<size_t>(p.nx) * p.ny, 0);
+    for (int t = 0; t < p.tl.ntiles; ++t) {
+        const Tile x = locate(p.tl, t, p.T);
+        const int c0 = x.g0 + csim::strip_overlap(p.T), c1 = c0 + csim::strip_stride(p.T, x.wide ? 4 : 2);
+        for (int j = x.jb; j <= x.je; ++j)
+            for (int i = c0; i < c1 && i < p.nx; ++i)
+                if (++c[static_cast<size_t>(j - 1) * p.nx + i] > 1) return false;
+    }
+    for (unsigned char v : c)
+        if (v != 1) return false;
+    return true;
 }
 bool all_are(const std::vector<int>& c, int nstrips, int ny, int v) {
     for (int s = 0; s < nstrips; ++s)
@@ -177,8 +238,29 @@ bool check_set(SweepPlanIn in) {
     const size_t cells = static_cast<size_t>(ns) * (ny + 1);
     // C
     std::vector<int> c(cells, 0);
-    cover(p[0], &c);
-    EXPECT(all_are(c, ns, ny, 1));
+    if (p[0].wide) {
+        EXPECT(cells_once(p[0]));
+    } else {
+        cover(p[0], &c);
+        EXPECT(all_are(c, ns, ny, 1));
+    }
+    if (in.wide) {  // asked for wide strips: only part 0 may differ from the narrow plans, and only where one fits
+        SweepPlanIn nin = in;
+        nin.wide = 0;
+        for (int part = 0; part < 4; ++part) {
+            nin.part = part;
+            const SweepPlan n = csim::sweep_plan(nin);
+            const bool same = std::memcmp(&n.tl, &p[part].tl, sizeof(Tiling)) == 0 && n.nblocks == p[part].nblocks &&
+                              n.rows == p[part].rows && n.nstrips == p[part].nstrips;
+            EXPECT(same == !p[part].wide);
+        }
+        const int fits = (in.nx - csim::strip_overlap(in.T) - csim::strip_stride(in.T)) / csim::strip_stride(in.T, 4);
+        bool lone = true;
+        for (int k = 0; k < 4; ++k) lone = lone && in.kind[k] != 3;
+        const int hb = csim::whole_groups(in.T, in.T - 1);
+        EXPECT(p[0].wide == (fits >= 1 && lone && csim::wide_strips_compiled(in.div_mode, in.T) && ny >= 2 * hb + 6 &&
+                             in.tail_split != 2));
+    }
     c.assign(cells, 0);
     cover(p[3], &c);
     EXPECT(all_are(c, ns, ny, 1));
@@ -195,7 +277,7 @@ bool check_set(SweepPlanIn in) {
     EXPECT(p[3].tl.frame_tiles == p[1].tl.ntiles && p[3].nframe == static_cast<unsigned>(p[1].tl.ntiles));
     EXPECT(p[3].tl.frame_blocks == csim::cdiv(p[3].tl.frame_tiles, 4));
     for (int part = 0; part < 3; ++part) EXPECT(p[part].tl.frame_tiles == 0 && p[part].tl.frame_blocks == 0);
-    for (int t = 0; t < p[1].tl.ntiles; ++t) EXPECT(locate(p[3].tl, t) == locate(p[1].tl, t));
+    for (int t = 0; t < p[1].tl.ntiles; ++t) EXPECT(locate(p[3].tl, t, in.T) == locate(p[1].tl, t, in.T));
     // E
     const int S = csim::strip_stride(in.T);
     const int hx = in.nx < csim::MAX_FUSE ? in.nx : csim::MAX_FUSE, hy = ny < csim::MAX_FUSE ? ny : csim::MAX_FUSE;
@@ -281,6 +363,49 @@ int main() {
                     }
                     fold(static_cast<std::uint32_t>(ry));
                 }
+    // ---- the second enumeration: the same conditions over plans that ask for wide strips -------------------------
+    g_wide_run = true;
+    const int dnpd[4] = {D, N, P, D};
+    for (int T = 4; T <= csim::MAX_FUSE; ++T) {
+        const int S = csim::strip_stride(T), S4 = csim::strip_stride(T, 4), TP = csim::strip_overlap(T);
+        if (S4 != csim::wave_cols(4) - 2 * TP || csim::wave_cols(4) != 256) {
+            std::printf("FAILED: wide strip geometry at T = %d\n", T);
+            return 1;
+        }
+        // no wide strip fits / exactly one / one and a remainder / odd nx / several and a short remainder / none left over
+        const int nxs[] = {S, S + TP + S4 - 1, S + TP + S4, 608, 849, 1100, S + 3 * S4 + TP, S + 2 * S4 + TP + 1, 2 * S + 3 * S4 + 5};
+        for (int div : {0, 1, 2})
+            for (const int* kind : {kinds[1], kinds[2], kinds[3], dnpd, kinds[4], kinds[5]})
+                for (int nx : nxs)
+                    for (int ny : {12, 17, 18, 21, 22, 30, 37, 40, 64, 100})
+                        for (int rows : {0, 5, 6, 13})
+                            for (int ts : {1, 2}) {
+                                const SweepPlanIn in{nx, ny, T, div, {kind[0], kind[1], kind[2], kind[3]}, 0, rows, 0, ts, 0, 1};
+                                if (!check_set(in)) return 1;
+                            }
+    }
+    // wide plans with a tail region (half as many tiles make a round), and the bench grid with a tuned height
+    for (int T : {6, 7})
+        for (const auto& sh : {std::pair<int, int>{8192, 48 * 130 + 5}, {4096, 48 * 260 + 1}}) {
+            const SweepPlanIn in{sh.first, sh.second, T, 0, {D, D, D, D}, 0, 48, 0, 1, 0, 1};
+            const long before = g_tails;
+            if (!check_set(in)) return 1;
+            if (g_tails == before) {
+                std::printf("FAILED: no tail region in the wide plan of %d x %d at T = %d\n", sh.first, sh.second, T);
+                return 1;
+            }
+        }
+    if (g_wide_tiles == 0) {
+        std::printf("FAILED: the second enumeration saw no wide tile\n");
+        return 1;
+    }
+    g_wide_run = false;
+    std::printf("%ld plans asked for wide strips, hash 0x%016llx\n", g_plans_wide, static_cast<unsigned long long>(g_hash_wide));
+    if (g_plans_wide != EXPECT_PLANS_WIDE || g_hash_wide != EXPECT_HASH_WIDE) {
+        std::printf("FAILED: expected %ld plans, hash 0x%016llx: a plan with wide strips changed\n", EXPECT_PLANS_WIDE,
+                    static_cast<unsigned long long>(EXPECT_HASH_WIDE));
+        return 1;
+    }
     std::printf("%ld plans, hash 0x%016llx\n", g_plans, static_cast<unsigned long long>(g_hash));
     if (g_plans != EXPECT_PLANS || g_hash != EXPECT_HASH) {
         std::printf("FAILED: expected %ld plans, hash 0x%016llx: a plan changed\n", EXPECT_PLANS,
