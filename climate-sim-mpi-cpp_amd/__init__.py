@@ -283,6 +283,13 @@ def lib() -> C.CDLL:
         "csim_etkf_weights_ordered": (i, [i, dp, d, i, dp, dp, dp, dp, ip]),
         "csim_ensemble_assimilate_etkf_device": (i, [vp, vp, d, i, i, d]),
         "csim_ensemble_etkf_info2": (i, [vp, C.POINTER(C.c_longlong), dp, dp, dp, ip, ip, ip]),
+        "csim_obs_slots_present": (i, [i, ip, C.POINTER(C.c_ulonglong)]),
+        "csim_obs_network_set_slots": (i, [vp, ip]),
+        "csim_obs_network_hold": (i, [vp, i, i]),
+        "csim_obs_network_observe_slot": (i, [vp, i, i, C.c_ulonglong, C.c_uint, i]),
+        "csim_obs_network_held": (i, [vp, dp, ip, ip]),
+        "csim_ensemble_obs_gram_held": (i, [vp, vp, dp, dp, C.POINTER(C.c_longlong)]),
+        "csim_ensemble_assimilate_etkf_held": (i, [vp, vp, d, i, i, d, i]),
         "csim_ensemble_assimilate_letkf": (i, [vp, vp, d, i, i, d, i]),
         "csim_ensemble_letkf_info": (i, [vp, ip, ip, dp, ip, ip, ip]),
         "csim_letkf_nodes": (i, [i, i, i, ip, ip, ip, ip]),
@@ -860,6 +867,7 @@ def obs_noise(seed, draw, o):
 
 
 OBS_MAX_TAPS = 64  # CSIM_OBS_MAX_TAPS
+OBS_MAX_SLOTS = 64  # CSIM_OBS_MAX_SLOTS
 ObsTaps = collections.namedtuple("ObsTaps", "start di dj w")
 ObsTaps.__doc__ = """the taps of linear observations (csim_obs_network_create_linear): observation o observes
 sum_s w[s] x(i[o] + di[s], j[o] + dj[s]) over s = start[o] .. start[o + 1] - 1"""
@@ -936,6 +944,18 @@ variance at the cell before and after the last recorded analysis"""
 OBS_CYCLE_FIELDS = tuple(k for k, _ in CsimObsCycle._fields_)
 OBS_SCREEN_FIELDS = tuple(k for k, _ in CsimObsScreenCycle._fields_)
 OBS_USED, OBS_INACTIVE, OBS_REJECTED = 0, 1, 2
+
+
+def obs_slots_present(slot, nobs=None) -> int:
+    """the mask of the time slots that occur among the observations' slots (None: every observation in slot 0): bit s
+    for slot s; what a network holds against the slots held or observed (csim_obs_slots_present) — host only"""
+    m = C.c_ulonglong()
+    if slot is None:
+        _ck(lib().csim_obs_slots_present(1 if nobs is None else int(nobs), None, C.byref(m)))
+    else:
+        ss = _ints(slot, nobs)
+        _ck(lib().csim_obs_slots_present(len(ss), _ip(ss), C.byref(m)))
+    return m.value
 
 
 def obs_screen_decide(y, hb, vb, r, tol, active=True) -> int:
@@ -1261,12 +1281,42 @@ class ObsNetwork:
         as a structured array parallel to log() (csim_obs_network_screen_log)"""
         return self._log(lib().csim_obs_network_screen_log, CsimObsScreenCycle, OBS_SCREEN_FIELDS)
 
-    def observe(self, source_member, seed, draw=0, noise=True):
+    def set_slots(self, slot=None):
+        """the time slot of every observation, 0 .. OBS_MAX_SLOTS - 1 in input order (None: all 0, as at first); forgets
+        which slots are held and observed; enqueued without waiting (csim_obs_network_set_slots)"""
+        if slot is None:
+            _ck(lib().csim_obs_network_set_slots(self._h, None))
+            return
+        ss = _ints(slot, self.nobs)
+        _ck(lib().csim_obs_network_set_slots(self._h, _ip(ss)))
+
+    def hold(self, slot=None, truth_member=None):
+        """keeps h_k of every forecast member for the observations of the slot (None: all), from the members as they
+        are now, in rows of the network's own that stay across run(): what Ensemble.assimilate_etkf(held=True) reads at
+        the end of the window; enqueued without waiting (csim_obs_network_hold)"""
+        _ck(lib().csim_obs_network_hold(self._h, -1 if slot is None else int(slot),
+                                        -1 if truth_member is None else int(truth_member)))
+
+    def held(self) -> np.ndarray:
+        """waits for the ensemble's stream; the held rows, (nobs, M) in input order: the forecast in observation space
+        at the observations' own times, after a held analysis the analysis there (csim_obs_network_held)"""
+        M = C.c_int()
+        _ck(lib().csim_obs_network_held(self._h, None, C.byref(M), None))
+        H = np.empty((self.nobs, M.value))
+        _ck(lib().csim_obs_network_held(self._h, _dp(H), None, None))
+        return H
+
+    def observe(self, source_member, seed, draw=0, noise=True, slot=None):
         """the values from member source_member at the observed cells, with noise plus sqrt(r) times the seeded
-        deviates obs_noise(seed, draw, o); enqueued without waiting (csim_obs_network_observe)"""
+        deviates obs_noise(seed, draw, o); enqueued without waiting (csim_obs_network_observe).  slot: only the
+        observations of that time slot, the others keep their values (csim_obs_network_observe_slot)"""
         seed, draw = int(seed), int(draw)
         if not (0 <= seed < 1 << 64 and 0 <= draw < 1 << 32):
             raise ValueError("seed must fit 64 bits and draw 32 bits, unsigned")
+        if slot is not None:
+            _ck(lib().csim_obs_network_observe_slot(self._h, int(slot), int(source_member), seed, draw,
+                                                    noise if isinstance(noise, int) else int(bool(noise))))
+            return
         _ck(lib().csim_obs_network_observe(self._h, int(source_member), seed, draw,
                                            noise if isinstance(noise, int) else int(bool(noise))))
 
@@ -1597,10 +1647,22 @@ class Ensemble:
         _ck(rc)
         return self.letkf_last
 
-    def obs_gram(self, net: ObsNetwork, truth_member=None, loglik=False) -> ObsGram:
+    def obs_gram(self, net: ObsNetwork, truth_member=None, loglik=False, held=False) -> ObsGram:
         """the observation-space Gram matrix of the forecast members over the network's active observations, and with
         loglik=True each member's sum of squared normalised departures (a particle weight is exp(-loglik / 2));
-        synchronous, writes nothing of the network (csim_ensemble_obs_gram)"""
+        synchronous, writes nothing of the network (csim_ensemble_obs_gram).  held=True: from the rows that the network
+        holds (ObsNetwork.hold) instead of the current members; the members and the truth member are the hold's
+        (csim_ensemble_obs_gram_held)"""
+        if held:
+            Mh = C.c_int()
+            _ck(lib().csim_obs_network_held(net._h, None, C.byref(Mh), None))
+            M = Mh.value
+            A = np.empty((M + 1, M + 1))
+            ll = np.empty(M) if loglik else None
+            used = C.c_longlong()
+            _ck(lib().csim_ensemble_obs_gram_held(self._h, net._h, _dp(A), None if ll is None else _dp(ll),
+                                                  C.byref(used)))
+            return ObsGram(A, ll, used.value)
         tm, M = self._forecast(truth_member)
         A = np.empty((max(M, 0) + 1, max(M, 0) + 1))
         ll = np.empty(max(M, 0)) if loglik else None
@@ -1610,21 +1672,29 @@ class Ensemble:
         return ObsGram(A, ll, used.value)
 
     def assimilate_etkf(self, net: ObsNetwork, inflation=1.0, truth_member=None, record=False,
-                        screen=None, device=False):
+                        screen=None, device=False, held=False):
         """the global ETKF analysis with the network's observations: obs_gram() over the used ones, etkf_weights() and
         transform() composed in the library; waits for the Gram matrix, the transform is enqueued.  inflation (taken in
         ensemble space), truth_member, record and screen as in assimilate_network; the network's loc plays no part
         (csim_ensemble_assimilate_etkf).  device=True: the eigensolver and the weights run on the GPU in the
         round-robin order, the call only enqueues and returns None; etkf_info() waits and tells what it found
-        (csim_ensemble_assimilate_etkf_device)"""
+        (csim_ensemble_assimilate_etkf_device).  held=True: the 4D form, with the weights from the rows that the network
+        holds from its observations' own times (ObsNetwork.hold) and the rows transformed with the members
+        (csim_ensemble_assimilate_etkf_held)"""
         tm, M = self._forecast(truth_member)
         rec = record if isinstance(record, int) else int(bool(record))
-        if device:
+        if held:
+            _ck(lib().csim_ensemble_assimilate_etkf_held(self._h, net._h, float(inflation), tm, rec,
+                                                         0.0 if screen is None else float(screen), int(bool(device))))
+            if device:
+                return None
+        elif device:
             _ck(lib().csim_ensemble_assimilate_etkf_device(self._h, net._h, float(inflation), tm, rec,
                                                            0.0 if screen is None else float(screen)))
             return None
-        _ck(lib().csim_ensemble_assimilate_etkf(self._h, net._h, float(inflation), tm, rec,
-                                                0.0 if screen is None else float(screen)))
+        else:
+            _ck(lib().csim_ensemble_assimilate_etkf(self._h, net._h, float(inflation), tm, rec,
+                                                    0.0 if screen is None else float(screen)))
         used, chi2, dfs, ng = C.c_longlong(), C.c_double(), C.c_double(), C.c_int()
         gamma = np.empty(M)
         _ck(lib().csim_ensemble_etkf_info(self._h, C.byref(used), C.byref(chi2), C.byref(dfs), _dp(gamma),

@@ -364,6 +364,9 @@ struct ObsGramArgs {
     const int* tstart;            // the taps, as in AssimArgs; null: point observations
     const int* toff;
     const double* tw;
+    // csim_ensemble_obs_gram_held: M doubles per plan position, read as h_k in place of the gather (then i, j and the
+    // taps are not read, and truth_member plays no part); null: gather.  Last, as the taps are in AssimArgs
+    const double* rows;
 };
 // doubles of `partial` for a call: per class the packed upper triangle of A, M sums of loglik and one count
 size_t ens_obs_gram_partial_doubles(int forecast, int nobs);
@@ -371,6 +374,22 @@ size_t ens_obs_gram_partial_doubles(int forecast, int nobs);
 // one long long.  form: 0 (the launcher's choice) or 1 .. GRAM_FORMS; the result does not depend on it
 hipError_t ens_launch_obs_gram(const EnsGeom& g, const double* f, const ObsGramArgs& a, bool want_loglik,
                                double* partial, double* out, int form, hipStream_t st);
+
+// held observation-space rows (ensemble_held.hip; csim_obs_network_hold, csim_ensemble_assimilate_etkf_held): M doubles
+// per plan position, [plan position][member], the layout of the local analysis's priors.
+// h_k of `count` observations from the current members: block b serves plan position list[b] (list null: b).  The
+// AssimArgs as for ens_launch_local_prior; status is not read
+hipError_t ens_launch_obs_hold(const EnsGeom& g, const double* f, const AssimArgs& a, const int* list, int count,
+                               double* rows, hipStream_t st);
+// mv of csim_ensemble_relax over the M values of every row, 2 per input index (idx: the input index of a position)
+hipError_t ens_launch_held_mv(const double* rows, int nobs, int M, const int* idx, double* out, hipStream_t st);
+// every row as one cell's M members under ens_launch_transform(centered), in place; gate as there
+hipError_t ens_launch_held_transform(double* rows, int nobs, int M, const double* W, const double* wbar, hipStream_t st,
+                                     const int* gate = nullptr);
+// ens_launch_obs_observe for the `count` plan positions list[0 .. count)
+hipError_t ens_launch_obs_observe_list(const EnsGeom& g, const double* f, const ObsArgs& a, const int* list, int count,
+                                       int member, unsigned seed_lo, unsigned seed_hi, unsigned draw, bool noise,
+                                       hipStream_t st);
 
 // the device eigensolver and the ETKF's weights on the device (sym_eigen_device.hip), in the round-robin order of
 // include/csim.h.  `batch` matrices of n x n (rows lda doubles apart, a_stride doubles from one to the next), one

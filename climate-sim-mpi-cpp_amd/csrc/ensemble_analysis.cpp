@@ -9,6 +9,9 @@
 //          the eigensolver and the weights of sym_eigen_device.hip with no host round trip
 //   LETKF  (ensemble_letkf.hip)  the local analysis's priors, a Gram matrix per node of a lattice, the batched
 //          eigensolver and weights, and a cell pass that interpolates the weights; a lookup per spacing
+//   held ETKF  (csim_ensemble_assimilate_etkf_held, ensemble_held.hip)  either ETKF with h_k read from the rows that the
+//          network holds from the observations' own times (csim_obs_network_hold) in place of the state: (hb, vb), A and
+//          (ha, va) come from the rows, and the rows are transformed with the members
 // Screening (csim_obs_network_set_active, csim_ensemble_assimilate_screened) is one k_obs_screen launch ahead of the
 // analysis, whose kernels then skip what is not used.
 #include <cmath>
@@ -65,7 +68,14 @@ struct Analysis {
     ObsScreen s;
     bool screen;
     const double* f;   // the current buffer
+    double* rows = nullptr;  // a held analysis: the network's held rows for a.forecast members, which stand for the state
 };
+
+// (mean, variance) of h_k of every observation, 2 per input index: from the state, or from the rows of a held analysis
+hipError_t analysis_mv(csim_ensemble* e, csim_obs_network* n, const Analysis& x, double* out) {
+    if (x.rows) return ens_launch_held_mv(x.rows, n->nobs, x.a.forecast, x.oa.idx, out, e->st);
+    return ens_launch_assim_post(e->g, x.f, x.a, n->nobs, out, e->st);
+}
 
 // the first launches of an analysis: (hb, vb) where they are wanted and the status bytes where something is screened;
 // sets the network's flags
@@ -79,7 +89,7 @@ int analysis_begin(csim_ensemble* e, csim_obs_network* n, int M, int t, int reco
     const bool check = tol > 0;
     x->screen = check || n->masked;
     double* bg = n->at<double>(record ? n->l.bg : n->l.sbg);
-    if (record || check) CSIM_HIP(ens_launch_assim_post(e->g, x->f, x->a, n->nobs, bg, e->st));
+    if (record || check) CSIM_HIP(analysis_mv(e, n, *x, bg));
     x->s = ObsScreen{};
     if (x->screen) {
         ObsScreen& s = x->s;
@@ -91,12 +101,13 @@ int analysis_begin(csim_ensemble* e, csim_obs_network* n, int M, int t, int reco
         x->a.status = s.status;
     }
     n->analysed = true, n->screened = x->screen, n->last_recorded = record == 1;
+    n->hold.last = x->rows != nullptr;
     return CSIM_OK;
 }
 
 // the last launches of a recorded analysis: (ha, va) and the cycle's records
 int analysis_record(csim_ensemble* e, csim_obs_network* n, const Analysis& x) {
-    CSIM_HIP(ens_launch_assim_post(e->g, x.f, x.a, n->nobs, n->at<double>(n->l.post), e->st));
+    CSIM_HIP(analysis_mv(e, n, x, n->at<double>(n->l.post)));
     double* slot = n->at<double>(n->l.log) + static_cast<size_t>(OBS_CYCLE_FIELDS) * n->cycles;
     // the screen record of a cycle that is not screened is the (nobs, 0, 0) that create and log_reset put there
     if (x.screen)
@@ -113,8 +124,9 @@ int analysis_record(csim_ensemble* e, csim_obs_network* n, const Analysis& x) {
 // observations whose flag byte is `used` (flag null: all), synchronous.  *out: (M + 1)^2 + M doubles, A first.  The
 // class partials and the result use the buffers of csim_ensemble_gram, which is synchronous as well.
 // obs_gram_enqueue only launches and leaves the result in Espace::gram
+// rows: the held rows to read h_k from (csim_ensemble_obs_gram_held); null: the gather from the current buffer
 int obs_gram_enqueue(csim_ensemble* e, csim_obs_network* n, int M, int t, const unsigned char* flag, int used,
-                     bool want_ll) {
+                     bool want_ll, const double* rows = nullptr) {
     csim_ensemble::Espace& x = e->espace;
     const ObsArgs oa = n->args();
     ObsGramArgs a{};
@@ -122,6 +134,7 @@ int obs_gram_enqueue(csim_ensemble* e, csim_obs_network* n, int M, int t, const 
     a.i = oa.i, a.j = oa.j, a.y = oa.y, a.sr = oa.sr;
     a.flag = flag, a.used = used;
     a.tstart = oa.tstart, a.toff = oa.toff, a.tw = oa.tw;
+    a.rows = rows;
     const size_t ma = static_cast<size_t>(M) + 1, doubles = ma * ma + M + 1;
     CSIM_TRY(x.partial.reserve(sizeof(double) * ens_obs_gram_partial_doubles(M, n->nobs), e->st));
     CSIM_TRY(x.gram.reserve(sizeof(double) * doubles, e->st));
@@ -130,16 +143,106 @@ int obs_gram_enqueue(csim_ensemble* e, csim_obs_network* n, int M, int t, const 
 }
 
 int obs_gram(csim_ensemble* e, csim_obs_network* n, int M, int t, const unsigned char* flag, int used, bool want_ll,
-             std::vector<double>* out, long long* n_used) {
+             std::vector<double>* out, long long* n_used, const double* rows = nullptr) {
     csim_ensemble::Espace& x = e->espace;
     const size_t ma = static_cast<size_t>(M) + 1, doubles = ma * ma + M + 1;
-    CSIM_TRY(obs_gram_enqueue(e, n, M, t, flag, used, want_ll));
+    CSIM_TRY(obs_gram_enqueue(e, n, M, t, flag, used, want_ll, rows));
     out->resize(doubles);
     CSIM_HIP(hipMemcpyAsync(out->data(), x.gram.p, sizeof(double) * doubles, hipMemcpyDeviceToHost, e->st));
     CSIM_HIP(hipStreamSynchronize(e->st));
     static_assert(sizeof(long long) == sizeof(double), "the count travels behind loglik");
     std::memcpy(n_used, out->data() + ma * ma + M, sizeof(long long));
     return CSIM_OK;
+}
+
+// the state checks of a held analysis, after the analysis's own: every slot that occurs is held, for these members
+int held_check(const csim_obs_network* n, int M, int t) {
+    const csim_obs_network::Held& h = n->hold;
+    if (!h.M || !h.all_held())
+        return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_etkf_held: not every slot that occurs has been held since "
+                                    "the last held analysis (csim_obs_network_hold)");
+    if (h.M != M || h.t != t)
+        return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_etkf_held: the rows were held with another truth_member");
+    return CSIM_OK;
+}
+
+// a held analysis ends the window: no slot counts as held, the transformed rows stay until the next hold
+void held_done(csim_obs_network* n) { n->hold.held = 0, n->hold.done = true; }
+
+// csim_ensemble_assimilate_etkf, and with held csim_ensemble_assimilate_etkf_held(device = 0)
+int etkf_host(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member, int record, double tol,
+              bool held) {
+    int M = 0, t = 0;
+    CSIM_TRY(etkf_check(e, n, inflation, truth_member, record, tol, &M, &t));
+    if (held) CSIM_TRY(held_check(n, M, t));
+    try {
+        const size_t m = static_cast<size_t>(M), ma = m + 1;
+        std::vector<double> out, W(m * m), wbar(m), gamma(m);
+        long long used = 0;
+        double dfs = 0.0;
+        Analysis x;
+        if (held) x.rows = n->hold.rows.as();
+        e->espace.etkf_valid = false, e->espace.etkf_pending = false;
+        CSIM_TRY(analysis_begin(e, n, M, t, record, tol, &x));
+        CSIM_TRY(obs_gram(e, n, M, t, x.screen ? x.s.status : nullptr, CSIM_OBS_USED, false, &out, &used, x.rows));
+        for (size_t k = 0; k < ma * ma; ++k)
+            if (!std::isfinite(out[k])) return fail(CSIM_ERR_STATE, ETKF_NONFINITE_TEXT);
+        CSIM_TRY(csim_etkf_weights(M, out.data(), inflation, W.data(), wbar.data(), gamma.data(), &dfs, nullptr));
+        // nothing to assimilate and nothing to inflate: W would be the identity up to rounding, the members keep their bits
+        if (used != 0 || inflation != 1.0) {
+            CSIM_TRY(csim_ensemble_transform(e, truth_member, 1, W.data(), wbar.data()));
+            // the same (W, wbar), where the transform has put them, for the rows
+            const double* w = e->espace.w.as();
+            if (held) CSIM_HIP(ens_launch_held_transform(x.rows, n->nobs, M, w, w + m * m, e->st));
+        }
+        csim_ensemble::Espace& s = e->espace;
+        s.etkf_gamma.swap(gamma);
+        s.etkf_used = used, s.etkf_chi2 = out[ma * ma - 1], s.etkf_dfs = dfs, s.etkf_valid = true;
+        s.etkf_sweeps = 0, s.etkf_status = CSIM_EIGEN_OK;
+        if (held) held_done(n);
+        return record ? analysis_record(e, n, x) : CSIM_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_etkf: out of host memory");
+    }
+}
+
+// csim_ensemble_assimilate_etkf_device, and with held csim_ensemble_assimilate_etkf_held(device = 1)
+int etkf_device(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member, int record, double tol,
+                bool held) {
+    int M = 0, t = 0;
+    CSIM_TRY(etkf_check(e, n, inflation, truth_member, record, tol, &M, &t));
+    CSIM_REQUIRE(e->g.slab <= 0x7fffffffL, "grid too large for the ensemble-space kernels");
+    csim_ensemble::Espace& s = e->espace;
+    if (!eigen_device_form(M, s.eigen_form))
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_etkf_device: the eigen_form that is set does not "
+                                          "admit this many forecast members");
+    if (held) CSIM_TRY(held_check(n, M, t));
+    const size_t m = static_cast<size_t>(M);
+    const EtkfLayout l(M);
+    s.etkf_valid = false, s.etkf_pending = false;
+    CSIM_TRY(s.w.reserve(sizeof(double) * (m * m + m), e->st));
+    CSIM_TRY(s.eig.reserve(sizeof(double) * l.doubles, e->st));
+    Analysis x;
+    if (held) x.rows = n->hold.rows.as();
+    CSIM_TRY(analysis_begin(e, n, M, t, record, tol, &x));
+    CSIM_TRY(obs_gram_enqueue(e, n, M, t, x.screen ? x.s.status : nullptr, CSIM_OBS_USED, false, x.rows));
+    double* d = s.eig.as();
+    int* info = reinterpret_cast<int*>(d + l.info);
+    auto* rec = reinterpret_cast<EtkfRecord*>(d + l.rec);
+    CSIM_HIP(ens_launch_sym_eigen(M, 1, s.gram.as(), M + 1, 0, d + l.work, d + l.lam, d + l.V, info, s.eigen_form,
+                                  e->st));
+    CSIM_HIP(ens_launch_etkf_weights(M, s.gram.as(), d + l.lam, d + l.V, info, inflation, s.w.as(), s.w.as() + m * m,
+                                     rec, d + l.gamma, e->st));
+    // as csim_ensemble_transform: only interior cells of the forecast members in the current buffer are written; the
+    // kernel returns at once where the record says that there is nothing to do or that A is not finite
+    CSIM_HIP(ens_launch_transform(e->g, e->base(e->cur), M, t, true, s.w.as(), s.w.as() + m * m, s.project_form, e->st,
+                                  &rec->status));
+    if (held) {
+        CSIM_HIP(ens_launch_held_transform(x.rows, n->nobs, M, s.w.as(), s.w.as() + m * m, e->st, &rec->status));
+        held_done(n);
+    }
+    s.etkf_pending = true, s.etkf_m = M;
+    return record ? analysis_record(e, n, x) : CSIM_OK;
 }
 
 // max_local of the network, counted once
@@ -256,62 +359,45 @@ int csim_ensemble_obs_gram(csim_ensemble* e, csim_obs_network* n, int truth_memb
 
 int csim_ensemble_assimilate_etkf(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
                                   int record, double tol) {
-    int M = 0, t = 0;
-    CSIM_TRY(etkf_check(e, n, inflation, truth_member, record, tol, &M, &t));
-    try {
-        const size_t m = static_cast<size_t>(M), ma = m + 1;
-        std::vector<double> out, W(m * m), wbar(m), gamma(m);
-        long long used = 0;
-        double dfs = 0.0;
-        Analysis x;
-        e->espace.etkf_valid = false, e->espace.etkf_pending = false;
-        CSIM_TRY(analysis_begin(e, n, M, t, record, tol, &x));
-        CSIM_TRY(obs_gram(e, n, M, t, x.screen ? x.s.status : nullptr, CSIM_OBS_USED, false, &out, &used));
-        for (size_t k = 0; k < ma * ma; ++k)
-            if (!std::isfinite(out[k])) return fail(CSIM_ERR_STATE, ETKF_NONFINITE_TEXT);
-        CSIM_TRY(csim_etkf_weights(M, out.data(), inflation, W.data(), wbar.data(), gamma.data(), &dfs, nullptr));
-        // nothing to assimilate and nothing to inflate: W would be the identity up to rounding, the members keep their bits
-        if (used != 0 || inflation != 1.0) CSIM_TRY(csim_ensemble_transform(e, truth_member, 1, W.data(), wbar.data()));
-        csim_ensemble::Espace& s = e->espace;
-        s.etkf_gamma.swap(gamma);
-        s.etkf_used = used, s.etkf_chi2 = out[ma * ma - 1], s.etkf_dfs = dfs, s.etkf_valid = true;
-        s.etkf_sweeps = 0, s.etkf_status = CSIM_EIGEN_OK;
-        return record ? analysis_record(e, n, x) : CSIM_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(CSIM_ERR_STATE, "csim_ensemble_assimilate_etkf: out of host memory");
-    }
+    return etkf_host(e, n, inflation, truth_member, record, tol, false);
 }
 
 int csim_ensemble_assimilate_etkf_device(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
                                          int record, double tol) {
-    int M = 0, t = 0;
-    CSIM_TRY(etkf_check(e, n, inflation, truth_member, record, tol, &M, &t));
-    CSIM_REQUIRE(e->g.slab <= 0x7fffffffL, "grid too large for the ensemble-space kernels");
-    csim_ensemble::Espace& s = e->espace;
-    if (!eigen_device_form(M, s.eigen_form))
-        return fail(CSIM_ERR_UNSUPPORTED, "csim_ensemble_assimilate_etkf_device: the eigen_form that is set does not "
-                                          "admit this many forecast members");
-    const size_t m = static_cast<size_t>(M);
-    const EtkfLayout l(M);
-    s.etkf_valid = false, s.etkf_pending = false;
-    CSIM_TRY(s.w.reserve(sizeof(double) * (m * m + m), e->st));
-    CSIM_TRY(s.eig.reserve(sizeof(double) * l.doubles, e->st));
-    Analysis x;
-    CSIM_TRY(analysis_begin(e, n, M, t, record, tol, &x));
-    CSIM_TRY(obs_gram_enqueue(e, n, M, t, x.screen ? x.s.status : nullptr, CSIM_OBS_USED, false));
-    double* d = s.eig.as();
-    int* info = reinterpret_cast<int*>(d + l.info);
-    auto* rec = reinterpret_cast<EtkfRecord*>(d + l.rec);
-    CSIM_HIP(ens_launch_sym_eigen(M, 1, s.gram.as(), M + 1, 0, d + l.work, d + l.lam, d + l.V, info, s.eigen_form,
-                                  e->st));
-    CSIM_HIP(ens_launch_etkf_weights(M, s.gram.as(), d + l.lam, d + l.V, info, inflation, s.w.as(), s.w.as() + m * m,
-                                     rec, d + l.gamma, e->st));
-    // as csim_ensemble_transform: only interior cells of the forecast members in the current buffer are written; the
-    // kernel returns at once where the record says that there is nothing to do or that A is not finite
-    CSIM_HIP(ens_launch_transform(e->g, e->base(e->cur), M, t, true, s.w.as(), s.w.as() + m * m, s.project_form, e->st,
-                                  &rec->status));
-    s.etkf_pending = true, s.etkf_m = M;
-    return record ? analysis_record(e, n, x) : CSIM_OK;
+    return etkf_device(e, n, inflation, truth_member, record, tol, false);
+}
+
+int csim_ensemble_obs_gram_held(csim_ensemble* e, csim_obs_network* n, double* A, double* loglik, long long* n_used) {
+    CSIM_REQUIRE(e, "null ensemble");
+    CSIM_REQUIRE(n, "null network");
+    CSIM_REQUIRE(n->e == e, "the network belongs to another ensemble");
+    const csim_obs_network::Held& h = n->hold;
+    if (!h.M || !h.all_held())
+        return fail(CSIM_ERR_STATE, "csim_ensemble_obs_gram_held: not every slot that occurs has been held "
+                                    "(csim_obs_network_hold)");
+    if (!n->has_values)
+        return fail(CSIM_ERR_STATE, "csim_ensemble_obs_gram_held: the network has no values yet");
+    try {
+        std::vector<double> out;
+        long long used = 0;
+        const int M = h.M;
+        CSIM_TRY(obs_gram(e, n, M, h.t, n->masked ? n->at<unsigned char>(n->l.mask) : nullptr, 1, loglik != nullptr, &out,
+                          &used, h.rows.as()));
+        const size_t ma = static_cast<size_t>(M) + 1;
+        if (A) std::copy(out.begin(), out.begin() + ma * ma, A);
+        if (loglik) std::copy(out.begin() + ma * ma, out.begin() + ma * ma + M, loglik);
+        if (n_used) *n_used = used;
+        return CSIM_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(CSIM_ERR_STATE, "csim_ensemble_obs_gram_held: out of host memory");
+    }
+}
+
+int csim_ensemble_assimilate_etkf_held(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
+                                       int record, double tol, int device) {
+    CSIM_REQUIRE(device == 0 || device == 1, "device must be 0 or 1");
+    return device ? etkf_device(e, n, inflation, truth_member, record, tol, true)
+                  : etkf_host(e, n, inflation, truth_member, record, tol, true);
 }
 
 int csim_ensemble_etkf_info2(csim_ensemble* e, long long* n_used, double* chi2, double* dfs, double* gamma,

@@ -2,8 +2,9 @@
 // kernels are in ensemble_obs.hip): observations that are planned once and live on the device.  create builds the
 // plan that csim_ensemble_assimilate builds per call (assim_plan_build of assim_plan.hpp) and uploads it; here are also
 // its values (from the host or observed from a member), the mask of csim_obs_network_set_active, and what comes back:
-// fetch, the two logs and the status bytes.  The analyses that run on a network are ensemble_analysis.cpp, the forecast
-// impact is ensemble_obs_impact.cpp.
+// fetch, the two logs and the status bytes; and the time slots with the rows held at their times (set_slots, hold,
+// observe_slot, held; kernels in ensemble_held.hip), which csim_ensemble_assimilate_etkf_held reads.  The analyses that
+// run on a network are ensemble_analysis.cpp, the forecast impact is ensemble_obs_impact.cpp.
 #include <cmath>
 #include <memory>
 #include <new>
@@ -146,6 +147,21 @@ int network_create(csim_ensemble* e, int nobs, const int* i, const int* j, const
     }
 }
 
+// the observations of `slot` (-1: all) as a launch: their number and the device list of their plan positions (null: the
+// positions 0 .. count - 1 themselves)
+void slot_launch(const csim_obs_network* n, int slot, int* count, const int** list) {
+    const csim_obs_network::Held& x = n->hold;
+    *list = nullptr;
+    if (slot < 0 || (x.start.empty() && slot == 0)) {
+        *count = n->nobs;
+    } else if (x.start.empty()) {
+        *count = 0;
+    } else {
+        *count = x.start[slot + 1] - x.start[slot];
+        *list = x.list.cpos() + x.start[slot];
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -198,6 +214,7 @@ int csim_obs_network_set_values(csim_obs_network* n, const double* y) {
     CSIM_TRY(n->stage.send(n->at<char>(n->l.y), sizeof(double) * n->nobs, n->e->st));
     n->has_values = true;
     n->has_truth = false;
+    n->hold.seen = 0;
     return CSIM_OK;
 }
 
@@ -233,6 +250,121 @@ int csim_obs_network_observe(csim_obs_network* n, int source_member, unsigned lo
     n->has_values = true;
     n->has_truth = true;
     return CSIM_OK;
+}
+
+int csim_obs_slots_present(int nobs, const int* slot, unsigned long long* mask) {
+    CSIM_REQUIRE(nobs >= 1, "nobs must be >= 1");
+    CSIM_REQUIRE(mask, "null argument");
+    unsigned long long m = slot ? 0ull : 1ull;
+    if (slot)
+        for (int o = 0; o < nobs; ++o) {
+            CSIM_REQUIRE(slot[o] >= 0 && slot[o] < CSIM_OBS_MAX_SLOTS, "a slot must be in 0 .. CSIM_OBS_MAX_SLOTS - 1");
+            m |= 1ull << slot[o];
+        }
+    *mask = m;
+    return CSIM_OK;
+}
+
+int csim_obs_network_set_slots(csim_obs_network* n, const int* slot) {
+    CSIM_REQUIRE(n, "null network");
+    unsigned long long present = 1;
+    CSIM_TRY(csim_obs_slots_present(n->nobs, slot, &present));
+    csim_obs_network::Held& x = n->hold;
+    try {
+        // the plan positions grouped by slot, increasing within one; all in slot 0: no list, a position is its own entry
+        std::vector<int> start, pos;
+        if (slot && present != 1ull) {
+            start.assign(CSIM_OBS_MAX_SLOTS + 1, 0);
+            pos.resize(n->nobs);
+            for (int o = 0; o < n->nobs; ++o) ++start[slot[o] + 1];
+            for (int s = 0; s < CSIM_OBS_MAX_SLOTS; ++s) start[s + 1] += start[s];
+            std::vector<int> at(start.begin(), start.end() - 1);
+            for (int q = 0; q < n->nobs; ++q) pos[at[slot[n->idx[q]]]++] = q;
+            CSIM_TRY(x.list.upload(start, pos, 1, n->e->st));
+        } else {
+            x.list.key = 0;
+        }
+        x.start.swap(start);
+    } catch (const std::bad_alloc&) {
+        return fail(CSIM_ERR_STATE, "csim_obs_network_set_slots: out of host memory");
+    }
+    x.present = present, x.held = 0, x.seen = 0, x.done = false;
+    return CSIM_OK;
+}
+
+int csim_obs_network_hold(csim_obs_network* n, int slot, int truth_member) {
+    CSIM_REQUIRE(n, "null network");
+    CSIM_REQUIRE(slot >= -1 && slot < CSIM_OBS_MAX_SLOTS, "slot must be -1 or in 0 .. CSIM_OBS_MAX_SLOTS - 1");
+    csim_ensemble* e = n->e;
+    int M = 0, t = 0;
+    CSIM_TRY(forecast_split(e->g.members, truth_member, &M, &t));
+    if (M < 2 || M > ESPACE_MAX_MEMBERS)
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_obs_network_hold: 2 .. CSIM_ESPACE_MAX_MEMBERS forecast members");
+    const size_t doubles = static_cast<size_t>(n->nobs) * M;
+    if (doubles > static_cast<size_t>(CSIM_LOCAL_MAX_PRIOR_DOUBLES))
+        return fail(CSIM_ERR_UNSUPPORTED, "csim_obs_network_hold: nobs times the forecast members exceeds "
+                                          "CSIM_LOCAL_MAX_PRIOR_DOUBLES");
+    csim_obs_network::Held& x = n->hold;
+    if (x.M != M || x.t != t) x.held = 0;  // rows of other members are forgotten
+    if (sizeof(double) * doubles > x.rows.cap) x.held = 0, x.M = 0;  // a buffer that grows loses its rows
+    CSIM_TRY(x.rows.reserve(sizeof(double) * doubles, e->st));
+    x.M = M, x.t = t;
+    int count = 0;
+    const int* list = nullptr;
+    slot_launch(n, slot, &count, &list);
+    const ObsArgs oa = n->args();
+    const AssimArgs a = assim_args(M, t, *n, n->at<double>(n->l.rho), {oa.i, oa.j, oa.idx, oa.y, oa.r}, nullptr, nullptr,
+                                   nullptr, oa.tstart, oa.toff, oa.tw, n->tmax);
+    CSIM_HIP(ens_launch_obs_hold(e->g, e->base(e->cur), a, list, count, x.rows.as(), e->st));
+    x.held |= slot < 0 ? ~0ull : 1ull << slot;
+    x.done = false;
+    return CSIM_OK;
+}
+
+int csim_obs_network_observe_slot(csim_obs_network* n, int slot, int source_member, unsigned long long seed,
+                                  unsigned draw, int noise) {
+    CSIM_REQUIRE(n, "null network");
+    CSIM_REQUIRE(slot >= 0 && slot < CSIM_OBS_MAX_SLOTS, "slot must be in 0 .. CSIM_OBS_MAX_SLOTS - 1");
+    csim_ensemble* e = n->e;
+    CSIM_REQUIRE(source_member >= 0 && source_member < e->g.members, "source_member out of range");
+    CSIM_REQUIRE(noise == 0 || noise == 1, "noise must be 0 or 1");
+    int count = 0;
+    const int* list = nullptr;
+    slot_launch(n, slot, &count, &list);
+    if (!list && count)
+        CSIM_HIP(ens_launch_obs_observe(e->g, e->base(e->cur), n->args(), source_member, static_cast<unsigned>(seed),
+                                        static_cast<unsigned>(seed >> 32), draw, noise == 1, e->st));
+    else
+        CSIM_HIP(ens_launch_obs_observe_list(e->g, e->base(e->cur), n->args(), list, count, source_member,
+                                             static_cast<unsigned>(seed), static_cast<unsigned>(seed >> 32), draw,
+                                             noise == 1, e->st));
+    csim_obs_network::Held& x = n->hold;
+    x.seen |= 1ull << slot;
+    if ((x.seen & x.present) == x.present) n->has_values = true, n->has_truth = true;
+    return CSIM_OK;
+}
+
+int csim_obs_network_held(csim_obs_network* n, double* H, int* M, int* truth_member) {
+    CSIM_REQUIRE(n, "null network");
+    const csim_obs_network::Held& x = n->hold;
+    // after a held analysis no slot counts as held, but its transformed rows stay until the next hold
+    if (!x.M || !(x.all_held() || x.done))
+        return fail(CSIM_ERR_STATE, "csim_obs_network_held: not every slot that occurs has been held "
+                                    "(csim_obs_network_hold)");
+    if (M) *M = x.M;
+    if (truth_member) *truth_member = x.t < n->e->g.members ? x.t : -1;
+    CSIM_HIP(hipStreamSynchronize(n->e->st));
+    if (!H) return CSIM_OK;
+    try {
+        const size_t m = static_cast<size_t>(x.M);
+        std::vector<double> buf(m * n->nobs);
+        CSIM_HIP(hipMemcpyAsync(buf.data(), x.rows.p, sizeof(double) * buf.size(), hipMemcpyDeviceToHost, n->e->st));
+        CSIM_HIP(hipStreamSynchronize(n->e->st));
+        for (int q = 0; q < n->nobs; ++q) std::copy(buf.begin() + q * m, buf.begin() + (q + 1) * m, H + n->idx[q] * m);
+        return CSIM_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(CSIM_ERR_STATE, "csim_obs_network_held: out of host memory");
+    }
 }
 
 int csim_obs_noise(unsigned long long seed, unsigned draw, unsigned o, double* z) {

@@ -7,6 +7,8 @@
 //                  index alone, so neither the plan nor the launch geometry shows in the result.  Linear
 //                  observations (a.tstart): xt = h of the source member, sum_s w_s x(anchor + tap s) in tap order
 //                  from +0; the taps of a footprint are neighbours, so a lane's loads stay in a few cache lines.
+//                  LIST (csim_obs_network_observe_slot): the lanes serve the plan positions of a list, the observations
+//                  of one time slot; every other observation keeps y and xt.
 //   k_obs_chunks   one lane per chunk of OBS_CHUNK consecutive input indices: T_c of the eleven sums of a
 //                  csim_obs_cycle, each a running sum from +0 in input order.
 //   k_obs_cycle    one wave: lane f folds T_c of sum f in chunk order from +0 into the log's record.
@@ -26,11 +28,15 @@ namespace csim {
 
 namespace {
 
-template <bool LIN>
+template <bool LIN, bool LIST = false>
 __global__ __launch_bounds__(256) void k_obs_observe(const double* __restrict__ f, int pitch, long slab, ObsArgs a,
                                                      int member, unsigned seed_lo, unsigned seed_hi, unsigned draw,
-                                                     int noise) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
+                                                     int noise, const int* __restrict__ list = nullptr, int count = 0) {
+    int q = blockIdx.x * 256 + threadIdx.x;
+    if constexpr (LIST) {
+        if (q >= count) return;
+        q = list[q];
+    }
     if (q >= a.nobs) return;
     const double* p = f + static_cast<ptrdiff_t>(member) * slab + static_cast<ptrdiff_t>(a.j[q]) * pitch + (LPAD - 1) +
                       a.i[q];
@@ -158,6 +164,20 @@ hipError_t ens_launch_obs_observe(const EnsGeom& g, const double* f, const ObsAr
     else
         hipLaunchKernelGGL(k_obs_observe<false>, dim3((a.nobs + 255) / 256), dim3(256), 0, st, f, g.pitch, g.slab, a,
                            member, seed_lo, seed_hi, draw, noise ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t ens_launch_obs_observe_list(const EnsGeom& g, const double* f, const ObsArgs& a, const int* list, int count,
+                                       int member, unsigned seed_lo, unsigned seed_hi, unsigned draw, bool noise,
+                                       hipStream_t st) {
+    if (count <= 0) return hipSuccess;
+    if (a.nobs <= 0 || count > a.nobs || !list || member < 0 || member >= g.members) return hipErrorInvalidValue;
+    if (a.tstart)
+        hipLaunchKernelGGL((k_obs_observe<true, true>), dim3((count + 255) / 256), dim3(256), 0, st, f, g.pitch, g.slab,
+                           a, member, seed_lo, seed_hi, draw, noise ? 1 : 0, list, count);
+    else
+        hipLaunchKernelGGL((k_obs_observe<false, true>), dim3((count + 255) / 256), dim3(256), 0, st, f, g.pitch, g.slab,
+                           a, member, seed_lo, seed_hi, draw, noise ? 1 : 0, list, count);
     return hipGetLastError();
 }
 

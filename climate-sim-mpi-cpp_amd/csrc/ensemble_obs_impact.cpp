@@ -99,6 +99,10 @@ int csim_obs_network_impact_capture(csim_obs_network* n, int truth_member) {
     if (doubles > static_cast<size_t>(CSIM_IMPACT_MAX_DOUBLES))
         return fail(CSIM_ERR_UNSUPPORTED, "csim_obs_network_impact_capture: nobs times the forecast members exceeds "
                                           "CSIM_IMPACT_MAX_DOUBLES");
+    if (n->hold.last)
+        return fail(CSIM_ERR_STATE, "csim_obs_network_impact_capture: the network's last analysis was a held one "
+                                    "(csim_ensemble_assimilate_etkf_held); the forecast impact of held observations is "
+                                    "not built");
     if (!n->has_diag || !n->last_recorded)
         return fail(CSIM_ERR_STATE, "csim_obs_network_impact_capture: the network's last analysis was not recorded "
                                     "(csim_ensemble_assimilate_network with record = 1)");

@@ -11,6 +11,11 @@
 //                      the arithmetic of the others, and +0 leaves a running sum that started from +0 as it is.
 //                      LL: lane k of workgroup (g, 0) then adds e_k e_k of the raw rows to its running sum.  64 lanes
 //                      form hb, the rows are normalised, z_M goes to column M, and the tile walks the segment's rows.
+//                      ROWS (csim_ensemble_obs_gram_held): h_k is read from rows that the network holds, M per plan
+//                      position ([plan position][member], ensemble_held.hip), in place of the gather: a segment's 64
+//                      rows are one contiguous run of 64 M doubles, which the 256 lanes load side by side and scatter
+//                      into the same [observation][member] tile; the flag of every row goes through LDS first, so that
+//                      a row that is not used is not read.  Everything after the staging is the text of the others.
 //   k_obsgram_fold     entry (a, b), a <= b, folded over the classes and written to A[a][b] and A[b][a]; the row
 //                      after the last folds loglik the same way and adds up the counts.
 // Every product and every sum is one rounded fp64 operation, no FMA contraction.
@@ -29,7 +34,7 @@ static_assert(ESPACE_MAX_MEMBERS <= GRAM_THREADS, "one lane per member in the lo
 // dynamic LDS: the rows, then hb, y and sqrt(r) of the segment's observations
 inline size_t og_lds(int M) { return sizeof(double) * (static_cast<size_t>(GRAM_SEG) * gram_stride(M + 1) + 3 * GRAM_SEG); }
 
-template <int NB, bool LIN, bool LL>
+template <int NB, bool LIN, bool LL, bool ROWS = false>
 __global__ __launch_bounds__(GRAM_THREADS) void k_obsgram_partial(
     const double* __restrict__ f, int pitch, long slab, ObsGramArgs a, long nseg, double* __restrict__ partial,
     double* __restrict__ llpart, int* __restrict__ cntpart) {
@@ -52,7 +57,30 @@ __global__ __launch_bounds__(GRAM_THREADS) void k_obsgram_partial(
         const long e0 = q * GRAM_SEG;
         const int nc = static_cast<int>(min(static_cast<long>(GRAM_SEG), a.nobs - e0));
         bool used = false;
-        if (c < nc) {
+        if constexpr (ROWS) {
+            // wave 0 decides and publishes the flags (in hbs, which is free until the means); then element e = c M + k
+            // of the segment's run goes from lane e % 256 to row c, column k: 256 elements further is (dc, dk) further
+            if (kq == 0) {
+                const int o = static_cast<int>(e0) + c;
+                used = c < nc && (!a.flag || a.flag[o] == a.used);
+                hbs[c] = used ? 1.0 : 0.0;
+                ys[c] = used ? a.y[o] : 0.0;
+                srs[c] = used ? a.sr[o] : 1.0;
+            }
+            __syncthreads();
+            const double* __restrict__ src = a.rows + static_cast<size_t>(e0) * M;
+            const int n = nc * M, dc = GRAM_THREADS / M, dk = GRAM_THREADS - dc * M;
+            int rc = tid / M, rk = tid - rc * M;
+            for (int e = tid; e < n; e += GRAM_THREADS) {
+                double v = 0.0;
+                if (hbs[rc] != 0.0) v = src[e];
+                held[rc * stride + rk] = v;
+                rc += dc, rk += dk;
+                if (rk >= M) rk -= M, ++rc;
+            }
+            if (c < nc)
+                for (int k = M + kq; k < mpad; k += 4) row[k] = 0.0;
+        } else if (c < nc) {
             const int o = static_cast<int>(e0) + c;
             used = !a.flag || a.flag[o] == a.used;
             if (used) {
@@ -144,17 +172,17 @@ OgPartials og_partials(int M, int nobs) {
     return p;
 }
 
-template <int NB, bool LIN, bool LL>
+template <int NB, bool LIN, bool LL, bool ROWS = false>
 hipError_t launch_obsgram(const EnsGeom& g, const double* f, const ObsGramArgs& a, double* partial, double* out,
                           hipStream_t st) {
     const int M = a.forecast, MA = M + 1;
     const int classes = gram_classes(M, a.nobs);
     const OgPartials p = og_partials(M, a.nobs);
-    const hipError_t attr = dynamic_lds_once<k_obsgram_partial<NB, LIN, LL>>(og_lds(ESPACE_MAX_MEMBERS));
+    const hipError_t attr = dynamic_lds_once<k_obsgram_partial<NB, LIN, LL, ROWS>>(og_lds(ESPACE_MAX_MEMBERS));
     if (attr != hipSuccess) return attr;
     double* llpart = partial + p.ll;
     int* cntpart = reinterpret_cast<int*>(partial + p.cnt);
-    hipLaunchKernelGGL((k_obsgram_partial<NB, LIN, LL>), dim3(classes, gram_shares(MA, NB)), dim3(GRAM_THREADS),
+    hipLaunchKernelGGL((k_obsgram_partial<NB, LIN, LL, ROWS>), dim3(classes, gram_shares(MA, NB)), dim3(GRAM_THREADS),
                        og_lds(M), st, f, g.pitch, g.slab, a, gram_segments(a.nobs), partial, llpart, cntpart);
     hipError_t rc = hipGetLastError();
     if (rc != hipSuccess) return rc;
@@ -173,6 +201,9 @@ hipError_t ens_launch_obs_gram(const EnsGeom& g, const double* f, const ObsGramA
     if (M < 2 || M > ESPACE_MAX_MEMBERS || a.nobs < 1 || form < 0 || form > GRAM_FORMS) return hipErrorInvalidValue;
     return for_gram_form(form, M, [&](auto nb) {
         constexpr int NB = decltype(nb)::value;
+        if (a.rows)
+            return want_loglik ? launch_obsgram<NB, false, true, true>(g, f, a, partial, out, st)
+                               : launch_obsgram<NB, false, false, true>(g, f, a, partial, out, st);
         if (a.tstart)
             return want_loglik ? launch_obsgram<NB, true, true>(g, f, a, partial, out, st)
                                : launch_obsgram<NB, true, false>(g, f, a, partial, out, st);

@@ -73,6 +73,23 @@ struct csim_obs_network : csim::AssimPlan {   // the plan: nobs, nlevels, lx, ly
         csim::DeviceLookup nodes;       // the lookup (LetkfLookup), its key the spacing
         void release() { nodes.release(); }
     } letkf;
+    // time slots and held rows (csim_obs_network_set_slots, _hold, csim_ensemble_assimilate_etkf_held): nothing here is
+    // allocated before the first set_slots (the list) or the first hold (the rows)
+    struct Held {
+        std::vector<int> start;         // per slot, one more than slots: where its plan positions start in the list;
+                                        // empty: every observation in slot 0, and there is no list
+        csim::DeviceLookup list;        // starts and plan positions, grouped by slot, increasing within one; key 1: made
+        unsigned long long present = 1; // bit s: slot s occurs (csim_obs_slots_present)
+        unsigned long long held = 0;    // bit s: slot s has been held since set_slots, the last held analysis, or a
+                                        // hold with another (M, t)
+        unsigned long long seen = 0;    // bit s: slot s has been observed since set_slots or set_values
+        csim::DeviceBuf rows;           // M doubles per plan position: h_{o,k} at its slot's time
+        int M = 0, t = 0;               // of the rows (M = 0: there are none)
+        bool last = false;              // the network's last analysis was a held one
+        bool done = false;              // the rows are those a held analysis left, and there was no hold since
+        bool all_held() const { return (held & present) == present; }
+        void release() { list.release(), rows.release(); }
+    } hold;
     size_t imp_dn() const { return 0; }
     size_t imp_out() const { return csim::up(sizeof(double) * nobs); }
     size_t imp_snap() const { return 2 * csim::up(sizeof(double) * nobs); }
@@ -88,5 +105,5 @@ struct csim_obs_network : csim::AssimPlan {   // the plan: nobs, nlevels, lx, ly
         if (ntaps) a.tstart = at<int>(l.tstart), a.toff = at<int>(l.toff), a.tw = at<double>(l.tw);
         return a;
     }
-    ~csim_obs_network() { dev.release(), stage.release(), mstage.release(), imp.release(), loc.release(), letkf.release(); }
+    ~csim_obs_network() { dev.release(), stage.release(), mstage.release(), imp.release(), loc.release(), letkf.release(), hold.release(); }
 };

@@ -232,6 +232,28 @@ public:
     void observe(int source_member, unsigned long long seed, unsigned draw = 0, bool noise = true) {
         check(csim_obs_network_observe(handle(), source_member, seed, draw, noise ? 1 : 0));
     }
+    // the same for the observations of one time slot, the others keep their values (see csim_obs_network_observe_slot)
+    void observe_slot(int slot, int source_member, unsigned long long seed, unsigned draw = 0, bool noise = true) {
+        check(csim_obs_network_observe_slot(handle(), slot, source_member, seed, draw, noise ? 1 : 0));
+    }
+    // the time slot of every observation, 0 .. CSIM_OBS_MAX_SLOTS - 1; forgets which slots are held; enqueued
+    void set_slots(const std::vector<int>& slot) {
+        if (slot.size() != nobs_) throw std::invalid_argument("obs network: one slot per observation");
+        check(csim_obs_network_set_slots(handle(), slot.data()));
+    }
+    // keeps h_k of every forecast member for the observations of the slot (-1: all) from the members as they are now,
+    // for Ensemble::assimilate_etkf_held() at the end of the window (see csim_obs_network_hold); t as in
+    // Ensemble::assimilate.  Enqueued
+    void hold(int slot = -1, int t = -1) { check(csim_obs_network_hold(handle(), slot, t)); }
+    // waits for the ensemble's stream: the held rows, size() x M row-major in input order; after a held analysis the
+    // transformed rows (see csim_obs_network_held)
+    std::vector<double> held() {
+        int M = 0;
+        check(csim_obs_network_held(handle(), nullptr, &M, nullptr));
+        std::vector<double> H(nobs_ * static_cast<std::size_t>(M));
+        check(csim_obs_network_held(handle(), H.data(), nullptr, nullptr));
+        return H;
+    }
     // waits for the ensemble's stream
     ObsValues fetch(bool truth = false, bool diagnostics = false) {
         ObsValues v;
@@ -603,6 +625,18 @@ public:
         check(csim_ensemble_obs_gram(h_, net.handle(), t, g.A.data(), loglik ? g.loglik.data() : nullptr, &g.n_used));
         return g;
     }
+    // the same from the rows that the network holds (ObsNetwork::hold) instead of the current members; the members and
+    // the truth member are the hold's (see csim_ensemble_obs_gram_held)
+    ObsGram obs_gram_held(ObsNetwork& net, bool loglik = false) {
+        int m = 0;
+        check(csim_obs_network_held(net.handle(), nullptr, &m, nullptr));
+        const std::size_t M = static_cast<std::size_t>(m);
+        ObsGram g;
+        g.A.resize((M + 1) * (M + 1));
+        if (loglik) g.loglik.resize(M);
+        check(csim_ensemble_obs_gram_held(h_, net.handle(), g.A.data(), loglik ? g.loglik.data() : nullptr, &g.n_used));
+        return g;
+    }
     // the global ETKF analysis with the network's observations: obs_gram() over the used ones, etkf_weights() and
     // transform() composed in the library; waits for the Gram matrix, the transform is enqueued (see
     // csim_ensemble_assimilate_etkf); the arguments as for assimilate(ObsNetwork&, ...)
@@ -619,6 +653,14 @@ public:
     void assimilate_etkf_device(ObsNetwork& net, double inflation = 1.0, int t = -1, bool record = false,
                                 double screen_tol = 0.0) {
         check(csim_ensemble_assimilate_etkf_device(h_, net.handle(), inflation, t, record ? 1 : 0, screen_tol));
+    }
+    // the 4D form of either: the weights from the rows that the network holds from its observations' own times, applied
+    // to the members and to the rows; ends the window (see csim_ensemble_assimilate_etkf_held).  etkf_info(t) tells what
+    // it found
+    void assimilate_etkf_held(ObsNetwork& net, double inflation = 1.0, int t = -1, bool record = false,
+                              double screen_tol = 0.0, bool device = false) {
+        check(csim_ensemble_assimilate_etkf_held(h_, net.handle(), inflation, t, record ? 1 : 0, screen_tol,
+                                                 device ? 1 : 0));
     }
     // what the last ETKF analysis found; after assimilate_etkf_device it waits for the stream first, and throws when
     // the Gram matrix was not finite (the members are then unchanged; see csim_ensemble_etkf_info2)

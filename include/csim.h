@@ -1176,6 +1176,59 @@ int csim_ensemble_assimilate_etkf_device(csim_ensemble* e, csim_obs_network* n, 
                                          int record, double tol);
 int csim_ensemble_etkf_info2(csim_ensemble* e, long long* n_used, double* chi2, double* dfs, double* gamma,
                              int* n_gamma, int* sweeps, int* status);
+/* 4D-ETKF: observations assimilated at their own times in the window (Hunt et al. 2004, 2007).  A network has time
+ * slots 0 .. CSIM_OBS_MAX_SLOTS - 1 and every observation belongs to one.  While the forecast runs the caller holds a
+ * slot when the model reaches its time: h_k of every forecast member for the slot's observations goes into rows of the
+ * network's own, which stay across run calls.  At the end of the window a held analysis forms the ETKF's weights from the
+ * rows instead of the current state and applies them to the members and to the rows.  Every * + - / sqrt is one IEEE
+ * fp64 operation, no FMA contraction; running sums start from +0 in the stated order.
+ * slots_present (host-only): *mask gets bit s for every slot s that occurs among the nobs values (slot NULL: bit 0);
+ *   CSIM_ERR_ARG for a value outside 0 .. CSIM_OBS_MAX_SLOTS - 1, nobs < 1 or a NULL mask.  The rule of the library's own
+ *   bookkeeping: a network is "held" ("observed") when every bit of this mask is.
+ * set_slots: nobs values in input order, NULL: all 0, which is also a new network's state.  CSIM_ERR_ARG for a value out
+ *   of range, before anything changes.  Forgets which slots are held and which are observed; enqueues an upload only.
+ * hold: slot = -1 means every observation.  For every plan position q of the slot, whatever the mask and the status bytes
+ *   say, H[q][k] = h_k of obs_gram above (the point cell's bits, or the tap sum in tap order from +0) of the M forecast
+ *   members in forecast order, from the current buffer after everything enqueued so far.  Rows of other slots keep their
+ *   bits; a slot without observations is a no-op that still counts as held.  Enqueues only.  The rows are nobs x M
+ *   doubles, [plan position][member], the layout of the local analysis's priors, reserved at the first hold.
+ *   CSIM_ERR_ARG: slot or truth_member out of range; CSIM_ERR_UNSUPPORTED: nobs M above CSIM_LOCAL_MAX_PRIOR_DOUBLES, or M
+ *   outside 2 .. CSIM_ESPACE_MAX_MEMBERS.  A hold with another (M, truth_member) than the rows already held forgets those
+ *   rows first.
+ * observe_slot: csim_obs_network_observe restricted to the observations of the slot: xt_o and y_o get the bits that
+ *   observe would give them at this moment (the noise depends on the input index o alone), every other observation
+ *   keeps y and xt.  The network has values once set_values or observe was called, or once every slot that occurs has
+ *   been observed since set_slots (and since the last set_values); that it has a truth follows the same rule.
+ * held: waits for the stream; the rows in input order, nobs x M (H NULL: not wanted), *M and *truth_member (-1: none) of
+ *   the hold (either may be NULL).  CSIM_ERR_STATE when not every slot that occurs is held; after a held analysis it
+ *   returns the transformed rows until the next hold.
+ * obs_gram_held: obs_gram above word for word with h_k = H[q][k]: the mask, an observation that is not used not being
+ *   read, the segment, class and fold order and the symmetry; M and t are those of the hold.  CSIM_ERR_STATE when not
+ *   every slot that occurs is held, or when the network has no values.  Writes nothing of the network.  The result does
+ *   not depend on the option obs_gram_form.
+ * assimilate_etkf_held: the steps of assimilate_etkf (device = 0) or assimilate_etkf_device (device = 1) with these
+ *   differences: (hb, vb) of the screening and the record are mv of csim_ensemble_relax over the M values of the held
+ *   row, not of the state; A is obs_gram_held over the used observations; the same (W, wbar) is applied twice, to the
+ *   members by transform(centered = 1), and to every held row, which is treated exactly as one cell's M members are
+ *   under transform(centered = 1), all M values read before any is written; where the analysis launches no transform (no
+ *   used observation and inflation 1; on the device path the status record says nothing to do or non-finite) the rows
+ *   keep their bits too; with record = 1, (ha, va) are mv of the transformed rows.  So after the call the rows are the
+ *   analysis in observation space at report time.  Errors: the analysis's own, first and in their order; then
+ *   CSIM_ERR_STATE when not every slot that occurs is held, or when truth_member or M differ from the hold's.  A held
+ *   analysis ends the window: afterwards no slot counts as held, and a second one without new holds is CSIM_ERR_STATE.
+ *   etkf_info and etkf_info2 work as after the calls above.  csim_obs_network_impact_capture after a held analysis is
+ *   CSIM_ERR_STATE: a_k at report time is not what the impact's estimate takes.
+ * Not built: the held form of the serial, local and LETKF analyses, and forecast impact for held observations. */
+#define CSIM_OBS_MAX_SLOTS 64
+int csim_obs_slots_present(int nobs, const int* slot, unsigned long long* mask);
+int csim_obs_network_set_slots(csim_obs_network* n, const int* slot);
+int csim_obs_network_hold(csim_obs_network* n, int slot, int truth_member);
+int csim_obs_network_observe_slot(csim_obs_network* n, int slot, int source_member, unsigned long long seed,
+                                  unsigned draw, int noise);
+int csim_obs_network_held(csim_obs_network* n, double* H, int* M, int* truth_member);
+int csim_ensemble_obs_gram_held(csim_ensemble* e, csim_obs_network* n, double* A, double* loglik, long long* n_used);
+int csim_ensemble_assimilate_etkf_held(csim_ensemble* e, csim_obs_network* n, double inflation, int truth_member,
+                                       int record, double tol, int device);
 /* LETKF: the ETKF made local (Hunt et al. 2007): ensemble-space weights from the observations near a point, with the
  * network's localisation in the observation error, computed on a coarse lattice of analysis nodes and interpolated to
  * the cells (Yang et al. 2009).  The node spacing s trades cost against locality; s = 1 has a node on every cell and is
