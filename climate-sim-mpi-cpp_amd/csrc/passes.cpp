@@ -130,6 +130,11 @@ static hipError_t launch_fused(csim_stepper* s, const Phys& p, const int kind[4]
         kept.valid = true;
     }
     if (part != 1) s->last_rows = kept.plan.rows;  // the frame's heights are fixed
+    if (part == 0) {  // which plan went out (read-only options "last_regions", "last_tiles", "last_tail_blocks")
+        s->last_regions = kept.plan.tl.nregions;
+        s->last_tiles = kept.plan.tl.ntiles;
+        s->last_tail_blocks = kept.plan.tl.tail_blocks;
+    }
     if (part == 0 && kept.plan.wide) s->wide_strips_active = 1;  // of this run (csim_stepper_run clears it)
     return launch_sweepO(s->cur, s->nxt, s->pitch, p, cfg, kind, s->bc_value, kept.plan, st, final_pass ? s->fin : nullptr, sync, lease);
 }

@@ -524,7 +524,7 @@ int csim_stepper_set_option(csim_stepper* s, const char* key, long value) {
     } else if (k == "autotune") {
         s->autotune = value != 0;
         s->forget_tuning();
-    } else if (k == "tuned_rows" || k == "last_rows") {  // read back through csim_stepper_get_option
+    } else if (k == "tuned_rows" || k == "last_rows" || k == "last_regions" || k == "last_tiles" || k == "last_tail_blocks") {  // read back through csim_stepper_get_option
         return fail(CSIM_ERR_ARG, k + " is read-only");
     } else if (k == "sync_timeout_ms") {
         CSIM_REQUIRE(value >= 0, "sync_timeout_ms must be >= 0");
@@ -566,6 +566,9 @@ int csim_stepper_get_option(const csim_stepper* s, const char* key, long* value)
     else if (k.size() == 17 && k.compare(0, 16, "tuned_rows_wide_") == 0 && k[16] >= '2' && k[16] <= '0' + MAX_FUSE)
         *value = s->tuned_W[k[16] - '0'];  // the same for launches with wide strips ("wide_strips")
     else if (k == "last_rows") *value = s->last_rows;
+    else if (k == "last_regions") *value = s->last_regions;
+    else if (k == "last_tiles") *value = s->last_tiles;
+    else if (k == "last_tail_blocks") *value = s->last_tail_blocks;
     else if (k == "prefetch") *value = s->cfg.prefetch;
     else if (k == "xcd_swizzle") *value = s->cfg.xcd_swizzle;
     else if (k == "tail_split") *value = s->cfg.tail_split;

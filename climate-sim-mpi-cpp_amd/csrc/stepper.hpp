@@ -114,6 +114,7 @@ struct csim_stepper {
     bool bulk_first_run = false;          // the current csim_stepper_run uses pass_fused_bulk_first
     csim::Capture snap;   // asynchronous snapshot of the interior (device staging copy + pinned host buffer + I/O stream)
     int last_rows = 0;    // chunk height the last fused whole-field / bulk launch used
+    int last_regions = 0, last_tiles = 0, last_tail_blocks = 0;  // read-only: the Tiling of the last whole-field (part 0) launch's plan
     // the tile plans of the fused passes, one per (depth, part): built at the first launch and again when an input
     // (an option, a tuned height, the division mode) differs from what the kept plan was made from
     struct KeptPlan {

@@ -318,7 +318,10 @@ int csim_stepper_sum(csim_stepper* s, double* out);
  *   "autotune"       0/1 (default 1) with rows_per_chunk = 0: the first long run times the candidate
  *                    chunk heights on this GPU (trial launches that do not advance the field) and keeps
  *                    the fastest; "tuned_rows" (read-only) reports it, "last_rows" (read-only) the chunk
- *                    height the most recent fused launch actually used */
+ *                    height the most recent fused launch actually used
+ *   "last_regions", "last_tiles", "last_tail_blocks" (read-only): the tile plan of the most recent whole-field launch
+ *                    of a fused pass — its regions (at most 8: left, wide and right strips of the main part and of the
+ *                    half-height tail, and the two bands), its tiles, and the blocks dispatched last in plain order */
 int csim_stepper_set_option(csim_stepper* s, const char* key, long value);
 int csim_stepper_get_option(const csim_stepper* s, const char* key, long* value);
 /* with option "profile"=1: HIP-event time and count of the sweep launches since the last reset, per kernel
