@@ -1219,6 +1219,9 @@ int csim_ensemble_etkf_info2(csim_ensemble* e, long long* n_used, double* chi2, 
  *   analysis in observation space at report time.  Errors: the analysis's own, first and in their order; then
  *   CSIM_ERR_STATE when not every slot that occurs is held, or when truth_member or M differ from the hold's.  A held
  *   analysis ends the window: afterwards no slot counts as held, and a second one without new holds is CSIM_ERR_STATE.
+ *   On the host path a call that fails, the non-finite A among its errors, has not ended the window: the rows and the
+ *   holds stand, and the call may be repeated without a new hold, after set_active for instance; on the device path the
+ *   window is over once the call has returned CSIM_OK, also where etkf_info later reports a non-finite A.
  *   etkf_info and etkf_info2 work as after the calls above.  csim_obs_network_impact_capture after a held analysis is
  *   CSIM_ERR_STATE: a_k at report time is not what the impact's estimate takes.
  * Not built: the held form of the serial, local and LETKF analyses, and forecast impact for held observations. */
